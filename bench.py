@@ -2,6 +2,7 @@
 """bench.py -- frames/sec of the Farnebäck + remap hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload 4k|1080p|1080p-1level] [--batch B]
+                    [--dump-outputs DIR] [--full]
 
 The workload is BASELINE.json configs[4] (and configs[3] at N = 1): ONE clip of T = 256 synthetic 4K
 frames, its 255 frame pairs sharded over the N ranks (`shard_range`, one-frame halo).  A "step" is
@@ -23,8 +24,15 @@ rank 0 through RCCL (tf_batch_broadcast), and the gather of finished frames to r
 timed region, the path has no data-path collective.  Weak scaling: every rank does
 one batch per step.
 
-Before anything is timed, rank 0 runs the parity gate: two pairs of the first batch through the
-very calls the timed loop makes, against the CPU oracle; no value is printed if it fails.
+A plain run does what the headline figure needs and nothing else: it sets up, burns in, warms up, times the K
+steps, writes --dump-outputs DIR if asked and prints the line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, the configuration).  The timed steps start on a fresh remap layer at the clip's first
+pass, so what they compute depends on the arguments alone.
+
+--full adds everything else, as before: before anything is timed, rank 0 runs the parity gate (pairs of the
+first batch through the very calls the timed loop makes, against the CPU oracle; no value is printed if it
+fails); the timed region brackets the dominant kernel with events; after it come the re-check, the
+roofline, the CPU baseline, the copy ceiling, the exact mode, the other workloads and the RCCL legs.
 
 Rank 0 prints ONE JSON line (README / DESIGN.md §5 describe the fields).
 """
@@ -878,6 +886,38 @@ def line_skeleton(args, wl, world, plans):
     }
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs: at most this many bytes in all
+DUMP_SEED = 20251015       # seed of the pixel sample --dump-outputs takes where the whole outputs do not fit
+
+
+def dump_outputs(job, directory):
+    """--dump-outputs: what the last timed step computed, as a caller of the path receives it, at one fixed, seeded sample
+    of pixels (every pixel where the whole outputs fit in DUMP_BYTES):
+        frames.npy      float32 [B, S, 3]  the B frames the step rendered (uint8 RGB values)
+        flows.npy       float32 [B, S, 2]  the B flows the step computed (u, v)
+        layer_data.npy  float64 [S, D]     the remap layer's state after the step (int32 values)
+        pixels.npy      float64 [S]        the sample: row-major pixel indices, ascending
+    Rank 0's outputs.  The timed steps start on a fresh layer at the clip's first pass (main): the arrays depend on the
+    arguments alone."""
+    w, h = job.wl["w"], job.wl["h"]
+    n, batch = w * h, job.batch
+    data, _ = job.layer.get_state()
+    depth = data.shape[2]
+    s = min(n, DUMP_BYTES // (batch * (3 + 2) * 4 + depth * 8 + 8))
+    idx = np.arange(n) if s == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, s, replace=False))
+    frames = np.empty((batch, s, 3), np.float32)
+    flows = np.empty((batch, s, 2), np.float32)
+    image = np.empty((h, w, 3), np.uint8)
+    flow = np.empty((h, w, 2), np.float32)
+    for i in range(batch):
+        frames[i] = job.comps[i].download(image).reshape(n, 3)[idx]
+        flows[i] = job.fb.get_flow_into(i, flow).reshape(n, 2)[idx]
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in (("frames", frames), ("flows", flows), ("layer_data", data.reshape(n, depth)[idx].astype(np.float64)),
+                      ("pixels", idx.astype(np.float64))):
+        np.save(os.path.join(directory, name + ".npy"), arr)
+
+
 def main():
     global STUCK_THREADS, EXIT_CODE
     ap = argparse.ArgumentParser()
@@ -919,7 +959,18 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="ranks meet, shard the clip and report the plan; no GPU call")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="a run-time option of the library (tf_set_option; include/tfhip.h) for A/B runs; recorded in the JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: the parity gate, the per-kernel profile and the "
+                         "roofline, the timed region's re-check, the synchronised `alone` steps, the CPU baseline, the copy "
+                         "ceiling, the exact mode and the other workloads, and the RCCL gather legs.  Without it a run sets "
+                         "up, warms up, times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write what its last step computed as DIR/<name>.npy (float32 / "
+                         "float64, rank 0's): the rendered frames, the flows and the layer state at a fixed seeded sample "
+                         "of pixels (dump_outputs).  The same arguments give the same arrays from run to run")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     from transflow_amd import batch as B
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -978,14 +1029,15 @@ def main():
         job.pixmap_buffer = pix_buf     # the job gathers from this buffer: it lives as long as the job
 
     gate, gate_times = None, None
-    if rank == 0 and not args.no_gate:
-        gate, gate_times = parity_gate(job)
-    gate = host.broadcast(gate)
-    if gate is not None and not gate["ok"]:
-        if rank == 0:
-            print(f"[bench] parity gate FAILED, nothing is reported: {json.dumps(gate)}", file=sys.stderr)
-        host.close()
-        sys.exit(3)
+    if args.full:
+        if rank == 0 and not args.no_gate:
+            gate, gate_times = parity_gate(job)
+        gate = host.broadcast(gate)
+        if gate is not None and not gate["ok"]:
+            if rank == 0:
+                print(f"[bench] parity gate FAILED, nothing is reported: {json.dumps(gate)}", file=sys.stderr)
+            host.close()
+            sys.exit(3)
 
     # Untimed passes before the W warm-up steps: the first process on a fresh box measured up to 2 - 3 % below the next
     # one (1992 -> 2013, 2018 -> 2058 frames/s: the kernels themselves ran slower), and not with ~4 s of passes in front
@@ -1003,22 +1055,29 @@ def main():
                 job.step()
             job.sync()
             burn_in_steps += 5
-    # warmup; the last warmup step is profiled per kernel to find the dominant one (the first step of a
+    # The burn-in's length depends on the box's speed: the warm-up and the timed steps start over on a fresh layer at the
+    # clip's first pass, so that what the timed region computes depends on the arguments alone (--dump-outputs)
+    job.sync()
+    job.layer.close()
+    job.layer = job.make_layer()
+    job.n_steps = 0
+    # warmup; with --full the last warmup step is profiled per kernel to find the dominant one (the first step of a
     # process pays one-off costs inside whichever kernel happens to run first)
-    n_warm = max(1, args.warmup)
+    n_warm = max(1, args.warmup) if args.full else args.warmup
     for i in range(n_warm):
-        if i == n_warm - 1:
+        if args.full and i == n_warm - 1:
             job.sync()
             job.prof(True)
             job.prof_reset()
         job.step()
     job.sync()
-    per_kernel = job.prof_report()
-    job.prof(False)
-    fb_kernels = {k: v for k, v in per_kernel.items() if k.startswith("fb_")}
-    dominant = max(fb_kernels, key=lambda k: fb_kernels[k][1])
-    job.prof_reset()
-    job.prof(True, dominant)  # only the dominant kernel is bracketed by events in the timed region
+    if args.full:
+        per_kernel = job.prof_report()
+        job.prof(False)
+        fb_kernels = {k: v for k, v in per_kernel.items() if k.startswith("fb_")}
+        dominant = max(fb_kernels, key=lambda k: fb_kernels[k][1])
+        job.prof_reset()
+        job.prof(True, dominant)  # only the dominant kernel is bracketed by events in the timed region
 
     job.sync()
     host.barrier()
@@ -1029,8 +1088,39 @@ def main():
     t_rank = time.perf_counter() - t0
     host.barrier()
     elapsed = host.max_over_ranks(time.perf_counter() - t0)
+    if not args.full:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(job, args.dump_outputs)
+        rank_fps = host.gather(args.steps * job.batch / t_rank)
+        rccl_version = None
+        if rccl is not None:
+            rccl_version = rccl.rccl_version
+            rccl.close()
+        if rank == 0:
+            out = line_skeleton(args, wl, world, plans)
+            out.update({"value": args.steps * sum(p["pairs_per_pass"] for p in plans) / elapsed,
+                        "ms_per_step": elapsed / args.steps * 1e3, "full": False,
+                        "burn_in_steps": burn_in_steps, "untimed_steps_before_timed_region": burn_in_steps + n_warm,
+                        "per_rank_frames_per_s": rank_fps,
+                        "rccl_ranks": world if rccl_version is not None else 0, "rccl_version": rccl_version})
+            if rccl_error:
+                out["rccl_error"] = rccl_error
+            if options:
+                out["library_options"] = options
+            print(json.dumps(out, allow_nan=False), flush=True)
+            no_rccl = missing_rccl_exit_code(world, args.rccl, out["rccl_ranks"], args.allow_no_rccl)
+            if no_rccl:
+                print(f"[bench] this run was to use RCCL on {world} rank(s) and had {out['rccl_ranks']}: the line above is "
+                      f"the fallback's (every rank made the shared inputs itself), exit code {no_rccl}; --allow-no-rccl "
+                      "accepts it", file=sys.stderr)
+                EXIT_CODE = no_rccl
+        if not STUCK_THREADS:
+            host.close()
+        return
     job.prof(False)
     dom_cnt, dom_ms = job.prof_report()[dominant]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs)
     recheck = host.gather(timed_region_recheck(job, lanes))
     # the same kernel with nothing beside it: a few steps with a synchronisation after each, so neither the other lane's
     # batch nor the previous batch's remap shares the chip with it (in the timed region they do: that is what two lanes
@@ -1113,7 +1203,7 @@ def main():
     step_built = rf.built_step_bytes(w, h, wl["levels"], P, reset_mask=wl["reset"], forward=wl["direction"] == 0)
     per_gpu_s = args.steps / elapsed
     out = line_skeleton(args, wl, world, plans)
-    out.update({"value": fps, "ms_per_step": elapsed / args.steps * 1e3, "burn_in_steps": burn_in_steps,
+    out.update({"value": fps, "ms_per_step": elapsed / args.steps * 1e3, "full": True, "burn_in_steps": burn_in_steps,
                 # `warmup` is the W that was asked for; what ran in front of the timed region is this many untimed steps
                 # (about three seconds of passes for the clocks, then the W warm-up steps, the last of them profiled)
                 "untimed_steps_before_timed_region": burn_in_steps + n_warm})

@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests (oracle side + golden fixtures)."""
 import glob
+import json
 import os
 
 import numpy as np
@@ -157,3 +158,153 @@ def cv2_fixture_grey(path):
     if zlib.crc32(bgr.tobytes()) & 0xFFFFFFFF != g["crc_bgr"]:
         return None
     return bgr, [(o["width"], o["height"], z[o["key"]]) for o in g["outputs"]]
+
+
+# ---- inputs of the differential tests against the reference (tests/test_oracle_vs_reference_live.py,
+# tests/test_host_mirror.py).  Every case is drawn here from a fixed seed; tools/capture_live_reference.py ran the
+# reference on the very same cases and stored what it returned under tests/golden/live_*.  The draws keep the order
+# in which the tests made them when they ran the reference live.
+
+LIVE_LAYER_SEEDS = {"moveref": 11, "sum": 12, "introduction": 13}
+
+
+def _live_layer_case(rng, cls):
+    h, w = int(rng.integers(1, 26)), int(rng.integers(1, 34))
+    cfg = dict(transparent_pixels_can_move=bool(rng.integers(2)), pixels_can_move_to_empty_spot=bool(rng.integers(2)),
+               pixels_can_move_to_filled_spot=bool(rng.integers(2)), moving_pixels_leave_empty_spot=bool(rng.integers(2)))
+    if cls == "introduction":
+        cfg.update({k: bool(rng.integers(2)) for k in INTRO_KEYS})
+    else:
+        cfg.update(reset_mode=str(rng.choice(["off", "random", "constant", "linear"])),
+                   reset_random_factor=float(rng.choice([0.0, 0.3, 1.0])),
+                   reset_constant_step=float(rng.choice([0.5, 1.0, 2.5])),
+                   reset_linear_factor=float(rng.choice([0.1, 0.5])), reset_source=bool(rng.integers(2)))
+    masks = dict(mask_alpha=rng.choice([0.0, 0.5, 1.0], (h, w)).astype(np.float32))
+    if cls != "sum":
+        masks.update(mask_src=rng.random((h, w)) < 0.85, mask_dst=rng.random((h, w)) < 0.85)
+    if cls != "introduction":
+        masks.update(reset_mask=rng.random((h, w)).astype(np.float32))
+    ns = int(rng.integers(1, 3))
+    intro = [rng.random((h, w)) < 0.6 for _ in range(ns)]
+    chans = [int(rng.choice([3, 4])) for _ in range(ns)]
+    return h, w, cfg, masks, intro, chans
+
+
+def live_layer_cases(cls, trials=60, nframes=4):
+    """Random layer configurations of class `cls` -- every move flag, reset mode and introduce_* flag, masks, one or two
+    sources of 3 or 4 channels, shapes down to one pixel -- with their pixmaps, background colour, raw flows and
+    uniform fields, one dict per trial."""
+    rng = np.random.default_rng(LIVE_LAYER_SEEDS[cls])
+    for trial in range(trials):
+        h, w, cfg, masks, intro, chans = _live_layer_case(rng, cls)
+        pixmaps = [[rng.integers(0, 256, (h, w, c), dtype=np.uint8) for _ in range(nframes)] for c in chans]
+        bg = "#%02x%02x%02x" % tuple(int(v) for v in rng.integers(0, 256, 3))
+        raws, us = [], []
+        for _ in range(nframes):
+            raws.append(rng.normal(0, 2.5, (h, w, 2)).astype(np.float32))
+            us.append(rng.random((h, w)))
+        yield dict(trial=trial, h=h, w=w, cfg=cfg, masks=masks, intro=intro, pixmaps=pixmaps, bg=bg, raws=raws, us=us)
+
+
+def live_flow_ops_cases(trials=40):
+    """Random inputs of flow merging, upscale, post_process with a convolution kernel (random shapes and dtypes; one raw
+    flow per direction, FORWARD first), render1d / render2d."""
+    rng = np.random.default_rng(2718)
+    for trial in range(trials):
+        h, w = int(rng.integers(1, 30)), int(rng.integers(1, 40))
+        n = int(rng.integers(1, 5))
+        flows = [rng.normal(0, 1.5, (h, w, 2)).astype(np.float32) for _ in range(n)]
+        for f in flows[1:]:
+            f[rng.random((h, w, 2)) < 0.3] = 0
+        wf, hf = int(rng.integers(1, 4)), int(rng.integers(1, 4))
+        kh, kw_ = int(rng.integers(1, 7)), int(rng.integers(1, 7))
+        kernel = rng.normal(0, 0.3, (kh, kw_))
+        kernel = [kernel, kernel.astype(np.float32), np.rint(kernel * 4).astype(np.int64)][int(rng.integers(3))]
+        raws = [rng.normal(0, 3.0, (h, w, 2)).astype(np.float32) for _ in range(2)]
+        arr = np.abs(rng.normal(0, 2, (h, w))).astype(np.float32)
+        scale, binary = float(rng.choice([0.25, 0.5, 1.0, 2.0])), bool(rng.integers(2))
+        yield dict(trial=trial, h=h, w=w, flows=flows, wf=wf, hf=hf, kernel=kernel, raws=raws, arr=arr, scale=scale,
+                   binary=binary)
+
+
+def live_mask_specs(count=1500):
+    """(spec, shape) pairs walking the mask argument grammar at random: every rule name, 0-5 arguments from pixels /
+    percentages / blanks / junk, dimensions larger than the frame, ':inv'."""
+    import random
+    rnd = random.Random(5)
+    names = ["border", "border-top", "border-right", "border-bottom", "border-left", "hline", "vline", "circle",
+             "rect", "grid", "zeros", "ones", "Border", "CIRCLE", "Rect"]
+    tokens = ["", "0", "1", "2", "3", "4", "7", "15", "200", "5%", "50%", "120%", "x"]
+    out = []
+    for _ in range(count):
+        spec = ":".join([rnd.choice(names)] + [rnd.choice(tokens) for _ in range(rnd.choice([0, 1, 1, 2, 2, 3, 4, 5]))])
+        spec += rnd.choice(["", ":inv"])
+        out.append((spec, rnd.choice([(37, 53), (60, 80), (8, 8), (5, 9), (1, 1)])))
+    return out
+
+
+def live_iteration_cases(trials=300):
+    """Random frame ranges, lengths, STAY schedules and SKIP windows of FlowSource's iteration logic: one dict per trial
+    (mode 0: no lock, 1: STAY over `pairs`, 2: SKIP while a < t < b)."""
+    rng = np.random.default_rng(31337)
+    for trial in range(trials):
+        fps = float(rng.choice([1.0, 10.0, 24.0, 29.97]))
+        start = int(rng.integers(0, 4))
+        end = start + int(rng.integers(1, 8))
+        ckpt = int(rng.integers(start, end + 1))
+        length = None if rng.random() < 0.2 else int(rng.integers(0, 25))
+        mode = int(rng.integers(3))
+        pairs, window = None, None
+        if mode == 1:
+            pairs, t0 = [], 0.0
+            for _ in range(int(rng.integers(1, 4))):
+                t0 += float(rng.uniform(0, 6 / fps))
+                d = float(rng.uniform(0, 5 / fps))
+                pairs.append((t0, d))
+                t0 += d
+            pairs = tuple(pairs)
+        elif mode == 2:
+            window = tuple(sorted(float(v) for v in rng.uniform(0, 20 / fps, 2)))
+        yield dict(trial=trial, fps=fps, start=start, end=end, ckpt=ckpt, length=length, mode=mode, pairs=pairs,
+                   window=window)
+
+
+def live_builder_cases(trials=400):
+    """Random seek / duration / repeat / checkpoint / lock arguments of FlowSource.Builder over random base lengths and
+    frame rates, streams included: (trial, builder kwargs, base_length, fps)."""
+    rng = np.random.default_rng(8086)
+    for trial in range(trials):
+        kw = dict(direction=str(rng.choice(["forward", "backward"])),
+                  seek_time=None if rng.random() < 0.4 else float(rng.choice([0.0, 0.25, 1.0, 2.5, 3.3333])),
+                  duration_time=None if rng.random() < 0.4 else float(rng.choice([0.1, 0.5, 1.0, 7.0])),
+                  repeat=int(rng.choice([0, 1, 1, 2, 5])),
+                  seek_ckpt=None if rng.random() < 0.6 else int(rng.integers(0, 200)))
+        r = rng.random()
+        if r < 0.3:
+            kw.update(lock_mode="stay", lock_expr=str(rng.choice(["0.5,0.2", "(0.2,0.4),(1,0.2)", "(0,1)"])))
+        elif r < 0.5:
+            kw.update(lock_mode="skip", lock_expr="t > 1")
+        base_length = int(rng.choice([-1, 0, 1, 7, 50, 300]))
+        fps = float(rng.choice([10.0, 25.0, 29.97, 60.0]))
+        yield trial, kw, base_length, fps
+
+
+BUILDER_FIELDS = ("start_frame", "end_frame", "length", "ckpt_start_frame", "is_stream", "repeat", "seek_time",
+                  "base_length", "lock_expr_stay")
+ARCHIVE_BUILDER_FIELDS = ("width", "height", "framerate", "base_length", "length", "start_frame", "end_frame")
+UNIQUE_PATH_NAMES = ("a.flow.zip", "clip.mp4", "x.000.flow.zip", "x.004.map.zip", "noext", "b.7.txt", "c.123", "d.tar.gz")
+
+
+def live_archive_flows():
+    rng = np.random.default_rng(3)
+    return [rng.normal(0, 2, (6, 9, 2)).astype(np.float32) for _ in range(3)]
+
+
+def as_json(value):
+    """`value` as it reads back from JSON, tuples and lists kept apart ({"tuple": [...]}, {"list": [...]}) as == keeps
+    them apart: the form the stored reference outcomes are compared in."""
+    def enc(v):
+        if isinstance(v, (tuple, list)):
+            return {type(v).__name__: [enc(x) for x in v]}
+        return v
+    return json.loads(json.dumps(enc(value)))

@@ -1,9 +1,11 @@
 """CPU-side checks of the drop-in boundary: libtfhip.so loads without a GPU and
 exports exactly the symbols include/tfhip.h declares; no compute is attempted."""
 import ctypes
+import json
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -40,10 +42,16 @@ def test_header_and_library_agree(lib):
 def test_load_makes_no_gpu_call_and_errors_are_reported(lib):
     dll = lib.load()
     assert dll.tf_abi_version() == 1
-    n = ctypes.c_int(-1)
-    rc = dll.tf_device_count(ctypes.byref(n))
+    # the device query starts the HIP runtime where there is a GPU: it runs in a child of its own, so that this process
+    # stays one whose forked children may still use the GPU (tests/test_gpu_a_forked_pipeline.py, same session)
+    code = ("import ctypes, json, sys; sys.path.insert(0, %r); from transflow_amd import _lib; dll = _lib.load(); "
+            "n = ctypes.c_int(-1); rc = dll.tf_device_count(ctypes.byref(n)); "
+            "print(json.dumps([rc, bool(dll.tf_last_error()) if rc != 0 else None]))") % ROOT
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rc, reported = json.loads(out.stdout.strip().splitlines()[-1])
     if rc != 0:  # no GPU here: the failure is reported, not swallowed
-        assert rc == lib.TF_ERR_HIP and dll.tf_last_error()
+        assert rc == lib.TF_ERR_HIP and reported
         with pytest.raises(lib.TfError):
             lib.check(rc)
 

@@ -71,7 +71,7 @@ def test_bench_runs_its_rccl_legs_with_one_rank():
     """bench.py --rccl at a small frame size: shared inputs through tf_batch_broadcast, the gather leg
     verified by CRC, the parity gate on, one JSON line out."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rccl", "--size", "640x360", "--clip-frames",
-                          "40", "--batch", "7", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline"],
+                          "40", "--batch", "7", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -96,7 +96,7 @@ def test_bench_line_carries_the_round_6_keys_at_a_small_size():
     table for the workload."""
     env = dict(os.environ, TF_BENCH_CPU_THREADS="5")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", "640x360", "--clip-frames", "17", "--batch",
-                          "8", "--steps", "3", "--warmup", "2", "--burn-in", "4", "--no-extra"],
+                          "8", "--steps", "3", "--warmup", "2", "--burn-in", "4", "--no-extra", "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -115,6 +115,38 @@ def test_bench_line_carries_the_round_6_keys_at_a_small_size():
     ws = d["roofline"]["whole_step"]
     assert ws["counter_GBs"] is None and ws["counter_frac"] is None and "no counter table" in ws["counter_source"]
     assert d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["multi_core"]["cores"] == 5
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline keys and nothing that --full measures;
+    --dump-outputs writes the last timed step's frames, flows and layer state as float arrays.  A plain run and a --full
+    run with another burn-in write the same arrays: what the timed steps compute depends on the arguments alone."""
+    common = ["--size", "640x360", "--clip-frames", "17", "--batch", "8", "--steps", "3", "--warmup", "2"]
+    runs = {}
+    for name, extra in (("plain", ["--burn-in", "0"]), ("full", ["--burn-in", "3", "--full", "--no-extra", "--no-cpu-baseline"])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + extra +
+                             ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        runs[name] = json.loads(out.stdout.strip().splitlines()[-1])
+    d = runs["plain"]
+    assert d["metric"] == "frames/sec (Farneback+remap)" and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 3 and d["full"] is False
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 8) < 1e-6 * 8          # 8 pairs per step
+    assert d["untimed_steps_before_timed_region"] == 2 and d["burn_in_steps"] == 0
+    for key in ("parity_gate", "roofline", "cpu_baseline", "kernels_ms_per_step", "timed_region_recheck"):
+        assert key not in d
+    assert runs["full"]["full"] is True and runs["full"]["parity_gate"]["ok"] and runs["full"]["roofline"]["kernel"]
+    total = 0
+    for name, shape, dtype in (("frames", (8, 640 * 360, 3), np.float32), ("flows", (8, 640 * 360, 2), np.float32),
+                               ("layer_data", (640 * 360, 4), np.float64), ("pixels", (640 * 360,), np.float64)):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.shape == shape and a.dtype == dtype, name
+        np.testing.assert_array_equal(a, b, err_msg=name)
+        total += os.path.getsize(tmp_path / "plain" / f"{name}.npy")
+    assert total <= 64 << 20
+    frames = np.load(tmp_path / "plain" / "frames.npy")
+    assert np.isfinite(np.load(tmp_path / "plain" / "flows.npy")).all() and frames.min() >= 0 and frames.max() <= 255
+    assert frames.std() > 0
 
 
 def test_flows_to_root_paints_the_clip_as_one_compositor_would():
@@ -210,7 +242,7 @@ def test_bench_with_three_ranks_sharing_the_one_gpu():
     env["TF_BENCH_SHARE_GPU"] = "1"
     env["TF_BENCH_RCCL_TIMEOUT"] = "60"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--size", "640x360", "--clip-frames",
-                          "40", "--batch", "7", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline"],
+                          "40", "--batch", "7", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
     assert lines, out.stderr[-3000:]
@@ -224,7 +256,7 @@ def test_bench_with_three_ranks_sharing_the_one_gpu():
         assert "exit code 6" in out.stderr
         again = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--size", "640x360",
                                 "--clip-frames", "40", "--batch", "7", "--steps", "2", "--warmup", "1", "--no-extra",
-                                "--no-cpu-baseline", "--no-gate", "--burn-in", "0", "--allow-no-rccl"],
+                                "--no-cpu-baseline", "--no-gate", "--burn-in", "0", "--allow-no-rccl", "--full"],
                                env=env, capture_output=True, text=True, timeout=900)
         assert again.returncode == 0, again.stderr[-2000:]
     assert d["n_gpus"] == 3 and d["config"]["pairs_per_rank"] == [13, 13, 13]
@@ -252,7 +284,7 @@ def test_a_lost_side_leg_never_loses_the_line(fault, rc, needle):
               "sys.argv = ['bench.py'] + sys.argv[1:]\n"
               "bench.run_as_main()\n") % (ROOT, fault)
     out = subprocess.run([sys.executable, "-c", driver, "--rccl", "--size", "640x360", "--clip-frames",
-                          "9", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline"],
+                          "9", "--batch", "4", "--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == rc, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -270,7 +302,7 @@ def test_bench_on_two_gpus_with_real_rccl_when_the_box_has_them():
     if n.value < 2:
         pytest.skip(f"{n.value} GPU visible: RCCL needs one device per rank")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "640x360", "--clip-frames", "41",
-                          "--batch", "20", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline"],
+                          "--batch", "20", "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])

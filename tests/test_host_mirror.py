@@ -236,39 +236,36 @@ def test_dropin_install_patches_reference_factories():
             del sys.modules[m]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/transflow"), reason="reference tree not present")
 def test_flow_archive_format_is_the_references(tmp_path):
-    """.flow.zip written here is read by the reference's ArchiveFlowSource and vice versa
-    (output/zip.py, output/numpy.py, flow/sources/archive.py)."""
-    import sys
-    if "/root/reference" not in sys.path:
-        sys.path.insert(0, "/root/reference")
-    from transflow.flow.sources.archive import ArchiveFlowSource as RefArchive
-    from transflow.output.numpy import NumpyOutput as RefNumpyOutput
-    from transflow.utils import find_unique_path as ref_unique_path
-    from transflow_amd.archive import ArchiveFlowSource, NumpyOutput, flow_export_meta, unique_path
-    rng = np.random.default_rng(3)
-    flows = [rng.normal(0, 2, (6, 9, 2)).astype(np.float32) for _ in range(3)]
-    ours, theirs = str(tmp_path / "a.flow.zip"), str(tmp_path / "b.flow.zip")
-    for cls, path in ((NumpyOutput, ours), (RefNumpyOutput, theirs)):
-        out = cls(path, True)
-        out.write_meta(flow_export_meta("clip.mp4", 9, 6, 25.0, "backward"))
-        for f in flows:
-            out.write_array(f)
-        out.close()
-    # byte-identical members
+    """.flow.zip written here is byte for byte the archive the reference writes of the same flows, and each side reads
+    the other's (output/zip.py, output/numpy.py, flow/sources/archive.py).  The reference's archive, what its
+    ArchiveFlowSource.Builder derives from those bytes and the names its find_unique_path gives were recorded by running
+    it (tools/capture_live_reference.py: tests/golden/live_archive*)."""
+    import json
     import zipfile
+
+    from tests.helpers import ARCHIVE_BUILDER_FIELDS, UNIQUE_PATH_NAMES, live_archive_flows
+    from transflow_amd.archive import ArchiveFlowSource, NumpyOutput, flow_export_meta, unique_path
+    with open(os.path.join(GOLDEN, "live_archive.json")) as f:
+        ref = json.load(f)
+    flows = live_archive_flows()
+    ours, theirs = str(tmp_path / "a.flow.zip"), os.path.join(GOLDEN, "live_archive_reference.flow.zip")
+    out = NumpyOutput(ours, True)
+    out.write_meta(flow_export_meta("clip.mp4", 9, 6, 25.0, "backward"))
+    for f in flows:
+        out.write_array(f)
+    out.close()
+    # byte-identical members
     with zipfile.ZipFile(ours) as a, zipfile.ZipFile(theirs) as b:
         assert a.namelist() == b.namelist() == ["meta.json", "000000000.npy", "000000001.npy", "000000002.npy"]
         for name in a.namelist():
             assert a.read(name) == b.read(name), name
-    # cross reading: builders agree on everything they derive
-    rb, ob = RefArchive.Builder(ours), ArchiveFlowSource.Builder(theirs)
-    rb.build()
+    # cross reading: builders agree on everything they derive (the reference's builder read these very members)
+    ob = ArchiveFlowSource.Builder(theirs)
     ob.build()
-    for attr in ("width", "height", "framerate", "base_length", "length", "start_frame", "end_frame"):
-        assert getattr(rb, attr) == getattr(ob, attr), attr
-    assert rb.direction.value == ob.direction.value == 1
+    for attr in ARCHIVE_BUILDER_FIELDS:
+        assert ref["builder"][attr] == getattr(ob, attr), attr
+    assert ref["direction"] == ob.direction.value == 1
     src = ArchiveFlowSource(*ob.args(), **ob.kwargs())
     src.validate()
     for t in range(3):
@@ -277,125 +274,102 @@ def test_flow_archive_format_is_the_references(tmp_path):
     with pytest.raises(KeyError):
         src.next()                                   # how an archive ends in the reference
     src.archive.close()
-    rb.archive.close()
     assert unique_path(ours) == str(tmp_path / "a.000.flow.zip")
     # the naming of a taken path agrees with the reference's on every shape of name
-    for name in ("a.flow.zip", "clip.mp4", "x.000.flow.zip", "x.004.map.zip", "noext", "b.7.txt", "c.123", "d.tar.gz"):
-        (tmp_path / "names").mkdir(exist_ok=True)
-        target = tmp_path / "names" / name
-        assert unique_path(str(target)) == ref_unique_path(str(target)) == str(target)      # free: unchanged
+    names = tmp_path / "names"
+    names.mkdir()
+    for name in UNIQUE_PATH_NAMES:
+        free, taken, again = (str(names / n) for n in ref["unique_path"][name])
+        target = names / name
+        assert unique_path(str(target)) == free == str(target)      # free: unchanged
         target.write_bytes(b"")
-        assert unique_path(str(target)) == ref_unique_path(str(target)), name
-        (tmp_path / "names" / os.path.basename(unique_path(str(target)))).write_bytes(b"")
-        assert unique_path(str(target)) == ref_unique_path(str(target)), name
+        assert unique_path(str(target)) == taken, name
+        (names / os.path.basename(unique_path(str(target)))).write_bytes(b"")
+        assert unique_path(str(target)) == again, name
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/transflow"), reason="needs the reference tree (build container only)")
+def _scripted(base):
+    class S(base):
+        def __init__(self, *a, **k):
+            self.calls, self.rewinds = 0, 0
+            base.__init__(self, *a, **k)
+
+        def next(self):
+            self.calls += 1
+            return np.full((2, 3, 2), float(self.calls), np.float32)
+
+        def rewind(self):
+            self.rewinds += 1
+            base.rewind(self)
+
+        def post_process(self, raw):
+            return raw
+    return S
+
+
 def test_iteration_logic_matches_the_reference_class_on_random_schedules():
     """Differential check of FlowSource.__next__ (locks, rewinds, lengths: source.py:286-332) against
     the reference's own class driven by the same scripted next(): random frame ranges, lengths, STAY
-    schedules and SKIP predicates; same values, same input-frame bookkeeping, same exceptions."""
-    import sys
-    if "/root/reference" not in sys.path:
-        sys.path.insert(0, "/root/reference")
-    from transflow.flow.sources.source import FlowSource as Ref
+    schedules and SKIP predicates; same values, same input-frame bookkeeping, same exceptions.  What the reference's
+    class did on each schedule was recorded by running it (tools/capture_live_reference.py:
+    tests/golden/live_iteration.json)."""
+    import json
 
-    def scripted(base):
-        class S(base):
-            def __init__(self, *a, **k):
-                self.calls, self.rewinds = 0, 0
-                base.__init__(self, *a, **k)
-
-            def next(self):
-                self.calls += 1
-                return np.full((2, 3, 2), float(self.calls), np.float32)
-
-            def rewind(self):
-                self.rewinds += 1
-                base.rewind(self)
-
-            def post_process(self, raw):
-                return raw
-        return S
-
-    Mine, Theirs = scripted(FlowSource), scripted(Ref)
-    rng = np.random.default_rng(31337)
-    for trial in range(300):
-        fps = float(rng.choice([1.0, 10.0, 24.0, 29.97]))
-        start = int(rng.integers(0, 4))
-        end = start + int(rng.integers(1, 8))
-        ckpt = int(rng.integers(start, end + 1))
-        length = None if rng.random() < 0.2 else int(rng.integers(0, 25))
-        mode = int(rng.integers(3))
-        kw_m, kw_t = {}, {}
-        if mode == 1:
-            pairs, t0 = [], 0.0
-            for _ in range(int(rng.integers(1, 4))):
-                t0 += float(rng.uniform(0, 6 / fps))
-                d = float(rng.uniform(0, 5 / fps))
-                pairs.append((t0, d))
-                t0 += d
-            kw_m = dict(lock_mode=FlowSource.LockMode.STAY, lock_expr_stay=tuple(pairs))
-            kw_t = dict(lock_mode=Ref.LockMode.STAY, lock_expr_stay=tuple(pairs))
-        elif mode == 2:
-            a, b = sorted(float(v) for v in rng.uniform(0, 20 / fps, 2))
-            pred = (lambda t, a=a, b=b: a < t < b)
-            kw_m = dict(lock_mode=FlowSource.LockMode.SKIP, lock_expr_skip=pred)
-            kw_t = dict(lock_mode=Ref.LockMode.SKIP, lock_expr_skip=pred)
-        m = Mine(FlowSource.Direction.BACKWARD, 3, 2, fps, length, start, ckpt, end, **kw_m)
-        r = Theirs(Ref.Direction.BACKWARD, 3, 2, fps, length, start, ckpt, end, **kw_t)
+    from tests.helpers import as_json, live_iteration_cases
+    with open(os.path.join(GOLDEN, "live_iteration.json")) as f:
+        recorded = json.load(f)
+    Mine = _scripted(FlowSource)
+    trials = 0
+    for c, theirs in zip(live_iteration_cases(), recorded):
+        kw = {}
+        if c["mode"] == 1:
+            kw = dict(lock_mode=FlowSource.LockMode.STAY, lock_expr_stay=c["pairs"])
+        elif c["mode"] == 2:
+            a, b = c["window"]
+            kw = dict(lock_mode=FlowSource.LockMode.SKIP, lock_expr_skip=lambda t, a=a, b=b: a < t < b)
+        m = Mine(FlowSource.Direction.BACKWARD, 3, 2, c["fps"], c["length"], c["start"], c["ckpt"], c["end"], **kw)
+        theirs = theirs["list"]
         for step in range(30):
-            out = []
-            for obj in (m, r):
-                try:
-                    out.append(("value", float(next(obj)[0, 0, 0])))
-                except (StopIteration, IndexError, RuntimeError) as e:
-                    out.append((type(e).__name__, None))
-            ctx = f"trial {trial} step {step}: fps={fps} range=({start},{ckpt},{end}) length={length} mode={mode}"
-            assert out[0] == out[1], ctx
-            assert (m.calls, m.rewinds, m.input_frame_index, m.output_frame_index) == \
-                   (r.calls, r.rewinds, r.input_frame_index, r.output_frame_index), ctx
-            if out[0][0] != "value":
+            try:
+                out = ["value", float(next(m)[0, 0, 0])]
+            except (StopIteration, IndexError, RuntimeError) as e:
+                out = [type(e).__name__, None]
+            ctx = (f"trial {c['trial']} step {step}: fps={c['fps']} range=({c['start']},{c['ckpt']},{c['end']}) "
+                   f"length={c['length']} mode={c['mode']}")
+            assert step < len(theirs), ctx
+            assert as_json(out + [m.calls, m.rewinds, m.input_frame_index, m.output_frame_index]) == theirs[step], ctx
+            if out[0] != "value":
                 break
+        assert step + 1 == len(theirs), ctx
+        trials += 1
+    assert trials == len(recorded) == 300
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/transflow"), reason="needs the reference tree (build container only)")
 def test_builder_arithmetic_matches_the_reference_class_on_random_arguments():
     """Differential check of FlowSource.Builder.build (source.py:125-197): random seek / duration /
-    repeat / checkpoint / lock arguments over random base lengths and frame rates, streams included."""
-    import sys
+    repeat / checkpoint / lock arguments over random base lengths and frame rates, streams included.  What the
+    reference's Builder derived (or raised) on each was recorded by running it (tools/capture_live_reference.py:
+    tests/golden/live_builder.json)."""
+    import json
     import warnings
-    if "/root/reference" not in sys.path:
-        sys.path.insert(0, "/root/reference")
-    from transflow.flow.sources.source import FlowSource as Ref
-    rng = np.random.default_rng(8086)
-    fields = ("start_frame", "end_frame", "length", "ckpt_start_frame", "is_stream", "repeat", "seek_time",
-              "base_length", "lock_expr_stay")
-    for trial in range(400):
-        kw = dict(direction=str(rng.choice(["forward", "backward"])),
-                  seek_time=None if rng.random() < 0.4 else float(rng.choice([0.0, 0.25, 1.0, 2.5, 3.3333])),
-                  duration_time=None if rng.random() < 0.4 else float(rng.choice([0.1, 0.5, 1.0, 7.0])),
-                  repeat=int(rng.choice([0, 1, 1, 2, 5])),
-                  seek_ckpt=None if rng.random() < 0.6 else int(rng.integers(0, 200)))
-        r = rng.random()
-        if r < 0.3:
-            kw.update(lock_mode="stay", lock_expr=str(rng.choice(["0.5,0.2", "(0.2,0.4),(1,0.2)", "(0,1)"])))
-        elif r < 0.5:
-            kw.update(lock_mode="skip", lock_expr="t > 1")
-        base_length = int(rng.choice([-1, 0, 1, 7, 50, 300]))
-        fps = float(rng.choice([10.0, 25.0, 29.97, 60.0]))
-        out = []
-        for cls in (FlowSource, Ref):
-            b = cls.Builder(**kw)
-            b.width, b.height, b.framerate, b.base_length = 6, 4, fps, base_length
-            try:
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore")
-                    b.build()
-                out.append(tuple(getattr(b, f) for f in fields))
-            except Exception as e:                      # e.g. a stream with a duration-less range: both must agree
-                out.append(type(e).__name__)
-        assert out[0] == out[1], f"trial {trial}: {kw} base_length={base_length} fps={fps}: {out}"
+
+    from tests.helpers import BUILDER_FIELDS, as_json, live_builder_cases
+    with open(os.path.join(GOLDEN, "live_builder.json")) as f:
+        recorded = json.load(f)
+    trials = 0
+    for (trial, kw, base_length, fps), theirs in zip(live_builder_cases(), recorded):
+        b = FlowSource.Builder(**kw)
+        b.width, b.height, b.framerate, b.base_length = 6, 4, fps, base_length
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                b.build()
+            out = as_json(tuple(getattr(b, f) for f in BUILDER_FIELDS))
+        except Exception as e:                      # e.g. a stream with a duration-less range: both must agree
+            out = type(e).__name__
+        assert out == theirs, f"trial {trial}: {kw} base_length={base_length} fps={fps}: {out} vs {theirs}"
+        trials += 1
+    assert trials == len(recorded) == 400
 
 
 @pytest.mark.skipif(not os.path.isdir("/root/reference/transflow"), reason="needs the reference tree (build container only)")

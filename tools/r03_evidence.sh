@@ -14,9 +14,9 @@ root=$(pwd)
 out=$root/gpurun_out
 mkdir -p $out
 if [ "$part" = a ]; then
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/r03_bench_4k_default.json 2> $out/r03_bench_4k_default.err
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/r03_bench_4k_default.json 2> $out/r03_bench_4k_default.err
   tail -c 300 $out/r03_bench_4k_default.err
-  (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/r03_stats -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --no-extra > $out/r03_bench_4k_under_rocprof.json 2> $out/r03_bench_under_rocprof.err)
+  (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/r03_stats -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extra > $out/r03_bench_4k_under_rocprof.json 2> $out/r03_bench_under_rocprof.err)
   cp $(find $out/r03_stats -name "*kernel_stats.csv" | head -1) $out/r03_bench_4k_kernel_stats.csv
   python3 tools/kprof.py 4k 32 > $out/r03_kprof_4k_batch32.txt 2>&1
   head -8 $out/r03_bench_4k_kernel_stats.csv

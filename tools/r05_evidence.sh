@@ -14,12 +14,12 @@ root=$(pwd)
 out=$root/gpurun_out
 mkdir -p $out
 if [ "$part" = a ]; then
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench_4k_default.json 2> $out/r05_bench_4k_default.err
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/r05_bench_4k_default.json 2> $out/r05_bench_4k_default.err
   tail -c 300 $out/r05_bench_4k_default.err
-  (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/r05_stats -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --no-extra --no-alone > $out/r05_bench_4k_one_lane_under_rocprof.json 2> $out/r05_bench_under_rocprof.err)
+  (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/r05_stats -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extra --no-alone > $out/r05_bench_4k_one_lane_under_rocprof.json 2> $out/r05_bench_under_rocprof.err)
   cp $(find $out/r05_stats -name "*kernel_stats.csv" | head -1) $out/r05_bench_4k_one_lane_kernel_stats.csv
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 --batch 32 --no-extra > $out/r05_bench_4k_batch32_two_lanes.json 2> $out/r05_bench_4k_batch32.err
-  (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/r05_stats32 -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --batch 32 --lanes 1 --no-extra --no-alone > $out/r05_bench_4k_batch32_one_lane_under_rocprof.json 2> $out/r05_bench_b32_under_rocprof.err)
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --batch 32 --no-extra > $out/r05_bench_4k_batch32_two_lanes.json 2> $out/r05_bench_4k_batch32.err
+  (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/r05_stats32 -- python3 $root/bench.py --gpus 1 --steps 20 --warmup 5 --full --batch 32 --lanes 1 --no-extra --no-alone > $out/r05_bench_4k_batch32_one_lane_under_rocprof.json 2> $out/r05_bench_b32_under_rocprof.err)
   cp $(find $out/r05_stats32 -name "*kernel_stats.csv" | head -1) $out/r05_bench_4k_batch32_one_lane_kernel_stats.csv
   python3 tools/kprof.py 4k 128 > $out/r05_kprof_4k_batch128.txt 2>&1
   python3 tools/kprof.py 4k 32 > $out/r05_kprof_4k_batch32.txt 2>&1
