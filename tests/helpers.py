@@ -308,3 +308,23 @@ def as_json(value):
             return {type(v).__name__: [enc(x) for x in v]}
         return v
     return json.loads(json.dumps(enc(value)))
+
+
+def polar_values() -> np.ndarray:
+    """float32 values x for polar-filter flows (x, 0): r = |x| exactly (the square of a float32 is exact in the
+    float32 norm's sqrt away from under- / overflow) and a = 0 or pi.  Signed zeros, the integers 0..64 and
+    their negatives, multiples of 0.1f and 0.3f, half-integers (rint's ties), squares that overflow, values
+    whose square underflows, NaN, +-inf and a random normal block."""
+    f = np.float32
+    v = [0.0, -0.0, np.nan, np.inf, -np.inf, 1e19, -1e19, 3e38, -3e38, 1e-20, 1e-39, 1e-45]
+    v += list(range(-64, 65))
+    v += [k * f(0.1) for k in range(-60, 61)] + [k * f(0.3) for k in range(-40, 41)]
+    v += [k + 0.5 for k in range(-12, 12)]
+    v += list(np.random.default_rng(21).normal(0, 3, 400)) + list(np.random.default_rng(22).normal(0, 40, 100))
+    return np.array(v, f)
+
+
+def polar_flow(x) -> np.ndarray:
+    """The flow (x, 0) as a C-contiguous float32 (1, N, 2) array."""
+    x = np.asarray(x, np.float32).ravel()
+    return np.ascontiguousarray(np.stack([x, np.zeros_like(x)], axis=-1)[None])

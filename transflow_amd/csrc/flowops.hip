@@ -367,12 +367,49 @@ struct PolarProg {
     double imm[TF_MAX_POLAR_STEPS];
 };
 
+// numpy.floor_divide / numpy.mod of floats (numpy's npy_divmod): the quotient is (a - fmod(a, b)) / b snapped to
+// an integer, not floor(a / b) -- 5f // 0.1f is 49 (fmod leaves 0.0999999, a rounded 5f / 0.1f is 50) -- and a zero
+// remainder takes the divisor's sign
+template <typename T> __device__ __forceinline__ T pfmod(T a, T b)
+{
+    return sizeof(T) == 4 ? (T)fmodf((float)a, (float)b) : (T)fmod((double)a, (double)b);
+}
+
 template <typename T> __device__ __forceinline__ T pmod(T a, T b)
-{ // numpy.mod: the result takes the divisor's sign
-    T r = sizeof(T) == 4 ? (T)fmodf((float)a, (float)b) : (T)fmod((double)a, (double)b);
-    if (r != 0 && ((r < 0) != (b < 0)))
-        r += b;
-    return r;
+{
+    if (b == 0)
+        return pfmod<T>(a, b);
+    T mod = pfmod<T>(a, b);
+    if (mod != 0) {
+        if ((b < 0) != (mod < 0))
+            mod += b;
+    } else {
+        mod = copysign((T)0, b);
+    }
+    return mod;
+}
+
+template <typename T> __device__ __forceinline__ T pfloordiv(T a, T b)
+{
+    if (b == 0)
+        return a / b;
+    const T mod = pfmod<T>(a, b);
+    T div = (a - mod) / b;
+    if (mod != 0 && ((b < 0) != (mod < 0)))
+        div -= (T)1;
+    if (div == 0)
+        return copysign((T)0, a / b);
+    T fd = sizeof(T) == 4 ? (T)floorf((float)div) : (T)floor((double)div);
+    if (div - fd > (T)0.5)
+        fd += (T)1;
+    return fd;
+}
+
+// numpy.clip of floats: x stays where it equals a bound (clip(-0.0, 0, 1) is -0.0), NaN in x or a bound propagates
+template <typename T> __device__ __forceinline__ T pclip(T x, T lo, T hi)
+{
+    T v = x != x ? x : (lo != lo ? lo : (x < lo ? lo : x));
+    return v != v ? v : (hi != hi ? hi : (v > hi ? hi : v));
 }
 
 template <typename T> __device__ __forceinline__ T pnanmin(T a, T b) { return (a != a || b != b) ? (a != a ? a : b) : (a < b ? a : b); }
@@ -415,7 +452,7 @@ template <typename T> __device__ __forceinline__ double polar_binary(int op, T a
     case P_DIV: return a / b;
     case P_POW: return f ? powf(a, b) : pow((double)a, (double)b);
     case P_MOD: return pmod<T>(a, b);
-    case P_FLOORDIV: return f ? floorf(a / b) : floor((double)a / (double)b);
+    case P_FLOORDIV: return pfloordiv<T>(a, b);
     case P_ATAN2: return f ? atan2f(a, b) : atan2((double)a, (double)b);
     case P_MIN: return pnanmin<T>(a, b);
     case P_MAX: return pnanmax<T>(a, b);
@@ -449,8 +486,7 @@ __device__ double polar_eval(const PolarProg &p, float r, float a)
             st[sp++] = wide ? v : (double)(float)v;
         } else if (op == P_CLIP) {
             const double hi = st[--sp], lo = st[--sp], x = st[--sp];
-            st[sp++] = wide ? pnanmin<double>(pnanmax<double>(x, lo), hi)
-                            : (double)pnanmin<float>(pnanmax<float>((float)x, (float)lo), (float)hi);
+            st[sp++] = wide ? pclip<double>(x, lo, hi) : (double)pclip<float>((float)x, (float)lo, (float)hi);
         } else if (op == P_NOT) {
             st[sp - 1] = st[sp - 1] == 0;
         } else if (op == P_ADD || op == P_SUB || op == P_MUL || op == P_DIV || op == P_POW || op == P_MOD ||
