@@ -321,6 +321,46 @@ int tf_fb_stage_initial_flow(tf_fb *fb, const float *flow, float *coarse_out);
 int tf_fb_level_count(tf_fb *fb, int *n_scales); /* K+1 */
 int tf_fb_level_size(tf_fb *fb, int level, int *w, int *h);
 
+/* ---- Horn-Schunck (transflow/flow/methods/horn_schunck.py) ------------------------
+ * calc_optical_flow_horn_schunck(prev, next, flow, alpha, max_iters, decay, delta), bit for bit, for up to
+ * max_pairs (<= 64) frame pairs per call.  Frame slots as tf_fb's.  A pair with an initial flow
+ * (tf_hs_set_initial_flow) runs the float32 chain from u = decay * flow; one without runs the float64 chain
+ * from zeros (the reference's flow=None).  The convergence test sigma_max(u - u_prev) < delta is decided on the
+ * device when it can be, with a relative guard of 1e-3 (cheap bounds, power iteration, a Gram certificate);
+ * otherwise the pair WAITS: the caller downloads du (tf_hs_delta_download), evaluates numpy.linalg.norm(du, 2) <
+ * delta itself, reports it (tf_hs_resolve) and calls tf_hs_resume.  tf_hs_calc_slots / tf_hs_resume return
+ * once every pair is done or waiting; tf_hs_waiting says which wait (n = 0: the flows are ready). */
+typedef struct tf_hs_params {
+    double alpha_sq;   /* alpha ** 2 as Python evaluates it; rounded to float32 in the denominator */
+    double decay;      /* rounded to float32: u = decay * flow[..., 0] */
+    int max_iters;     /* <= 0: the initial field */
+    double delta;
+    int has_delta;     /* 0: delta is None, every call runs max_iters iterations */
+} tf_hs_params;
+typedef struct tf_hs tf_hs;
+int tf_hs_create(tf_hs **out, int width, int height, int frame_slots, int max_pairs);
+void tf_hs_destroy(tf_hs *hs);
+int tf_hs_set_frame(tf_hs *hs, int slot, const uint8_t *grey, ptrdiff_t stride);
+int tf_hs_set_frame_bgr(tf_hs *hs, int slot, const uint8_t *bgr, int src_width, int src_height, ptrdiff_t stride);
+/* flow [H][W][2] float32 for the next call's `pair`, or NULL: the float64 chain.  Read by the next call only. */
+int tf_hs_set_initial_flow(tf_hs *hs, int pair, const float *flow);
+int tf_hs_calc_slots(tf_hs *hs, const tf_hs_params *params, int n_pairs, const int *prev_slots, const int *next_slots);
+int tf_hs_waiting(tf_hs *hs, int *pairs_out /* [max_pairs] */, int *n_waiting);
+/* du = u - u_prev of a waiting pair: [H][W] float64 (*is_f64 = 1) or float32 */
+int tf_hs_delta_download(tf_hs *hs, int pair, void *out, int *is_f64);
+int tf_hs_resolve(tf_hs *hs, int pair, int converged);
+int tf_hs_resume(tf_hs *hs);
+int tf_hs_get_flow(tf_hs *hs, int pair, float *flow_out /* [H][W][2] */);
+int tf_hs_flow_ptr(tf_hs *hs, int pair, void **dev);
+/* stats[5] of `pair` in the last call: iterations run, then how many convergence decisions each stage made:
+   cheap bounds, power iteration, Gram certificate, host */
+int tf_hs_stats(tf_hs *hs, int pair, int *stats);
+/* The prepare kernel alone: out [H][W][4] float32 {ex, ey, et, alpha_sq + ex^2 + ey^2} */
+int tf_hs_stage_derivatives(tf_hs *hs, const uint8_t *prev, const uint8_t *next, double alpha_sq, float *out);
+/* The device stages of the convergence test on a host field du [h][w] (float64 if is_f64, else float32):
+   *decision 1 (sigma_max < delta), 0 (not), -1 (the host must decide); *stage 0 bounds, 1 power, 2 Gram, 3 host. */
+int tf_hs_stage_norm_test(const void *field, int w, int h, int is_f64, double delta, int *decision, int *stage);
+
 /* ---- compositor layers -----------------------------------------------------------
  * One handle = one layer of the compositor.  layer_class selects which of the reference's
  * layer classes it is (Layer.from_args, transflow/compositor/layers/layer.py:44-56):

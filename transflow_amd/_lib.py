@@ -28,6 +28,11 @@ class TfFbParams(C.Structure):
                 ("flags", C.c_int)]
 
 
+class TfHsParams(C.Structure):
+    _fields_ = [("alpha_sq", C.c_double), ("decay", C.c_double), ("max_iters", C.c_int), ("delta", C.c_double),
+                ("has_delta", C.c_int)]
+
+
 class TfPolarStep(C.Structure):
     _fields_ = [("op", C.c_int), ("wide", C.c_int), ("imm", C.c_double)]
 
@@ -117,6 +122,21 @@ PROTOTYPES = {
     "tf_fb_stage_blur_solve": (_I, [_P, _P, _I, _I, _P]),
     "tf_fb_level_count": (_I, [_P, _PI]),
     "tf_fb_level_size": (_I, [_P, _I, _PI, _PI]),
+    "tf_hs_create": (_I, [_PP, _I, _I, _I, _I]),
+    "tf_hs_destroy": (None, [_P]),
+    "tf_hs_set_frame": (_I, [_P, _I, _P, C.c_ssize_t]),
+    "tf_hs_set_frame_bgr": (_I, [_P, _I, _P, _I, _I, C.c_ssize_t]),
+    "tf_hs_set_initial_flow": (_I, [_P, _I, _P]),
+    "tf_hs_calc_slots": (_I, [_P, C.POINTER(TfHsParams), _I, _PI, _PI]),
+    "tf_hs_waiting": (_I, [_P, _PI, _PI]),
+    "tf_hs_delta_download": (_I, [_P, _I, _P, _PI]),
+    "tf_hs_resolve": (_I, [_P, _I, _I]),
+    "tf_hs_resume": (_I, [_P]),
+    "tf_hs_get_flow": (_I, [_P, _I, _P]),
+    "tf_hs_flow_ptr": (_I, [_P, _I, _PP]),
+    "tf_hs_stats": (_I, [_P, _I, _PI]),
+    "tf_hs_stage_derivatives": (_I, [_P, _P, _P, C.c_double, _P]),
+    "tf_hs_stage_norm_test": (_I, [_P, _I, _I, _I, C.c_double, _PI, _PI]),
     "tf_remap_create": (_I, [_PP, _I, _I, C.POINTER(TfLayerCfg), _P, _P, _P, _P]),
     "tf_remap_destroy": (None, [_P]),
     "tf_remap_set_sources": (_I, [_P, _I, C.POINTER(C.c_void_p)]),

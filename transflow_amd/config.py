@@ -4,6 +4,7 @@ backend unchanged.
 
   LayerConfig   <- transflow/config.py:57-104   (fields the compositor reads)
   FlowConfig    <- CvFlowConfig, transflow/flow/sources/cv.py:271-363 (the fb_* fields)
+  HornSchunckConfig <- the same, method "horn-schunck" (the hs_* fields)
 """
 from __future__ import annotations
 
@@ -148,3 +149,95 @@ class FlowConfig:
         if isinstance(cfg, cls):
             return cfg
         return cls(**{k: getattr(cfg, k) for k in cls.FB_DEFAULTS if hasattr(cfg, k)})
+
+
+class HornSchunckConfig:
+    """The Horn-Schunck fields of CvFlowConfig (cv.py:282-285) and their defaults; `hs_delta` may be None (JSON null:
+    every call runs hs_iterations iterations).  fb_*, lk_* and other keys are carried in `.extra`."""
+
+    HS_DEFAULTS = dict(hs_alpha=1, hs_iterations=3, hs_decay=0, hs_delta=1)
+    # this backend's keys that Horn-Schunck has no use for (they shape the Farnebäck path)
+    _FB_ONLY_HIP = ("hip_exact_sums", "hip_batch", "hip_device_flows")
+
+    def __init__(self, method: str = "horn-schunck", **kwargs):
+        if method != "horn-schunck":
+            raise ValueError(f"HornSchunckConfig is the 'horn-schunck' method, got {method!r}")
+        self.method = method
+        for k, v in self.HS_DEFAULTS.items():
+            setattr(self, k, kwargs.pop(k, v))
+        for k in list(kwargs):
+            if k.startswith("hip_") and k != "hip_prefetch":
+                raise ValueError(f"{k!r} is not available with the horn-schunck method (only 'hip_prefetch' is)")
+        # "hip_prefetch": as FlowConfig's
+        self.hip_prefetch = int(kwargs.pop("hip_prefetch", 0) or 0)
+        self.extra = dict(kwargs)
+
+    def hs_kwargs(self) -> dict:
+        """The keyword arguments of calc_optical_flow_horn_schunck (cv.py:495-498)."""
+        return dict(alpha=self.hs_alpha, max_iters=self.hs_iterations, decay=self.hs_decay, delta=self.hs_delta)
+
+    def to_dict(self) -> dict:
+        d = {"method": self.method}
+        d.update({k: getattr(self, k) for k in self.HS_DEFAULTS})
+        d.update(self.extra)
+        if self.hip_prefetch:
+            d["hip_prefetch"] = self.hip_prefetch
+        return d
+
+    def to_file(self, path: str):
+        with open(path, "w", encoding="utf8") as f:
+            json.dump(self.to_dict(), f, indent=4)
+
+    @classmethod
+    def from_file(cls, path: str):
+        with open(path, "r", encoding="utf8") as f:
+            return cls(**json.load(f))
+
+    @classmethod
+    def from_reference(cls, cfg):
+        if isinstance(cfg, cls):
+            return cfg
+        return cls(**{k: getattr(cfg, k) for k in cls.HS_DEFAULTS if hasattr(cfg, k)})
+
+
+_UNSERVED_METHODS = ("lukas-kanade", "liteflownet")   # CvFlowSource.Method names this backend does not compute
+
+
+def _method_name(method) -> str:
+    """A method given as the reference's enum (CvFlowSource.Method) or as its string."""
+    if method is None:
+        return "farneback"
+    if isinstance(method, str):
+        return method.lower().strip()
+    name = getattr(method, "name", str(method)).lower()
+    return name.replace("_", "-")
+
+
+def flow_config_from_dict(d: dict):
+    method = _method_name(d.get("method", "farneback"))
+    if method in _UNSERVED_METHODS:
+        raise ValueError(f"transflow_amd does not implement the {method!r} flow method")
+    if method == "horn-schunck":
+        return HornSchunckConfig(**{**d, "method": method})
+    return FlowConfig(**d)
+
+
+def flow_config_from_file(path: str):
+    """A CvFlowConfig JSON file -> FlowConfig (farneback) or HornSchunckConfig; ValueError for the methods this backend
+    does not compute (lukas-kanade, liteflownet) and for unknown ones."""
+    with open(path, "r", encoding="utf8") as f:
+        return flow_config_from_dict(json.load(f))
+
+
+def flow_config_from_reference(cfg):
+    """A reference CvFlowConfig object (or one of ours, or None) -> FlowConfig or HornSchunckConfig, by its method."""
+    if cfg is None:
+        return FlowConfig()
+    if isinstance(cfg, (FlowConfig, HornSchunckConfig)):
+        return cfg
+    method = _method_name(getattr(cfg, "method", None))
+    if method in _UNSERVED_METHODS:
+        raise ValueError(f"transflow_amd does not implement the {method!r} flow method")
+    if method == "horn-schunck":
+        return HornSchunckConfig.from_reference(cfg)
+    return FlowConfig.from_reference(cfg)

@@ -19,7 +19,7 @@ import os
 import warnings
 import numpy as np
 
-from .config import FlowConfig
+from .config import FlowConfig, HornSchunckConfig, flow_config_from_file, flow_config_from_reference
 
 logger = logging.getLogger(__name__)
 
@@ -540,14 +540,16 @@ class _Prefetch:
 
 
 class HipFlowSource(FlowSource):
-    """CvFlowSource's Farnebäck branch on the GPU (cv.py:434-521)."""
+    """CvFlowSource's Farnebäck and Horn-Schunck branches on the GPU (cv.py:434-521).  The config says which: a
+    FlowConfig (Farnebäck) or a HornSchunckConfig.  Horn-Schunck flows always come down to the host, where the
+    post-process runs (each call starts from the previous, post-processed, flow: cv.py:494)."""
 
     class Builder(FlowSource.Builder):
 
         def __init__(self, provider, config=None, size=None, device: int | None = None, **kwargs):
             super().__init__(**kwargs)
             self.provider_arg, self.size, self.device = provider, size, device
-            self.config = FlowConfig.from_reference(config)
+            self.config = flow_config_from_reference(config)
             self.provider = None
 
         @property
@@ -590,10 +592,17 @@ class HipFlowSource(FlowSource):
 
     def validate(self):
         super().validate()
-        if not isinstance(self.config, FlowConfig):
+        if not isinstance(self.config, (FlowConfig, HornSchunckConfig)):
             raise ValueError("Attribute config has incorrect type")
 
+    @property
+    def _is_hs(self) -> bool:
+        return isinstance(self.config, HornSchunckConfig)
+
     def _handle(self):
+        if self._fb is None and self._is_hs:
+            from .hornschunck import HornSchunck
+            self._fb = HornSchunck(self.width, self.height, device=self.device)   # (post_process keeps its own handle)
         if self._fb is None:
             from .farneback import Farneback
             # Exactness belongs to the handle (tf_fb_set_exact): this source states what its configuration says, on OR off,
@@ -677,13 +686,17 @@ class HipFlowSource(FlowSource):
             older.append(slot)
             newer.append(new_slot)
             slot = new_slot
-        if self._uses_initial_flow():                # cv.py:478: a copy of the previous flow, zeros before the first
+        kw = {}
+        if self._is_hs:                              # cv.py:491-500: the previous flow, or None (the float64 chain)
+            fb.set_initial_flow(0, self.prev_flow)
+            kw = self.config.hs_kwargs()
+        elif self._uses_initial_flow():              # cv.py:478: a copy of the previous flow, zeros before the first
             init = self.prev_flow if self.prev_flow is not None else np.zeros((self.height, self.width, 2), np.float32)
             fb.set_initial_flow(0, init)
         if self.direction == FlowSource.Direction.FORWARD:      # cv.py:467-472
-            fb.calc_slots(older, newer)
+            fb.calc_slots(older, newer, **kw)
         elif self.direction == FlowSource.Direction.BACKWARD:
-            fb.calc_slots(newer, older)
+            fb.calc_slots(newer, older, **kw)
         else:
             raise ValueError(f"Invalid flow direction '{self.direction}'")
         self._prev_slot, self._prev_frame = slot, frames[-1]
@@ -697,9 +710,11 @@ class HipFlowSource(FlowSource):
     # down -- one transfer each instead of two frames up and the flow down, up and down again.  The
     # public next() / post_process() pair keeps working on host arrays for any other caller.
     def _uses_initial_flow(self) -> bool:
-        return bool(self.config.fb_flags & 4)      # cv2.OPTFLOW_USE_INITIAL_FLOW
+        return not self._is_hs and bool(self.config.fb_flags & 4)      # cv2.OPTFLOW_USE_INITIAL_FLOW
 
     def _resident_ok(self) -> bool:
+        if self._is_hs:
+            return False     # (a device-resident post-process of Horn-Schunck flows is not built)
         # with OPTFLOW_USE_INITIAL_FLOW every call starts from the previous OUTPUT (cv.py:478 passes a copy of
         # prev_flow, which __next__ has post-processed in place): that array lives on the host
         return (self.lock_expr_stay is None and self.lock_expr_skip is None and self.kernel is None
@@ -789,7 +804,7 @@ class HipFlowSource(FlowSource):
         if self._prefetch is not None:
             self._prefetch.stop()
             self._prefetch = None
-            if self._fb is not None:
+            if self._fb is not None and not self._is_hs:
                 self._fb.async_io(False)    # waits for a download the worker left on its way
         if self._mask_dev is not None:
             self._mask_dev.close()
@@ -804,6 +819,8 @@ class HipFlowSource(FlowSource):
             self._flow_ring.drain()
         self._flow_ring = None      # (buffers live as long as a DeviceFlow the caller still holds)
         if self._fb is not None:
+            if self._pp is not None and self._pp is not self._fb:
+                self._pp.close()
             self._fb.close()
             self._fb = None
             self._pp = None
@@ -827,9 +844,9 @@ class HipFlowSource(FlowSource):
         if use_mvs:
             raise NotImplementedError("transflow_amd does not read codec motion vectors")
         if isinstance(cv_config, str):
-            config = FlowConfig.from_file(cv_config) if os.path.isfile(cv_config) else FlowConfig()
+            config = flow_config_from_file(cv_config) if os.path.isfile(cv_config) else FlowConfig()
         else:
-            config = FlowConfig.from_reference(cv_config)
+            config = flow_config_from_reference(cv_config)
         if isinstance(flow_path, str) and "::" in flow_path:
             flow_path = flow_path.split("::")[1]
         return cls.Builder(flow_path, config, size, direction=direction, mask_path=mask_path,
