@@ -361,6 +361,34 @@ int tf_hs_stage_derivatives(tf_hs *hs, const uint8_t *prev, const uint8_t *next,
    *decision 1 (sigma_max < delta), 0 (not), -1 (the host must decide); *stage 0 bounds, 1 power, 2 Gram, 3 host. */
 int tf_hs_stage_norm_test(const void *field, int w, int h, int is_f64, double delta, int *decision, int *stage);
 
+/* ---- Lucas-Kanade (transflow/flow/methods/lukas_kanade.py) ---------------------------
+ * calc_optical_flow_lukas_kanade(prev, next, win_size, max_level, step): cv2.calcOpticalFlowPyrLK over the grid
+ * arange(0, W, step) x arange(0, H, step) with the default criteria and flags, flow = nextPts - p0 whatever the
+ * status, block-replicated to step x step and cropped to H x W: a float32 [H][W][2] per pair, for up to max_pairs
+ * (<= 64) pairs per call.  Bit for bit with the numpy restatement tests/lk_ref.py.  Frame slots as tf_fb's: a slot
+ * keeps its pyramid (and, as a prev frame, its derivatives) until set_frame or a call with another win_size /
+ * level count.  collect_stats: count the steps run per point and level (tf_lk_stats). */
+#define TF_LK_MAX_LEVELS 20
+typedef struct tf_lk tf_lk;
+int tf_lk_create(tf_lk **out, int width, int height, int frame_slots, int max_pairs);
+void tf_lk_destroy(tf_lk *lk);
+int tf_lk_set_frame(tf_lk *lk, int slot, const uint8_t *grey, ptrdiff_t stride);
+int tf_lk_set_frame_bgr(tf_lk *lk, int slot, const uint8_t *bgr, int src_width, int src_height, ptrdiff_t stride);
+int tf_lk_calc_slots(tf_lk *lk, int win_size, int max_level, int step, int n_pairs, const int *prev_slots,
+                     const int *next_slots, int collect_stats);
+int tf_lk_get_flow(tf_lk *lk, int pair, float *flow_out /* [H][W][2] */);
+int tf_lk_flow_ptr(tf_lk *lk, int pair, void **dev);
+/* Of the last call (zeros unless it collected them): *n_levels, and sum_max[TF_LK_MAX_LEVELS][2] = {sum, max} over
+   the points of the steps run at each level */
+int tf_lk_stats(tf_lk *lk, int pair, int *n_levels, unsigned long long *sum_max);
+/* Stage entry points.  A pyramid level of a slot, padded by win_size with reflect-101: uint8 [h+2w][w+2w]; the Scharr
+   derivatives of one, zero-padded: int16 [h+2w][w+2w][2] {dx, dy}; one point's trace: out[level][4] = {nextPts.x,
+   nextPts.y, steps run, code (0 done, 1 lost at the prev bounds, 2 at the eigenvalue test, 3 at the next bounds)}
+   after each level, for levels 0 .. the pyramid's count. */
+int tf_lk_stage_pyramid(tf_lk *lk, int slot, int win_size, int max_level, int level, uint8_t *out);
+int tf_lk_stage_scharr(tf_lk *lk, int slot, int win_size, int max_level, int level, int16_t *out);
+int tf_lk_stage_trace(tf_lk *lk, int prev_slot, int next_slot, int win_size, int max_level, float x, float y, float *out);
+
 /* ---- compositor layers -----------------------------------------------------------
  * One handle = one layer of the compositor.  layer_class selects which of the reference's
  * layer classes it is (Layer.from_args, transflow/compositor/layers/layer.py:44-56):

@@ -137,6 +137,17 @@ PROTOTYPES = {
     "tf_hs_stats": (_I, [_P, _I, _PI]),
     "tf_hs_stage_derivatives": (_I, [_P, _P, _P, C.c_double, _P]),
     "tf_hs_stage_norm_test": (_I, [_P, _I, _I, _I, C.c_double, _PI, _PI]),
+    "tf_lk_create": (_I, [_PP, _I, _I, _I, _I]),
+    "tf_lk_destroy": (None, [_P]),
+    "tf_lk_set_frame": (_I, [_P, _I, _P, C.c_ssize_t]),
+    "tf_lk_set_frame_bgr": (_I, [_P, _I, _P, _I, _I, C.c_ssize_t]),
+    "tf_lk_calc_slots": (_I, [_P, _I, _I, _I, _I, _PI, _PI, _I]),
+    "tf_lk_get_flow": (_I, [_P, _I, _P]),
+    "tf_lk_flow_ptr": (_I, [_P, _I, _PP]),
+    "tf_lk_stats": (_I, [_P, _I, _PI, C.POINTER(C.c_ulonglong)]),
+    "tf_lk_stage_pyramid": (_I, [_P, _I, _I, _I, _I, _P]),
+    "tf_lk_stage_scharr": (_I, [_P, _I, _I, _I, _I, _P]),
+    "tf_lk_stage_trace": (_I, [_P, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
     "tf_remap_create": (_I, [_PP, _I, _I, C.POINTER(TfLayerCfg), _P, _P, _P, _P]),
     "tf_remap_destroy": (None, [_P]),
     "tf_remap_set_sources": (_I, [_P, _I, C.POINTER(C.c_void_p)]),

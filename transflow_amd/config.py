@@ -5,6 +5,7 @@ backend unchanged.
   LayerConfig   <- transflow/config.py:57-104   (fields the compositor reads)
   FlowConfig    <- CvFlowConfig, transflow/flow/sources/cv.py:271-363 (the fb_* fields)
   HornSchunckConfig <- the same, method "horn-schunck" (the hs_* fields)
+  LucasKanadeConfig <- the same, method "lukas-kanade" (the lk_* fields; opt-in: lucas_kanade=True)
 """
 from __future__ import annotations
 
@@ -200,7 +201,53 @@ class HornSchunckConfig:
         return cls(**{k: getattr(cfg, k) for k in cls.HS_DEFAULTS if hasattr(cfg, k)})
 
 
-_UNSERVED_METHODS = ("lukas-kanade", "liteflownet")   # CvFlowSource.Method names this backend does not compute
+class LucasKanadeConfig:
+    """The Lucas-Kanade fields of CvFlowConfig and their defaults (lk_window_size 15, lk_max_level 2, lk_step 1).
+    fb_*, hs_* and other keys are carried in `.extra`."""
+
+    LK_DEFAULTS = dict(lk_window_size=15, lk_max_level=2, lk_step=1)
+
+    def __init__(self, method: str = "lukas-kanade", **kwargs):
+        if method != "lukas-kanade":
+            raise ValueError(f"LucasKanadeConfig is the 'lukas-kanade' method, got {method!r}")
+        self.method = method
+        for k, v in self.LK_DEFAULTS.items():
+            setattr(self, k, kwargs.pop(k, v))
+        for k in list(kwargs):
+            if k.startswith("hip_") and k != "hip_prefetch":
+                raise ValueError(f"{k!r} is not available with the lukas-kanade method (only 'hip_prefetch' is)")
+        self.hip_prefetch = int(kwargs.pop("hip_prefetch", 0) or 0)
+        self.extra = dict(kwargs)
+
+    def lk_kwargs(self) -> dict:
+        """The keyword arguments of calc_optical_flow_lukas_kanade (cv.py:501-508)."""
+        return dict(win_size=self.lk_window_size, max_level=self.lk_max_level, step=self.lk_step)
+
+    def to_dict(self) -> dict:
+        d = {"method": self.method}
+        d.update({k: getattr(self, k) for k in self.LK_DEFAULTS})
+        d.update(self.extra)
+        if self.hip_prefetch:
+            d["hip_prefetch"] = self.hip_prefetch
+        return d
+
+    def to_file(self, path: str):
+        with open(path, "w", encoding="utf8") as f:
+            json.dump(self.to_dict(), f, indent=4)
+
+    @classmethod
+    def from_file(cls, path: str):
+        with open(path, "r", encoding="utf8") as f:
+            return cls(**json.load(f))
+
+    @classmethod
+    def from_reference(cls, cfg):
+        if isinstance(cfg, cls):
+            return cfg
+        return cls(**{k: getattr(cfg, k) for k in cls.LK_DEFAULTS if hasattr(cfg, k)})
+
+
+_UNSERVED_METHODS = ("lukas-kanade", "liteflownet")   # CvFlowSource.Method names this backend does not compute by default
 
 
 def _method_name(method) -> str:
@@ -213,31 +260,43 @@ def _method_name(method) -> str:
     return name.replace("_", "-")
 
 
-def flow_config_from_dict(d: dict):
-    method = _method_name(d.get("method", "farneback"))
+def _refuse(method: str, lucas_kanade: bool) -> None:
+    if method == "lukas-kanade" and lucas_kanade:
+        return
     if method in _UNSERVED_METHODS:
-        raise ValueError(f"transflow_amd does not implement the {method!r} flow method")
+        hint = " (lucas_kanade=True serves it)" if method == "lukas-kanade" else ""
+        raise ValueError(f"transflow_amd does not implement the {method!r} flow method{hint}")
+
+
+def flow_config_from_dict(d: dict, lucas_kanade: bool = False):
+    method = _method_name(d.get("method", "farneback"))
+    _refuse(method, lucas_kanade)
+    if method == "lukas-kanade":
+        return LucasKanadeConfig(**{**d, "method": method})
     if method == "horn-schunck":
         return HornSchunckConfig(**{**d, "method": method})
     return FlowConfig(**d)
 
 
-def flow_config_from_file(path: str):
-    """A CvFlowConfig JSON file -> FlowConfig (farneback) or HornSchunckConfig; ValueError for the methods this backend
-    does not compute (lukas-kanade, liteflownet) and for unknown ones."""
+def flow_config_from_file(path: str, lucas_kanade: bool = False):
+    """A CvFlowConfig JSON file -> FlowConfig (farneback), HornSchunckConfig, or LucasKanadeConfig when lucas_kanade
+    is true; ValueError for the methods this backend does not compute (liteflownet, and lukas-kanade by default) and
+    for unknown ones."""
     with open(path, "r", encoding="utf8") as f:
-        return flow_config_from_dict(json.load(f))
+        return flow_config_from_dict(json.load(f), lucas_kanade=lucas_kanade)
 
 
-def flow_config_from_reference(cfg):
-    """A reference CvFlowConfig object (or one of ours, or None) -> FlowConfig or HornSchunckConfig, by its method."""
+def flow_config_from_reference(cfg, lucas_kanade: bool = False):
+    """A reference CvFlowConfig object (or one of ours, or None) -> FlowConfig, HornSchunckConfig or (lucas_kanade)
+    LucasKanadeConfig, by its method."""
     if cfg is None:
         return FlowConfig()
-    if isinstance(cfg, (FlowConfig, HornSchunckConfig)):
+    if isinstance(cfg, (FlowConfig, HornSchunckConfig, LucasKanadeConfig)):
         return cfg
     method = _method_name(getattr(cfg, "method", None))
-    if method in _UNSERVED_METHODS:
-        raise ValueError(f"transflow_amd does not implement the {method!r} flow method")
+    _refuse(method, lucas_kanade)
+    if method == "lukas-kanade":
+        return LucasKanadeConfig.from_reference(cfg)
     if method == "horn-schunck":
         return HornSchunckConfig.from_reference(cfg)
     return FlowConfig.from_reference(cfg)

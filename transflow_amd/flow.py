@@ -19,7 +19,7 @@ import os
 import warnings
 import numpy as np
 
-from .config import FlowConfig, HornSchunckConfig, flow_config_from_file, flow_config_from_reference
+from .config import FlowConfig, HornSchunckConfig, LucasKanadeConfig, flow_config_from_file, flow_config_from_reference
 
 logger = logging.getLogger(__name__)
 
@@ -540,9 +540,10 @@ class _Prefetch:
 
 
 class HipFlowSource(FlowSource):
-    """CvFlowSource's Farnebäck and Horn-Schunck branches on the GPU (cv.py:434-521).  The config says which: a
-    FlowConfig (Farnebäck) or a HornSchunckConfig.  Horn-Schunck flows always come down to the host, where the
-    post-process runs (each call starts from the previous, post-processed, flow: cv.py:494)."""
+    """CvFlowSource's Farnebäck, Horn-Schunck and Lucas-Kanade branches on the GPU (cv.py:434-521).  The config says
+    which: a FlowConfig (Farnebäck), a HornSchunckConfig or a LucasKanadeConfig.  Horn-Schunck and Lucas-Kanade flows
+    always come down to the host, where the post-process runs (each Horn-Schunck call starts from the previous,
+    post-processed, flow: cv.py:494; Lucas-Kanade takes no initial flow: cv.py:501-508)."""
 
     class Builder(FlowSource.Builder):
 
@@ -592,14 +593,21 @@ class HipFlowSource(FlowSource):
 
     def validate(self):
         super().validate()
-        if not isinstance(self.config, (FlowConfig, HornSchunckConfig)):
+        if not isinstance(self.config, (FlowConfig, HornSchunckConfig, LucasKanadeConfig)):
             raise ValueError("Attribute config has incorrect type")
 
     @property
     def _is_hs(self) -> bool:
         return isinstance(self.config, HornSchunckConfig)
 
+    @property
+    def _is_lk(self) -> bool:
+        return isinstance(self.config, LucasKanadeConfig)
+
     def _handle(self):
+        if self._fb is None and self._is_lk:
+            from .lucaskanade import LucasKanade
+            self._fb = LucasKanade(self.width, self.height, device=self.device)   # (post_process keeps its own handle)
         if self._fb is None and self._is_hs:
             from .hornschunck import HornSchunck
             self._fb = HornSchunck(self.width, self.height, device=self.device)   # (post_process keeps its own handle)
@@ -690,6 +698,8 @@ class HipFlowSource(FlowSource):
         if self._is_hs:                              # cv.py:491-500: the previous flow, or None (the float64 chain)
             fb.set_initial_flow(0, self.prev_flow)
             kw = self.config.hs_kwargs()
+        elif self._is_lk:                            # cv.py:501-508: no initial flow
+            kw = self.config.lk_kwargs()
         elif self._uses_initial_flow():              # cv.py:478: a copy of the previous flow, zeros before the first
             init = self.prev_flow if self.prev_flow is not None else np.zeros((self.height, self.width, 2), np.float32)
             fb.set_initial_flow(0, init)
@@ -710,11 +720,11 @@ class HipFlowSource(FlowSource):
     # down -- one transfer each instead of two frames up and the flow down, up and down again.  The
     # public next() / post_process() pair keeps working on host arrays for any other caller.
     def _uses_initial_flow(self) -> bool:
-        return not self._is_hs and bool(self.config.fb_flags & 4)      # cv2.OPTFLOW_USE_INITIAL_FLOW
+        return not self._is_hs and not self._is_lk and bool(self.config.fb_flags & 4)      # cv2.OPTFLOW_USE_INITIAL_FLOW
 
     def _resident_ok(self) -> bool:
-        if self._is_hs:
-            return False     # (a device-resident post-process of Horn-Schunck flows is not built)
+        if self._is_hs or self._is_lk:
+            return False     # (a device-resident post-process of Horn-Schunck or Lucas-Kanade flows is not built)
         # with OPTFLOW_USE_INITIAL_FLOW every call starts from the previous OUTPUT (cv.py:478 passes a copy of
         # prev_flow, which __next__ has post-processed in place): that array lives on the host
         return (self.lock_expr_stay is None and self.lock_expr_skip is None and self.kernel is None
@@ -804,7 +814,7 @@ class HipFlowSource(FlowSource):
         if self._prefetch is not None:
             self._prefetch.stop()
             self._prefetch = None
-            if self._fb is not None and not self._is_hs:
+            if self._fb is not None and not self._is_hs and not self._is_lk:
                 self._fb.async_io(False)    # waits for a download the worker left on its way
         if self._mask_dev is not None:
             self._mask_dev.close()
@@ -831,9 +841,9 @@ class HipFlowSource(FlowSource):
     @classmethod
     def from_args(cls, flow_path, use_mvs: bool = False, mask_path=None, kernel_path=None, cv_config=None,
                   flow_filters=None, size=None, direction=None, seek_ckpt=None, seek_time=None,
-                  duration_time=None, repeat: int = 1, lock_expr=None, lock_mode="stay"):
+                  duration_time=None, repeat: int = 1, lock_expr=None, lock_mode="stay", lucas_kanade: bool = False):
         """Same signature as FlowSource.from_args (source.py:365-411); `flow_path` may also be
-        a frame provider object.  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399);
+        a frame provider object.  lucas_kanade: a config naming "lukas-kanade" is served (else it raises ValueError).  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399);
         motion-vector sources are not this backend's."""
         if isinstance(flow_path, str) and flow_path.split("::")[-1].endswith(".flow.zip"):
             from .archive import ArchiveFlowSource
@@ -844,9 +854,10 @@ class HipFlowSource(FlowSource):
         if use_mvs:
             raise NotImplementedError("transflow_amd does not read codec motion vectors")
         if isinstance(cv_config, str):
-            config = flow_config_from_file(cv_config) if os.path.isfile(cv_config) else FlowConfig()
+            config = (flow_config_from_file(cv_config, lucas_kanade=lucas_kanade) if os.path.isfile(cv_config)
+                      else FlowConfig())
         else:
-            config = flow_config_from_reference(cv_config)
+            config = flow_config_from_reference(cv_config, lucas_kanade=lucas_kanade)
         if isinstance(flow_path, str) and "::" in flow_path:
             flow_path = flow_path.split("::")[1]
         return cls.Builder(flow_path, config, size, direction=direction, mask_path=mask_path,
