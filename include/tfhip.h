@@ -389,6 +389,42 @@ int tf_lk_stage_pyramid(tf_lk *lk, int slot, int win_size, int max_level, int le
 int tf_lk_stage_scharr(tf_lk *lk, int slot, int win_size, int max_level, int level, int16_t *out);
 int tf_lk_stage_trace(tf_lk *lk, int prev_slot, int next_slot, int win_size, int max_level, float x, float y, float *out);
 
+/* ---- LiteFlowNet (transflow/flow/methods/liteflownet.py) ------------------------------
+ * calc_optical_flow_liteflownet(prev, next) of cv.py:509-516: the network on the pair's BGR frames (x 1/255, bilinear
+ * to Hp x Wp = W, H rounded up to multiples of 32, the per-role mean subtracted), the flow x 20 resized back to W x H
+ * and scaled by W / Wp, H / Hp: a float32 [H][W][2] per pair, for up to max_pairs (<= TF_LFN_MAX_PAIRS) pairs per
+ * call, all batched.  Float32 throughout; the convolutions sum in their own order, the correlation in the reference's
+ * (tests/lfn_ref.py).  The weights are the caller's: tf_lfn_set_weights takes every layer's weight and bias as one
+ * float32 blob in the order of transflow_amd/liteflownet.py param_spec() and repacks them on the device.  W and H
+ * must exceed 32 (at 32 or less the reference divides by zero in its backwarp).  A frame slot holds the frame
+ * (uint8 BGR, W x H); nothing computed from it is kept between calls (a frame's features depend on its role). */
+#define TF_LFN_MAX_PAIRS 16
+typedef struct tf_lfn tf_lfn;
+int tf_lfn_create(tf_lfn **out, int width, int height, int frame_slots, int max_pairs);
+void tf_lfn_destroy(tf_lfn *lfn);
+int tf_lfn_set_weights(tf_lfn *lfn, const float *blob, long long n_floats);
+int tf_lfn_set_frame_bgr(tf_lfn *lfn, int slot, const uint8_t *bgr, int src_width, int src_height, ptrdiff_t stride);
+int tf_lfn_calc_slots(tf_lfn *lfn, int n_pairs, const int *prev_slots, const int *next_slots);
+int tf_lfn_get_flow(tf_lfn *lfn, int pair, float *flow_out /* [H][W][2] */);
+int tf_lfn_flow_ptr(tf_lfn *lfn, int pair, void **dev);
+/* Stage entry points, host arrays in and out, activations NHWC float32.  conv: layer `layer` of param_spec's layer
+   list on n images h x w, its Cin input channels at in_off of in_cs, written at out_off of out_cs (the other channels
+   of out are kept), plus the residual at res_off of res_cs when res is not null; bias and LeakyReLU as the layer has
+   them.  deconv: a depthwise 4x4 stride-2 transposed conv [n][h][w][C] -> [n][2h][2w][C].  correlation:
+   LeakyReLU(correlation) [n][ceil(h/s)][ceil(w/s)][49].  backwarp: in [n][h][w][c] at flow [n][h][w][2] x scale.
+   regularize_tail: the level's -d^2 / softmax / netScaleX, Y / divisor on dist [n][h][w][k^2] and flow [n][h][w][2].
+   prep: a slot's frame in role 0 (one) or 1 (two), [Hp][Wp][3]. */
+int tf_lfn_stage_conv(tf_lfn *lfn, int layer, int n, int h, int w, const float *in, int in_cs, int in_off,
+                      const float *res, int res_cs, int res_off, float *out, int out_cs, int out_off);
+int tf_lfn_stage_deconv(tf_lfn *lfn, int layer, int n, int h, int w, const float *in, float *out);
+int tf_lfn_stage_correlation(tf_lfn *lfn, int stride, int n, int h, int w, int c, const float *one, const float *two,
+                             float *out);
+int tf_lfn_stage_backwarp(tf_lfn *lfn, int n, int h, int w, int c, const float *in, const float *flow, float scale,
+                          float *out);
+int tf_lfn_stage_regularize_tail(tf_lfn *lfn, int level, int n, int h, int w, const float *dist, const float *flow,
+                                 float *out);
+int tf_lfn_stage_prep(tf_lfn *lfn, int slot, int role, float *out);
+
 /* ---- compositor layers -----------------------------------------------------------
  * One handle = one layer of the compositor.  layer_class selects which of the reference's
  * layer classes it is (Layer.from_args, transflow/compositor/layers/layer.py:44-56):

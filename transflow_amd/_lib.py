@@ -148,6 +148,19 @@ PROTOTYPES = {
     "tf_lk_stage_pyramid": (_I, [_P, _I, _I, _I, _I, _P]),
     "tf_lk_stage_scharr": (_I, [_P, _I, _I, _I, _I, _P]),
     "tf_lk_stage_trace": (_I, [_P, _I, _I, _I, _I, C.c_float, C.c_float, _P]),
+    "tf_lfn_create": (_I, [_PP, _I, _I, _I, _I]),
+    "tf_lfn_destroy": (None, [_P]),
+    "tf_lfn_set_weights": (_I, [_P, _P, C.c_longlong]),
+    "tf_lfn_set_frame_bgr": (_I, [_P, _I, _P, _I, _I, C.c_ssize_t]),
+    "tf_lfn_calc_slots": (_I, [_P, _I, _PI, _PI]),
+    "tf_lfn_get_flow": (_I, [_P, _I, _P]),
+    "tf_lfn_flow_ptr": (_I, [_P, _I, _PP]),
+    "tf_lfn_stage_conv": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I]),
+    "tf_lfn_stage_deconv": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "tf_lfn_stage_correlation": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "tf_lfn_stage_backwarp": (_I, [_P, _I, _I, _I, _I, _P, _P, C.c_float, _P]),
+    "tf_lfn_stage_regularize_tail": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "tf_lfn_stage_prep": (_I, [_P, _I, _I, _P]),
     "tf_remap_create": (_I, [_PP, _I, _I, C.POINTER(TfLayerCfg), _P, _P, _P, _P]),
     "tf_remap_destroy": (None, [_P]),
     "tf_remap_set_sources": (_I, [_P, _I, C.POINTER(C.c_void_p)]),

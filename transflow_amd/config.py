@@ -6,6 +6,7 @@ backend unchanged.
   FlowConfig    <- CvFlowConfig, transflow/flow/sources/cv.py:271-363 (the fb_* fields)
   HornSchunckConfig <- the same, method "horn-schunck" (the hs_* fields)
   LucasKanadeConfig <- the same, method "lukas-kanade" (the lk_* fields; opt-in: lucas_kanade=True)
+  LiteFlowNetConfig <- the same, method "liteflownet" (no fields; opt-in: liteflownet=<weights path or dict>)
 """
 from __future__ import annotations
 
@@ -247,6 +248,39 @@ class LucasKanadeConfig:
         return cls(**{k: getattr(cfg, k) for k in cls.LK_DEFAULTS if hasattr(cfg, k)})
 
 
+class LiteFlowNetConfig:
+    """The "liteflownet" method of CvFlowConfig (assets/configs/liteflownet.json: only the method key) and the weights
+    that serve it: a path to the network's state dict or a dict of arrays (transflow_amd/liteflownet.py).  Other keys
+    are carried in `.extra`; the weights never go into to_dict()."""
+
+    def __init__(self, method: str = "liteflownet", weights=None, **kwargs):
+        if method != "liteflownet":
+            raise ValueError(f"LiteFlowNetConfig is the 'liteflownet' method, got {method!r}")
+        if weights is None:
+            raise ValueError("LiteFlowNetConfig needs the network's weights (a path or a dict of arrays)")
+        self.method = method
+        self.weights = weights
+        for k in list(kwargs):
+            if k.startswith("hip_"):
+                raise ValueError(f"{k!r} is not available with the liteflownet method")
+        self.extra = dict(kwargs)
+
+    def to_dict(self) -> dict:
+        d = {"method": self.method}
+        d.update(self.extra)
+        return d
+
+    def to_file(self, path: str):
+        with open(path, "w", encoding="utf8") as f:
+            json.dump(self.to_dict(), f, indent=4)
+
+    @classmethod
+    def from_reference(cls, cfg, weights):
+        if isinstance(cfg, cls):
+            return cfg
+        return cls(weights=weights)
+
+
 _UNSERVED_METHODS = ("lukas-kanade", "liteflownet")   # CvFlowSource.Method names this backend does not compute by default
 
 
@@ -260,17 +294,23 @@ def _method_name(method) -> str:
     return name.replace("_", "-")
 
 
-def _refuse(method: str, lucas_kanade: bool) -> None:
+def _refuse(method: str, lucas_kanade: bool, liteflownet=None) -> None:
     if method == "lukas-kanade" and lucas_kanade:
         return
+    if method == "liteflownet" and liteflownet is not None:
+        return
     if method in _UNSERVED_METHODS:
-        hint = " (lucas_kanade=True serves it)" if method == "lukas-kanade" else ""
+        hint = {"lukas-kanade": " (lucas_kanade=True serves it)",
+                "liteflownet": " (liteflownet=<weights> serves it)"}.get(method, "")
         raise ValueError(f"transflow_amd does not implement the {method!r} flow method{hint}")
 
 
-def flow_config_from_dict(d: dict, lucas_kanade: bool = False):
+def flow_config_from_dict(d: dict, lucas_kanade: bool = False, liteflownet=None):
+    """liteflownet: the network's weights (a path or a dict of arrays); with them a "liteflownet" config is served."""
     method = _method_name(d.get("method", "farneback"))
-    _refuse(method, lucas_kanade)
+    _refuse(method, lucas_kanade, liteflownet)
+    if method == "liteflownet":
+        return LiteFlowNetConfig(**{**d, "method": method, "weights": liteflownet})
     if method == "lukas-kanade":
         return LucasKanadeConfig(**{**d, "method": method})
     if method == "horn-schunck":
@@ -278,23 +318,25 @@ def flow_config_from_dict(d: dict, lucas_kanade: bool = False):
     return FlowConfig(**d)
 
 
-def flow_config_from_file(path: str, lucas_kanade: bool = False):
-    """A CvFlowConfig JSON file -> FlowConfig (farneback), HornSchunckConfig, or LucasKanadeConfig when lucas_kanade
-    is true; ValueError for the methods this backend does not compute (liteflownet, and lukas-kanade by default) and
-    for unknown ones."""
+def flow_config_from_file(path: str, lucas_kanade: bool = False, liteflownet=None):
+    """A CvFlowConfig JSON file -> FlowConfig (farneback), HornSchunckConfig, LucasKanadeConfig when lucas_kanade
+    is true, or LiteFlowNetConfig when liteflownet (the weights) is given; ValueError for the methods this backend
+    does not compute (lukas-kanade and liteflownet by default) and for unknown ones."""
     with open(path, "r", encoding="utf8") as f:
-        return flow_config_from_dict(json.load(f), lucas_kanade=lucas_kanade)
+        return flow_config_from_dict(json.load(f), lucas_kanade=lucas_kanade, liteflownet=liteflownet)
 
 
-def flow_config_from_reference(cfg, lucas_kanade: bool = False):
-    """A reference CvFlowConfig object (or one of ours, or None) -> FlowConfig, HornSchunckConfig or (lucas_kanade)
-    LucasKanadeConfig, by its method."""
+def flow_config_from_reference(cfg, lucas_kanade: bool = False, liteflownet=None):
+    """A reference CvFlowConfig object (or one of ours, or None) -> FlowConfig, HornSchunckConfig, (lucas_kanade)
+    LucasKanadeConfig or (liteflownet weights) LiteFlowNetConfig, by its method."""
     if cfg is None:
         return FlowConfig()
-    if isinstance(cfg, (FlowConfig, HornSchunckConfig, LucasKanadeConfig)):
+    if isinstance(cfg, (FlowConfig, HornSchunckConfig, LucasKanadeConfig, LiteFlowNetConfig)):
         return cfg
     method = _method_name(getattr(cfg, "method", None))
-    _refuse(method, lucas_kanade)
+    _refuse(method, lucas_kanade, liteflownet)
+    if method == "liteflownet":
+        return LiteFlowNetConfig.from_reference(cfg, liteflownet)
     if method == "lukas-kanade":
         return LucasKanadeConfig.from_reference(cfg)
     if method == "horn-schunck":

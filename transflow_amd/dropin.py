@@ -9,7 +9,8 @@
 (transflow/pipeline.py:325 FlowSource.from_args, :445 Compositor.from_args) with
 dispatchers that build HipFlowSource / HipCompositor when the request is one this
 backend serves -- a video path (or webcam index) with the Farnebäck method, or Horn-Schunck when
-`install(horn_schunck=True)` asks for it, or Lucas-Kanade when `install(lucas_kanade=True)` does (flow mask and the
+`install(horn_schunck=True)` asks for it, or Lucas-Kanade when `install(lucas_kanade=True)` does, or LiteFlowNet when
+`install(liteflownet=<weights>)` gives the network's weights (flow mask and the
 scale/threshold/clip filters, the convolution kernel and per-pixel polar expressions included), layers of
 any of the reference's classes (`moveref`, `sum`, `static`, `introduction`) -- and fall through to
 the reference's own factory otherwise (motion vectors, other flow methods, polar expressions that are
@@ -24,20 +25,21 @@ import os
 _saved = {}
 
 
-def _served_config(cv_config, horn_schunck: bool, lucas_kanade: bool = False) -> bool:
+def _served_config(cv_config, horn_schunck: bool, lucas_kanade: bool = False, liteflownet=None) -> bool:
     """Whether the flow method a cv_config (a JSON path, a CvFlowConfig object, None) names is one this backend runs."""
     from .config import HornSchunckConfig, flow_config_from_file, flow_config_from_reference
     if cv_config is None or (isinstance(cv_config, str) and not os.path.isfile(cv_config)):
         return True
     try:
-        cfg = (flow_config_from_file(cv_config, lucas_kanade=lucas_kanade) if isinstance(cv_config, str)
-               else flow_config_from_reference(cv_config, lucas_kanade=lucas_kanade))
+        cfg = (flow_config_from_file(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
+               if isinstance(cv_config, str)
+               else flow_config_from_reference(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet))
     except ValueError:          # another flow method: the reference's own source
         return False
     return horn_schunck or not isinstance(cfg, HornSchunckConfig)
 
 
-def _flow_from_args(original, horn_schunck=False, lucas_kanade=False):
+def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None):
     from .flow import HipFlowSource
 
     def from_args(cls, flow_path, use_mvs=False, mask_path=None, kernel_path=None, cv_config=None,
@@ -51,7 +53,7 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False):
                     FlowFilter.from_string(part)
             except NotImplementedError:
                 served = False
-        if served and not _served_config(cv_config, horn_schunck, lucas_kanade):
+        if served and not _served_config(cv_config, horn_schunck, lucas_kanade, liteflownet):
             served = False
         if not served:
             return original(flow_path, use_mvs=use_mvs, mask_path=mask_path, kernel_path=kernel_path,
@@ -60,7 +62,7 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False):
                             lock_expr=lock_expr, lock_mode=lock_mode)
         return HipFlowSource.from_args(flow_path, use_mvs, mask_path, kernel_path, cv_config, flow_filters, size,
                                        direction, seek_ckpt, seek_time, duration_time, repeat, lock_expr, lock_mode,
-                                       lucas_kanade=lucas_kanade)
+                                       lucas_kanade=lucas_kanade, liteflownet=liteflownet)
 
     return classmethod(from_args)
 
@@ -78,16 +80,18 @@ def _compositor_from_args(original, lazy_frames=False):
 
 
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
-            lucas_kanade: bool = False) -> None:
+            lucas_kanade: bool = False, liteflownet=None) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
-    the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  lazy_frames: the compositors built for the pipeline return
+    the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
+    to the state dict, or a dict of arrays): flow sources of the "liteflownet" method are then this backend's
+    (transflow_amd/liteflownet.py); without them they stay the reference's.  lazy_frames: the compositors built for the pipeline return
     DeviceFrames from render() (transflow_amd/deviceframe.py): the pipeline's `oq.put(frame)` (pipeline.py:518-522) then
     pickles the frame -- and waits for its download -- in the queue's feeder thread, beside the next update."""
     if flow and "flow" not in _saved:
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
-        RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade)
+        RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet)
     if compositor and "compositor" not in _saved:
         from transflow.compositor.compositor import Compositor as RefCompositor
 

@@ -19,7 +19,8 @@ import os
 import warnings
 import numpy as np
 
-from .config import FlowConfig, HornSchunckConfig, LucasKanadeConfig, flow_config_from_file, flow_config_from_reference
+from .config import (FlowConfig, HornSchunckConfig, LiteFlowNetConfig, LucasKanadeConfig, flow_config_from_file,
+                     flow_config_from_reference)
 
 logger = logging.getLogger(__name__)
 
@@ -593,7 +594,7 @@ class HipFlowSource(FlowSource):
 
     def validate(self):
         super().validate()
-        if not isinstance(self.config, (FlowConfig, HornSchunckConfig, LucasKanadeConfig)):
+        if not isinstance(self.config, (FlowConfig, HornSchunckConfig, LucasKanadeConfig, LiteFlowNetConfig)):
             raise ValueError("Attribute config has incorrect type")
 
     @property
@@ -604,7 +605,14 @@ class HipFlowSource(FlowSource):
     def _is_lk(self) -> bool:
         return isinstance(self.config, LucasKanadeConfig)
 
+    @property
+    def _is_lfn(self) -> bool:
+        return isinstance(self.config, LiteFlowNetConfig)
+
     def _handle(self):
+        if self._fb is None and self._is_lfn:
+            from .liteflownet import LiteFlowNet
+            self._fb = LiteFlowNet(self.width, self.height, self.config.weights, device=self.device)
         if self._fb is None and self._is_lk:
             from .lucaskanade import LucasKanade
             self._fb = LucasKanade(self.width, self.height, device=self.device)   # (post_process keeps its own handle)
@@ -644,7 +652,11 @@ class HipFlowSource(FlowSource):
 
     def _ingest(self, slot: int, frame) -> None:
         a = np.asarray(frame)
-        if a.ndim == 2:
+        if self._is_lfn:                             # cv.py:464-465, 509-516: the network reads colour
+            if a.ndim != 3:
+                raise ValueError("the liteflownet method needs colour (BGR) frames; the frame provider gives grey ones")
+            self._handle().set_frame_bgr(slot, a)
+        elif a.ndim == 2:
             self._handle().set_frame(slot, a)
         else:
             self._handle().set_frame_bgr(slot, a)
@@ -700,6 +712,8 @@ class HipFlowSource(FlowSource):
             kw = self.config.hs_kwargs()
         elif self._is_lk:                            # cv.py:501-508: no initial flow
             kw = self.config.lk_kwargs()
+        elif self._is_lfn:                           # cv.py:509-516: the two frames only
+            pass
         elif self._uses_initial_flow():              # cv.py:478: a copy of the previous flow, zeros before the first
             init = self.prev_flow if self.prev_flow is not None else np.zeros((self.height, self.width, 2), np.float32)
             fb.set_initial_flow(0, init)
@@ -720,11 +734,12 @@ class HipFlowSource(FlowSource):
     # down -- one transfer each instead of two frames up and the flow down, up and down again.  The
     # public next() / post_process() pair keeps working on host arrays for any other caller.
     def _uses_initial_flow(self) -> bool:
-        return not self._is_hs and not self._is_lk and bool(self.config.fb_flags & 4)      # cv2.OPTFLOW_USE_INITIAL_FLOW
+        return (not self._is_hs and not self._is_lk and not self._is_lfn
+                and bool(self.config.fb_flags & 4))      # cv2.OPTFLOW_USE_INITIAL_FLOW
 
     def _resident_ok(self) -> bool:
-        if self._is_hs or self._is_lk:
-            return False     # (a device-resident post-process of Horn-Schunck or Lucas-Kanade flows is not built)
+        if self._is_hs or self._is_lk or self._is_lfn:
+            return False     # (a device-resident post-process of Horn-Schunck, Lucas-Kanade or LiteFlowNet flows is not built)
         # with OPTFLOW_USE_INITIAL_FLOW every call starts from the previous OUTPUT (cv.py:478 passes a copy of
         # prev_flow, which __next__ has post-processed in place): that array lives on the host
         return (self.lock_expr_stay is None and self.lock_expr_skip is None and self.kernel is None
@@ -814,7 +829,7 @@ class HipFlowSource(FlowSource):
         if self._prefetch is not None:
             self._prefetch.stop()
             self._prefetch = None
-            if self._fb is not None and not self._is_hs and not self._is_lk:
+            if self._fb is not None and not self._is_hs and not self._is_lk and not self._is_lfn:
                 self._fb.async_io(False)    # waits for a download the worker left on its way
         if self._mask_dev is not None:
             self._mask_dev.close()
@@ -841,9 +856,11 @@ class HipFlowSource(FlowSource):
     @classmethod
     def from_args(cls, flow_path, use_mvs: bool = False, mask_path=None, kernel_path=None, cv_config=None,
                   flow_filters=None, size=None, direction=None, seek_ckpt=None, seek_time=None,
-                  duration_time=None, repeat: int = 1, lock_expr=None, lock_mode="stay", lucas_kanade: bool = False):
+                  duration_time=None, repeat: int = 1, lock_expr=None, lock_mode="stay", lucas_kanade: bool = False,
+                  liteflownet=None):
         """Same signature as FlowSource.from_args (source.py:365-411); `flow_path` may also be
-        a frame provider object.  lucas_kanade: a config naming "lukas-kanade" is served (else it raises ValueError).  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399);
+        a frame provider object.  lucas_kanade: a config naming "lukas-kanade" is served (else it raises ValueError);
+        liteflownet: the network's weights (a path or a dict of arrays), with which a config naming "liteflownet" is.  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399);
         motion-vector sources are not this backend's."""
         if isinstance(flow_path, str) and flow_path.split("::")[-1].endswith(".flow.zip"):
             from .archive import ArchiveFlowSource
@@ -854,10 +871,10 @@ class HipFlowSource(FlowSource):
         if use_mvs:
             raise NotImplementedError("transflow_amd does not read codec motion vectors")
         if isinstance(cv_config, str):
-            config = (flow_config_from_file(cv_config, lucas_kanade=lucas_kanade) if os.path.isfile(cv_config)
-                      else FlowConfig())
+            config = (flow_config_from_file(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
+                      if os.path.isfile(cv_config) else FlowConfig())
         else:
-            config = flow_config_from_reference(cv_config, lucas_kanade=lucas_kanade)
+            config = flow_config_from_reference(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
         if isinstance(flow_path, str) and "::" in flow_path:
             flow_path = flow_path.split("::")[1]
         return cls.Builder(flow_path, config, size, direction=direction, mask_path=mask_path,
