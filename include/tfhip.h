@@ -425,6 +425,32 @@ int tf_lfn_stage_regularize_tail(tf_lfn *lfn, int level, int n, int h, int w, co
                                  float *out);
 int tf_lfn_stage_prep(tf_lfn *lfn, int slot, int role, float *out);
 
+/* ---- codec motion vectors (transflow/flow/sources/av.py) -------------------------------
+ * AvFlowSource.next() (av.py:61-77): flow = zeros [H][W][2] float32; then, for each vector in list order,
+ *   flow[src_y - h//2 : src_y + h//2, src_x - w//2 : src_x + w//2] = -motion_x / motion_scale, -motion_y / motion_scale
+ * with numpy's slice semantics (a negative bound counts from the end, then both clamp to [0, n]: rectangles near the
+ * top or left edge wrap, they are not clipped), float64 quotients rounded to float32 on assignment (motion 0 paints
+ * -0.0) and the last writer of a pixel winning.  The entries take the RAW fields of libavutil's AVMotionVector and do
+ * the slice resolution, the division and the checks themselves.  A vector with source != -1 (the assert of av.py:69)
+ * or motion_scale == 0 (the ZeroDivisionError of av.py:74) is TF_ERR_ARG, the message names its index, and nothing
+ * is launched.  n == 0 (v may be null then; a frame without MOTION_VECTORS side data, av.py:66-67) gives all +0.0.
+ * A tf_mv belongs to one calling thread: its upload stage and event are the handle's, the stream is the thread's. */
+typedef struct tf_mv_vector {
+    int32_t source, w, h, src_x, src_y, motion_x, motion_y, motion_scale;
+} tf_mv_vector;
+typedef struct tf_mv tf_mv;
+int tf_mv_create(tf_mv **out, int width, int height);
+void tf_mv_destroy(tf_mv *mv);
+/* av.py:62-77 for one frame, into a host array ... */
+int tf_mv_rasterize(tf_mv *mv, const tf_mv_vector *v, int n, float *flow_out /* host [H][W][2] */);
+/* ... or into device memory (8-byte aligned), queued on the calling thread's stream: nothing is waited for */
+int tf_mv_rasterize_dev(tf_mv *mv, const tf_mv_vector *v, int n, void *flow_dev /* device [H][W][2] */);
+/* Stage entry point, host arithmetic only (no device needed): av.py:70-75 per vector.  rects_out[k] = {i0, i1, j0, j1}
+   after the slice resolution (rows [i0, i1) x columns [j0, j1); empty when i0 >= i1 or j0 >= j1), values_out[k] =
+   {float32(-dx), float32(-dy)}. */
+int tf_mv_stage_resolve_rects(int width, int height, const tf_mv_vector *v, int n, int32_t *rects_out /* n x 4 */,
+                              float *values_out /* n x 2 */);
+
 /* ---- compositor layers -----------------------------------------------------------
  * One handle = one layer of the compositor.  layer_class selects which of the reference's
  * layer classes it is (Layer.from_args, transflow/compositor/layers/layer.py:44-56):

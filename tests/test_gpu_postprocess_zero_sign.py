@@ -1,0 +1,46 @@
+"""FlowSource.post_process on the GPU keeps numpy.clip's zero signs: the reference clips with array bounds, which numpy
+evaluates as comparisons (x > lo ? x : lo, then t < hi ? t : hi), so a -0.0 that meets a bound of 0 -- column 0 and row 0
+from below, column W - 1 and row H - 1 from above -- comes out as +0.0.  Compared on bit patterns against
+oracle.remap_ref.post_process, on the host-array entry and on the device-resident one."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import remap_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+def _flows(h, w):
+    f = np.float32
+    rng = np.random.default_rng(12)
+    zeros = np.full((h, w, 2), f(-0.0))                       # -0.0 everywhere: all four borders meet a bound of 0
+    mixed = rng.choice(np.array([-0.0, 0.0, -0.25, 0.25, -3.0, 3.0, 1e3, -1e3], f), (h, w, 2)).astype(f)
+    masked = (rng.normal(0, 2, (h, w, 2)).astype(f) * rng.choice(np.array([0.0, 1.0], f), (h, w, 1))).astype(f)
+    return {"negative_zeros": zeros, "mixed": mixed, "mask_products": masked}
+
+
+@pytest.mark.parametrize("direction", [R.BACKWARD, R.FORWARD])
+@pytest.mark.parametrize("name", ["negative_zeros", "mixed", "mask_products"])
+@pytest.mark.parametrize("w,h", [(37, 23), (1, 1), (64, 2)])
+def test_post_process_zero_signs(direction, name, w, h):
+    from transflow_amd import _lib
+    from transflow_amd.farneback import Farneback
+    raw = _flows(h, w)[name]
+    exp = R.post_process(raw.copy(), direction)
+    fb = Farneback(w, h, levels=0)
+    try:
+        got = fb.post_process_host(raw.copy(), direction)
+        np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
+        _lib.check(_lib.load().tf_dev_upload(C.c_void_p(fb.flow_ptr(0)), C.c_void_p(raw.ctypes.data), raw.nbytes))
+        fb.post_process_ex(0, direction)
+        out = np.empty_like(raw)
+        _lib.check(_lib.load().tf_dev_download(C.c_void_p(out.ctypes.data), C.c_void_p(fb.flow_ptr(0)), out.nbytes))
+        np.testing.assert_array_equal(out.view(np.uint32), exp.view(np.uint32))
+    finally:
+        fb.close()
+    if name == "negative_zeros" and direction == R.BACKWARD and (w, h) == (37, 23):
+        b = exp.view(np.uint32)
+        assert (b[:, 0, 0] == 0).all() and (b[:, -1, 0] == 0).all() and (b[0, :, 1] == 0).all() and (b[-1, :, 1] == 0).all()
+        assert (b[1:-1, 1:-1] == 0x80000000).all()           # the interior keeps its -0.0

@@ -33,6 +33,11 @@ class TfHsParams(C.Structure):
                 ("has_delta", C.c_int)]
 
 
+class TfMvVector(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in ("source", "w", "h", "src_x", "src_y", "motion_x", "motion_y",
+                                               "motion_scale")]
+
+
 class TfPolarStep(C.Structure):
     _fields_ = [("op", C.c_int), ("wide", C.c_int), ("imm", C.c_double)]
 
@@ -161,6 +166,11 @@ PROTOTYPES = {
     "tf_lfn_stage_backwarp": (_I, [_P, _I, _I, _I, _I, _P, _P, C.c_float, _P]),
     "tf_lfn_stage_regularize_tail": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "tf_lfn_stage_prep": (_I, [_P, _I, _I, _P]),
+    "tf_mv_create": (_I, [_PP, _I, _I]),
+    "tf_mv_destroy": (None, [_P]),
+    "tf_mv_rasterize": (_I, [_P, _P, _I, _P]),
+    "tf_mv_rasterize_dev": (_I, [_P, _P, _I, _P]),
+    "tf_mv_stage_resolve_rects": (_I, [_I, _I, _P, _I, _P, _P]),
     "tf_remap_create": (_I, [_PP, _I, _I, C.POINTER(TfLayerCfg), _P, _P, _P, _P]),
     "tf_remap_destroy": (None, [_P]),
     "tf_remap_set_sources": (_I, [_P, _I, C.POINTER(C.c_void_p)]),

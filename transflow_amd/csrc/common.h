@@ -112,7 +112,6 @@ struct DevBuf {
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
-// numpy.clip semantics: minimum(maximum(v, lo), hi) with NaN propagated (fminf/fmaxf drop it)
 // Unsigned division by a launch-wide constant d >= 1 (Granlund-Montgomery, round-up form): with
 // s = ceil(log2 d), m = floor(2^32 (2^s - d) / d) + 1:  q = (((t - hi) >> min(s,1)) + hi) >> max(s-1,0),
 // hi = umulhi(t, m).  Exact for every 32-bit t; 5 instructions instead of the ~40 of a division.
@@ -137,6 +136,9 @@ __device__ __forceinline__ uint32_t fast_div(uint32_t t, FastDiv f)
     return (((t - hi) >> f.s1) + hi) >> f.s2;
 }
 
+// numpy.clip's values: minimum(maximum(v, lo), hi) with NaN propagated (fminf / fmaxf drop it).  Not its zero signs:
+// the hardware's min / max order -0 below +0, numpy compares.  For results that are rounded to integers or bytes next;
+// a flow that is handed out goes through clip_np (fb_postprocess.hip).
 __device__ __forceinline__ float clip_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
 
 } // namespace tf

@@ -7,10 +7,21 @@ namespace {
 // ---------------------------------------------------------------------------------
 // B1: FlowSource.post_process (source.py:337-363)
 // ---------------------------------------------------------------------------------
+// numpy.clip, to the bit: min(max(v, lo), hi) as comparisons (v > lo ? v : lo, then t < hi ? t : hi), so a -0.0 meeting
+// a bound of 0 comes out as the bound's +0.0 on either side; the hardware's min / max order -0 below +0 and would keep
+// the -0.0 at an upper bound of 0 (the last column / row).  Painted motion-vector flows are full of -0.0.
+__device__ __forceinline__ float clip_np(float v, float lo, float hi)
+{
+    if (v != v)
+        return v;
+    const float t = v > lo ? v : lo;
+    return t < hi ? t : hi;
+}
+
 __device__ __forceinline__ float2 clip_to_frame(float2 f, int i, int j, int W, int H)
 {
-    f.x = clip_nan(f.x, (float)(-j), (float)(W - 1 - j));
-    f.y = clip_nan(f.y, (float)(-i), (float)(H - 1 - i));
+    f.x = clip_np(f.x, (float)(-j), (float)(W - 1 - j));
+    f.y = clip_np(f.y, (float)(-i), (float)(H - 1 - i));
     return f;
 }
 

@@ -11,9 +11,10 @@ dispatchers that build HipFlowSource / HipCompositor when the request is one thi
 backend serves -- a video path (or webcam index) with the Farnebäck method, or Horn-Schunck when
 `install(horn_schunck=True)` asks for it, or Lucas-Kanade when `install(lucas_kanade=True)` does, or LiteFlowNet when
 `install(liteflownet=<weights>)` gives the network's weights (flow mask and the
-scale/threshold/clip filters, the convolution kernel and per-pixel polar expressions included), layers of
+scale/threshold/clip filters, the convolution kernel and per-pixel polar expressions included), or codec motion
+vectors (`use_mvs`, transflow's `-m`) when `install(motion_vectors=True)` asks for them, layers of
 any of the reference's classes (`moveref`, `sum`, `static`, `introduction`) -- and fall through to
-the reference's own factory otherwise (motion vectors, other flow methods, polar expressions that are
+the reference's own factory otherwise (other flow methods, polar expressions that are
 not per-pixel formulas).
 `.flow.zip` archives are served too (their flows are post-processed on the GPU).
 INTEGRATION.md shows the three-line patch a maintainer would add instead.
@@ -39,13 +40,14 @@ def _served_config(cv_config, horn_schunck: bool, lucas_kanade: bool = False, li
     return horn_schunck or not isinstance(cfg, HornSchunckConfig)
 
 
-def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None):
+def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None, motion_vectors=False):
     from .flow import HipFlowSource
 
     def from_args(cls, flow_path, use_mvs=False, mask_path=None, kernel_path=None, cv_config=None,
                   flow_filters=None, size=None, direction=None, seek_ckpt=None, seek_time=None,
                   duration_time=None, repeat=1, lock_expr=None, lock_mode="stay"):
-        served = isinstance(flow_path, str) and not use_mvs and cv_config != "window"
+        # (a motion-vector source reads no cv_config: source.py:400-402)
+        served = isinstance(flow_path, str) and (motion_vectors if use_mvs else cv_config != "window")
         if served and flow_filters is not None and "polar" in flow_filters:
             try:                                   # polar expressions the device cannot run stay the reference's
                 from .flow import FlowFilter
@@ -53,7 +55,7 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
                     FlowFilter.from_string(part)
             except NotImplementedError:
                 served = False
-        if served and not _served_config(cv_config, horn_schunck, lucas_kanade, liteflownet):
+        if served and not use_mvs and not _served_config(cv_config, horn_schunck, lucas_kanade, liteflownet):
             served = False
         if not served:
             return original(flow_path, use_mvs=use_mvs, mask_path=mask_path, kernel_path=kernel_path,
@@ -80,18 +82,21 @@ def _compositor_from_args(original, lazy_frames=False):
 
 
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
-            lucas_kanade: bool = False, liteflownet=None) -> None:
+            lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
     to the state dict, or a dict of arrays): flow sources of the "liteflownet" method are then this backend's
-    (transflow_amd/liteflownet.py); without them they stay the reference's.  lazy_frames: the compositors built for the pipeline return
+    (transflow_amd/liteflownet.py); without them they stay the reference's.  motion_vectors: `use_mvs` requests (codec
+    motion vectors, transflow's -m) are this backend's too (transflow_amd/motionvectors.py; PyAV still decodes); by
+    default they stay the reference's.  lazy_frames: the compositors built for the pipeline return
     DeviceFrames from render() (transflow_amd/deviceframe.py): the pipeline's `oq.put(frame)` (pipeline.py:518-522) then
     pickles the frame -- and waits for its download -- in the queue's feeder thread, beside the next update."""
     if flow and "flow" not in _saved:
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
-        RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet)
+        RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet,
+                                                     motion_vectors)
     if compositor and "compositor" not in _saved:
         from transflow.compositor.compositor import Compositor as RefCompositor
 

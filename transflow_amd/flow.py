@@ -861,15 +861,23 @@ class HipFlowSource(FlowSource):
         """Same signature as FlowSource.from_args (source.py:365-411); `flow_path` may also be
         a frame provider object.  lucas_kanade: a config naming "lukas-kanade" is served (else it raises ValueError);
         liteflownet: the network's weights (a path or a dict of arrays), with which a config naming "liteflownet" is.  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399);
-        motion-vector sources are not this backend's."""
+        use_mvs: codec motion vectors (source.py:400-402) go to MotionVectorFlowSource (transflow_amd/motionvectors.py),
+        `flow_path` being a video path for PyAV (`avformat::path` as the reference splits it) or a vector provider."""
         if isinstance(flow_path, str) and flow_path.split("::")[-1].endswith(".flow.zip"):
             from .archive import ArchiveFlowSource
             return ArchiveFlowSource.Builder(flow_path.split("::")[-1], direction=direction, mask_path=mask_path,
                                              kernel_path=kernel_path, flow_filters=flow_filters, seek_ckpt=seek_ckpt,
                                              seek_time=seek_time, duration_time=duration_time, repeat=repeat,
                                              lock_expr=lock_expr, lock_mode=lock_mode)
-        if use_mvs:
-            raise NotImplementedError("transflow_amd does not read codec motion vectors")
+        if use_mvs:                                        # source.py:381-384, 400-402
+            from .motionvectors import MotionVectorFlowSource
+            avformat = None
+            if isinstance(flow_path, str) and "::" in flow_path:
+                avformat, flow_path = flow_path.split("::")
+            return MotionVectorFlowSource.Builder(flow_path, avformat, direction=direction, mask_path=mask_path,
+                                                  kernel_path=kernel_path, flow_filters=flow_filters, seek_ckpt=seek_ckpt,
+                                                  seek_time=seek_time, duration_time=duration_time, repeat=repeat,
+                                                  lock_expr=lock_expr, lock_mode=lock_mode)
         if isinstance(cv_config, str):
             config = (flow_config_from_file(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
                       if os.path.isfile(cv_config) else FlowConfig())
