@@ -174,6 +174,46 @@ def test_polar_inside_post_process_chain():
     out = src.post_process(ZP["chain_in"].copy())
     _close(out, ZP["chain_out"])
     src.close()
+    # Which array comes back and what is left in the one given (source.py:339-348: `prev_flow` is the array given, so
+    # it sees the filters and neither the mask nor what follows), with the polar filter between two plain ones.
+    from oracle import remap_ref as R
+    h, w, t = 37, 53, 21 / 30.0
+    rng = np.random.default_rng(15)
+    raw = rng.normal(0, 3, (h, w, 2)).astype(np.float32)
+    mask = rng.random((h, w, 1)).astype(np.float32)
+    kernel = rng.normal(0, 0.3, (3, 5))
+    filtered = R.pre_steps(raw.copy(), [("scale", 1.5)])
+    F.polar(filtered, "r+1", "a*2", t)
+    R.pre_steps(filtered, [("clip", 4)])
+
+    def run(given, direction="backward", filters=("scale=1.5", "polar=r+1:a*2", "clip=4"), **kw):
+        src = FlowSource(direction, w, h, 30.0, 100, 0, 0, 100, flow_filters=[FlowFilter.from_string(f) for f in filters], **kw)
+        src.output_frame_index = 21
+        try:
+            return src.post_process(given)
+        finally:
+            src.close()
+
+    given = raw.copy()                              # filters only: the same object, modified
+    out = run(given)
+    assert out is given
+    _close(given, R.post_process(filtered.copy(), R.BACKWARD))
+    given = raw.copy()                              # mask: a new object; the one given carries the filters only
+    out = run(given, mask=mask)
+    assert out is not given and out.dtype == np.float32
+    _close(given, filtered)
+    np.testing.assert_array_equal(out, R.post_process(R.pre_steps(given.copy(), (), mask), R.BACKWARD))
+    for m in (None, mask):                          # kernel: a new object of the kernel's result type
+        given = raw.copy()
+        out = run(given, mask=m, kernel=kernel)
+        assert out is not given and out.dtype == np.float64
+        _close(given, filtered)
+        np.testing.assert_array_equal(out, F.post_process_with_kernel(R.pre_steps(given.copy(), (), m), kernel, R.BACKWARD))
+    given = np.round(raw).astype(int)               # integer archive: the same integer object
+    expected = R.post_process(given.astype(np.float32), R.FORWARD).astype(int)
+    out = run(given, direction="forward", filters=())
+    assert out is given and out.dtype == int
+    np.testing.assert_array_equal(given, expected)
 
 
 def test_polar_full_size_vs_oracle():

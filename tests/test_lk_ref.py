@@ -158,7 +158,7 @@ def test_hip_flow_source_takes_lk_config_when_asked():
     b.build()
     src = HipFlowSource(*b.args(), **b.kwargs())
     src.validate()
-    assert src._is_lk and not src._is_hs
+    assert isinstance(src.config, LucasKanadeConfig) and not isinstance(src.config, HornSchunckConfig)
     assert not src._resident_ok() and not src._uses_initial_flow()
     b2 = HipFlowSource.from_args(ArrayFrameProvider(frames, 10.0), cv_config=LucasKanadeConfig())
     assert isinstance(b2.config, LucasKanadeConfig)

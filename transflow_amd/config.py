@@ -7,10 +7,14 @@ backend unchanged.
   HornSchunckConfig <- the same, method "horn-schunck" (the hs_* fields)
   LucasKanadeConfig <- the same, method "lukas-kanade" (the lk_* fields; opt-in: lucas_kanade=True)
   LiteFlowNetConfig <- the same, method "liteflownet" (no fields; opt-in: liteflownet=<weights path or dict>)
+
+The four are MethodConfig subclasses; METHODS is the one table of the methods served and of what opts each in, which
+the flow_config_from_* readers (and through them HipFlowSource.from_args and the drop-in) ask.
 """
 from __future__ import annotations
 
 import json
+import os
 
 _TRUE_WORDS = ("1", "on", "o", "oui", "yes", "y")  # config.py:49-54
 
@@ -81,207 +85,182 @@ class LayerConfig:
         return cls(cfg.index, **{k: getattr(cfg, k) for k in cls._KEYS if k != "index" and hasattr(cfg, k)})
 
 
-class FlowConfig:
+def _exact_sums(v):
+    return bool(parse_bool_arg(v, False))
+
+
+def _device_flows(v):
+    return "ipc" if isinstance(v, str) and v.lower() == "ipc" else parse_bool_arg(v, False)
+
+
+# This backend's own keys in a CvFlowConfig JSON, each with what makes its attribute of the value given (None: the key
+# is not there); to_dict() writes them in this order, and only where they differ from their default.  The reference
+# ignores keys it does not know only if they are not there: leave them out of files the reference itself must read.
+_HIP_KEYS = {
+    # "hip_exact_sums": true asks for the box window summed in OpenCV's own order (library option fb_exact_sums: flows
+    # bit-identical to the CPU path's, about 1.5 times the Farnebäck time for a single 4K pair).
+    "hip_exact_sums": _exact_sums,
+    # "hip_prefetch": n > 0 lets the flow source run up to n flows ahead of its consumer in a worker thread with a
+    # library stream of its own (what the reference gets from running the source in a child process behind a
+    # queue, pipeline.py:56-64, for a source used in-process).  Its position attributes then run ahead by as much.
+    "hip_prefetch": lambda v: int(v or 0),
+    # "hip_device_flows": true -- the source yields DeviceFlow objects (transflow_amd/deviceflow.py): flows that stay in
+    # HBM until something reads them on the host, and that HipCompositor.update takes by device address (no 66 MB per
+    # 4K frame down the link and up again across pipeline.py:562-567).  "ipc": the same, and through a multiprocessing
+    # queue (pipeline.py:85-86) such a flow travels as a 64-byte HIP IPC handle instead of the pickled array.
+    "hip_device_flows": _device_flows,
+    # "hip_batch": n > 1 -- where nothing can look at a raw flow in between (no lock expressions, no convolution kernel,
+    # no initial flow), the source reads n frames ahead and computes their n pairs in ONE Farneback call: a single 4K
+    # pair leaves most of the chip idle at the coarse levels, a batch of four costs 0.6 of four single calls.  Flows
+    # still come out one at a time, in order, each post-processed with its own t.
+    "hip_batch": lambda v: max(1, int(v or 1)),
+}
+
+
+class MethodConfig:
+    """One flow method's part of CvFlowConfig (cv.py:271-363): the method's own fields with their defaults as
+    attributes, the `hip_*` keys it accepts, and every other key carried in `.extra` so that a CvFlowConfig JSON
+    loads and is written back whole.  A subclass states the method's name, its fields and its `hip_*` keys."""
+
+    METHOD = None
+    DEFAULTS: dict = {}
+    HIP_KEYS: tuple = ()        # the keys of _HIP_KEYS the method accepts; another `hip_*` key is a ValueError
+    # the attributes of the keys a method does not accept: what they mean when they are not given
+    hip_exact_sums, hip_prefetch, hip_device_flows, hip_batch = False, 0, False, 1
+
+    def __init__(self, method: str, **kwargs):
+        if method != self.METHOD:
+            raise ValueError(self._wrong_method(method))
+        self.method = method
+        for k, v in self.DEFAULTS.items():
+            setattr(self, k, kwargs.pop(k, v))
+        for k in kwargs:
+            if k.startswith("hip_") and k not in self.HIP_KEYS:
+                self._refuse_hip_key(k)
+        for k in self.HIP_KEYS:
+            setattr(self, k, _HIP_KEYS[k](kwargs.pop(k, None)))
+        self.extra = dict(kwargs)  # the other methods' fields, show_window ...: not used by this backend
+
+    def _wrong_method(self, method) -> str:
+        return f"{type(self).__name__} is the {self.METHOD!r} method, got {method!r}"
+
+    def _refuse_hip_key(self, key):
+        only = f" (only {', '.join(map(repr, self.HIP_KEYS))} is)" if self.HIP_KEYS else ""
+        raise ValueError(f"{key!r} is not available with the {self.METHOD} method{only}")
+
+    def to_dict(self) -> dict:
+        d = {"method": self.method}
+        d.update({k: getattr(self, k) for k in self.DEFAULTS})
+        d.update(self.extra)
+        for k in _HIP_KEYS:
+            if k in self.HIP_KEYS and getattr(self, k) != _HIP_KEYS[k](None):
+                d[k] = getattr(self, k)
+        return d
+
+    def to_file(self, path: str):
+        with open(path, "w", encoding="utf8") as f:
+            json.dump(self.to_dict(), f, indent=4)
+
+    @classmethod
+    def from_reference(cls, cfg, **given):
+        """A reference CvFlowConfig (or anything with its attributes, or None) -> this method's fields of it."""
+        if isinstance(cfg, cls):
+            return cfg
+        return cls(**{k: getattr(cfg, k) for k in cls.DEFAULTS if hasattr(cfg, k)}, **given)
+
+
+def _from_file(cls, path: str):
+    with open(path, "r", encoding="utf8") as f:
+        return cls(**json.load(f))
+
+
+class FlowConfig(MethodConfig):
     """The Farnebäck fields of CvFlowConfig (cv.py:273-281) and their defaults; other
     methods' fields (hs_*, lk_*) are accepted and carried so a CvFlowConfig JSON loads."""
 
-    FB_DEFAULTS = dict(fb_pyr_scale=0.5, fb_levels=3, fb_winsize=15, fb_iterations=3, fb_poly_n=5,
-                       fb_poly_sigma=1.2, fb_flags=0)
+    METHOD = "farneback"
+    DEFAULTS = FB_DEFAULTS = dict(fb_pyr_scale=0.5, fb_levels=3, fb_winsize=15, fb_iterations=3, fb_poly_n=5,
+                                  fb_poly_sigma=1.2, fb_flags=0)
+    HIP_KEYS = tuple(_HIP_KEYS)
+    from_file = classmethod(_from_file)
 
     def __init__(self, method: str = "farneback", **kwargs):
-        if method != "farneback":
-            raise ValueError(f"transflow_amd implements the 'farneback' method only, got {method!r}")
-        self.method = method
-        for k, v in self.FB_DEFAULTS.items():
-            setattr(self, k, kwargs.pop(k, v))
-        # This backend's own key in a CvFlowConfig JSON: "hip_exact_sums": true asks for the box window summed in
-        # OpenCV's own order (library option fb_exact_sums: flows bit-identical to the CPU path's, about 1.5 times
-        # the Farnebäck time for a single 4K pair).  The reference ignores keys it does not know only if they are not there: leave it out
-        # of files the reference itself must read.
-        self.hip_exact_sums = parse_bool_arg(kwargs.pop("hip_exact_sums", None), False)
-        # "hip_prefetch": n > 0 lets the flow source run up to n flows ahead of its consumer in a worker thread with a
-        # library stream of its own (what the reference gets from running the source in a child process behind a
-        # queue, pipeline.py:56-64, for a source used in-process).  Its position attributes then run ahead by as much.
-        self.hip_prefetch = int(kwargs.pop("hip_prefetch", 0) or 0)
-        # "hip_device_flows": true -- the source yields DeviceFlow objects (transflow_amd/deviceflow.py): flows that stay in
-        # HBM until something reads them on the host, and that HipCompositor.update takes by device address (no 66 MB per
-        # 4K frame down the link and up again across pipeline.py:562-567).  "ipc": the same, and through a multiprocessing
-        # queue (pipeline.py:85-86) such a flow travels as a 64-byte HIP IPC handle instead of the pickled array.
-        # "hip_batch": n > 1 -- where nothing can look at a raw flow in between (no lock expressions, no convolution kernel,
-        # no initial flow), the source reads n frames ahead and computes their n pairs in ONE Farneback call: a single 4K
-        # pair leaves most of the chip idle at the coarse levels, a batch of four costs 0.6 of four single calls.  Flows
-        # still come out one at a time, in order, each post-processed with its own t.
-        self.hip_batch = max(1, int(kwargs.pop("hip_batch", 1) or 1))
-        v = kwargs.pop("hip_device_flows", None)
-        self.hip_device_flows = "ipc" if isinstance(v, str) and v.lower() == "ipc" else parse_bool_arg(v, False)
-        self.extra = dict(kwargs)  # hs_*, lk_*, show_window ...: not used by this backend
+        super().__init__(method, **kwargs)
+
+    def _wrong_method(self, method) -> str:
+        return f"transflow_amd implements the 'farneback' method only, got {method!r}"
+
+    def _refuse_hip_key(self, key):
+        pass                       # (a `hip_*` key this backend does not know is carried in `.extra` like any other)
 
     def fb_kwargs(self) -> dict:
         return dict(pyr_scale=self.fb_pyr_scale, levels=self.fb_levels, winsize=self.fb_winsize,
                     iterations=self.fb_iterations, poly_n=self.fb_poly_n, poly_sigma=self.fb_poly_sigma,
                     flags=self.fb_flags)
 
-    def to_dict(self) -> dict:
-        d = {"method": self.method}
-        d.update({k: getattr(self, k) for k in self.FB_DEFAULTS})
-        d.update(self.extra)
-        if self.hip_exact_sums:
-            d["hip_exact_sums"] = True
-        if self.hip_prefetch:
-            d["hip_prefetch"] = self.hip_prefetch
-        if self.hip_device_flows:
-            d["hip_device_flows"] = self.hip_device_flows
-        if self.hip_batch > 1:
-            d["hip_batch"] = self.hip_batch
-        return d
 
-    def to_file(self, path: str):
-        with open(path, "w", encoding="utf8") as f:
-            json.dump(self.to_dict(), f, indent=4)
-
-    @classmethod
-    def from_file(cls, path: str):
-        with open(path, "r", encoding="utf8") as f:
-            return cls(**json.load(f))
-
-    @classmethod
-    def from_reference(cls, cfg):
-        if cfg is None:
-            return cls()
-        if isinstance(cfg, cls):
-            return cfg
-        return cls(**{k: getattr(cfg, k) for k in cls.FB_DEFAULTS if hasattr(cfg, k)})
-
-
-class HornSchunckConfig:
+class HornSchunckConfig(MethodConfig):
     """The Horn-Schunck fields of CvFlowConfig (cv.py:282-285) and their defaults; `hs_delta` may be None (JSON null:
     every call runs hs_iterations iterations).  fb_*, lk_* and other keys are carried in `.extra`."""
 
-    HS_DEFAULTS = dict(hs_alpha=1, hs_iterations=3, hs_decay=0, hs_delta=1)
-    # this backend's keys that Horn-Schunck has no use for (they shape the Farnebäck path)
-    _FB_ONLY_HIP = ("hip_exact_sums", "hip_batch", "hip_device_flows")
+    METHOD = "horn-schunck"
+    DEFAULTS = HS_DEFAULTS = dict(hs_alpha=1, hs_iterations=3, hs_decay=0, hs_delta=1)
+    HIP_KEYS = ("hip_prefetch",)
+    from_file = classmethod(_from_file)
 
     def __init__(self, method: str = "horn-schunck", **kwargs):
-        if method != "horn-schunck":
-            raise ValueError(f"HornSchunckConfig is the 'horn-schunck' method, got {method!r}")
-        self.method = method
-        for k, v in self.HS_DEFAULTS.items():
-            setattr(self, k, kwargs.pop(k, v))
-        for k in list(kwargs):
-            if k.startswith("hip_") and k != "hip_prefetch":
-                raise ValueError(f"{k!r} is not available with the horn-schunck method (only 'hip_prefetch' is)")
-        # "hip_prefetch": as FlowConfig's
-        self.hip_prefetch = int(kwargs.pop("hip_prefetch", 0) or 0)
-        self.extra = dict(kwargs)
+        super().__init__(method, **kwargs)
 
     def hs_kwargs(self) -> dict:
         """The keyword arguments of calc_optical_flow_horn_schunck (cv.py:495-498)."""
         return dict(alpha=self.hs_alpha, max_iters=self.hs_iterations, decay=self.hs_decay, delta=self.hs_delta)
 
-    def to_dict(self) -> dict:
-        d = {"method": self.method}
-        d.update({k: getattr(self, k) for k in self.HS_DEFAULTS})
-        d.update(self.extra)
-        if self.hip_prefetch:
-            d["hip_prefetch"] = self.hip_prefetch
-        return d
 
-    def to_file(self, path: str):
-        with open(path, "w", encoding="utf8") as f:
-            json.dump(self.to_dict(), f, indent=4)
-
-    @classmethod
-    def from_file(cls, path: str):
-        with open(path, "r", encoding="utf8") as f:
-            return cls(**json.load(f))
-
-    @classmethod
-    def from_reference(cls, cfg):
-        if isinstance(cfg, cls):
-            return cfg
-        return cls(**{k: getattr(cfg, k) for k in cls.HS_DEFAULTS if hasattr(cfg, k)})
-
-
-class LucasKanadeConfig:
+class LucasKanadeConfig(MethodConfig):
     """The Lucas-Kanade fields of CvFlowConfig and their defaults (lk_window_size 15, lk_max_level 2, lk_step 1).
     fb_*, hs_* and other keys are carried in `.extra`."""
 
-    LK_DEFAULTS = dict(lk_window_size=15, lk_max_level=2, lk_step=1)
+    METHOD = "lukas-kanade"
+    DEFAULTS = LK_DEFAULTS = dict(lk_window_size=15, lk_max_level=2, lk_step=1)
+    HIP_KEYS = ("hip_prefetch",)
+    from_file = classmethod(_from_file)
 
     def __init__(self, method: str = "lukas-kanade", **kwargs):
-        if method != "lukas-kanade":
-            raise ValueError(f"LucasKanadeConfig is the 'lukas-kanade' method, got {method!r}")
-        self.method = method
-        for k, v in self.LK_DEFAULTS.items():
-            setattr(self, k, kwargs.pop(k, v))
-        for k in list(kwargs):
-            if k.startswith("hip_") and k != "hip_prefetch":
-                raise ValueError(f"{k!r} is not available with the lukas-kanade method (only 'hip_prefetch' is)")
-        self.hip_prefetch = int(kwargs.pop("hip_prefetch", 0) or 0)
-        self.extra = dict(kwargs)
+        super().__init__(method, **kwargs)
 
     def lk_kwargs(self) -> dict:
         """The keyword arguments of calc_optical_flow_lukas_kanade (cv.py:501-508)."""
         return dict(win_size=self.lk_window_size, max_level=self.lk_max_level, step=self.lk_step)
 
-    def to_dict(self) -> dict:
-        d = {"method": self.method}
-        d.update({k: getattr(self, k) for k in self.LK_DEFAULTS})
-        d.update(self.extra)
-        if self.hip_prefetch:
-            d["hip_prefetch"] = self.hip_prefetch
-        return d
 
-    def to_file(self, path: str):
-        with open(path, "w", encoding="utf8") as f:
-            json.dump(self.to_dict(), f, indent=4)
-
-    @classmethod
-    def from_file(cls, path: str):
-        with open(path, "r", encoding="utf8") as f:
-            return cls(**json.load(f))
-
-    @classmethod
-    def from_reference(cls, cfg):
-        if isinstance(cfg, cls):
-            return cfg
-        return cls(**{k: getattr(cfg, k) for k in cls.LK_DEFAULTS if hasattr(cfg, k)})
-
-
-class LiteFlowNetConfig:
+class LiteFlowNetConfig(MethodConfig):
     """The "liteflownet" method of CvFlowConfig (assets/configs/liteflownet.json: only the method key) and the weights
     that serve it: a path to the network's state dict or a dict of arrays (transflow_amd/liteflownet.py).  Other keys
-    are carried in `.extra`; the weights never go into to_dict()."""
+    are carried in `.extra`; the weights never go into to_dict(), so no file alone makes this config (no from_file)."""
+
+    METHOD = "liteflownet"
 
     def __init__(self, method: str = "liteflownet", weights=None, **kwargs):
-        if method != "liteflownet":
-            raise ValueError(f"LiteFlowNetConfig is the 'liteflownet' method, got {method!r}")
-        if weights is None:
+        if method == self.METHOD and weights is None:
             raise ValueError("LiteFlowNetConfig needs the network's weights (a path or a dict of arrays)")
-        self.method = method
+        super().__init__(method, **kwargs)
         self.weights = weights
-        for k in list(kwargs):
-            if k.startswith("hip_"):
-                raise ValueError(f"{k!r} is not available with the liteflownet method")
-        self.extra = dict(kwargs)
-
-    def to_dict(self) -> dict:
-        d = {"method": self.method}
-        d.update(self.extra)
-        return d
-
-    def to_file(self, path: str):
-        with open(path, "w", encoding="utf8") as f:
-            json.dump(self.to_dict(), f, indent=4)
 
     @classmethod
     def from_reference(cls, cfg, weights):
-        if isinstance(cfg, cls):
-            return cfg
-        return cls(weights=weights)
+        return super().from_reference(cfg, weights=weights)
 
 
-_UNSERVED_METHODS = ("lukas-kanade", "liteflownet")   # CvFlowSource.Method names this backend does not compute by default
+# The flow methods this backend serves: CvFlowSource.Method's name -> (the config class, the keyword argument of the
+# readers below that opts the method in (None: served as it is), how the refusal without it shows that keyword, the
+# constructor argument the opt-in's value becomes (None: it only switches)).
+METHODS = {
+    "farneback": (FlowConfig, None, None, None),
+    "horn-schunck": (HornSchunckConfig, None, None, None),
+    "lukas-kanade": (LucasKanadeConfig, "lucas_kanade", "lucas_kanade=True", None),
+    "liteflownet": (LiteFlowNetConfig, "liteflownet", "liteflownet=<weights>", "weights"),
+}
+CONFIG_CLASSES = tuple(row[0] for row in METHODS.values())
 
 
 def _method_name(method) -> str:
@@ -294,28 +273,26 @@ def _method_name(method) -> str:
     return name.replace("_", "-")
 
 
-def _refuse(method: str, lucas_kanade: bool, liteflownet=None) -> None:
-    if method == "lukas-kanade" and lucas_kanade:
-        return
-    if method == "liteflownet" and liteflownet is not None:
-        return
-    if method in _UNSERVED_METHODS:
-        hint = {"lukas-kanade": " (lucas_kanade=True serves it)",
-                "liteflownet": " (liteflownet=<weights> serves it)"}.get(method, "")
-        raise ValueError(f"transflow_amd does not implement the {method!r} flow method{hint}")
+def _serving(method, lucas_kanade, liteflownet):
+    """METHODS' row for a method as a reader needs it: (name or None, config class, constructor arguments from the
+    opt-in).  ValueError for a method whose opt-in was not given.  A name the table does not hold goes to FlowConfig
+    as it came (name None)."""
+    name = _method_name(method)
+    if name not in METHODS:
+        return None, FlowConfig, {}
+    cls, opt_in, shown, becomes = METHODS[name]
+    value = {"lucas_kanade": lucas_kanade or None, "liteflownet": liteflownet}.get(opt_in)
+    if opt_in is not None and value is None:
+        raise ValueError(f"transflow_amd does not implement the {name!r} flow method ({shown} serves it)")
+    return name, cls, ({becomes: value} if becomes else {})
 
 
 def flow_config_from_dict(d: dict, lucas_kanade: bool = False, liteflownet=None):
     """liteflownet: the network's weights (a path or a dict of arrays); with them a "liteflownet" config is served."""
-    method = _method_name(d.get("method", "farneback"))
-    _refuse(method, lucas_kanade, liteflownet)
-    if method == "liteflownet":
-        return LiteFlowNetConfig(**{**d, "method": method, "weights": liteflownet})
-    if method == "lukas-kanade":
-        return LucasKanadeConfig(**{**d, "method": method})
-    if method == "horn-schunck":
-        return HornSchunckConfig(**{**d, "method": method})
-    return FlowConfig(**d)
+    name, cls, given = _serving(d.get("method", "farneback"), lucas_kanade, liteflownet)
+    if name in (None, "farneback"):
+        return cls(**d)             # (the method as the file spells it: FlowConfig refuses what is not "farneback")
+    return cls(**{**d, "method": name, **given})
 
 
 def flow_config_from_file(path: str, lucas_kanade: bool = False, liteflownet=None):
@@ -329,16 +306,17 @@ def flow_config_from_file(path: str, lucas_kanade: bool = False, liteflownet=Non
 def flow_config_from_reference(cfg, lucas_kanade: bool = False, liteflownet=None):
     """A reference CvFlowConfig object (or one of ours, or None) -> FlowConfig, HornSchunckConfig, (lucas_kanade)
     LucasKanadeConfig or (liteflownet weights) LiteFlowNetConfig, by its method."""
-    if cfg is None:
-        return FlowConfig()
-    if isinstance(cfg, (FlowConfig, HornSchunckConfig, LucasKanadeConfig, LiteFlowNetConfig)):
+    if isinstance(cfg, CONFIG_CLASSES):
         return cfg
-    method = _method_name(getattr(cfg, "method", None))
-    _refuse(method, lucas_kanade, liteflownet)
-    if method == "liteflownet":
-        return LiteFlowNetConfig.from_reference(cfg, liteflownet)
-    if method == "lukas-kanade":
-        return LucasKanadeConfig.from_reference(cfg)
-    if method == "horn-schunck":
-        return HornSchunckConfig.from_reference(cfg)
-    return FlowConfig.from_reference(cfg)
+    _, cls, given = _serving(getattr(cfg, "method", None), lucas_kanade, liteflownet)
+    return cls.from_reference(cfg, **given)
+
+
+def flow_config_from_arg(cv_config, lucas_kanade: bool = False, liteflownet=None):
+    """The `cv_config` argument of FlowSource.from_args (source.py:365-411): a JSON path (the defaults when there is
+    no such file, source.py:405-410), a CvFlowConfig object, one of ours, or None."""
+    if isinstance(cv_config, str):
+        if not os.path.isfile(cv_config):
+            return FlowConfig()
+        return flow_config_from_file(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
+    return flow_config_from_reference(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)

@@ -21,22 +21,17 @@ INTEGRATION.md shows the three-line patch a maintainer would add instead.
 """
 from __future__ import annotations
 
-import os
-
 _saved = {}
 
 
 def _served_config(cv_config, horn_schunck: bool, lucas_kanade: bool = False, liteflownet=None) -> bool:
     """Whether the flow method a cv_config (a JSON path, a CvFlowConfig object, None) names is one this backend runs."""
-    from .config import HornSchunckConfig, flow_config_from_file, flow_config_from_reference
-    if cv_config is None or (isinstance(cv_config, str) and not os.path.isfile(cv_config)):
-        return True
-    try:
-        cfg = (flow_config_from_file(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
-               if isinstance(cv_config, str)
-               else flow_config_from_reference(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet))
+    from .config import HornSchunckConfig, flow_config_from_arg
+    try:                        # config.METHODS says which methods are served, and behind which of these opt-ins
+        cfg = flow_config_from_arg(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
     except ValueError:          # another flow method: the reference's own source
         return False
+    # (the library serves Horn-Schunck either way; the drop-in routes it here only on request)
     return horn_schunck or not isinstance(cfg, HornSchunckConfig)
 
 

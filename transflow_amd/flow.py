@@ -2,9 +2,9 @@
 
 `FlowSource` mirrors transflow/flow/sources/source.py:17-415 (Direction, LockMode,
 Builder with its seek/duration/repeat/lock arithmetic, the iterator protocol and
-post_process); `HipFlowSource` mirrors CvFlowSource's Farnebäck branch
+post_process); `HipFlowSource` mirrors CvFlowSource
 (transflow/flow/sources/cv.py:366-524): frames come from a frame provider, the
-flow from the GPU.  Items yielded are numpy float32 arrays of shape (H, W, 2),
+flow from the GPU, by the method the config names (the table `_METHODS`).  Items yielded are numpy float32 arrays of shape (H, W, 2),
 picklable, exactly what pipeline.py:85-86 puts on its queue.
 
 No HIP call happens before Builder.__enter__/build(): the reference forks the
@@ -19,8 +19,8 @@ import os
 import warnings
 import numpy as np
 
-from .config import (FlowConfig, HornSchunckConfig, LiteFlowNetConfig, LucasKanadeConfig, flow_config_from_file,
-                     flow_config_from_reference)
+from .config import (CONFIG_CLASSES, FlowConfig, HornSchunckConfig, LiteFlowNetConfig, LucasKanadeConfig,
+                     flow_config_from_arg, flow_config_from_reference)
 
 logger = logging.getLogger(__name__)
 
@@ -271,6 +271,9 @@ class FlowSource:
         self.output_frame_index = 0
         self.prev_flow = None
         self._pp = None  # device handle used by post_process, created on first use
+        # the resident tail (below): what read_next_flow handed out whose flow is still on the device, the mask on the
+        # device, and where the yielded arrays / DeviceFlows (transflow_amd/deviceflow.py) live
+        self._pending = self._mask_dev = self._flow_pool = self._flow_ring = None
         # the first pass starts where a checkpoint left off, later passes at start_frame (source.py:246-248)
         self.input_frame_index = 0
         self.start_frame, later_passes = ckpt_start_frame, start_frame
@@ -337,65 +340,132 @@ class FlowSource:
     def post_process(self, raw):
         """source.py:337-363 on the GPU (tf_fb_post_process_host): FORWARD inverts the push
         field with last-write-wins, both directions clip to the frame.  In place, like the
-        reference (so `prev_flow` sees the processed array, source.py:317)."""
-        flow = raw
-        if (isinstance(raw, np.ndarray) and np.issubdtype(raw.dtype, np.integer) and not self.flow_filters
-                and self.mask is None and self.kernel is None):
-            # a rounded archive (pipeline.py:506 writes numpy.round(flow).astype(int)): the reference clips
-            # and inverts the integer array in place; small integers are exact in float32
-            out = self.post_process(raw.astype(np.float32))
-            raw[...] = out.astype(raw.dtype)
-            return raw
+        reference (so `prev_flow` sees the processed array, source.py:317): the filters work on the array given, the
+        mask and the convolution kernel each make a new one, which the steps after them work on."""
+        if self._pending is not None and raw is self._pending:
+            return self._post_process_resident(raw)
+        from .flowops import convolve_post_process, polar_filter
+        # 1. a rounded archive (pipeline.py:506 writes numpy.round(flow).astype(int)): the reference clips and inverts
+        # the integer array in place; small integers are exact in float32
+        archive = raw if (isinstance(raw, np.ndarray) and np.issubdtype(raw.dtype, np.integer) and not self.flow_filters
+                          and self.mask is None and self.kernel is None) else None
+        flow = raw if archive is None else raw.astype(np.float32)
+        # 2. the library works on contiguous float32
         if not (isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.flags.c_contiguous):
-            flow = np.ascontiguousarray(raw, dtype=np.float32)
+            flow = np.ascontiguousarray(flow, dtype=np.float32)
+        pp, direction = self._post_handle(), self.direction.value
+        # 3. the filters, in order and in place (source.py:339-341; filters.py: lambdas of t, evaluated here): runs of
+        # scale/threshold/clip go to the device as one launch each, every polar filter as its own.  Where that is one
+        # run and nothing comes between it and the direction handling, the two share a launch (step 5).
+        fused = self.mask is None and self.kernel is None and not any(f.name == "polar" for f in self.flow_filters)
+        run = []
+        for f in [*self.flow_filters, None]:
+            if f is not None and f.name != "polar":
+                run.append((f.name, f.expr(self.t)))
+                continue
+            if run and not fused:
+                pp.post_process_host_ex(flow, None, run)
+                run = []
+            if f is not None:
+                polar_filter(flow, f.polar, self.t)
+        # 4. the mask multiply makes a NEW array (source.py:342-343: prev_flow sees the filters and not the mask); it
+        # shares its launch with the direction handling unless the convolution comes between them
+        if self.mask is not None:
+            flow = flow.copy()
+            pp.post_process_host_ex(flow, None if self.kernel is not None else direction, (), self.mask)
+        # 5. the convolution of both channels (source.py:344-348: a NEW array of the convolution's type, float64 unless
+        # the kernel is float32) which the direction handling and the clip then work on; or these two alone
+        if self.kernel is not None:
+            flow = convolve_post_process(flow, self.kernel, direction)
+        elif self.mask is None:
+            pp.post_process_host_ex(flow, direction, run)
+        if archive is None:
+            return flow
+        archive[...] = flow.astype(archive.dtype)
+        return archive
+
+    # ---- the resident tail ---------------------------------------------------------------------
+    # __next__ (source.py:293-321) calls read_next_flow() and hands its result straight to post_process().  When
+    # nothing can look at the raw flow in between (_resident_ok) a source that makes its flows on the device keeps
+    # them there through the filters, the mask and the direction handling, and only the final flow comes down, or
+    # none (a DeviceFlow).  Such a source's read_next_flow leaves the raw flow in a post-processing handle and
+    # returns _take_output(); post_process, given that very object back, fills it.  It says where the flow sits
+    # (_resident_flow) and how a host array is filled from there (_download).
+    device = None     # the device argument of the sources that take one
+
+    def _post_handle(self):
         if self._pp is None:
             from .farneback import Farneback
-            self._pp = Farneback(self.width, self.height, levels=0)
-        if any(f.name == "polar" for f in self.flow_filters):
-            # filters apply in order (source.py:339-341): runs of scale/threshold/clip go to the device as
-            # one launch each, every polar filter as its own; the rest of post_process follows unfiltered
-            from .flowops import polar_filter
-            run = []
-            for f in list(self.flow_filters) + [None]:
-                if f is not None and f.name != "polar":
-                    run.append((f.name, f.expr(self.t)))
-                    continue
-                if run:
-                    self._pp.post_process_host_ex(flow, None, run)
-                    run = []
-                if f is not None:
-                    polar_filter(flow, f.polar, self.t)
-            filters, self.flow_filters = self.flow_filters, []
-            try:
-                out = self.post_process(flow)
-            finally:
-                self.flow_filters = filters
-            return out
-        ops = [(f.name, f.expr(self.t)) for f in self.flow_filters]   # filters.py: lambdas of t, host side
-        if self.kernel is not None:
-            # source.py:339-348: filters in place, mask multiply into a new array, then the convolution
-            # of both channels (a NEW array of the convolution's type, float64 unless the kernel is
-            # float32) which the direction handling and the clip then work on
-            from .flowops import convolve_post_process
-            if ops:
-                self._pp.post_process_host_ex(flow, None, ops)
-            pre = flow
-            if self.mask is not None:
-                pre = flow.copy()
-                self._pp.post_process_host_ex(pre, None, (), self.mask)
-            return convolve_post_process(pre, self.kernel, self.direction.value)
-        if self.mask is None:
-            self._pp.post_process_host_ex(flow, self.direction.value, ops)
-            return flow
-        # the reference applies the filters IN PLACE on the raw flow (so prev_flow sees them) and
-        # then builds a NEW array with the mask multiply (source.py:339-343)
-        if ops:
-            self._pp.post_process_host_ex(flow, None, ops)
-        out = flow.copy()
-        self._pp.post_process_host_ex(out, self.direction.value, (), self.mask)
-        return out
+            self._pp = Farneback(self.width, self.height, levels=0, device=self.device)
+        return self._pp
+
+    def _resident_ok(self) -> bool:
+        """Nothing reads a raw flow or prev_flow on the host (the lock expressions do), and every step of
+        post_process has a device form."""
+        return (self.lock_expr_stay is None and self.lock_expr_skip is None and self.kernel is None
+                and not any(f.name == "polar" for f in self.flow_filters))
+
+    def _take_output(self, device_flows, depth: int):
+        """What the resident post_process fills: a DeviceFlow over a buffer of the source's ring (device_flows: True
+        or "ipc"), else a pinned host array of its pool; `depth` of them can be out at a time."""
+        shape = (self.height, self.width, 2)
+        if device_flows:
+            from .deviceflow import DeviceFlow, FlowRing
+            if self._flow_ring is None:
+                self._flow_ring = FlowRing(shape, slots=depth)
+            slot = self._flow_ring.take()
+            self._pending = DeviceFlow(shape, slot.flow_ptr, slot.ready, ring=self._flow_ring, slot=slot,
+                                       cross_process="ipc" if device_flows == "ipc" else None)
+        else:
+            if self._flow_pool is None:
+                from .device import ArrayPool
+                self._flow_pool = ArrayPool(shape, np.float32, limit=depth, pinned=True)
+            self._pending = self._flow_pool.take()
+        return self._pending
+
+    def _resident_flow(self):
+        """(handle, pair): where the flow behind `_pending` sits."""
+        raise NotImplementedError()
+
+    def _download(self, handle, pair: int, out: np.ndarray) -> None:
+        raise NotImplementedError()
+
+    def _post_process_resident(self, raw):
+        self._pending = None
+        handle, pair = self._resident_flow()
+        ops = [(f.name, f.expr(self.t)) for f in self.flow_filters]
+        if self.mask is not None and self._mask_dev is None:
+            from .device import DevBuffer
+            self._mask_dev = DevBuffer.from_array(
+                np.ascontiguousarray(self.mask, dtype=np.float32).reshape(self.height, self.width))
+        handle.post_process_ex(pair, self.direction.value, ops, None if self.mask is None else self._mask_dev.ptr)
+        if isinstance(raw, np.ndarray):
+            self._download(handle, pair, raw)
+            return raw
+        # a DeviceFlow: out of the handle's buffer (which the source writes again) into the flow's own, device to
+        # device on this thread's stream; the event behind the copy is what consumers wait for
+        import ctypes as C
+
+        from . import _lib
+        _lib.check(_lib.load().tf_dev_copy(C.c_void_p(raw.dev_ptr), C.c_void_p(handle.flow_ptr(pair)), raw.nbytes))
+        raw._ready.record()
+        raw.in_frame = True          # both directions of post_process end with the clip (source.py:361-362)
+        return raw
 
     def close(self):
+        if self._mask_dev is not None:
+            self._mask_dev.close()
+            self._mask_dev = None
+        self._pending = None
+        if self._flow_ring is not None:
+            # flows that left this process as IPC tokens: multiprocessing's Queue.get() frees the queue's slot before it
+            # unpickles, so the last put() of SourceProcess.run (pipeline.py:85-86) can return -- and this process end --
+            # before the consumer has opened the last flow's handle.  Wait (bounded) until every token on its way has
+            # been made and acknowledged; our own reference to the last flow goes first.
+            self.prev_flow = None
+            self._flow_ring.drain()
+        self._flow_ring = None      # (buffers live as long as a DeviceFlow the caller still holds)
+        self._flow_pool = None
         if self._pp is not None:
             self._pp.close()
             self._pp = None
@@ -540,11 +610,76 @@ class _Prefetch:
             self.thread.join(timeout=0.05)
 
 
+def _open_farneback(source):
+    from .farneback import Farneback
+
+    # Exactness belongs to the handle (tf_fb_set_exact): this source states what its configuration says, on OR off,
+    # and touches nothing process-wide -- sources that disagree may be open together, in any threads.
+    batch = source._batch_size()
+    fb = Farneback(source.width, source.height, device=source.device, frame_slots=batch + 1, max_pairs=batch,
+                   exact=bool(source.config.hip_exact_sums), **source.config.fb_kwargs())
+    fb.keep_expansions(True)  # the frame that was "next" stays expanded for its turn as "prev"
+    if source.config.hip_prefetch:
+        fb.async_io(True)     # the next frame up and the previous flow down beside this pair's kernels
+    return fb
+
+
+def _open_horn_schunck(source):
+    from .hornschunck import HornSchunck
+    return HornSchunck(source.width, source.height, device=source.device)
+
+
+def _open_lucas_kanade(source):
+    from .lucaskanade import LucasKanade
+    return LucasKanade(source.width, source.height, device=source.device)
+
+
+def _open_liteflownet(source):
+    from .liteflownet import LiteFlowNet
+    return LiteFlowNet(source.width, source.height, source.config.weights, device=source.device)
+
+
+def _previous_flow_or_zeros(source):
+    if source.prev_flow is not None:
+        return source.prev_flow
+    return np.zeros((source.height, source.width, 2), np.float32)
+
+
+@dataclasses.dataclass(frozen=True)
+class _Method:
+    """What HipFlowSource needs of a flow method, by the class of its config (_METHODS): this is where a method is
+    wired into the source."""
+    open: object                            # (source) -> the method's handle (imported here: no HIP call before build())
+    calc_kwargs: object = lambda config: {}     # (config) -> the keyword arguments of the handle's calc_slots
+    # (source) -> the flow set_initial_flow gets before a call; None: the method takes none.  `initial_flow_switch`:
+    # (config) -> whether the configuration asks for it; None: there is no switch, every call gets one.
+    initial_flow: object = None
+    initial_flow_switch: object = None
+    colour: bool = False                    # the method reads colour frames: grey ones are refused
+    # the handle post-processes its flows where they are (post_process_ex) and brings them down beside its kernels
+    # (async_io, get_flow_begin): the resident path exists.  For the others it is not built: their flows come down
+    # raw and FlowSource.post_process works on the host array, with a handle of its own.
+    resident: bool = False
+
+
+_METHODS = {
+    # cv.py:473-490; cv.py:478 with cv2.OPTFLOW_USE_INITIAL_FLOW: a copy of the previous flow, zeros before the first
+    FlowConfig: _Method(_open_farneback, initial_flow=_previous_flow_or_zeros,
+                        initial_flow_switch=lambda config: bool(config.fb_flags & 4), resident=True),
+    # cv.py:491-500: the previous (post-processed) flow, or None (the float64 chain from zeros)
+    HornSchunckConfig: _Method(_open_horn_schunck, HornSchunckConfig.hs_kwargs, initial_flow=lambda source: source.prev_flow),
+    # cv.py:501-508: no initial flow
+    LucasKanadeConfig: _Method(_open_lucas_kanade, LucasKanadeConfig.lk_kwargs),
+    # cv.py:464-465, 509-516: the two frames only, in colour
+    LiteFlowNetConfig: _Method(_open_liteflownet, colour=True),
+}
+assert set(_METHODS) == set(CONFIG_CLASSES)
+
+
 class HipFlowSource(FlowSource):
-    """CvFlowSource's Farnebäck, Horn-Schunck and Lucas-Kanade branches on the GPU (cv.py:434-521).  The config says
-    which: a FlowConfig (Farnebäck), a HornSchunckConfig or a LucasKanadeConfig.  Horn-Schunck and Lucas-Kanade flows
-    always come down to the host, where the post-process runs (each Horn-Schunck call starts from the previous,
-    post-processed, flow: cv.py:494; Lucas-Kanade takes no initial flow: cv.py:501-508)."""
+    """CvFlowSource's flow methods on the GPU (cv.py:434-521).  The config says which: its class is the key of
+    _METHODS above, where everything this source needs to know of a method is said.  Flows of a method without a
+    resident path always come down to the host, where the post-process runs."""
 
     class Builder(FlowSource.Builder):
 
@@ -576,6 +711,8 @@ class HipFlowSource(FlowSource):
 
     def __init__(self, provider, config: FlowConfig, *args, device: int | None = None, **kwargs):
         self.config = config
+        # (validate() refuses a config of no method's class)
+        self._method = next((m for cls, m in _METHODS.items() if isinstance(config, cls)), None)
         self.provider = provider
         self.device = device
         self._prev_frame = None  # the decoded frame behind prev_gray
@@ -584,52 +721,20 @@ class HipFlowSource(FlowSource):
         self._batch_left = 0     # FlowConfig.hip_batch: flows of the last call not handed out yet ...
         self._batch_pos = 0      # ... and which pair of the call comes next
         self._pending_pair = 0   # the pair of the call behind the array read_next_flow handed out
-        self._pending = None     # array handed out by read_next_flow whose flow is still on the device
-        self._mask_dev = None
-        self._flow_pool = None
-        self._flow_ring = None   # FlowConfig.hip_device_flows: the device buffers the yielded DeviceFlows live in
         self._prefetch = None
         self._download_token = None
         FlowSource.__init__(self, *args, **kwargs)
 
     def validate(self):
         super().validate()
-        if not isinstance(self.config, (FlowConfig, HornSchunckConfig, LucasKanadeConfig, LiteFlowNetConfig)):
+        if self._method is None:
             raise ValueError("Attribute config has incorrect type")
 
-    @property
-    def _is_hs(self) -> bool:
-        return isinstance(self.config, HornSchunckConfig)
-
-    @property
-    def _is_lk(self) -> bool:
-        return isinstance(self.config, LucasKanadeConfig)
-
-    @property
-    def _is_lfn(self) -> bool:
-        return isinstance(self.config, LiteFlowNetConfig)
-
     def _handle(self):
-        if self._fb is None and self._is_lfn:
-            from .liteflownet import LiteFlowNet
-            self._fb = LiteFlowNet(self.width, self.height, self.config.weights, device=self.device)
-        if self._fb is None and self._is_lk:
-            from .lucaskanade import LucasKanade
-            self._fb = LucasKanade(self.width, self.height, device=self.device)   # (post_process keeps its own handle)
-        if self._fb is None and self._is_hs:
-            from .hornschunck import HornSchunck
-            self._fb = HornSchunck(self.width, self.height, device=self.device)   # (post_process keeps its own handle)
         if self._fb is None:
-            from .farneback import Farneback
-            # Exactness belongs to the handle (tf_fb_set_exact): this source states what its configuration says, on OR off,
-            # and touches nothing process-wide -- sources that disagree may be open together, in any threads.
-            batch = self._batch_size()
-            self._fb = Farneback(self.width, self.height, device=self.device, frame_slots=batch + 1, max_pairs=batch,
-                                 exact=bool(getattr(self.config, "hip_exact_sums", False)), **self.config.fb_kwargs())
-            self._fb.keep_expansions(True)  # the frame that was "next" stays expanded for its turn as "prev"
-            if getattr(self.config, "hip_prefetch", 0):
-                self._fb.async_io(True)     # the next frame up and the previous flow down beside this pair's kernels
-            self._pp = self._fb  # one handle serves both calls
+            self._fb = self._method.open(self)
+            if self._method.resident:
+                self._pp = self._fb  # one handle serves both calls
         return self._fb
 
     # The frame the reference keeps as `prev_gray` (cv.py:456, 519) lives in a frame slot of the handle; on the
@@ -652,11 +757,9 @@ class HipFlowSource(FlowSource):
 
     def _ingest(self, slot: int, frame) -> None:
         a = np.asarray(frame)
-        if self._is_lfn:                             # cv.py:464-465, 509-516: the network reads colour
-            if a.ndim != 3:
-                raise ValueError("the liteflownet method needs colour (BGR) frames; the frame provider gives grey ones")
-            self._handle().set_frame_bgr(slot, a)
-        elif a.ndim == 2:
+        if self._method.colour and a.ndim != 3:
+            raise ValueError(f"the {self.config.method} method needs colour (BGR) frames; the frame provider gives grey ones")
+        if a.ndim == 2:
             self._handle().set_frame(slot, a)
         else:
             self._handle().set_frame_bgr(slot, a)
@@ -676,11 +779,11 @@ class HipFlowSource(FlowSource):
         self._batch_left = self._batch_pos = 0     # (an external rewind while a hip_batch call still had flows queued)
 
     def _batch_size(self) -> int:
-        return max(1, int(getattr(self.config, "hip_batch", 1))) if self._resident_ok() else 1
+        return max(1, int(self.config.hip_batch)) if self._resident_ok() else 1
 
     def _advance(self, want: int = 1) -> int:
         """cv.py:460-490 up to the call: read a frame, make it grey in a slot no pair still needs, order (prev, next) by
-        direction, run Farnebäck on the two slots.  The flow stays on the device.  `want` > 1 (FlowConfig.hip_batch): read
+        direction, run the method's handle on the two slots.  The flow stays on the device.  `want` > 1 (FlowConfig.hip_batch): read
         up to that many frames and run their consecutive pairs in ONE call -- frame slots are a ring of hip_batch + 1, the
         last frame of a call is the first of the next; returns how many pairs were computed."""
         frames = []
@@ -706,17 +809,10 @@ class HipFlowSource(FlowSource):
             older.append(slot)
             newer.append(new_slot)
             slot = new_slot
-        kw = {}
-        if self._is_hs:                              # cv.py:491-500: the previous flow, or None (the float64 chain)
-            fb.set_initial_flow(0, self.prev_flow)
-            kw = self.config.hs_kwargs()
-        elif self._is_lk:                            # cv.py:501-508: no initial flow
-            kw = self.config.lk_kwargs()
-        elif self._is_lfn:                           # cv.py:509-516: the two frames only
-            pass
-        elif self._uses_initial_flow():              # cv.py:478: a copy of the previous flow, zeros before the first
-            init = self.prev_flow if self.prev_flow is not None else np.zeros((self.height, self.width, 2), np.float32)
-            fb.set_initial_flow(0, init)
+        method = self._method
+        if method.initial_flow is not None and (method.initial_flow_switch is None or self._uses_initial_flow()):
+            fb.set_initial_flow(0, method.initial_flow(self))
+        kw = method.calc_kwargs(self.config)
         if self.direction == FlowSource.Direction.FORWARD:      # cv.py:467-472
             fb.calc_slots(older, newer, **kw)
         elif self.direction == FlowSource.Direction.BACKWARD:
@@ -726,24 +822,18 @@ class HipFlowSource(FlowSource):
         self._prev_slot, self._prev_frame = slot, frames[-1]
         return len(frames)
 
-    # ---- resident form of one iteration -------------------------------------------------------
-    # __next__ (source.py:293-321) calls read_next_flow() and hands its result straight to
-    # post_process().  When nothing can look at the raw flow in between (no lock expressions: they are
-    # what reads prev_flow) the flow stays on the device from the Farnebäck call through the filters,
-    # the mask and the direction handling, only the new frame goes up and only the final flow comes
-    # down -- one transfer each instead of two frames up and the flow down, up and down again.  The
+    # ---- resident form of one iteration (FlowSource's resident tail): only the new frame goes up and only the final
+    # flow comes down -- one transfer each instead of two frames up and the flow down, up and down again.  The
     # public next() / post_process() pair keeps working on host arrays for any other caller.
     def _uses_initial_flow(self) -> bool:
-        return (not self._is_hs and not self._is_lk and not self._is_lfn
-                and bool(self.config.fb_flags & 4))      # cv2.OPTFLOW_USE_INITIAL_FLOW
+        """The configuration's switch for an initial flow (cv2.OPTFLOW_USE_INITIAL_FLOW) is on."""
+        switch = self._method.initial_flow_switch
+        return switch is not None and switch(self.config)
 
     def _resident_ok(self) -> bool:
-        if self._is_hs or self._is_lk or self._is_lfn:
-            return False     # (a device-resident post-process of Horn-Schunck, Lucas-Kanade or LiteFlowNet flows is not built)
-        # with OPTFLOW_USE_INITIAL_FLOW every call starts from the previous OUTPUT (cv.py:478 passes a copy of
+        # with the initial flow switched on every call starts from the previous OUTPUT (cv.py:478 passes a copy of
         # prev_flow, which __next__ has post-processed in place): that array lives on the host
-        return (self.lock_expr_stay is None and self.lock_expr_skip is None and self.kernel is None
-                and not self._uses_initial_flow() and not any(f.name == "polar" for f in self.flow_filters))
+        return self._method.resident and not self._uses_initial_flow() and FlowSource._resident_ok(self)
 
     def read_next_flow(self):
         if not self._resident_ok():
@@ -760,55 +850,22 @@ class HipFlowSource(FlowSource):
         self._batch_pos += 1
         self._batch_left -= 1
         self.input_frame_index += 1
-        if getattr(self.config, "hip_device_flows", False):
-            # the flow stays in HBM: a DeviceFlow over a buffer of the source's ring, filled by post_process
-            from .deviceflow import DeviceFlow, FlowRing
-            if self._flow_ring is None:
-                self._flow_ring = FlowRing((self.height, self.width, 2), slots=4 + self.config.hip_prefetch)
-            slot = self._flow_ring.take()
-            self._pending = DeviceFlow((self.height, self.width, 2), slot.flow_ptr, slot.ready, ring=self._flow_ring, slot=slot,
-                                       cross_process="ipc" if self.config.hip_device_flows == "ipc" else None)
-            return self._pending
-        if self._flow_pool is None:
-            from .device import ArrayPool
-            self._flow_pool = ArrayPool((self.height, self.width, 2), np.float32, limit=4 + self.config.hip_prefetch, pinned=True)
-        self._pending = self._flow_pool.take()       # filled by post_process
-        return self._pending
+        # hip_device_flows: the flow stays in HBM, in a DeviceFlow that post_process fills
+        return self._take_output(self.config.hip_device_flows, 4 + self.config.hip_prefetch)
 
-    def post_process(self, raw):
-        if self._pending is None or raw is not self._pending:
-            return FlowSource.post_process(self, raw)
-        self._pending = None
-        fb = self._fb
-        ops = [(f.name, f.expr(self.t)) for f in self.flow_filters]
-        mask_dev = None
-        if self.mask is not None:
-            if self._mask_dev is None:
-                from .device import DevBuffer
-                self._mask_dev = DevBuffer.from_array(
-                    np.ascontiguousarray(self.mask, dtype=np.float32).reshape(self.height, self.width))
-            mask_dev = self._mask_dev.ptr
-        pair = self._pending_pair
-        fb.post_process_ex(pair, self.direction.value, ops, mask_dev)
-        if not isinstance(raw, np.ndarray):
-            # a DeviceFlow: out of the handle's result buffer (the next call but one writes it again) into the flow's own,
-            # device to device on this thread's stream; the event behind the copy is what consumers wait for
-            from . import _lib
-            import ctypes as C
-            _lib.check(_lib.load().tf_dev_copy(C.c_void_p(raw.dev_ptr), C.c_void_p(fb.flow_ptr(pair)), raw.nbytes))
-            raw._ready.record()
-            raw.in_frame = True          # both directions of post_process end with the clip (source.py:361-362)
-            return raw
+    def _resident_flow(self):
+        return self._fb, self._pending_pair
+
+    def _download(self, fb, pair, out):
         if self._prefetch is not None:
             # the worker thread: the flow starts its way down and the worker goes on to the next frame; it hands this
             # array to the consumer only once the transfer has ended (_Prefetch._run)
-            self._download_token = fb.get_flow_begin(pair, raw)
+            self._download_token = fb.get_flow_begin(pair, out)
         else:
-            fb.get_flow_into(pair, raw)
-        return raw
+            fb.get_flow_into(pair, out)
 
     def next(self):
-        """cv.py:460-490: (prev, next) ordered by direction, one Farnebäck call; the flow as a host array."""
+        """cv.py:460-490: (prev, next) ordered by direction, one call of the method; the flow as a host array."""
         self._advance()
         return self._handle().get_flow(0)
 
@@ -819,7 +876,7 @@ class HipFlowSource(FlowSource):
     # `hip_prefetch` flows ahead, queueing everything it launches on a library stream of its own (tf_thread_stream),
     # beside the compositor's uploads, kernels and downloads.  ctypes releases the GIL inside every library call.
     def __next__(self):
-        if not getattr(self.config, "hip_prefetch", 0):
+        if not self.config.hip_prefetch:
             return FlowSource.__next__(self)
         if self._prefetch is None:
             self._prefetch = _Prefetch(self, self.config.hip_prefetch)
@@ -829,28 +886,14 @@ class HipFlowSource(FlowSource):
         if self._prefetch is not None:
             self._prefetch.stop()
             self._prefetch = None
-            if self._fb is not None and not self._is_hs and not self._is_lk and not self._is_lfn:
+            if self._fb is not None and self._method.resident:
                 self._fb.async_io(False)    # waits for a download the worker left on its way
-        if self._mask_dev is not None:
-            self._mask_dev.close()
-            self._mask_dev = None
-        self._pending = None
-        if self._flow_ring is not None:
-            # flows that left this process as IPC tokens: multiprocessing's Queue.get() frees the queue's slot before it
-            # unpickles, so the last put() of SourceProcess.run (pipeline.py:85-86) can return -- and this process end --
-            # before the consumer has opened the last flow's handle.  Wait (bounded) until every token on its way has
-            # been made and acknowledged; our own reference to the last flow goes first.
-            self.prev_flow = None
-            self._flow_ring.drain()
-        self._flow_ring = None      # (buffers live as long as a DeviceFlow the caller still holds)
-        if self._fb is not None:
-            if self._pp is not None and self._pp is not self._fb:
-                self._pp.close()
-            self._fb.close()
-            self._fb = None
-            self._pp = None
-        else:
-            FlowSource.close(self)
+        fb, self._fb = self._fb, None
+        if self._pp is fb:
+            self._pp = None                 # (one handle serves both calls: closed once, below)
+        FlowSource.close(self)
+        if fb is not None:
+            fb.close()
         self.provider.release()
 
     @classmethod
@@ -863,29 +906,19 @@ class HipFlowSource(FlowSource):
         liteflownet: the network's weights (a path or a dict of arrays), with which a config naming "liteflownet" is.  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399);
         use_mvs: codec motion vectors (source.py:400-402) go to MotionVectorFlowSource (transflow_amd/motionvectors.py),
         `flow_path` being a video path for PyAV (`avformat::path` as the reference splits it) or a vector provider."""
+        common = dict(direction=direction, mask_path=mask_path, kernel_path=kernel_path, flow_filters=flow_filters,
+                      seek_ckpt=seek_ckpt, seek_time=seek_time, duration_time=duration_time, repeat=repeat,
+                      lock_expr=lock_expr, lock_mode=lock_mode)
         if isinstance(flow_path, str) and flow_path.split("::")[-1].endswith(".flow.zip"):
             from .archive import ArchiveFlowSource
-            return ArchiveFlowSource.Builder(flow_path.split("::")[-1], direction=direction, mask_path=mask_path,
-                                             kernel_path=kernel_path, flow_filters=flow_filters, seek_ckpt=seek_ckpt,
-                                             seek_time=seek_time, duration_time=duration_time, repeat=repeat,
-                                             lock_expr=lock_expr, lock_mode=lock_mode)
+            return ArchiveFlowSource.Builder(flow_path.split("::")[-1], **common)
         if use_mvs:                                        # source.py:381-384, 400-402
             from .motionvectors import MotionVectorFlowSource
             avformat = None
             if isinstance(flow_path, str) and "::" in flow_path:
                 avformat, flow_path = flow_path.split("::")
-            return MotionVectorFlowSource.Builder(flow_path, avformat, direction=direction, mask_path=mask_path,
-                                                  kernel_path=kernel_path, flow_filters=flow_filters, seek_ckpt=seek_ckpt,
-                                                  seek_time=seek_time, duration_time=duration_time, repeat=repeat,
-                                                  lock_expr=lock_expr, lock_mode=lock_mode)
-        if isinstance(cv_config, str):
-            config = (flow_config_from_file(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
-                      if os.path.isfile(cv_config) else FlowConfig())
-        else:
-            config = flow_config_from_reference(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
+            return MotionVectorFlowSource.Builder(flow_path, avformat, **common)
+        config = flow_config_from_arg(cv_config, lucas_kanade=lucas_kanade, liteflownet=liteflownet)
         if isinstance(flow_path, str) and "::" in flow_path:
             flow_path = flow_path.split("::")[1]
-        return cls.Builder(flow_path, config, size, direction=direction, mask_path=mask_path,
-                           kernel_path=kernel_path, flow_filters=flow_filters, seek_ckpt=seek_ckpt,
-                           seek_time=seek_time, duration_time=duration_time, repeat=repeat, lock_expr=lock_expr,
-                           lock_mode=lock_mode)
+        return cls.Builder(flow_path, config, size, **common)

@@ -214,10 +214,6 @@ class MotionVectorFlowSource(FlowSource):
         self.provider = provider
         self.device, self.device_flows = device, device_flows
         self._mv = None
-        self._pending = None     # array (or DeviceFlow) handed out by read_next_flow whose flow is still on the device
-        self._mask_dev = None
-        self._flow_pool = None
-        self._flow_ring = None
         FlowSource.__init__(self, *args, **kwargs)
 
     def validate(self):
@@ -231,14 +227,6 @@ class MotionVectorFlowSource(FlowSource):
             self._mv = MotionVectors(self.width, self.height, device=self.device)
         return self._mv
 
-    def _post_handle(self):
-        if self._pp is None:
-            if self.device is not None:
-                check(_lib.load().tf_init(int(self.device)))
-            from .farneback import Farneback
-            self._pp = Farneback(self.width, self.height, levels=0)
-        return self._pp
-
     def rewind(self):
         """av.py:55-59: seek to the start and skip the frames up to and including the start frame."""
         FlowSource.rewind(self)
@@ -250,12 +238,8 @@ class MotionVectorFlowSource(FlowSource):
         """av.py:61-77: the next frame's vectors painted into a new host array."""
         return self._handle().rasterize(self.provider.read())
 
-    # ---- resident form of one iteration (as HipFlowSource's): the painted flow never leaves the device before the
-    # filters, the mask and the direction handling have run on it
-    def _resident_ok(self) -> bool:
-        return (self.lock_expr_stay is None and self.lock_expr_skip is None and self.kernel is None
-                and not any(f.name == "polar" for f in self.flow_filters))
-
+    # ---- resident form of one iteration (FlowSource's resident tail): the painted flow never leaves the device before
+    # the filters, the mask and the direction handling have run on it
     def read_next_flow(self):
         if not self._resident_ok():
             return FlowSource.read_next_flow(self)
@@ -264,58 +248,17 @@ class MotionVectorFlowSource(FlowSource):
         vectors = self.provider.read()
         self._handle().rasterize_into(vectors, self._post_handle().flow_ptr(0))
         self.input_frame_index += 1
-        shape = (self.height, self.width, 2)
-        if self.device_flows:
-            from .deviceflow import DeviceFlow, FlowRing
-            if self._flow_ring is None:
-                self._flow_ring = FlowRing(shape, slots=4)
-            slot = self._flow_ring.take()
-            self._pending = DeviceFlow(shape, slot.flow_ptr, slot.ready, ring=self._flow_ring, slot=slot,
-                                       cross_process="ipc" if self.device_flows == "ipc" else None)
-            return self._pending
-        if self._flow_pool is None:
-            from .device import ArrayPool
-            self._flow_pool = ArrayPool(shape, np.float32, limit=4, pinned=True)
-        self._pending = self._flow_pool.take()       # filled by post_process
-        return self._pending
+        return self._take_output(self.device_flows, 4)
 
-    def post_process(self, raw):
-        if self._pending is None or raw is not self._pending:
-            return FlowSource.post_process(self, raw)
-        self._pending = None
-        pp = self._pp
-        ops = [(f.name, f.expr(self.t)) for f in self.flow_filters]
-        mask_dev = None
-        if self.mask is not None:
-            if self._mask_dev is None:
-                from .device import DevBuffer
-                self._mask_dev = DevBuffer.from_array(
-                    np.ascontiguousarray(self.mask, dtype=np.float32).reshape(self.height, self.width))
-            mask_dev = self._mask_dev.ptr
-        pp.post_process_ex(0, self.direction.value, ops, mask_dev)
-        lib = _lib.load()
-        if not isinstance(raw, np.ndarray):
-            # a DeviceFlow: out of the handle's buffer (the next frame is painted there) into the flow's own, device
-            # to device on this thread's stream; the event behind the copy is what consumers wait for
-            check(lib.tf_dev_copy(C.c_void_p(raw.dev_ptr), C.c_void_p(pp.flow_ptr(0)), raw.nbytes))
-            raw._ready.record()
-            raw.in_frame = True          # both directions of post_process end with the clip (source.py:361-362)
-            return raw
-        check(lib.tf_dev_download(C.c_void_p(raw.ctypes.data), C.c_void_p(pp.flow_ptr(0)), raw.nbytes))
-        return raw
+    def _resident_flow(self):
+        return self._pp, 0
+
+    def _download(self, pp, pair, out):
+        check(_lib.load().tf_dev_download(C.c_void_p(out.ctypes.data), C.c_void_p(pp.flow_ptr(pair)), out.nbytes))
 
     def close(self):
-        if self._mask_dev is not None:
-            self._mask_dev.close()
-            self._mask_dev = None
-        self._pending = None
-        if self._flow_ring is not None:
-            self.prev_flow = None        # our own reference to the last flow goes first (HipFlowSource.close says why)
-            self._flow_ring.drain()
-        self._flow_ring = None           # (buffers live as long as a DeviceFlow the caller still holds)
-        self._flow_pool = None
+        FlowSource.close(self)
         if self._mv is not None:
             self._mv.close()
             self._mv = None
-        FlowSource.close(self)
         self.provider.release()
