@@ -393,16 +393,32 @@ int tf_lk_stage_trace(tf_lk *lk, int prev_slot, int next_slot, int win_size, int
  * calc_optical_flow_liteflownet(prev, next) of cv.py:509-516: the network on the pair's BGR frames (x 1/255, bilinear
  * to Hp x Wp = W, H rounded up to multiples of 32, the per-role mean subtracted), the flow x 20 resized back to W x H
  * and scaled by W / Wp, H / Hp: a float32 [H][W][2] per pair, for up to max_pairs (<= TF_LFN_MAX_PAIRS) pairs per
- * call, all batched.  Float32 throughout; the convolutions sum in their own order, the correlation in the reference's
- * (tests/lfn_ref.py).  The weights are the caller's: tf_lfn_set_weights takes every layer's weight and bias as one
- * float32 blob in the order of transflow_amd/liteflownet.py param_spec() and repacks them on the device.  W and H
- * must exceed 32 (at 32 or less the reference divides by zero in its backwarp).  A frame slot holds the frame
- * (uint8 BGR, W x H); nothing computed from it is kept between calls (a frame's features depend on its role). */
+ * call, all batched.  Float32 throughout in the default precision; the convolutions sum in their own order, the
+ * correlation in the reference's (tests/lfn_ref.py).  tf_lfn_set_precision chooses, per handle, how the network's
+ * convolutions (and nothing else: netScaleX/Y, the correlation, the transposed convs, backwarp and the resizes never
+ * change) multiply.  With q(v) = v rounded to bfloat16, ties to even:
+ *   TF_LFN_F32     sum x w + b in float32 (the default)
+ *   TF_LFN_BF16    sum q(x) q(w) + b: activations are rounded where a convolution reads them (they stay float32 in
+ *                  memory), weights once; products are exact in float32, sums, bias, LeakyReLU and residual float32
+ *   TF_LFN_BF16X3  with xh = q(x), xl = q(x - xh), wh = q(w), wl = q(w - wh):
+ *                  sum (xh wh + xh wl + xl wh) + b, one float32 chain over K ascending that takes, for each step of
+ *                  16 k, xh wh, then xh wl, then xl wh
+ * The mode may be set before or after the weights and between calls; another value is TF_ERR_ARG and the handle keeps
+ * its mode.  Every mode is bit-identical from run to run and for a pair alone or in a batch.  The weights are the
+ * caller's: tf_lfn_set_weights takes every layer's weight and bias as one float32 blob in the order of
+ * transflow_amd/liteflownet.py param_spec() and repacks them on the device.  W and H must exceed 32 (at 32 or less the
+ * reference divides by zero in its backwarp).  A frame slot holds the frame (uint8 BGR, W x H); nothing computed from
+ * it is kept between calls (a frame's features depend on its role). */
 #define TF_LFN_MAX_PAIRS 16
 typedef struct tf_lfn tf_lfn;
 int tf_lfn_create(tf_lfn **out, int width, int height, int frame_slots, int max_pairs);
 void tf_lfn_destroy(tf_lfn *lfn);
 int tf_lfn_set_weights(tf_lfn *lfn, const float *blob, long long n_floats);
+#define TF_LFN_F32 0
+#define TF_LFN_BF16 1
+#define TF_LFN_BF16X3 2
+int tf_lfn_set_precision(tf_lfn *lfn, int precision);
+int tf_lfn_get_precision(tf_lfn *lfn, int *precision);
 int tf_lfn_set_frame_bgr(tf_lfn *lfn, int slot, const uint8_t *bgr, int src_width, int src_height, ptrdiff_t stride);
 int tf_lfn_calc_slots(tf_lfn *lfn, int n_pairs, const int *prev_slots, const int *next_slots);
 int tf_lfn_get_flow(tf_lfn *lfn, int pair, float *flow_out /* [H][W][2] */);
@@ -410,10 +426,10 @@ int tf_lfn_flow_ptr(tf_lfn *lfn, int pair, void **dev);
 /* Stage entry points, host arrays in and out, activations NHWC float32.  conv: layer `layer` of param_spec's layer
    list on n images h x w, its Cin input channels at in_off of in_cs, written at out_off of out_cs (the other channels
    of out are kept), plus the residual at res_off of res_cs when res is not null; bias and LeakyReLU as the layer has
-   them.  deconv: a depthwise 4x4 stride-2 transposed conv [n][h][w][C] -> [n][2h][2w][C].  correlation:
-   LeakyReLU(correlation) [n][ceil(h/s)][ceil(w/s)][49].  backwarp: in [n][h][w][c] at flow [n][h][w][2] x scale.
-   regularize_tail: the level's -d^2 / softmax / netScaleX, Y / divisor on dist [n][h][w][k^2] and flow [n][h][w][2].
-   prep: a slot's frame in role 0 (one) or 1 (two), [Hp][Wp][3]. */
+   them, in the handle's precision.  deconv: a depthwise 4x4 stride-2 transposed conv [n][h][w][C] -> [n][2h][2w][C].
+   correlation: LeakyReLU(correlation) [n][ceil(h/s)][ceil(w/s)][49].  backwarp: in [n][h][w][c] at flow [n][h][w][2]
+   x scale.  regularize_tail: the level's -d^2 / softmax / netScaleX, Y / divisor on dist [n][h][w][k^2] and flow
+   [n][h][w][2].  prep: a slot's frame in role 0 (one) or 1 (two), [Hp][Wp][3]. */
 int tf_lfn_stage_conv(tf_lfn *lfn, int layer, int n, int h, int w, const float *in, int in_cs, int in_off,
                       const float *res, int res_cs, int res_off, float *out, int out_cs, int out_off);
 int tf_lfn_stage_deconv(tf_lfn *lfn, int layer, int n, int h, int w, const float *in, float *out);

@@ -156,6 +156,8 @@ PROTOTYPES = {
     "tf_lfn_create": (_I, [_PP, _I, _I, _I, _I]),
     "tf_lfn_destroy": (None, [_P]),
     "tf_lfn_set_weights": (_I, [_P, _P, C.c_longlong]),
+    "tf_lfn_set_precision": (_I, [_P, _I]),
+    "tf_lfn_get_precision": (_I, [_P, _PI]),
     "tf_lfn_set_frame_bgr": (_I, [_P, _I, _P, _I, _I, C.c_ssize_t]),
     "tf_lfn_calc_slots": (_I, [_P, _I, _PI, _PI]),
     "tf_lfn_get_flow": (_I, [_P, _I, _P]),

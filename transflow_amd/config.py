@@ -6,7 +6,8 @@ backend unchanged.
   FlowConfig    <- CvFlowConfig, transflow/flow/sources/cv.py:271-363 (the fb_* fields)
   HornSchunckConfig <- the same, method "horn-schunck" (the hs_* fields)
   LucasKanadeConfig <- the same, method "lukas-kanade" (the lk_* fields; opt-in: lucas_kanade=True)
-  LiteFlowNetConfig <- the same, method "liteflownet" (no fields; opt-in: liteflownet=<weights path or dict>)
+  LiteFlowNetConfig <- the same, method "liteflownet" (no fields; opt-in: liteflownet=<weights path or dict>;
+                       hip_lfn_precision chooses how its convolutions multiply)
 
 The four are MethodConfig subclasses; METHODS is the one table of the methods served and of what opts each in, which
 the flow_config_from_* readers (and through them HipFlowSource.from_args and the drop-in) ask.
@@ -89,6 +90,14 @@ def _exact_sums(v):
     return bool(parse_bool_arg(v, False))
 
 
+def _lfn_precision(v):
+    if v is None:
+        return "f32"
+    if not isinstance(v, str) or v not in ("f32", "bf16", "bf16x3"):
+        raise ValueError(f"hip_lfn_precision {v!r} is not 'f32', 'bf16' or 'bf16x3'")
+    return v
+
+
 def _device_flows(v):
     return "ipc" if isinstance(v, str) and v.lower() == "ipc" else parse_bool_arg(v, False)
 
@@ -114,6 +123,10 @@ _HIP_KEYS = {
     # pair leaves most of the chip idle at the coarse levels, a batch of four costs 0.6 of four single calls.  Flows
     # still come out one at a time, in order, each post-processed with its own t.
     "hip_batch": lambda v: max(1, int(v or 1)),
+    # "hip_lfn_precision": "bf16" or "bf16x3" -- LiteFlowNet's convolutions multiply bfloat16 operands on the bf16 matrix
+    # cores ("bf16": both operands rounded to bfloat16; "bf16x3": each split into a bfloat16 pair, three products) and
+    # sum in float32; "f32" (the default) is float32 throughout.  Only the liteflownet method takes it.
+    "hip_lfn_precision": _lfn_precision,
 }
 
 
@@ -127,6 +140,7 @@ class MethodConfig:
     HIP_KEYS: tuple = ()        # the keys of _HIP_KEYS the method accepts; another `hip_*` key is a ValueError
     # the attributes of the keys a method does not accept: what they mean when they are not given
     hip_exact_sums, hip_prefetch, hip_device_flows, hip_batch = False, 0, False, 1
+    hip_lfn_precision = "f32"
 
     def __init__(self, method: str, **kwargs):
         if method != self.METHOD:
@@ -181,7 +195,7 @@ class FlowConfig(MethodConfig):
     METHOD = "farneback"
     DEFAULTS = FB_DEFAULTS = dict(fb_pyr_scale=0.5, fb_levels=3, fb_winsize=15, fb_iterations=3, fb_poly_n=5,
                                   fb_poly_sigma=1.2, fb_flags=0)
-    HIP_KEYS = tuple(_HIP_KEYS)
+    HIP_KEYS = ("hip_exact_sums", "hip_prefetch", "hip_device_flows", "hip_batch")
     from_file = classmethod(_from_file)
 
     def __init__(self, method: str = "farneback", **kwargs):
@@ -239,6 +253,7 @@ class LiteFlowNetConfig(MethodConfig):
     are carried in `.extra`; the weights never go into to_dict(), so no file alone makes this config (no from_file)."""
 
     METHOD = "liteflownet"
+    HIP_KEYS = ("hip_lfn_precision",)
 
     def __init__(self, method: str = "liteflownet", weights=None, **kwargs):
         if method == self.METHOD and weights is None:

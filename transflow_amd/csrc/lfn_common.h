@@ -25,7 +25,30 @@ struct Layer {
     int nt, npad;           // MFMA N tiles of 32 per block, Cout padded to a multiple of 32 * nt
     long long pk_off;       // float offset of the packed [K][npad] weights (convolutions)
     int cls;
+    int kpad;               // K rounded up to QCONV_BK: the row length of the layer's bf16 weights [npad][kpad]
+    long long q_off;        // element offset of those rows in a bf16 plane (hi and lo planes share the layout)
 };
+
+// One convolution launch (k_lfn_conv, liteflownet.hip; k_lfn_conv_q, lfn_conv_bf16.hip).
+struct ConvArgs {
+    const float *in;     // [n][hin][win][in_cs], the layer's input channels at in_off ...
+    const float *wt;     // packed [K][npad], K ordered (ky, kx, ci)
+    const float *bias;   // [cout]
+    float *out;          // [n][ho][wo][out_cs], written at out_off ...
+    const float *res;    // optional residual [n][ho][wo][res_cs] at res_off
+    int in_cs, in_off, out_cs, out_off, res_cs, res_off;
+    int hin, win, ho, wo, M;
+    int cin, cout, kh, kw, stride, ph, pw, K, npad, leaky;
+};
+
+constexpr int QCONV_BK = 32;  // the bf16 kernel's K chunk: two k-steps of v_mfma_f32_32x32x16_bf16
+
+// lfn_conv_bf16.hip: the convolution of the bf16 (passes 1) and bf16x3 (passes 3) modes on the layer's bf16 weight
+// planes, and the repack of a layer's float32 weights [Cout][Cin][kh][kw] into them.
+// (name_vec: the launch's profiler label when it gathers with 128-bit loads, name otherwise)
+int launch_conv_q(const char *name, const char *name_vec, const ConvArgs &a, const uint16_t *w_hi, const uint16_t *w_lo,
+                  int kpad, int nt, int passes);
+int pack_weights_q(const Layer &l, const float *w, uint16_t *hi, uint16_t *lo);
 
 // Indices of the layers the driver runs, per level (index 0 = level 2); -1 where the level has none.
 struct LevelLayers {
@@ -38,7 +61,7 @@ struct Net {
     std::vector<Layer> layers;
     int feat[10];                 // the ten convolutions of the feature pyramid
     LevelLayers lv[N_LEVELS];
-    long long blob_floats, packed_floats;
+    long long blob_floats, packed_floats, q_elems;
 };
 
 inline Net make_net()
@@ -122,6 +145,15 @@ inline Net make_net()
                                              : CC_3X3_S1;
     }
     net.packed_floats = pk;
+    long long q = 0;
+    for (Layer &l : net.layers) {
+        if (l.deconv)
+            continue;
+        l.kpad = (l.kh * l.kw * l.cin + QCONV_BK - 1) / QCONV_BK * QCONV_BK;
+        l.q_off = q;
+        q += (long long)l.npad * l.kpad;
+    }
+    net.q_elems = q;
     return net;
 }
 

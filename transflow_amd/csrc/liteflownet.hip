@@ -1,5 +1,6 @@
-// LiteFlowNet: calc_optical_flow_liteflownet (transflow/flow/methods/liteflownet.py) on the GPU, float32 throughout,
-// for all pairs of a call at once (every kernel's M or grid runs over the pairs).
+// LiteFlowNet: calc_optical_flow_liteflownet (transflow/flow/methods/liteflownet.py) on the GPU, float32 throughout
+// by default, for all pairs of a call at once (every kernel's M or grid runs over the pairs).  A handle's precision
+// (tf_lfn_set_precision) may hand the convolutions, and nothing else, to the bf16 MFMA kernel of lfn_conv_bf16.hip.
 //
 //   k_lfn_ingest     a decoded BGR frame of any size -> INTER_NEAREST to W x H -> the frame slot (uint8 BGR)
 //   k_lfn_prep       slot -> x 1/255 -> bilinear (align_corners=False) to Hp x Wp -> minus the role's mean (NHWC)
@@ -113,18 +114,7 @@ __global__ void k_lfn_bilinear(const float *__restrict__ in, int C, int h, int w
     }
 }
 
-// ---- convolution: implicit GEMM on f32 MFMA -----------------------------------------------------------------------
-
-struct ConvArgs {
-    const float *in;     // [n][hin][win][in_cs], the layer's input channels at in_off ...
-    const float *wt;     // packed [K][npad], K ordered (ky, kx, ci)
-    const float *bias;   // [cout]
-    float *out;          // [n][ho][wo][out_cs], written at out_off ...
-    const float *res;    // optional residual [n][ho][wo][res_cs] at res_off
-    int in_cs, in_off, out_cs, out_off, res_cs, res_off;
-    int hin, win, ho, wo, M;
-    int cin, cout, kh, kw, stride, ph, pw, K, npad, leaky;
-};
+// ---- convolution: implicit GEMM on f32 MFMA (ConvArgs: lfn_common.h; the bf16 modes: lfn_conv_bf16.hip) -------------
 
 constexpr int CONV_BM = 128, CONV_BK = 16, CONV_THREADS = 256;
 
@@ -446,7 +436,9 @@ struct tf_lfn {
     int W, H, Wp, Hp, n_slots, max_pairs;
     Net net;
     bool has_weights = false;
-    DevBuf blob, packed, frames, bgr_stage;
+    int precision = TF_LFN_F32;
+    bool q_packed = false;          // qhi / qlo hold the current weights (repacked at the first call in a bf16 mode)
+    DevBuf blob, packed, qhi, qlo, frames, bgr_stage;
     // activations, sized for max_pairs (features and images: 2 max_pairs frames, "one" frames first)
     DevBuf img[6], feat[6], bufA, bufB, bufFM, bufFS, bufW, cat, corr, corr2, flow_up, flow_s, flow_r, distA, distB,
         mean, out;
@@ -460,6 +452,33 @@ const char *conv_label(int cls)
     static const char *names[CC_COUNT] = {"lfn_conv7x7",  "lfn_conv3x3_s1", "lfn_conv3x3_s2", "lfn_conv1x1",
                                           "lfn_conv_kx1", "lfn_conv_1xk",   "lfn_conv_head",  "lfn_conv_dist"};
     return names[cls];
+}
+
+// the labels of the bf16 kernel's launches that gather their input with 128-bit loads (tools/bench_lfn.py adds the two
+// labels of a class; the precision tests read them to see which gather ran)
+const char *conv_label_vec(int cls)
+{
+    static const char *names[CC_COUNT] = {"lfn_conv7x7_v",  "lfn_conv3x3_s1_v", "lfn_conv3x3_s2_v", "lfn_conv1x1_v",
+                                          "lfn_conv_kx1_v", "lfn_conv_1xk_v",   "lfn_conv_head_v",  "lfn_conv_dist_v"};
+    return names[cls];
+}
+
+// The bf16 weight planes of the bf16 and bf16x3 modes, made when a call first needs them and again after new weights.
+int ensure_q_weights(tf_lfn *L)
+{
+    if (L->precision == TF_LFN_F32 || L->q_packed)
+        return TF_OK;
+    const size_t bytes = (size_t)L->net.q_elems * sizeof(uint16_t);
+    if (!L->qhi.p)
+        TF_TRY(L->qhi.alloc(bytes));
+    if (!L->qlo.p)
+        TF_TRY(L->qlo.alloc(bytes));
+    for (const Layer &l : L->net.layers)
+        if (!l.deconv)
+            TF_TRY(pack_weights_q(l, L->blob.as<const float>() + l.w_off, L->qhi.as<uint16_t>() + l.q_off,
+                                  L->qlo.as<uint16_t>() + l.q_off));
+    L->q_packed = true;
+    return TF_OK;
 }
 
 // One convolution over n images of hin x win.  Buffers are NHWC with the given channel strides and offsets.
@@ -480,8 +499,11 @@ int run_conv(tf_lfn *L, int li, int n, int hin, int win, const float *in, int in
     a.M = (int)M;
     a.cin = l.cin, a.cout = l.cout, a.kh = l.kh, a.kw = l.kw, a.stride = l.stride, a.ph = l.ph, a.pw = l.pw;
     a.K = l.kh * l.kw * l.cin, a.npad = l.npad, a.leaky = l.leaky;
-    const dim3 grid(cdiv(a.M, CONV_BM), l.npad / (32 * l.nt));
     const char *name = conv_label(l.cls);
+    if (L->precision != TF_LFN_F32)
+        return launch_conv_q(name, conv_label_vec(l.cls), a, L->qhi.as<const uint16_t>() + l.q_off,
+                             L->qlo.as<const uint16_t>() + l.q_off, l.kpad, l.nt, L->precision == TF_LFN_BF16 ? 1 : 3);
+    const dim3 grid(cdiv(a.M, CONV_BM), l.npad / (32 * l.nt));
     switch (l.nt) {
     case 1: return launch(name, k_lfn_conv<1>, grid, dim3(CONV_THREADS), 0, a);
     case 2: return launch(name, k_lfn_conv<2>, grid, dim3(CONV_THREADS), 0, a);
@@ -740,6 +762,7 @@ TF_API int tf_lfn_set_weights(tf_lfn *L, const float *blob, long long n_floats)
     TF_REQUIRE(n_floats == L->net.blob_floats, "tf_lfn_set_weights: %lld floats, the network has %lld", n_floats,
                L->net.blob_floats);
     L->has_weights = false;
+    L->q_packed = false;
     if (!L->blob.p)
         TF_TRY(L->blob.alloc((size_t)n_floats * sizeof(float)));
     if (!L->packed.p)
@@ -754,6 +777,22 @@ TF_API int tf_lfn_set_weights(tf_lfn *L, const float *blob, long long n_floats)
     }
     TF_HIP(hipStreamSynchronize(stream())); // the host blob is borrowed for this call only
     L->has_weights = true;
+    return TF_OK;
+}
+
+TF_API int tf_lfn_set_precision(tf_lfn *L, int precision)
+{
+    TF_REQUIRE(L, "tf_lfn_set_precision: null pointer");
+    TF_REQUIRE(precision == TF_LFN_F32 || precision == TF_LFN_BF16 || precision == TF_LFN_BF16X3,
+               "tf_lfn_set_precision: %d is not TF_LFN_F32, TF_LFN_BF16 or TF_LFN_BF16X3", precision);
+    L->precision = precision;
+    return TF_OK;
+}
+
+TF_API int tf_lfn_get_precision(tf_lfn *L, int *precision)
+{
+    TF_REQUIRE(L && precision, "tf_lfn_get_precision: null pointer");
+    *precision = L->precision;
     return TF_OK;
 }
 
@@ -791,6 +830,7 @@ TF_API int tf_lfn_calc_slots(tf_lfn *L, int n_pairs, const int *prev_slots, cons
                    "tf_lfn_calc_slots: pair %d: slots (%d, %d) out of range (%d slots)", i, prev_slots[i], next_slots[i],
                    L->n_slots);
     L->last_pairs = 0;
+    TF_TRY(ensure_q_weights(L));
     TF_TRY(forward(L, n_pairs, prev_slots, next_slots));
     L->last_pairs = n_pairs;
     return TF_OK;
@@ -838,6 +878,7 @@ TF_API int tf_lfn_stage_conv(tf_lfn *L, int layer, int n, int h, int w, const fl
     TF_TRY(upload(dout, out, nout * 4));
     if (res)
         TF_TRY(upload(dres, res, nres * 4));
+    TF_TRY(ensure_q_weights(L));
     TF_TRY(run_conv(L, layer, n, h, w, di.as<float>(), in_cs, in_off, dout.as<float>(), out_cs, out_off,
                     res ? dres.as<float>() : nullptr, res_cs, res_off));
     return download(out, dout, nout * 4);

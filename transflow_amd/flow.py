@@ -636,7 +636,8 @@ def _open_lucas_kanade(source):
 
 def _open_liteflownet(source):
     from .liteflownet import LiteFlowNet
-    return LiteFlowNet(source.width, source.height, source.config.weights, device=source.device)
+    return LiteFlowNet(source.width, source.height, source.config.weights, device=source.device,
+                       precision=source.config.hip_lfn_precision)
 
 
 def _previous_flow_or_zeros(source):

@@ -28,6 +28,16 @@ REG_CIN = {2: 131, 3: 131, 4: 131, 5: 131, 6: 195}
 MEAN_ONE = (0.411618, 0.434631, 0.454253)    # per BGR channel, subtracted from frame one ...
 MEAN_TWO = (0.410782, 0.433645, 0.452793)    # ... and from frame two
 MAX_PAIRS = 16                                # TF_LFN_MAX_PAIRS
+# how the network's convolutions multiply (tf_lfn_set_precision): float32; operands rounded to bfloat16; or each
+# operand as a bfloat16 pair hi + lo and the three products that matter (hi hi, hi lo, lo hi).  Sums are float32.
+PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2}     # TF_LFN_F32, TF_LFN_BF16, TF_LFN_BF16X3
+
+
+def precision_code(name) -> int:
+    """The TF_LFN_* value of a precision name; ValueError for anything else."""
+    if not isinstance(name, str) or name not in PRECISIONS:
+        raise ValueError(f"LiteFlowNet precision {name!r} is not one of {', '.join(map(repr, PRECISIONS))}")
+    return PRECISIONS[name]
 
 
 class Layer:
@@ -194,7 +204,8 @@ def _nhwc(a, what: str, lead=None, channels=None) -> np.ndarray:
 
 class LiteFlowNet:
     def __init__(self, width: int, height: int, weights, frame_slots: int = 2, max_pairs: int = 1,
-                 device: int | None = None):
+                 device: int | None = None, precision: str = "f32"):
+        code = precision_code(precision)
         self._lib = _lib.load()
         self._h = C.c_void_p()
         if device is not None:
@@ -202,6 +213,8 @@ class LiteFlowNet:
         self.width, self.height = int(width), int(height)
         self.frame_slots, self.max_pairs = int(frame_slots), int(max_pairs)
         check(self._lib.tf_lfn_create(C.byref(self._h), self.width, self.height, self.frame_slots, self.max_pairs))
+        if code:
+            check(self._lib.tf_lfn_set_precision(self._h, code))
         self.set_weights(weights)
 
     def close(self):
@@ -222,6 +235,17 @@ class LiteFlowNet:
         else:
             blob = pack_weights(as_weights(weights))
         check(self._lib.tf_lfn_set_weights(self._h, _ptr(blob), int(blob.size)))
+
+    def set_precision(self, name: str) -> None:
+        """ "f32", "bf16" or "bf16x3": how the convolutions of the calls that follow multiply (PRECISIONS)."""
+        code = precision_code(name)
+        check(self._lib.tf_lfn_set_precision(self._h, code))
+
+    @property
+    def precision(self) -> str:
+        code = C.c_int()
+        check(self._lib.tf_lfn_get_precision(self._h, C.byref(code)))
+        return {v: k for k, v in PRECISIONS.items()}[code.value]
 
     # -- frames ------------------------------------------------------------------------------
     def set_frame_bgr(self, slot: int, frame) -> None:
