@@ -467,6 +467,35 @@ int tf_mv_rasterize_dev(tf_mv *mv, const tf_mv_vector *v, int n, void *flow_dev 
 int tf_mv_stage_resolve_rects(int width, int height, const tf_mv_vector *v, int n, int32_t *rects_out /* n x 4 */,
                               float *values_out /* n x 2 */);
 
+/* ---- still pixmaps generated where they are read (transflow/pixmap/still.py) -------------
+ * The image whose pixels the layers move, uint8 [H][W][3] in device memory the caller owns (4-byte aligned), for
+ * tf_remap_gather_dev / tf_remap_introduce_dev / tf_remap_step_dev to read.  Both calls queue on the calling thread's
+ * stream and wait for nothing.
+ * tf_pixmap_fill_dev: ColorPixmapSource._init_array (still.py:52-53), every pixel the one colour.
+ * tf_pixmap_gradient_dev: GradientPixmapSource.evaluate + _init_array (still.py:121-163) for every pixel of an
+ * expression tree given in postfix order (children before their parent, the root last).  In float64, one rounding
+ * per Python operation:
+ *   TF_PX_I       z = 2 * (i / (height - 1)) - 1 in all three channels     TF_PX_J  the same with j and width
+ *   TF_PX_RGB     (a, b, c)
+ *   TF_PX_MIX     of the three values A, B, C below it, per channel k: w = (1 + A[k]) / 2; (1 - w) * B[k] + w * C[k]
+ *   TF_PX_TRIPLE  (A[0], B[1], C[2])
+ *   the byte of a channel v: (255 * (v + 1)) / 2, truncated toward zero to a 32-bit integer, its low 8 bits.
+ * The trees still.py:94-119 generates have one shape -- a triple of three slots, each a leaf or a mix of three slots,
+ * each of those a leaf or a mix of three leaves: at most 40 nodes -- and that shape is what the kernel evaluates, with
+ * every register index a constant.  A root that is not a triple R is taken as the triple (R, R, R), which has the same
+ * value.  TF_ERR_ARG, and nothing launched: more than TF_PX_MAX_NODES nodes, an unknown type, a postfix order that does
+ * not reduce to one tree, TF_PX_I with height 1 or TF_PX_J with width 1 (the reference's ZeroDivisionError).
+ * TF_ERR_UNSUPPORTED, and nothing launched: a well-formed tree of another shape (a triple below the root, mixes nested
+ * three deep). */
+enum { TF_PX_I = 0, TF_PX_J = 1, TF_PX_RGB = 2, TF_PX_MIX = 3, TF_PX_TRIPLE = 4 };
+#define TF_PX_MAX_NODES 40
+typedef struct tf_px_node {
+    int type;
+    double a, b, c; /* TF_PX_RGB's channels; ignored for the other types */
+} tf_px_node;
+int tf_pixmap_fill_dev(void *rgb_dev, size_t n_pixels, const uint8_t rgb[3]);
+int tf_pixmap_gradient_dev(void *rgb_dev, int width, int height, int n_nodes, const tf_px_node *nodes);
+
 /* ---- compositor layers -----------------------------------------------------------
  * One handle = one layer of the compositor.  layer_class selects which of the reference's
  * layer classes it is (Layer.from_args, transflow/compositor/layers/layer.py:44-56):

@@ -13,7 +13,9 @@ frame still goes up and the rendered frame still comes down, the 66 MB per 4K fl
 `frame` (HipCompositor lazy_frames): render() returns a DeviceFrame whose download is under way; the loop reads frame
 t - 1 (as the reference's output process would, behind its queue) after it has issued frame t, so a frame's 25 MB come
 down beside the next frame's uploads.
-Usage on the GPU box:  python tools/bench_host_path.py [1080p|4k] [frames] [bgr|grey] [exact] [prefetch] [device] [frame] [batch=n] [reps=r]"""
+`devpix`: the pixmap is a DevicePixmap (transflow_amd/pixmap.py: a HipColoredNoisePixmapSource behind a
+HipPixmapInterface) -- made once, read by the layer where it is -- instead of a host array that goes up every frame.
+Usage on the GPU box:  python tools/bench_host_path.py [1080p|4k] [frames] [bgr|grey] [exact] [prefetch] [device] [frame] [devpix] [batch=n] [reps=r]"""
 import os
 import sys
 import time
@@ -36,6 +38,7 @@ exact = "exact" in sys.argv[4:]          # flows bit-identical to the CPU path's
 prefetch = "prefetch" in sys.argv[4:]
 device = "device" in sys.argv[4:]
 lazy = "frame" in sys.argv[4:]
+devpix = "devpix" in sys.argv[4:]
 if "nobeside" in sys.argv[4:]:        # A/B: the pixmap's upload on the caller's stream even behind a device-flow update
     from transflow_amd import remap as _remap
     _g = _remap.RemapLayer.gather
@@ -58,7 +61,12 @@ class Src:
 
 
 comp = HipCompositor.from_args(h, w, [LayerConfig(0)], lazy_frames=lazy)
-comp.set_sources({0: [Src()]})
+if devpix:
+    from transflow_amd.pixmap import HipColoredNoisePixmapSource, HipPixmapInterface  # noqa: E402
+    pixmap_source = HipColoredNoisePixmapSource(w, h, seed=1).__enter__()
+    comp.set_sources({0: [HipPixmapInterface(pixmap_source, Src.introduction_mask)]})
+else:
+    comp.set_sources({0: [Src()]})
 t_flow = t_comp = 0.0
 cfg = None
 if exact or prefetch or device or batch > 1:
@@ -87,5 +95,5 @@ with HipFlowSource.from_args(ArrayFrameProvider(frames, 30.0), direction="backwa
         t_flow += t1 - t0
         t_comp += t2 - t1
         k += 1
-print(f"{name} ({kind} frames in{', exact sums' if exact else ''}{', flow source prefetching' if prefetch else ''}{', flows stay on the device' if device else ''}{', frames read one late (lazy)' if lazy else ''}{f', {batch} pairs per call' if batch > 1 else ''}): {k} frames; flow source {t_flow / k * 1e3:.1f} ms/frame, compositor {t_comp / k * 1e3:.1f} ms/frame, "
+print(f"{name} ({kind} frames in{', exact sums' if exact else ''}{', flow source prefetching' if prefetch else ''}{', flows stay on the device' if device else ''}{', frames read one late (lazy)' if lazy else ''}{', pixmap on the device' if devpix else ''}{f', {batch} pairs per call' if batch > 1 else ''}): {k} frames; flow source {t_flow / k * 1e3:.1f} ms/frame, compositor {t_comp / k * 1e3:.1f} ms/frame, "
       f"{k / (t_flow + t_comp):.1f} frames/s end to end {'(frames in, frames out)' if device else 'through host arrays'} (one process)")

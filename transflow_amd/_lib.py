@@ -173,6 +173,8 @@ PROTOTYPES = {
     "tf_mv_rasterize": (_I, [_P, _P, _I, _P]),
     "tf_mv_rasterize_dev": (_I, [_P, _P, _I, _P]),
     "tf_mv_stage_resolve_rects": (_I, [_I, _I, _P, _I, _P, _P]),
+    "tf_pixmap_fill_dev": (_I, [_P, C.c_size_t, C.POINTER(C.c_uint8)]),
+    "tf_pixmap_gradient_dev": (_I, [_P, _I, _I, _I, _P]),
     "tf_remap_create": (_I, [_PP, _I, _I, C.POINTER(TfLayerCfg), _P, _P, _P, _P]),
     "tf_remap_destroy": (None, [_P]),
     "tf_remap_set_sources": (_I, [_P, _I, C.POINTER(C.c_void_p)]),

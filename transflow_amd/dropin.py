@@ -17,9 +17,14 @@ any of the reference's classes (`moveref`, `sum`, `static`, `introduction`) -- a
 the reference's own factory otherwise (other flow methods, polar expressions that are
 not per-pixel formulas).
 `.flow.zip` archives are served too (their flows are post-processed on the GPU).
+`install(pixmaps=True)` replaces a third factory, PixmapSource.from_args (pipeline.py:382): still pixmap sources are then
+transflow_amd/pixmap.py's; video pixmap sources stay the reference's.
 INTEGRATION.md shows the three-line patch a maintainer would add instead.
 """
 from __future__ import annotations
+
+import os
+import re
 
 _saved = {}
 
@@ -76,8 +81,22 @@ def _compositor_from_args(original, lazy_frames=False):
     return classmethod(from_args)
 
 
+def _pixmap_from_args(original):
+    from .pixmap import HipPixmapSource
+
+    def from_args(cls, path, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat=1, flow_path=None):
+        still = re.match(HipPixmapSource.STILL_RE, path.lower().strip()) is not None
+        image = os.path.isfile(path) and os.path.splitext(path)[1].lower() in HipPixmapSource.IMAGE_EXTS
+        if not (still or image):               # a video: the reference's CvPixmapSource
+            return original(path, size, seek=seek, seed=seed, seek_time=seek_time, alteration_path=alteration_path,
+                            repeat=repeat, flow_path=flow_path)
+        return HipPixmapSource.from_args(path, size, seek, seed, seek_time, alteration_path, repeat, flow_path)
+
+    return classmethod(from_args)
+
+
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
-            lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False) -> None:
+            lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -86,7 +105,10 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     motion vectors, transflow's -m) are this backend's too (transflow_amd/motionvectors.py; PyAV still decodes); by
     default they stay the reference's.  lazy_frames: the compositors built for the pipeline return
     DeviceFrames from render() (transflow_amd/deviceframe.py): the pipeline's `oq.put(frame)` (pipeline.py:518-522) then
-    pickles the frame -- and waits for its download -- in the queue's feeder thread, beside the next update."""
+    pickles the frame -- and waits for its download -- in the queue's feeder thread, beside the next update.
+    pixmaps: still pixmap sources (colours, the noises, gradient, images, a video's first frame) are this backend's
+    (transflow_amd/pixmap.py): made once, kept on the device, taken by the layers of a compositor of the same process by
+    address; across a process boundary they travel as host arrays.  By default they stay the reference's."""
     if flow and "flow" not in _saved:
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
@@ -99,6 +121,10 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         bind_reference_data_layer()    # extra/control.py:155 asks isinstance(layer, DataLayer) of checkpointed layers
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
         RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames)
+    if pixmaps and "pixmaps" not in _saved:
+        from transflow.pixmap.source import PixmapSource as RefPixmapSource
+        _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])
+        RefPixmapSource.from_args = _pixmap_from_args(RefPixmapSource.from_args)
 
 
 def uninstall() -> None:

@@ -16,6 +16,11 @@ def _ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _on_device(pixmap) -> bool:
+    """A pixmap that lives in HBM (transflow_amd/pixmap.py's DevicePixmap): the kernels read it where it is."""
+    return getattr(pixmap, "dev_ptr", None) is not None
+
+
 class CompImage:
     """Background + output frame of Compositor (compositor/compositor.py:17-40)."""
 
@@ -181,6 +186,9 @@ class RemapLayer:
     def gather(self, source_index: int, pixmap: np.ndarray, beside: bool = False) -> None:
         """beside: the pixmap goes up on the library's upload stream, beside the update queued before it
         (tf_remap_gather_beside: for updates whose flow was on the device already)."""
+        if _on_device(pixmap):             # nothing goes up: `beside` has nothing to place
+            self.gather_dev(source_index, *self._device_pixmap(pixmap))
+            return
         pm = np.ascontiguousarray(pixmap, dtype=np.uint8)
         if pm.ndim != 3 or pm.shape[:2] != (self.height, self.width):
             raise ValueError(f"pixmap shape {pm.shape} does not match the layer")
@@ -189,7 +197,10 @@ class RemapLayer:
 
     def stage_pixmap(self, pixmap: np.ndarray, beside: bool = False):
         """The upload of gather() alone (tf_remap_stage_pixmap): (device address, channels) of the staged pixmap, for
-        gather_dev / step_dev later on this thread's stream; staged_used() after the last kernel that reads it."""
+        gather_dev / step_dev later on this thread's stream; staged_used() after the last kernel that reads it.
+        A pixmap on the device is its own staging: its address, nothing copied (staged_used() then marks nothing)."""
+        if _on_device(pixmap):
+            return self._device_pixmap(pixmap)
         pm = np.ascontiguousarray(pixmap, dtype=np.uint8)
         if pm.ndim != 3 or pm.shape[:2] != (self.height, self.width):
             raise ValueError(f"pixmap shape {pm.shape} does not match the layer")
@@ -202,13 +213,29 @@ class RemapLayer:
 
     def introduce(self, source_index: int, pixmap: np.ndarray, frame_number: int) -> None:
         """Introduction layer: one iteration of introduction.py:46-63."""
+        if _on_device(pixmap):
+            ptr, channels = self._device_pixmap(pixmap)
+            self.introduce_dev(source_index, ptr, channels, frame_number)
+            return
         pm = np.ascontiguousarray(pixmap, dtype=np.uint8)
         if pm.ndim != 3 or pm.shape[:2] != (self.height, self.width):
             raise ValueError(f"pixmap shape {pm.shape} does not match the layer")
         check(self._lib.tf_remap_introduce(self._h, int(source_index), _ptr(pm), int(pm.shape[2]), int(frame_number)))
 
+    def _device_pixmap(self, pixmap):
+        """(device address, channels) of a pixmap in HBM, this thread's stream ordered behind whatever made it."""
+        shape = tuple(pixmap.shape)
+        if len(shape) != 3 or shape[:2] != (self.height, self.width) or np.dtype(pixmap.dtype) != np.uint8:
+            raise ValueError(f"pixmap shape {shape} does not match the layer")
+        pixmap.wait_on_stream()
+        return pixmap.dev_ptr, int(shape[2])
+
     def gather_dev(self, source_index: int, pixmap_dev: int, channels: int) -> None:
         check(self._lib.tf_remap_gather_dev(self._h, int(source_index), C.c_void_p(pixmap_dev), int(channels)))
+
+    def introduce_dev(self, source_index: int, pixmap_dev: int, channels: int, frame_number: int) -> None:
+        check(self._lib.tf_remap_introduce_dev(self._h, int(source_index), C.c_void_p(pixmap_dev), int(channels),
+                                               int(frame_number)))
 
     def step_dev(self, comp: "CompImage", flow_dev: int, pixmap_dev: int, channels: int = 3, clip_flow=False,
                  uniform_dev: int | None = None, seed: int = 0) -> None:
