@@ -271,6 +271,12 @@ int tf_flow_convolve_dev(const void *flow_dev, const void *kernel_dev, int kh, i
 /* source.py:349-362 on a flow of either type, in place (after a convolution the reference carries
    on in the convolution's type).  FORWARD needs scratch_dev: 4 bytes per pixel. */
 int tf_flow_post_process_dev(void *flow_dev, int wide, int width, int height, int direction, void *scratch_dev);
+/* The whole of post_process short of the convolution, on a device flow and without a handle: the flow filters and the
+   mask multiply (as tf_fb_post_process_ex: float32 flows only, wide with either is refused), then the direction
+   handling; direction -1: none.  mask_dev: float32 [H][W] or NULL.  winner_dev: 4 bytes per pixel of the caller's,
+   needed by FORWARD; it holds the winner map of tf_fb_post_process_scatter afterwards. */
+int tf_flow_post_process_ex_dev(void *flow_dev, int wide, int width, int height, int direction, int n_ops,
+                                const tf_flow_op *ops, const void *mask_dev, void *winner_dev);
 
 /* The `polar` flow filter, transflow/flow/filters.py:75-87, in place on a float32 flow: r = |v|,
    a = atan2(vy, vx), then v = (R cos A, R sin A) with R and A the filter's two user expressions of

@@ -1,12 +1,14 @@
 """FlowSource.post_process on the GPU keeps numpy.clip's zero signs: the reference clips with array bounds, which numpy
 evaluates as comparisons (x > lo ? x : lo, then t < hi ? t : hi), so a -0.0 that meets a bound of 0 -- column 0 and row 0
 from below, column W - 1 and row H - 1 from above -- comes out as +0.0.  Compared on bit patterns against
-oracle.remap_ref.post_process, on the host-array entry and on the device-resident one."""
+oracle.remap_ref.post_process, on the host-array entry and on the device-resident one -- of a Farnebäck handle, of the
+handle-free tf_flow_post_process_dev in both of its types (what follows a convolution kernel) and of a PostProcess."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from oracle import flow_ops_ref as F
 from oracle import remap_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -44,3 +46,54 @@ def test_post_process_zero_signs(direction, name, w, h):
         b = exp.view(np.uint32)
         assert (b[:, 0, 0] == 0).all() and (b[:, -1, 0] == 0).all() and (b[0, :, 1] == 0).all() and (b[-1, :, 1] == 0).all()
         assert (b[1:-1, 1:-1] == 0x80000000).all()           # the interior keeps its -0.0
+
+
+SHAPES = [(1, 1), (37, 23), (64, 2), (257, 3)]      # (257, 3): past one 256-thread block, a width that is no power of two
+NAMES = ["negative_zeros", "mixed", "mask_products"]
+
+
+@pytest.mark.parametrize("direction", [R.BACKWARD, R.FORWARD])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_flow_entry_zero_signs(direction, dtype, w, h):
+    """tf_flow_post_process_dev itself: upload, call, download, in float32 and in float64 with the flows cast."""
+    from transflow_amd import _lib
+    from transflow_amd.device import DevBuffer
+    lib = _lib.load()
+    bits = np.uint32 if dtype is np.float32 else np.uint64
+    winner = DevBuffer(4 * w * h)
+    for name in NAMES:
+        raw = _flows(h, w)[name].astype(dtype)
+        exp = F.post_process_any(raw.copy(), direction)
+        buf = DevBuffer.from_array(raw)
+        _lib.check(lib.tf_flow_post_process_dev(C.c_void_p(buf.ptr), int(dtype is np.float64), w, h, direction,
+                                                C.c_void_p(winner.ptr)))
+        got = buf.download(raw.shape, dtype)
+        buf.close()
+        np.testing.assert_array_equal(got.view(bits), exp.view(bits), err_msg=name)
+        if dtype is np.float32:
+            np.testing.assert_array_equal(got.view(bits), R.post_process(raw.copy(), direction).view(bits), err_msg=name)
+    winner.close()
+
+
+@pytest.mark.parametrize("direction", [R.BACKWARD, R.FORWARD])
+@pytest.mark.parametrize("w,h", SHAPES)
+def test_post_process_object_zero_signs(direction, w, h):
+    """PostProcess, what every source without a resident flow method post-processes with: its host entry and its
+    device entry."""
+    from transflow_amd import _lib
+    from transflow_amd.flowops import PostProcess
+    pp = PostProcess(w, h)
+    try:
+        for name in NAMES:
+            raw = _flows(h, w)[name]
+            exp = R.post_process(raw.copy(), direction)
+            got = pp.post_process_host_ex(raw.copy(), direction)
+            np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32), err_msg=name)
+            _lib.check(_lib.load().tf_dev_upload(C.c_void_p(pp.flow_ptr(0)), C.c_void_p(raw.ctypes.data), raw.nbytes))
+            pp.post_process_ex(0, direction)
+            out = np.empty_like(raw)
+            _lib.check(_lib.load().tf_dev_download(C.c_void_p(out.ctypes.data), C.c_void_p(pp.flow_ptr(0)), out.nbytes))
+            np.testing.assert_array_equal(out.view(np.uint32), exp.view(np.uint32), err_msg=name)
+    finally:
+        pp.close()

@@ -8,14 +8,14 @@ cd "$(dirname "$0")/../transflow_amd/csrc"
 out=../../build_abl
 CC="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -ffp-contract=off -Wno-unused-result -DTF_EXPERIMENT"
 mkdir -p $out/_common $out/$name
-COMMON="runtime remap remap_step flowops batch"
+COMMON="runtime remap remap_step flowops postprocess batch"
 pids=""
 for f in $COMMON; do
   if [ ! -f $out/_common/$f.o ] || [ $f.hip -nt $out/_common/$f.o ] || [ common.h -nt $out/_common/$f.o ] || [ remap_common.h -nt $out/_common/$f.o ]; then
     rm -f $out/_common/$f.o; $CC -c $f.hip -o $out/_common/$f.o & pids="$pids $!"
   fi
 done
-FB="farneback fb_level_image fb_pyramid fb_matrices fb_iterate fb_exact fb_postprocess fb_stages"
+FB="farneback fb_level_image fb_pyramid fb_matrices fb_iterate fb_exact fb_stages"
 # a unit that fails to compile must fail the build: old objects go first, and every job is waited for by pid
 # (a bare `wait` returns 0 whatever the jobs did)
 # (fb_iterate.hip is built without the SLP vectoriser, as transflow_amd/csrc/Makefile builds it)

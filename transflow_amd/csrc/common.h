@@ -138,7 +138,23 @@ __device__ __forceinline__ uint32_t fast_div(uint32_t t, FastDiv f)
 
 // numpy.clip's values: minimum(maximum(v, lo), hi) with NaN propagated (fminf / fmaxf drop it).  Not its zero signs:
 // the hardware's min / max order -0 below +0, numpy compares.  For results that are rounded to integers or bytes next;
-// a flow that is handed out goes through clip_np (fb_postprocess.hip).
+// a flow that is handed out goes through clip_np (postprocess.hip).
 __device__ __forceinline__ float clip_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---- postprocess.hip: FlowSource.post_process (source.py:337-363) on a device flow of W x H pixels, in place.  The
+// caller brings the winner buffer (int32 per pixel) that FORWARD needs and says which profiler labels its launches carry.
+struct PpLabels {
+    const char *clip, *fwd_scatter, *fwd_resolve, *ops;
+};
+constexpr PpLabels PP_FB{"pp_clip", "pp_fwd_scatter", "pp_fwd_resolve", "pp_ops"};                       // tf_fb_post_process*
+constexpr PpLabels PP_FLOW{"flow_pp_clip", "flow_pp_fwd_scatter", "flow_pp_fwd_resolve", "flow_pp_ops"}; // tf_flow_post_process*_dev
+// the filters (at most TF_MAX_FLOW_OPS) and the mask multiply (mask_dev: float32 per pixel, or null) on a float32 flow
+int pp_ops(float2 *flow, int W, int H, int n_ops, const tf_flow_op *ops, const float *mask_dev, const PpLabels &lb);
+// the first half of FORWARD: winner[target] = the highest source index that claims it, -1 where none does
+int pp_scatter(const float2 *flow, int W, int H, int *winner, const PpLabels &lb);
+// direction 0 = FORWARD (scatter, then resolve and clip), 1 = BACKWARD (the clip); wide: the flow is double2, else float2
+int pp_direction(void *flow, bool wide, int W, int H, int direction, int *winner, const PpLabels &lb);
 
 } // namespace tf

@@ -849,3 +849,77 @@ TF_API int tf_fb_calc(tf_fb *fb, const uint8_t *prev, ptrdiff_t prev_stride, con
     TF_TRY(tf_fb_calc_slots(fb, 1, &a, &b));
     return tf_fb_get_flow(fb, 0, flow_out);
 }
+
+// ---------------------------------------------------------------------------------
+// B1: FlowSource.post_process (source.py:337-363) on the handle's flows: postprocess.hip's core over the handle's
+// winner map, and for a host array over its scratch (20 B/px: the flow takes 8, the mask the next 4)
+// ---------------------------------------------------------------------------------
+static int pp_pair(tf_fb *fb, int pair, int direction, int n_ops, const tf_flow_op *ops, const void *mask_dev)
+{
+    TF_TRY(ensure_init());
+    void *p;
+    TF_TRY(tf_fb_flow_ptr(fb, pair, &p));
+    TF_TRY(pp_ops((float2 *)p, fb->W, fb->H, n_ops, ops, (const float *)mask_dev, PP_FB));
+    return pp_direction(p, false, fb->W, fb->H, direction, fb->winner.as<int>(), PP_FB);
+}
+
+// directed = false: the pre-steps alone
+static int pp_host(tf_fb *fb, float *flow_inout, bool directed, int direction, int n_ops, const tf_flow_op *ops,
+                   const float *mask)
+{
+    TF_TRY(ensure_init());
+    const size_t n = (size_t)fb->W * fb->H;
+    TF_HIP(hipMemcpyAsync(fb->scratch.p, flow_inout, n * 8, hipMemcpyHostToDevice, stream()));
+    const float *mask_dev = nullptr;
+    if (mask) {
+        float *m = fb->scratch.as<float>() + n * 2;
+        TF_HIP(hipMemcpyAsync(m, mask, n * 4, hipMemcpyHostToDevice, stream()));
+        mask_dev = m;
+    }
+    TF_TRY(pp_ops(fb->scratch.as<float2>(), fb->W, fb->H, n_ops, ops, mask_dev, PP_FB));
+    if (directed)
+        TF_TRY(pp_direction(fb->scratch.p, false, fb->W, fb->H, direction, fb->winner.as<int>(), PP_FB));
+    TF_HIP(hipMemcpyAsync(flow_inout, fb->scratch.p, n * 8, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    return TF_OK;
+}
+
+TF_API int tf_fb_post_process_ex(tf_fb *fb, int pair, int direction, int n_ops, const tf_flow_op *ops,
+                                 const void *mask_dev)
+{
+    TF_REQUIRE(fb, "tf_fb_post_process_ex: null handle");
+    TF_REQUIRE(pair >= 0 && pair < fb->max_pairs, "tf_fb_post_process_ex: pair %d out of range", pair);
+    return pp_pair(fb, pair, direction, n_ops, ops, mask_dev);
+}
+
+TF_API int tf_fb_post_process(tf_fb *fb, int pair, int direction)
+{
+    TF_REQUIRE(fb, "tf_fb_post_process: null handle");
+    TF_REQUIRE(pair >= 0 && pair < fb->max_pairs, "tf_fb_post_process: pair %d out of range", pair);
+    return pp_pair(fb, pair, direction, 0, nullptr, nullptr);
+}
+
+TF_API int tf_fb_post_process_host_ex(tf_fb *fb, float *flow_inout, int direction, int n_ops, const tf_flow_op *ops,
+                                      const float *mask)
+{
+    TF_REQUIRE(fb && flow_inout, "tf_fb_post_process_host_ex: null pointer");
+    return pp_host(fb, flow_inout, direction >= 0, direction, n_ops, ops, mask);
+}
+
+TF_API int tf_fb_post_process_host(tf_fb *fb, float *flow_inout, int direction)
+{
+    TF_REQUIRE(fb && flow_inout, "tf_fb_post_process_host: null pointer");
+    return pp_host(fb, flow_inout, true, direction, 0, nullptr, nullptr);
+}
+
+TF_API int tf_fb_post_process_scatter(tf_fb *fb, int pair, void **winners_dev)
+{
+    TF_REQUIRE(fb && winners_dev, "tf_fb_post_process_scatter: null pointer");
+    TF_REQUIRE(pair >= 0 && pair < fb->max_pairs, "tf_fb_post_process_scatter: pair %d out of range", pair);
+    TF_TRY(ensure_init());
+    void *p;
+    TF_TRY(tf_fb_flow_ptr(fb, pair, &p));
+    TF_TRY(pp_scatter((const float2 *)p, fb->W, fb->H, fb->winner.as<int>(), PP_FB));
+    *winners_dev = fb->winner.p;
+    return TF_OK;
+}

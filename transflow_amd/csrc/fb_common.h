@@ -4,9 +4,9 @@
 //   fb_matrices.hip     A3 / A4 as two kernels: update-matrices, the marching blur + solve, Gaussian window, INTER_AREA init
 //   fb_iterate.hip      A3 + A4 (+ A5) as ONE kernel: k_flow_iter_pc, its pre-pass, the march planner
 //   fb_exact.hip        A4 in OpenCV's own summation order (tf_fb_set_exact / option fb_exact_sums), winsize 1
-//   fb_postprocess.hip  B1: FlowSource.post_process and the flow filters
 //   fb_stages.hip       single-stage entry points for the parity tests
-//   farneback.hip       constants, the handle, the pyramid driver tf_fb_calc_slots, frames in / flows out
+//   farneback.hip       constants, the handle, the pyramid driver tf_fb_calc_slots, frames in / flows out, and the
+//                       tf_fb_post_process* entry points over postprocess.hip (B1, no unit of this path)
 #pragma once
 #include <type_traits>
 #include <algorithm>
@@ -96,8 +96,7 @@ __host__ __device__ __forceinline__ int reflect101(int p, int len)
     return p;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// the same for lo <= hi as one v_med3_i32
+// clampi (common.h) for lo <= hi as one v_med3_i32
 __device__ __forceinline__ int med3i(int v, int lo, int hi)
 {
     int r;

@@ -2,7 +2,7 @@
 //   flow merging            transflow/pipeline.py:149-158, transflow/utils.py:359-381
 //   integer upscaling       transflow/utils.py:417-418
 //   convolution kernel      transflow/flow/sources/source.py:344-348 (scipy.signal.convolve2d)
-//   post_process in the convolution's type (float64 unless the kernel is float32), :349-362
+//   (what follows it in the convolution's type, :349-362, is postprocess.hip's)
 //   flow visualisation      transflow/output/render.py:9-48
 //   BGR -> grey             transflow/flow/sources/cv.py:461-466 (cv2.cvtColor) + nearest resize
 // All element-wise or small-stencil, HBM-bound; arithmetic in the type and order numpy / scipy use.
@@ -181,60 +181,6 @@ k_flow_convolve_tiled(const float2 *__restrict__ flow, const T *__restrict__ ker
             }
         }
     }
-}
-
-template <typename T> __device__ __forceinline__ T clip_nan_t(T v, T lo, T hi)
-{
-    return v != v ? v : (v < lo ? lo : (v > hi ? hi : v));
-}
-
-template <typename T2> __device__ __forceinline__ T2 clip_frame_t(T2 f, int i, int j, int W, int H)
-{
-    typedef decltype(f.x) T;
-    f.x = clip_nan_t<T>(f.x, (T)(-j), (T)(W - 1 - j));
-    f.y = clip_nan_t<T>(f.y, (T)(-i), (T)(H - 1 - i));
-    return f;
-}
-
-template <typename T2> __global__ void k_pp_clip_t(T2 *flow, int W, int H)
-{
-    int t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= W * H)
-        return;
-    flow[t] = clip_frame_t(flow[t], t / W, t % W, W, H);
-}
-
-// source.py:350-358 (see k_pp_fwd_scatter in farneback.hip)
-template <typename T2>
-__global__ void k_pp_fwd_scatter_t(const T2 *__restrict__ flow, int *__restrict__ winner, int W, int H)
-{
-    int t = blockIdx.x * BLOCK + threadIdx.x;
-    const int N = W * H;
-    if (t >= N)
-        return;
-    T2 f = clip_frame_t(flow[t], t / W, t % W, W, H);
-    int ix = (int)rint((double)f.x), iy = (int)rint((double)f.y);
-    int d = iy * W + ix;
-    if (d == 0)
-        return;
-    int target = min(max(t + d, 0), N - 1);
-    atomicMax(&winner[target], t);
-}
-
-template <typename T2>
-__global__ void k_pp_fwd_resolve_t(T2 *__restrict__ flow, const int *__restrict__ winner, int W, int H)
-{
-    int t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= W * H)
-        return;
-    typedef decltype(flow[0].x) T;
-    int w = winner[t];
-    int src = w >= 0 ? w : t;
-    int i = t / W, j = t % W;
-    T2 f;
-    f.x = (T)(src % W - j);
-    f.y = (T)(src / W - i);
-    flow[t] = clip_frame_t(f, i, j, W, H);
 }
 
 struct Colors {
@@ -586,30 +532,6 @@ TF_API int tf_flow_convolve_dev(const void *flow_dev, const void *kernel_dev, in
                       (const float2 *)flow_dev, (const double *)kernel_dev, kh, kw, (double2 *)out_dev, width, height);
     return launch("flow_convolve_f32", k_flow_convolve<float>, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
                   (const float2 *)flow_dev, (const float *)kernel_dev, kh, kw, (float2 *)out_dev, width, height);
-}
-
-template <typename T2> static int pp_any(T2 *flow, int W, int H, int direction, int *winner)
-{
-    const size_t n = (size_t)W * H;
-    dim3 grid(cdiv(n, BLOCK)), block(BLOCK);
-    if (direction == 0) {
-        TF_REQUIRE(winner || n == 0, "tf_flow_post_process: FORWARD needs the 4 B/px scratch buffer");
-        TF_HIP(hipMemsetAsync(winner, 0xFF, n * 4, stream()));
-        TF_TRY(launch("flow_pp_fwd_scatter", k_pp_fwd_scatter_t<T2>, grid, block, 0, (const T2 *)flow, winner, W, H));
-        return launch("flow_pp_fwd_resolve", k_pp_fwd_resolve_t<T2>, grid, block, 0, flow, (const int *)winner, W, H);
-    }
-    return launch("flow_pp_clip", k_pp_clip_t<T2>, grid, block, 0, flow, W, H);
-}
-
-TF_API int tf_flow_post_process_dev(void *flow_dev, int wide, int width, int height, int direction, void *scratch_dev)
-{
-    TF_REQUIRE(direction == 0 || direction == 1, "tf_flow_post_process: direction must be 0 (FORWARD) or 1 (BACKWARD)");
-    TF_REQUIRE(width >= 0 && height >= 0 && (long long)width * height < (1ll << 31), "tf_flow_post_process: bad size");
-    TF_REQUIRE(flow_dev || (size_t)width * height == 0, "tf_flow_post_process: null pointer");
-    TF_TRY(ensure_init());
-    if (wide)
-        return pp_any((double2 *)flow_dev, width, height, direction, (int *)scratch_dev);
-    return pp_any((float2 *)flow_dev, width, height, direction, (int *)scratch_dev);
 }
 
 static Colors make_colors(const float *rgb, int n)

@@ -9,7 +9,7 @@
 //               the order of arrival, so the winner map -- and the flow -- is the same on every run.
 //   mv_resolve  one thread per pixel: flow[p] = value of winner[p] (or +0, +0), one 8-byte store, and winner[p] goes back
 //               to 0, so the next frame starts from a clean map without a memset.
-// The same form as k_pp_fwd_scatter / k_pp_fwd_resolve (fb_postprocess.hip).
+// The same form as k_pp_fwd_scatter / k_pp_fwd_resolve (postprocess.hip).
 #include "mv_common.h"
 
 #include <new>

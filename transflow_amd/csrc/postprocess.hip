@@ -1,0 +1,210 @@
+// B1: FlowSource.post_process (source.py:337-363) on a device flow -- the clip, the FORWARD scatter (last write wins)
+// and its resolve, in float32 or (after a float64 convolution kernel, :344-348) float64 -- and the flow filters / mask
+// multiply that precede it (filters.py:36-72).  One implementation for every caller: the tf_fb_post_process* entry
+// points (farneback.hip) and the handle-free tf_flow_post_process*_dev bring their own winner buffer.
+#include <cstring>
+
+#include "common.h"
+
+using namespace tf;
+
+namespace {
+
+// numpy.clip, to the bit: min(max(v, lo), hi) as comparisons (v > lo ? v : lo, then t < hi ? t : hi), so a -0.0 meeting
+// a bound of 0 comes out as the bound's +0.0 on either side; the hardware's min / max order -0 below +0 and would keep
+// the -0.0 at an upper bound of 0 (the last column / row).  Painted motion-vector flows are full of -0.0.
+template <typename T> __device__ __forceinline__ T clip_np(T v, T lo, T hi)
+{
+    if (v != v)
+        return v;
+    const T t = v > lo ? v : lo;
+    return t < hi ? t : hi;
+}
+
+template <typename T2> __device__ __forceinline__ T2 clip_to_frame(T2 f, int i, int j, int W, int H)
+{
+    typedef decltype(f.x) T;
+    f.x = clip_np<T>(f.x, (T)(-j), (T)(W - 1 - j));
+    f.y = clip_np<T>(f.y, (T)(-i), (T)(H - 1 - i));
+    return f;
+}
+
+__device__ __forceinline__ int rint_i(float v) { return (int)rintf(v); }
+__device__ __forceinline__ int rint_i(double v) { return (int)rint(v); }
+
+template <typename T2> __global__ void k_pp_clip(T2 *flow, int W, int H, FastDiv dw)
+{
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= W * H)
+        return;
+    const int i = (int)fast_div((uint32_t)t, dw);
+    flow[t] = clip_to_frame(flow[t], i, t - i * W, W, H);
+}
+
+// source.py:350-358: every moving source p claims target p+d; numpy.put writes in
+// ascending p, so the largest p wins -> atomicMax on the source index.
+template <typename T2>
+__global__ void k_pp_fwd_scatter(const T2 *__restrict__ flow, int *__restrict__ winner, int W, int H, FastDiv dw)
+{
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = W * H;
+    if (t >= N)
+        return;
+    const int i = (int)fast_div((uint32_t)t, dw);
+    T2 f = clip_to_frame(flow[t], i, t - i * W, W, H);
+    int ix = rint_i(f.x), iy = rint_i(f.y);
+    int d = iy * W + ix;
+    if (d == 0)
+        return;
+    int target = clampi(t + d, 0, N - 1); // mode="clip"
+    atomicMax(&winner[target], t);
+}
+
+template <typename T2>
+__global__ void k_pp_fwd_resolve(T2 *__restrict__ flow, const int *__restrict__ winner, int W, int H, FastDiv dw)
+{
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= W * H)
+        return;
+    typedef decltype(flow[0].x) T;
+    int w = winner[t];
+    int src = w >= 0 ? w : t;
+    const int i = (int)fast_div((uint32_t)t, dw), j = t - i * W;
+    const int si = (int)fast_div((uint32_t)src, dw);
+    T2 f;
+    f.x = (T)(src - si * W - j); // source.py:359-360
+    f.y = (T)(si - i);
+    flow[t] = clip_to_frame(f, i, j, W, H); // :361-362
+}
+
+// The optional pre-steps of post_process: filters.py:36-72 and the mask multiply of
+// source.py:342-343, per pixel, in numpy's arithmetic (float32 for weak scalars, float64 for
+// numpy.float64 values; numpy.linalg.norm of a float32 pair is sqrt(x*x + y*y) in float32).
+struct FlowOps {
+    int n;
+    tf_flow_op op[TF_MAX_FLOW_OPS];
+};
+
+__global__ void k_pp_ops(float2 *__restrict__ flow, const float *__restrict__ mask, int N, FlowOps ops)
+{
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= N)
+        return;
+    float2 f = flow[t];
+    for (int i = 0; i < ops.n; i++) {
+        const int kind = ops.op[i].kind, wide = ops.op[i].wide;
+        const double v = ops.op[i].value;
+        if (kind == TF_FLOW_SCALE) {
+            if (wide) {
+                f.x = (float)((double)f.x * v);
+                f.y = (float)((double)f.y * v);
+            } else {
+                f.x = f.x * (float)v;
+                f.y = f.y * (float)v;
+            }
+        } else {
+            const float norm = sqrtf(f.x * f.x + f.y * f.y);
+            if (kind == TF_FLOW_THRESHOLD) {
+                const bool hit = wide ? ((double)norm <= v) : (norm <= (float)v);
+                if (hit)
+                    f = make_float2(0.f, 0.f);
+            } else { // clip: factors stay 1.0 (float64) where the norm is below the threshold
+                const bool hit = wide ? ((double)norm >= v) : (norm >= (float)v);
+                if (hit) {
+                    const double factor = wide ? v / (double)norm : (double)((float)v / norm);
+                    f.x = (float)((double)f.x * factor);
+                    f.y = (float)((double)f.y * factor);
+                }
+            }
+        }
+    }
+    if (mask) {
+        const float m = mask[t];
+        f.x = m * f.x;
+        f.y = m * f.y;
+    }
+    flow[t] = f;
+}
+
+template <typename T2> int scatter(const T2 *flow, int W, int H, int *winner, const PpLabels &lb)
+{
+    const size_t N = (size_t)W * H;
+    if (N == 0)
+        return TF_OK;
+    TF_REQUIRE(winner, "post_process: FORWARD needs a winner buffer of 4 bytes per pixel");
+    TF_HIP(hipMemsetAsync(winner, 0xFF, N * 4, stream()));
+    return launch(lb.fwd_scatter, k_pp_fwd_scatter<T2>, dim3(cdiv(N, 256)), dim3(256), 0, flow, winner, W, H,
+                  fast_div_setup((uint32_t)W));
+}
+
+template <typename T2> int direction_t(T2 *flow, int W, int H, int direction, int *winner, const PpLabels &lb)
+{
+    const size_t N = (size_t)W * H;
+    if (N == 0)
+        return TF_OK;
+    dim3 grid(cdiv(N, 256)), block(256);
+    const FastDiv dw = fast_div_setup((uint32_t)W);
+    if (direction == 0) {
+        TF_TRY(scatter((const T2 *)flow, W, H, winner, lb));
+        return launch(lb.fwd_resolve, k_pp_fwd_resolve<T2>, grid, block, 0, flow, (const int *)winner, W, H, dw);
+    }
+    return launch(lb.clip, k_pp_clip<T2>, grid, block, 0, flow, W, H, dw);
+}
+
+} // namespace
+
+namespace tf {
+
+int pp_scatter(const float2 *flow, int W, int H, int *winner, const PpLabels &lb) { return scatter(flow, W, H, winner, lb); }
+
+int pp_direction(void *flow, bool wide, int W, int H, int direction, int *winner, const PpLabels &lb)
+{
+    TF_REQUIRE(direction == 0 || direction == 1, "post_process: direction must be 0 (FORWARD) or 1 (BACKWARD), got %d",
+               direction);
+    if (wide)
+        return direction_t((double2 *)flow, W, H, direction, winner, lb);
+    return direction_t((float2 *)flow, W, H, direction, winner, lb);
+}
+
+int pp_ops(float2 *flow, int W, int H, int n_ops, const tf_flow_op *ops, const float *mask_dev, const PpLabels &lb)
+{
+    TF_REQUIRE(n_ops >= 0 && n_ops <= TF_MAX_FLOW_OPS, "post_process: at most %d flow filters, got %d", TF_MAX_FLOW_OPS,
+               n_ops);
+    TF_REQUIRE(n_ops == 0 || ops, "post_process: null filter list");
+    if (n_ops == 0 && !mask_dev)
+        return TF_OK;
+    FlowOps fo;
+    memset(&fo, 0, sizeof(fo));
+    fo.n = n_ops;
+    for (int i = 0; i < n_ops; i++) {
+        TF_REQUIRE(ops[i].kind >= TF_FLOW_SCALE && ops[i].kind <= TF_FLOW_CLIP, "post_process: unknown filter kind %d",
+                   ops[i].kind);
+        fo.op[i] = ops[i];
+    }
+    const int N = W * H;
+    return launch(lb.ops, k_pp_ops, dim3(cdiv((size_t)N, 256)), dim3(256), 0, flow, mask_dev, N, fo);
+}
+
+} // namespace tf
+
+TF_API int tf_flow_post_process_ex_dev(void *flow_dev, int wide, int width, int height, int direction, int n_ops,
+                                       const tf_flow_op *ops, const void *mask_dev, void *winner_dev)
+{
+    TF_REQUIRE(direction >= -1 && direction <= 1,
+               "tf_flow_post_process: direction must be 0 (FORWARD), 1 (BACKWARD) or -1 (none)");
+    TF_REQUIRE(width >= 0 && height >= 0 && (long long)width * height < (1ll << 31), "tf_flow_post_process: bad size");
+    TF_REQUIRE(flow_dev || (size_t)width * height == 0, "tf_flow_post_process: null pointer");
+    TF_REQUIRE(!wide || (n_ops == 0 && !mask_dev),
+               "tf_flow_post_process: the flow filters and the mask work on float32 flows, not on a float64 one");
+    TF_TRY(ensure_init());
+    TF_TRY(pp_ops((float2 *)flow_dev, width, height, n_ops, ops, (const float *)mask_dev, PP_FLOW));
+    if (direction < 0)
+        return TF_OK;
+    return pp_direction(flow_dev, wide != 0, width, height, direction, (int *)winner_dev, PP_FLOW);
+}
+
+TF_API int tf_flow_post_process_dev(void *flow_dev, int wide, int width, int height, int direction, void *scratch_dev)
+{
+    TF_REQUIRE(direction == 0 || direction == 1, "tf_flow_post_process: direction must be 0 (FORWARD) or 1 (BACKWARD)");
+    return tf_flow_post_process_ex_dev(flow_dev, wide, width, height, direction, 0, nullptr, nullptr, scratch_dev);
+}

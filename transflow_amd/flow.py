@@ -270,7 +270,7 @@ class FlowSource:
         self._locks = LockSchedule(self.lock_mode, lock_expr_stay, lock_expr_skip)
         self.output_frame_index = 0
         self.prev_flow = None
-        self._pp = None  # device handle used by post_process, created on first use
+        self._pp = None  # what post_process runs on (a flowops.PostProcess, or a resident method's handle), made on first use
         # the resident tail (below): what read_next_flow handed out whose flow is still on the device, the mask on the
         # device, and where the yielded arrays / DeviceFlows (transflow_amd/deviceflow.py) live
         self._pending = self._mask_dev = self._flow_pool = self._flow_ring = None
@@ -338,7 +338,7 @@ class FlowSource:
         self.input_frame_index = self.start_frame
 
     def post_process(self, raw):
-        """source.py:337-363 on the GPU (tf_fb_post_process_host): FORWARD inverts the push
+        """source.py:337-363 on the GPU (flowops.PostProcess): FORWARD inverts the push
         field with last-write-wins, both directions clip to the frame.  In place, like the
         reference (so `prev_flow` sees the processed array, source.py:317): the filters work on the array given, the
         mask and the convolution kernel each make a new one, which the steps after them work on."""
@@ -395,8 +395,8 @@ class FlowSource:
 
     def _post_handle(self):
         if self._pp is None:
-            from .farneback import Farneback
-            self._pp = Farneback(self.width, self.height, levels=0, device=self.device)
+            from .flowops import PostProcess
+            self._pp = PostProcess(self.width, self.height, device=self.device)
         return self._pp
 
     def _resident_ok(self) -> bool:
@@ -659,7 +659,8 @@ class _Method:
     colour: bool = False                    # the method reads colour frames: grey ones are refused
     # the handle post-processes its flows where they are (post_process_ex) and brings them down beside its kernels
     # (async_io, get_flow_begin): the resident path exists.  For the others it is not built: their flows come down
-    # raw and FlowSource.post_process works on the host array, with a handle of its own.
+    # raw and FlowSource.post_process works on the host array, through a flowops.PostProcess (a flow, a winner map and
+    # the mask on the device; no second flow handle).
     resident: bool = False
 
 

@@ -7,6 +7,9 @@ for callers that keep the arrays resident).
   upscale_array(arr, wf, hf)      <- utils.upscale_array, utils.py:417-418
   convolve_post_process(...)      <- the kernel step and what follows it in FlowSource.post_process,
                                      flow/sources/source.py:344-362
+  PostProcess(width, height)      <- the rest of FlowSource.post_process (filters, mask, direction handling,
+                                     source.py:339-343, 349-362) for flows of any source: a flow buffer, a winner
+                                     map and the mask on the device, no flow method's handle
   render1d / render2d             <- output/render.py:9-48
   bgr_to_grey(frame, size)        <- cv2.resize(INTER_NEAREST) + cv2.cvtColor(BGR2GRAY), cv.py:461-466
 """
@@ -17,7 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import TfFlowOp, check
 from .device import DevBuffer
 from .masks import parse_color
 
@@ -99,6 +102,81 @@ def convolve_post_process(flow, kernel, direction: int | None) -> np.ndarray:
     for b in (src, kb, dst, scratch):
         b.close()
     return res
+
+
+FLOW_OPS = {"scale": 0, "threshold": 1, "clip": 2}
+
+
+def flow_ops_array(ops):
+    """ops: iterable of (name, value); value typed as the filter's lambda returned it."""
+    items = []
+    for name, value in ops:
+        if isinstance(value, np.generic):
+            if not np.issubdtype(value.dtype, np.floating) and not np.issubdtype(value.dtype, np.integer):
+                raise NotImplementedError(f"flow filter value of type {value.dtype}")
+            wide = int(value.dtype == np.float64)          # strong float64 scalar: float64 arithmetic
+        elif isinstance(value, (int, float)):
+            wide = 0                                        # weak Python scalar: float32 arithmetic
+        else:
+            raise NotImplementedError(f"flow filter value of type {type(value).__name__} (array-valued "
+                                      "expressions are not supported on the device)")
+        items.append(TfFlowOp(FLOW_OPS[name], wide, float(value)))
+    arr = (TfFlowOp * max(1, len(items)))(*items)
+    return arr, len(items)
+
+
+def check_host_flow(flow, width: int, height: int) -> None:
+    if (not isinstance(flow, np.ndarray) or flow.dtype != np.float32 or not flow.flags.c_contiguous
+            or flow.shape != (height, width, 2)):
+        raise ValueError("post_process needs a C-contiguous float32 array of shape (H, W, 2)")
+
+
+class PostProcess:
+    """FlowSource.post_process short of the convolution, on the device (tf_flow_post_process_ex_dev), with the
+    methods a source uses of a flow handle: one float32 flow (8 B/px), the winner map FORWARD needs (4 B/px) and,
+    from the first host mask on, the mask (4 B/px)."""
+
+    def __init__(self, width: int, height: int, device: int | None = None):
+        self._lib = _lib.load()
+        if device is not None:
+            check(self._lib.tf_init(int(device)))
+        self.width, self.height = int(width), int(height)
+        n = max(1, self.width * self.height)
+        self._flow, self._winner, self._mask = DevBuffer(8 * n), DevBuffer(4 * n), None
+
+    def close(self):
+        for buf in (self._flow, self._winner, self._mask):
+            if buf is not None:
+                buf.close()
+        self._mask = None
+
+    def flow_ptr(self, pair: int = 0) -> int:
+        if pair != 0:
+            raise ValueError(f"pair {pair} out of range")
+        return self._flow.ptr
+
+    def post_process_ex(self, pair: int, direction: int | None, ops=(), mask_dev: int | None = None) -> None:
+        """Filters + mask + (direction handling unless direction is None) on the flow at flow_ptr(pair)."""
+        arr, n = flow_ops_array(ops)
+        check(self._lib.tf_flow_post_process_ex_dev(
+            C.c_void_p(self.flow_ptr(pair)), 0, self.width, self.height, -1 if direction is None else int(direction),
+            n, arr, C.c_void_p(mask_dev) if mask_dev else None, C.c_void_p(self._winner.ptr)))
+
+    def post_process_host_ex(self, flow: np.ndarray, direction: int | None, ops=(), mask=None) -> np.ndarray:
+        """The same on a host array, in place."""
+        check_host_flow(flow, self.width, self.height)
+        mask_dev = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, dtype=np.float32).reshape(self.height, self.width)
+            if self._mask is None:
+                self._mask = DevBuffer(max(1, m.nbytes))
+            self._mask.upload(m)
+            mask_dev = self._mask.ptr
+        self._flow.upload(flow)
+        self.post_process_ex(0, direction, ops, mask_dev)
+        if flow.nbytes:
+            check(self._lib.tf_dev_download(C.c_void_p(flow.ctypes.data), C.c_void_p(self._flow.ptr), flow.nbytes))
+        return flow
 
 
 def polar_filter(flow, polar, t: float) -> np.ndarray:
