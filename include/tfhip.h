@@ -652,6 +652,33 @@ int tf_comp_download_begin(tf_comp *comp, uint8_t *rgb_out);
 int tf_comp_download_end(tf_comp *comp);
 int tf_comp_image_ptr(tf_comp *comp, void **dev);
 
+/* ---- baseline JPEG of a frame in device memory (transflow/output/mjpeg.py:58-60, output/frames.py: the outputs whose
+ * product is a compressed frame) --------------------------------------------------------------------------------------
+ * The file libjpeg writes for 8-bit YCbCr 4:2:0 (sampling 2x2, 1x1, 1x1), one interleaved scan, the Annex K Huffman
+ * tables, the tables of jpeg_set_quality(quality, force_baseline) and a restart interval of `restart_mcus` MCUs --
+ * Pillow's save(quality=q, subsampling=2, restart_marker_blocks=r), byte for byte.  The restart intervals are coded
+ * side by side on the device; every decoder reproduces the pixels of the file without them.
+ * restart_mcus: 1 to 65535, 0 = the library's default.  The handle owns the header (SOI, JFIF APP0, two DQT, SOF0,
+ * four DHT, DRI, SOS: made once) and its staging, scan and packed-stream buffers, sized for the worst case at creation. */
+typedef struct tf_jpeg tf_jpeg;
+int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int restart_mcus);
+void tf_jpeg_destroy(tf_jpeg *enc);
+int tf_jpeg_header(tf_jpeg *enc, const uint8_t **bytes, size_t *n); /* valid as long as the handle */
+/* rgb_dev: uint8 [H][W][3] in device memory (tf_comp_image_ptr's, a pixmap's ...).  Queues its kernels on the calling
+   thread's stream and waits; header and stream are then copied to `out` (host) and *n_bytes is the file's size.  A file
+   larger than `capacity` returns TF_ERR_ARG with *n_bytes the size needed; `out` is then not written at all, and in no
+   case is anything written at or beyond out + capacity. */
+int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, size_t capacity, size_t *n_bytes);
+/* The same for an image in host memory: uploaded to a buffer of the handle first. */
+int tf_jpeg_encode(tf_jpeg *enc, const uint8_t *rgb_host, uint8_t *out, size_t capacity, size_t *n_bytes);
+/* The file of the handle's last encode again, for a caller whose buffer was too small: the intervals are still in
+   the handle's staging slots, so only the packing runs again, up to the new capacity.  Same return values;
+   TF_ERR_STATE if nothing has been encoded. */
+int tf_jpeg_copy_last(tf_jpeg *enc, uint8_t *out, size_t capacity, size_t *n_bytes);
+/* The interval restart_mcus = 0 stands for.  No GPU call: a process that only encodes on the host with the same
+   settings (transflow_amd/output.py) asks here. */
+int tf_jpeg_default_restart_mcus(void);
+
 /* ---- batch-of-frames mode over the GPUs of one node ----------------------
  * With flags == 0 every Farnebäck pair is independent (transflow/flow/sources/cv.py:478-490: the
  * `flow=` argument is an output buffer only), so ranks take contiguous ranges of pairs and the path

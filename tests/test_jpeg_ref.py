@@ -1,0 +1,257 @@
+"""The numpy restatement of libjpeg's baseline encoder (tests/jpeg_ref.py) against libjpeg's own files, and the host
+side of the JPEG frame path: JpegFrame, HipMjpegOutput, the drop-in's routing.  No GPU."""
+import asyncio
+import glob
+import inspect
+import io
+import os
+import pickle
+import sys
+import types
+
+import numpy as np
+import pytest
+
+from tests import jpeg_ref
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "jpeg_*.npz")))
+
+
+def _pillow_with_restart():
+    try:
+        import PIL.JpegImagePlugin as plugin
+    except ImportError:
+        return False
+    return "restart_marker_blocks" in inspect.getsource(plugin._save)
+
+
+needs_pillow_restart = pytest.mark.skipif(not _pillow_with_restart(), reason="no Pillow with restart_marker_blocks")
+
+
+def test_every_case_has_its_fixture():
+    assert sorted(os.path.basename(p)[5:-4] for p in FIXTURES) == sorted(jpeg_ref.CASES)
+    for path in FIXTURES:
+        image, quality, restart, expected = jpeg_ref.load_case(path)
+        h, w, _, q, r = jpeg_ref.CASES[os.path.basename(path)[5:-4]]
+        assert image.shape == (h, w, 3) and image.dtype == np.uint8 and (quality, restart) == (q, r)
+        assert os.path.getsize(path) < (1 << 20)
+
+
+@pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[5:-4])
+def test_restatement_equals_libjpegs_file(path):
+    image, quality, restart, expected = jpeg_ref.load_case(path)
+    got = jpeg_ref.encode(image, quality, restart)
+    assert len(got) == len(expected)
+    assert got == expected
+
+
+def test_fixtures_exercise_what_they_are_for():
+    """The failure modes the cases are chosen for do occur in their files."""
+    def scan(name):
+        data = jpeg_ref.load_case(os.path.join(GOLDEN, f"jpeg_{name}.npz"))[3]
+        return data[data.index(b"\xff\xda") + 14:-2]
+    noisy = scan("33x47_noise_q100")
+    assert b"\xff\x00" in noisy                                            # byte stuffing
+    wrapped = scan("45x61_r1")                                             # 12 intervals: RST0 .. RST7, RST0, RST1, RST2
+    assert [wrapped.count(bytes([0xFF, 0xD0 + k])) for k in range(8)] == [2, 2, 2, 1, 1, 1, 1, 1]
+    assert not any(bytes([0xFF, 0xD0 + k]) in scan("45x61_r100") for k in range(8))            # one interval: no marker
+    # category 11: a DC step of 2040 between neighbouring blocks of the checkerboard
+    y = jpeg_ref.ycc(jpeg_ref.checkerboard(32, 32))[0]
+    dc = jpeg_ref.blocks_quantised(y, jpeg_ref.quant_table(jpeg_ref.QUANT_LUMA, 100))[..., 0]
+    assert int(abs(dc[0, 1] - dc[0, 0])).bit_length() == 11
+
+
+@needs_pillow_restart
+@pytest.mark.parametrize("shape,quality,restart", [((16, 16), 75, 1), ((10, 10), 50, 1), ((40, 24), 90, 2), ((23, 57), 30, 5),
+                                                   ((49, 31), 100, 7), ((8, 8), 1, 3)])
+def test_restatement_equals_live_pillow(shape, quality, restart):
+    from transflow_amd.jpeg import pillow_encode
+    for image in (jpeg_ref.stored_image(*shape, seed=quality), jpeg_ref.noise_image(*shape, seed=restart)):
+        assert jpeg_ref.encode(image, quality, restart) == pillow_encode(image, quality, restart)
+
+
+# ---- JpegFrame ---------------------------------------------------------------------------------------------------------
+def _frame(shape=(24, 40), quality=50, restart=4, seed=3):
+    from transflow_amd.jpeg import JpegFrame
+    image = jpeg_ref.stored_image(*shape, seed=seed)
+    return image, JpegFrame(jpeg_ref.encode(image, quality, restart), image.shape, quality, restart)
+
+
+def test_jpeg_frame_pickles_as_its_fields_only():
+    from transflow_amd.jpeg import JpegFrame
+    image, frame = _frame()
+    blob = pickle.dumps(frame)
+    back = pickle.loads(blob)
+    assert isinstance(back, JpegFrame) and back == frame
+    assert (back.data, back.shape, back.quality, back.restart_mcus) == (frame.data, (24, 40, 3), 50, 4)
+    assert len(blob) < len(frame.data) + 200                              # the file and four numbers: no array
+    assert bytes(frame) == frame.tobytes() == frame.data and len(frame) == len(frame.data)
+
+
+def test_jpeg_frame_decodes_to_the_picture():
+    pytest.importorskip("PIL")
+    image, frame = _frame(quality=95)
+    decoded = frame.decode()
+    assert decoded.shape == image.shape and decoded.dtype == np.uint8
+    # chroma is halved and the picture noisy: close in the mean, not pixel by pixel
+    assert np.abs(decoded.astype(int) - image.astype(int)).mean() < 16
+
+
+# ---- HipMjpegOutput ----------------------------------------------------------------------------------------------------
+def test_mjpeg_output_serves_a_jpeg_frame_as_it_is():
+    from transflow_amd.output import HipMjpegOutput
+    image, frame = _frame()
+    out = HipMjpegOutput("localhost", 8080, 40, 24, 30.0, quality=50)
+    out.feed(frame)
+    served = asyncio.run(out.stream.get_frame_processed())
+    assert served.tobytes() is frame.data
+    out.feed((frame, None))                                                # pipeline.py feeds tuples too (mjpeg.py:182)
+    assert out.stream.processed().tobytes() is frame.data
+    assert out.stream.get_bandwidth() == 2 * len(frame.data)
+    with pytest.raises(ValueError):
+        out.feed(_frame(shape=(16, 16))[1])
+    with pytest.raises(ValueError):
+        out.feed(np.zeros((24, 41, 3), np.uint8))
+
+
+@needs_pillow_restart
+def test_mjpeg_output_encodes_a_raw_frame_to_the_same_bytes():
+    from transflow_amd import output
+    image, frame = _frame(restart=output.default_restart_mcus())         # asked of the library: no GPU is opened
+    out = output.HipMjpegOutput("localhost", 8080, 40, 24, 30.0, quality=50)
+    out.feed(image)
+    assert out.stream.processed().tobytes() == frame.data                 # what the device encoder's frame would be
+
+
+def test_mjpeg_address():
+    from transflow_amd.output import mjpeg_address
+    assert mjpeg_address("mjpeg") == ("localhost", 8080)
+    assert mjpeg_address("MJPEG:9000") == ("localhost", 9000)
+    assert mjpeg_address("mjpeg:9000:my-host") == ("my-host", 9000)
+    assert mjpeg_address("out.mp4") is None and mjpeg_address(None) is None
+    with pytest.raises(ValueError):
+        mjpeg_address("mjpeg:1:2:3")
+
+
+# ---- the drop-in's routing, over stubs of the two reference classes it patches ---------------------------------------
+@pytest.fixture
+def stub_transflow():
+    saved = {m: sys.modules[m] for m in list(sys.modules) if m == "transflow" or m.startswith("transflow.")}
+    for m in saved:
+        del sys.modules[m]
+
+    class VideoOutput:
+        fed = []
+
+        def __init__(self, path):
+            self.path = path
+
+        @property
+        def output_path(self):                                            # video_output.py:62-64
+            return self.path
+
+        def feed(self, frame):
+            VideoOutput.fed.append(frame)
+
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            return None
+
+        @classmethod
+        def from_args(cls, path, width, height, framerate=None, vcodec="h264", execute=False, replace=False,
+                      initial_counter=0):
+            return cls(path)
+
+    class Compositor:
+        @classmethod
+        def from_args(cls, height, width, layer_configs, background_color="#ffffff"):
+            return "the reference's"
+
+    names = {"transflow": {}, "transflow.output": {}, "transflow.output.video_output": {"VideoOutput": VideoOutput},
+             "transflow.compositor": {}, "transflow.compositor.compositor": {"Compositor": Compositor}}
+    for name, attrs in names.items():
+        mod = types.ModuleType(name)
+        mod.__path__ = []
+        mod.__dict__.update(attrs)
+        sys.modules[name] = mod
+    try:
+        yield types.SimpleNamespace(VideoOutput=VideoOutput, Compositor=Compositor)
+    finally:
+        for name in names:
+            sys.modules.pop(name, None)
+        sys.modules.update(saved)
+
+
+def test_install_routes_outputs_and_uninstall_restores(stub_transflow):
+    from transflow_amd import dropin
+    from transflow_amd.compositor import HipCompositor
+    from transflow_amd.config import LayerConfig
+    from transflow_amd.output import HipMjpegOutput
+    Out, Comp = stub_transflow.VideoOutput, stub_transflow.Compositor
+    out_original, comp_original = Out.__dict__["from_args"], Comp.__dict__["from_args"]
+    dropin.install(flow=False)                                            # the default: the outputs are not touched
+    try:
+        assert Out.__dict__["from_args"] is out_original
+        assert Comp.from_args(8, 8, [LayerConfig(0)]).jpeg_frames is None
+    finally:
+        dropin.uninstall()
+    assert Comp.__dict__["from_args"] is comp_original
+    with pytest.raises(ValueError):
+        dropin.install(flow=False, jpeg_frames=50, lazy_frames=True)
+    dropin.install(flow=False, jpeg_frames=60)
+    try:
+        comp = Comp.from_args(8, 8, [LayerConfig(0)])
+        assert isinstance(comp, HipCompositor) and comp.jpeg_frames == 60
+        out = Out.from_args("mjpeg:9001", 40, 24, framerate=12.5)
+        assert isinstance(out, HipMjpegOutput)
+        assert (out.host, out.port, out.width, out.height, out.framerate, out.quality) == ("localhost", 9001, 40, 24, 12.5, 60)
+        assert out.output_path is None                                    # pipeline.py:479-481 reads it of every output
+        other = Out.from_args("out.mp4", 40, 24)
+        assert other.output_path == "out.mp4"                             # ... the wrapped one's is the reference's
+        image, frame = _frame()
+        with other as entered:
+            entered.feed(image)                                           # pixels pass through to the reference's output
+            assert Out.fed[-1] is image and other.path == "out.mp4"
+            with pytest.raises(TypeError, match="jpeg_frames"):
+                entered.feed(frame)
+            with pytest.raises(TypeError, match="jpeg_frames"):
+                entered.feed((frame, None))
+    finally:
+        dropin.uninstall()
+    assert Out.__dict__["from_args"] is out_original and Comp.__dict__["from_args"] is comp_original
+
+
+def test_wrapped_output_survives_pickling_and_copying():
+    """An object whose __init__ has not run (what unpickling makes first) has no `_output`: an AttributeError, not a
+    recursion."""
+    import copy
+    from transflow_amd.output import RawFramesOnly
+    blank = RawFramesOnly.__new__(RawFramesOnly)
+    with pytest.raises(AttributeError):
+        blank.feed_count
+    wrapped = RawFramesOnly(types.SimpleNamespace(output_path="x.mp4", feed=lambda frame: None))
+    again = copy.copy(wrapped)
+    assert again.output_path == "x.mp4"
+
+
+def test_host_encode_refuses_a_pillow_without_restart_markers(monkeypatch):
+    PIL = pytest.importorskip("PIL")
+    from transflow_amd.jpeg import pillow_encode
+    monkeypatch.setattr(PIL, "__version__", "9.5.0")
+    with pytest.raises(RuntimeError, match="restart_marker_blocks"):
+        pillow_encode(np.zeros((8, 8, 3), np.uint8), 50, 4)
+
+
+def test_compositor_flag_is_plain_state():
+    from transflow_amd.compositor import HipCompositor
+    comp = HipCompositor(8, 8, [], jpeg_frames=50)
+    back = pickle.loads(pickle.dumps(comp))
+    assert back.jpeg_frames == 50 and back._jpeg is None
+    assert pickle.loads(pickle.dumps(HipCompositor(8, 8, []))).jpeg_frames is None
+    with pytest.raises(ValueError):
+        HipCompositor(8, 8, [], jpeg_frames=50, lazy_frames=True)
+    with pytest.raises(ValueError):
+        HipCompositor(8, 8, [], jpeg_frames=0)

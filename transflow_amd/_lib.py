@@ -213,6 +213,13 @@ PROTOTYPES = {
     "tf_comp_download_begin": (_I, [_P, _P]),
     "tf_comp_download_end": (_I, [_P]),
     "tf_comp_image_ptr": (_I, [_P, _PP]),
+    "tf_jpeg_create": (_I, [_PP, _I, _I, _I, _I]),
+    "tf_jpeg_destroy": (None, [_P]),
+    "tf_jpeg_header": (_I, [_P, _PP, C.POINTER(C.c_size_t)]),
+    "tf_jpeg_encode_dev": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_jpeg_encode": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_jpeg_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_jpeg_default_restart_mcus": (_I, []),
     "tf_batch_unique_id": (_I, [_P]),
     "tf_batch_init": (_I, [_PP, _I, _I, _P]),
     "tf_batch_destroy": (None, [_P]),

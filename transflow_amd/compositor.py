@@ -309,16 +309,27 @@ LAYER_CLASSES = {"moveref": HipMoveReferenceLayer, "sum": HipSumLayer, "static":
 class HipCompositor:
     """Same constructor, methods and attributes as transflow.compositor.Compositor."""
 
-    def __init__(self, height: int, width: int, layers, background_color: str = "#ffffff", lazy_frames: bool = False):
+    def __init__(self, height: int, width: int, layers, background_color: str = "#ffffff", lazy_frames: bool = False,
+                 jpeg_frames: int | None = None):
         """lazy_frames: render() returns a DeviceFrame (transflow_amd/deviceframe.py) -- the uint8 (H, W, 3) array to
         everything numpy, its download started but not waited for, so that frame t comes down (pipeline.py:518,
-        output/ffmpeg.py:32-54) beside frame t + 1's uploads and kernels (pipeline.py:565).  Default: a plain ndarray."""
+        output/ffmpeg.py:32-54) beside frame t + 1's uploads and kernels (pipeline.py:565).  Default: a plain ndarray.
+        jpeg_frames: a quality, 1 to 100 -- render() returns a JpegFrame (transflow_amd/jpeg.py): the frame is encoded
+        where it is, the deferred one-launch frame included, and only the file comes down (an output whose product is
+        a compressed frame: output/mjpeg.py:58-60).  Not together with lazy_frames."""
+        if jpeg_frames is not None:
+            if lazy_frames:
+                raise ValueError("jpeg_frames and lazy_frames exclude each other: the encode is not overlapped")
+            if not 1 <= int(jpeg_frames) <= 100:
+                raise ValueError(f"jpeg_frames is a JPEG quality, 1 to 100, not {jpeg_frames}")
         self.height, self.width = int(height), int(width)
         self.background_color = parse_color(background_color)
         self.background = np.zeros((self.height, self.width, 3), dtype=np.uint8)
         self.background[:, :] = self.background_color
         self.layers = list(layers)
         self.lazy_frames = bool(lazy_frames)
+        self.jpeg_frames = None if jpeg_frames is None else int(jpeg_frames)
+        self._jpeg = None           # the encoder, made at the first render
         self._comp = None
         self._comp2 = None          # lazy frames: the second image (frame t downloads from one while t + 1 is rendered into the other)
         self._flip = False
@@ -352,6 +363,11 @@ class HipCompositor:
             comp.begin()
             for layer in self.layers:
                 layer.render_into(comp)
+        if self.jpeg_frames is not None:
+            if self._jpeg is None:
+                from .jpeg import JpegEncoder
+                self._jpeg = JpegEncoder(self.height, self.width, self.jpeg_frames)
+            return self._jpeg.frame(comp)
         if self._frame_pool is None:
             from .device import ArrayPool
             self._frame_pool = ArrayPool((self.height, self.width, 3), np.uint8, pinned=True)
@@ -364,25 +380,28 @@ class HipCompositor:
 
     @classmethod
     def from_args(cls, height: int, width: int, layer_configs, background_color: str = "#ffffff", rng: str = "numpy",
-                  lazy_frames: bool = False):
+                  lazy_frames: bool = False, jpeg_frames: int | None = None):
         layers = []
         for config in layer_configs:
             classname = getattr(config, "classname", "moveref")
             if classname not in LAYER_CLASSES:
                 raise ValueError(f"Unknown layer classname {classname}")                # layer.py:56
             layers.append(LAYER_CLASSES[classname](config, height, width, [], rng=rng))
-        return cls(height, width, layers, background_color=background_color, lazy_frames=lazy_frames)
+        return cls(height, width, layers, background_color=background_color, lazy_frames=lazy_frames,
+                   jpeg_frames=jpeg_frames)
 
     def set_sources(self, pixmap_interfaces: dict):
         for i, layer in enumerate(self.layers):
             layer.set_sources(pixmap_interfaces.get(i, []))
 
     def __getstate__(self):
-        return {k: v for k, v in self.__dict__.items() if k not in ("_comp", "_comp2", "_frame_pool")}
+        return {k: v for k, v in self.__dict__.items() if k not in ("_comp", "_comp2", "_frame_pool", "_jpeg")}
 
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.lazy_frames = bool(state.get("lazy_frames", False))
+        self.jpeg_frames = state.get("jpeg_frames")
+        self._jpeg = None
         self._comp = None
         self._comp2 = None
         self._flip = False
@@ -396,3 +415,6 @@ class HipCompositor:
             if comp is not None:
                 comp.close()
                 setattr(self, name, None)
+        if getattr(self, "_jpeg", None) is not None:
+            self._jpeg.close()
+            self._jpeg = None

@@ -1,0 +1,558 @@
+// Baseline JPEG of a device-resident RGB frame: what libjpeg writes for 8-bit YCbCr 4:2:0, one interleaved scan, the
+// Annex K Huffman tables, jpeg_set_quality's tables and a restart interval -- byte for byte (tests/jpeg_ref.py is the
+// numpy statement of the same rules, tests/golden/jpeg_*.npz are libjpeg's own files).
+//
+// Restart intervals are what make the entropy coder parallel: DC prediction starts over and the stream is byte-aligned
+// at each, so an interval's bytes depend on nothing but its own MCUs.
+//
+//   k_jpeg_encode  one wave per interval.  Per MCU: lane l owns the 2 x 2 pixels under chroma sample l of the 16 x 16
+//                  tile (the image's only read from HBM, 3 B/px), converts them (jccolor.c) and averages the chroma
+//                  (jcsample.c h2v2_downsample); 48 lanes run jfdctint.c's row pass, then its column pass, on the six
+//                  blocks in LDS; then block by block lane k takes zigzag coefficient k, quantises it (jcdctmgr.c), and
+//                  a ballot of the non-zero lanes gives it its zero run, hence its symbols (jchuff.c encode_one_block:
+//                  ZRLs, code, value bits; lane 0 the DC difference, lane 63 the EOB) -- a wave prefix sum of the bit
+//                  counts places them and they are ORed into an LDS bit buffer.  After the MCU the whole bytes of that
+//                  buffer go to the interval's staging slot, an 0x00 after every 0xFF (a ballot counts the 0xFFs
+//                  before a lane's byte), and the bits left over are carried to the front.  The buffer is zeroed by
+//                  the kernel before it is used and behind every flush.
+//   k_jpeg_scan    exclusive sum of the intervals' byte counts (one work-group).
+//   k_jpeg_pack    one wave per interval copies its slot to its place in the packed stream and puts RSTn behind it, EOI
+//                  behind the last; no byte at or past `capacity` is written.
+//
+// Dummy blocks (jccoefct.c compress_data): the luma blocks of an MCU beyond ceil(W / 8) x ceil(H / 8) are not made
+// from pixels; their AC coefficients are zero and their DC is that of the block coded before them.
+// Chroma rows (jcprepct.c pre_process_data): the input is padded to an even row count only, and the DOWNSAMPLED plane
+// is then padded with its last row -- a chroma row below the image averages rows H - 2 and H - 1 of an image of even
+// height, not H - 1 twice.
+#include "jpeg_common.h"
+
+#include <cstring>
+
+namespace tf {
+namespace jpeg {
+
+constexpr int WAVE = 64;
+
+// jfdctint.c (CONST_BITS 13, PASS1_BITS 2)
+constexpr int CONST_BITS = 13, PASS1_BITS = 2;
+constexpr int FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270,
+              FIX_0_899976223 = 7373, FIX_1_175875602 = 9633, FIX_1_501321110 = 12299, FIX_1_847759065 = 15137,
+              FIX_1_961570560 = 16069, FIX_2_053119869 = 16819, FIX_2_562915447 = 20995, FIX_3_072711026 = 25172;
+
+__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// one pass of jpeg_fdct_islow over 8 values `stride` apart
+template <bool FIRST> __device__ __forceinline__ void fdct_pass(int *d, int stride)
+{
+    int v[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        v[i] = d[i * stride];
+    int tmp0 = v[0] + v[7], tmp7 = v[0] - v[7], tmp1 = v[1] + v[6], tmp6 = v[1] - v[6];
+    int tmp2 = v[2] + v[5], tmp5 = v[2] - v[5], tmp3 = v[3] + v[4], tmp4 = v[3] - v[4];
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    constexpr int N = FIRST ? CONST_BITS - PASS1_BITS : CONST_BITS + PASS1_BITS;
+    if (FIRST) {
+        d[0] = (tmp10 + tmp11) << PASS1_BITS;
+        d[4 * stride] = (tmp10 - tmp11) << PASS1_BITS;
+    } else {
+        d[0] = descale(tmp10 + tmp11, PASS1_BITS);
+        d[4 * stride] = descale(tmp10 - tmp11, PASS1_BITS);
+    }
+    int z1 = (tmp12 + tmp13) * FIX_0_541196100;
+    d[2 * stride] = descale(z1 + tmp13 * FIX_0_765366865, N);
+    d[6 * stride] = descale(z1 + tmp12 * (-FIX_1_847759065), N);
+    z1 = tmp4 + tmp7;
+    int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
+    const int z5 = (z3 + z4) * FIX_1_175875602;
+    tmp4 *= FIX_0_298631336, tmp5 *= FIX_2_053119869, tmp6 *= FIX_3_072711026, tmp7 *= FIX_1_501321110;
+    z1 *= -FIX_0_899976223, z2 *= -FIX_2_562915447, z3 *= -FIX_1_961570560, z4 *= -FIX_0_390180644;
+    z3 += z5, z4 += z5;
+    d[7 * stride] = descale(tmp4 + z1 + z3, N);
+    d[5 * stride] = descale(tmp5 + z2 + z4, N);
+    d[3 * stride] = descale(tmp6 + z2 + z3, N);
+    d[1 * stride] = descale(tmp7 + z1 + z4, N);
+}
+
+struct Px {
+    int r, g, b;
+};
+
+__device__ __forceinline__ Px load_px(const uint8_t *__restrict__ rgb, int W, int y, int x)
+{
+    const uint8_t *p = rgb + ((size_t)y * W + x) * 3;
+    return Px{p[0], p[1], p[2]};
+}
+
+// jccolor.c rgb_ycc_convert, SCALEBITS 16
+__device__ __forceinline__ int ycc_y(Px p) { return (19595 * p.r + 38470 * p.g + 7471 * p.b + 32768) >> 16; }
+__device__ __forceinline__ int ycc_cb(Px p) { return (-11059 * p.r - 21709 * p.g + 32768 * p.b + (128 << 16) + 32767) >> 16; }
+__device__ __forceinline__ int ycc_cr(Px p) { return (32768 * p.r - 27439 * p.g - 5329 * p.b + (128 << 16) + 32767) >> 16; }
+
+__device__ __forceinline__ int wave_inclusive_sum(int v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const int up = __shfl_up(v, d, WAVE);
+        if (lane >= d)
+            v += up;
+    }
+    return v;
+}
+
+struct EncodeArgs {
+    const uint8_t *rgb;
+    int W, H;
+    int mcus_x, n_mcus, restart_mcus;
+    int lum_bx, lum_by;   // the luma block grid: ceil(W / 8) x ceil(H / 8)
+    int chroma_rows;      // ceil(H / 2): the downsampled rows that come from pixels
+    const Tables *tables;
+    uint8_t *staging;     // n_intervals slots of slot_bytes
+    uint32_t slot_bytes;
+    uint32_t *lengths;    // per interval: the bytes it wrote
+    uint32_t *overflow;   // set if an interval had more bytes than its slot (the bound of jpeg_common.h says: never)
+};
+
+__global__ __launch_bounds__(WAVE) void k_jpeg_encode(const EncodeArgs a, const FastDiv div_mcus_x)
+{
+    __shared__ int s_blk[6][64];          // samples - 128, then coefficients: Y00 Y01 Y10 Y11 Cb Cr
+    __shared__ uint32_t s_bits[BIT_WORDS]; // the MCU's bits, first bit of the stream in bit 31 of word 0
+    const int lane = threadIdx.x;
+    const Tables &t = *a.tables;
+    const int q_luma = t.q8[0][lane], q_chroma = t.q8[1][lane], zz = t.zz[lane];
+    for (int w = lane; w < BIT_WORDS; w += WAVE)
+        s_bits[w] = 0;
+    const int first = blockIdx.x * a.restart_mcus; // (n_intervals * restart_mcus < n_mcus + restart_mcus <= 2^25)
+    const int last = min(first + a.restart_mcus, a.n_mcus);
+    uint8_t *slot = a.staging + (size_t)blockIdx.x * a.slot_bytes;
+    int last_dc[3] = {0, 0, 0};
+    uint32_t bitpos = 0; // bits in s_bits
+    uint32_t outpos = 0; // bytes in the slot
+    const int cy = lane >> 3, cx = lane & 7;
+    __syncthreads();
+    for (int m = first; m < last; m++) {
+        const int my = (int)fast_div((uint32_t)m, div_mcus_x), mx = m - my * a.mcus_x;
+        // ---- colour, downsample
+        {
+            const int x0 = min(mx * 16 + 2 * cx, a.W - 1), x1 = min(mx * 16 + 2 * cx + 1, a.W - 1);
+            const int y0 = min(my * 16 + 2 * cy, a.H - 1), y1 = min(my * 16 + 2 * cy + 1, a.H - 1);
+            Px p00 = load_px(a.rgb, a.W, y0, x0), p01 = load_px(a.rgb, a.W, y0, x1);
+            Px p10 = load_px(a.rgb, a.W, y1, x0), p11 = load_px(a.rgb, a.W, y1, x1);
+            int *yb = &s_blk[(cy >> 2) * 2 + (cx >> 2)][((2 * cy) & 7) * 8 + ((2 * cx) & 7)];
+            yb[0] = ycc_y(p00) - 128, yb[1] = ycc_y(p01) - 128, yb[8] = ycc_y(p10) - 128, yb[9] = ycc_y(p11) - 128;
+            const int cr = min(my * 8 + cy, a.chroma_rows - 1); // below the image: the last downsampled row again
+            const int c0 = min(2 * cr, a.H - 1), c1 = min(2 * cr + 1, a.H - 1);
+            if (c0 != y0 || c1 != y1) {
+                p00 = load_px(a.rgb, a.W, c0, x0), p01 = load_px(a.rgb, a.W, c0, x1);
+                p10 = load_px(a.rgb, a.W, c1, x0), p11 = load_px(a.rgb, a.W, c1, x1);
+            }
+            const int bias = 1 + (cx & 1); // 1, 2, 1, 2 ... along the output row (an MCU starts at an even column)
+            s_blk[4][lane] = ((ycc_cb(p00) + ycc_cb(p01) + ycc_cb(p10) + ycc_cb(p11) + bias) >> 2) - 128;
+            s_blk[5][lane] = ((ycc_cr(p00) + ycc_cr(p01) + ycc_cr(p10) + ycc_cr(p11) + bias) >> 2) - 128;
+        }
+        __syncthreads();
+        // ---- DCT: rows, then columns
+        if (lane < 48)
+            fdct_pass<true>(&s_blk[lane >> 3][(lane & 7) * 8], 1);
+        __syncthreads();
+        if (lane < 48)
+            fdct_pass<false>(&s_blk[lane >> 3][lane & 7], 8);
+        __syncthreads();
+        // ---- quantise and code, block by block
+        int prev_dc = 0;
+#pragma unroll
+        for (int b = 0; b < 6; b++) {
+            const int comp = b < 4 ? 0 : b - 3, tb = b < 4 ? 0 : 1;
+            const int c = s_blk[b][zz];
+            const uint32_t q8 = (uint32_t)(tb ? q_chroma : q_luma);
+            const uint32_t mag = ((uint32_t)abs(c) + (q8 >> 1)) / q8;
+            int v = c < 0 ? -(int)mag : (int)mag;
+            if (b > 0 && b < 4 && (2 * mx + (b & 1) >= a.lum_bx || 2 * my + (b >> 1) >= a.lum_by))
+                v = lane == 0 ? prev_dc : 0; // a dummy block
+            if (lane > 0)
+                v = max(-1023, min(1023, v)); // (never: an AC coefficient of 8-bit samples has 10 bits)
+            const int dc = __builtin_amdgcn_readfirstlane(v);
+            prev_dc = dc;
+            const unsigned long long nonzero = __ballot(v != 0) & ~1ull; // the AC lanes
+            int sym_v = v;
+            uint32_t entry = 0; // what the lane's value is coded with
+            int n_zrl = 0;
+            if (lane == 0) {
+                sym_v = max(-2047, min(2047, dc - last_dc[comp]));
+                entry = t.dc[tb][32 - __clz(abs(sym_v))];
+            } else if (v != 0) {
+                const unsigned long long below = nonzero & ((1ull << lane) - 1);
+                const int prev = below ? 63 - __clzll((long long)below) : 0;
+                const int run = lane - 1 - prev;
+                n_zrl = run >> 4;
+                entry = t.ac[tb][((run & 15) << 4) | (32 - __clz(abs(v)))];
+            } else if (lane == 63) {
+                entry = t.ac[tb][0x00]; // EOB: the block ends in zeros
+            }
+            last_dc[comp] = dc;
+            const int nbits = sym_v == 0 ? 0 : 32 - __clz(abs(sym_v));
+            const uint32_t value = (uint32_t)(sym_v < 0 ? sym_v - 1 : sym_v) & ((1u << nbits) - 1);
+            unsigned long long bits = 0;
+            int len = 0;
+            if (n_zrl) {
+                const uint32_t zrl = t.ac[tb][0xF0];
+                for (int i = 0; i < n_zrl; i++)
+                    bits = (bits << (zrl >> 16)) | (zrl & 0xFFFF), len += zrl >> 16;
+            }
+            bits = (bits << (entry >> 16)) | (entry & 0xFFFF), len += entry >> 16;
+            bits = (bits << nbits) | value, len += nbits;
+            len = min(len, LANE_MAX_BITS); // (never: the host checked the tables)
+            const int incl = wave_inclusive_sum(len, lane);
+            if (len) {
+                const uint32_t p = bitpos + (uint32_t)(incl - len);
+                const unsigned long long w = bits << (64 - len);
+                const uint32_t word = p >> 5, sh = p & 31;
+                const uint32_t w0 = (uint32_t)(w >> 32 >> sh), w1 = (uint32_t)(w >> sh);
+                const uint32_t w2 = sh ? (uint32_t)(w << (32 - sh)) : 0u;
+                if (word + 2 < BIT_WORDS) {
+                    if (w0)
+                        atomicOr(&s_bits[word], w0);
+                    if (w1)
+                        atomicOr(&s_bits[word + 1], w1);
+                    if (w2)
+                        atomicOr(&s_bits[word + 2], w2);
+                }
+            }
+            bitpos += (uint32_t)__shfl(incl, WAVE - 1, WAVE);
+        }
+        // ---- the MCU's whole bytes to the slot; the interval's last MCU pads with ones first (flush_bits)
+        if (m == last - 1 && (bitpos & 7)) {
+            const uint32_t pad = 8 - (bitpos & 7);
+            if (lane == 0)
+                atomicOr(&s_bits[bitpos >> 5], ((1u << pad) - 1) << (32 - (bitpos & 31) - pad));
+            bitpos += pad;
+        }
+        __syncthreads();
+        const uint32_t n_bytes = bitpos >> 3;
+        for (uint32_t base = 0; base < n_bytes; base += WAVE) {
+            const uint32_t j = base + lane;
+            const bool valid = j < n_bytes;
+            const uint32_t byte = valid ? (s_bits[j >> 2] >> (24 - 8 * (j & 3))) & 0xFF : 0;
+            const unsigned long long ff = __ballot(valid && byte == 0xFF);
+            const uint32_t pos = outpos + lane + __popcll(ff & ((1ull << lane) - 1));
+            if (valid) {
+                if (pos < a.slot_bytes)
+                    slot[pos] = (uint8_t)byte;
+                if (byte == 0xFF && pos + 1 < a.slot_bytes)
+                    slot[pos + 1] = 0;
+            }
+            outpos += min((uint32_t)WAVE, n_bytes - base) + __popcll(ff);
+        }
+        // ---- the bits left over go to the front of a zeroed buffer
+        const uint32_t rem = bitpos & 7;
+        const uint32_t carry = rem ? ((s_bits[n_bytes >> 2] >> (24 - 8 * (n_bytes & 3))) & 0xFF) << 24 : 0;
+        const uint32_t used = (bitpos >> 5) + 3;
+        __syncthreads();
+        for (uint32_t w = lane; w < used && w < BIT_WORDS; w += WAVE)
+            s_bits[w] = w == 0 ? carry : 0;
+        bitpos = rem;
+        __syncthreads();
+    }
+    if (lane == 0) {
+        a.lengths[blockIdx.x] = min(outpos, a.slot_bytes);
+        if (outpos > a.slot_bytes)
+            *a.overflow = 1;
+    }
+}
+
+// lengths[n] -> offsets[n] (exclusive sums); info[0] = the scan's bytes: all intervals, a marker behind each
+constexpr int SCAN_BLOCK = 1024;
+__global__ __launch_bounds__(SCAN_BLOCK) void k_jpeg_scan(const uint32_t *__restrict__ lengths, uint32_t *__restrict__ offsets,
+                                                          int n, unsigned long long *__restrict__ info)
+{
+    __shared__ unsigned long long s_wave[SCAN_BLOCK / WAVE];
+    __shared__ unsigned long long s_carry;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (tid == 0)
+        s_carry = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += SCAN_BLOCK) {
+        const int i = base + tid;
+        const unsigned long long v = i < n ? lengths[i] : 0;
+        unsigned long long incl = v;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const unsigned long long up = __shfl_up(incl, d, WAVE);
+            if (lane >= d)
+                incl += up;
+        }
+        if (lane == WAVE - 1)
+            s_wave[wave] = incl;
+        __syncthreads();
+        unsigned long long before = s_carry;
+        for (int w = 0; w < wave; w++)
+            before += s_wave[w];
+        if (i < n)
+            offsets[i] = (uint32_t)(before + incl - v);
+        __syncthreads();
+        if (tid == SCAN_BLOCK - 1)
+            s_carry = before + incl;
+        __syncthreads();
+    }
+    if (tid == 0)
+        info[0] = s_carry + 2ull * (unsigned long long)n;
+}
+
+// interval i: its bytes to out + offsets[i] + 2 i, then FF D0+(i mod 8), or FF D9 behind the last one
+constexpr int PACK_BLOCK = 256;
+__global__ __launch_bounds__(PACK_BLOCK) void k_jpeg_pack(const uint8_t *__restrict__ staging, uint32_t slot_bytes,
+                                                          const uint32_t *__restrict__ lengths, const uint32_t *__restrict__ offsets,
+                                                          int n, uint8_t *__restrict__ out, size_t capacity)
+{
+    const int i = blockIdx.x * (PACK_BLOCK / WAVE) + threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    if (i >= n)
+        return;
+    const uint8_t *src = staging + (size_t)i * slot_bytes;
+    const uint32_t len = min(lengths[i], slot_bytes);
+    const size_t dst = (size_t)offsets[i] + 2 * (size_t)i;
+    for (uint32_t j = lane; j < len; j += WAVE)
+        if (dst + j < capacity)
+            out[dst + j] = src[j];
+    if (lane < 2 && dst + len + lane < capacity)
+        out[dst + len + lane] = lane == 0 ? 0xFF : (i == n - 1 ? 0xD9 : 0xD0 + (i & 7));
+}
+
+// ---- host: tables and header ----------------------------------------------------------------------------------------
+// jcparam.c jpeg_quality_scaling + jpeg_add_quant_table(force_baseline)
+static void quant_table(const uint8_t *base, int quality, uint8_t *out /*natural order*/)
+{
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int k = 0; k < 64; k++) {
+        const long v = ((long)base[k] * scale + 50) / 100;
+        out[k] = (uint8_t)(v < 1 ? 1 : (v > 255 ? 255 : v));
+    }
+}
+
+// jchuff.c jpeg_make_c_derived_tbl
+static void huff_entries(const uint8_t *bits, const uint8_t *vals, uint32_t *entries, int n_entries)
+{
+    for (int s = 0; s < n_entries; s++)
+        entries[s] = 0;
+    uint32_t code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; len++) {
+        for (int c = 0; c < bits[len - 1]; c++, k++, code++)
+            if (vals[k] < n_entries)
+                entries[vals[k]] = ((uint32_t)len << 16) | code;
+        code <<= 1;
+    }
+}
+
+static void put_segment(std::vector<uint8_t> &out, int marker, const std::vector<uint8_t> &payload)
+{
+    const size_t n = payload.size() + 2;
+    out.push_back(0xFF), out.push_back((uint8_t)marker), out.push_back((uint8_t)(n >> 8)), out.push_back((uint8_t)n);
+    out.insert(out.end(), payload.begin(), payload.end());
+}
+
+static void put_dht(std::vector<uint8_t> &out, int tc_th, const uint8_t *bits, const uint8_t *vals)
+{
+    std::vector<uint8_t> p{(uint8_t)tc_th};
+    int n = 0;
+    for (int i = 0; i < 16; i++)
+        p.push_back(bits[i]), n += bits[i];
+    p.insert(p.end(), vals, vals + n);
+    put_segment(out, 0xC4, p);
+}
+
+// jcmarker.c: write_file_header, write_frame_header, write_scan_header
+static std::vector<uint8_t> make_header(int H, int W, const uint8_t q[2][64], int restart_mcus)
+{
+    std::vector<uint8_t> out{0xFF, 0xD8};
+    put_segment(out, 0xE0, {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
+    for (int n = 0; n < 2; n++) {
+        std::vector<uint8_t> p{(uint8_t)n};
+        for (int k = 0; k < 64; k++)
+            p.push_back(q[n][ZIGZAG[k]]);
+        put_segment(out, 0xDB, p);
+    }
+    put_segment(out, 0xC0, {8, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1});
+    put_dht(out, 0x00, DC_LUMA_BITS, DC_LUMA_VALS);
+    put_dht(out, 0x10, AC_LUMA_BITS, AC_LUMA_VALS);
+    put_dht(out, 0x01, DC_CHROMA_BITS, DC_CHROMA_VALS);
+    put_dht(out, 0x11, AC_CHROMA_BITS, AC_CHROMA_VALS);
+    put_segment(out, 0xDD, {(uint8_t)(restart_mcus >> 8), (uint8_t)restart_mcus});
+    put_segment(out, 0xDA, {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
+    return out;
+}
+
+} // namespace jpeg
+} // namespace tf
+
+using namespace tf;
+using namespace tf::jpeg;
+
+// restart_mcus = 0: the fastest interval whose file is within 2 % of the smallest of the sweep 1, 2, 4, 8, 16, an MCU
+// row, at 4K and at 1080p alike (tools/bench_jpeg.py, profiles/jpeg_bench.json; DESIGN.md section 15 has the table).
+// Shorter intervals pay in markers and restarted DC prediction, longer ones in waves that code more MCUs one by one.
+static constexpr int DEFAULT_RESTART_MCUS = 8;
+
+struct tf_jpeg {
+    int H = 0, W = 0, quality = 0, restart_mcus = 0;
+    int mcus_x = 0, n_mcus = 0, n_intervals = 0;
+    uint32_t slot = 0;
+    std::vector<uint8_t> header;
+    DevBuf tables, staging, lengths, offsets, info, packed, upload;
+    unsigned long long *info_host = nullptr; // page-locked: [0] the scan's bytes, [1] the overflow flag
+    size_t last_scan = 0;                    // the scan's bytes of the last encode that ran; 0: none to copy again
+};
+
+TF_API void tf_jpeg_destroy(tf_jpeg *enc)
+{
+    if (!enc)
+        return;
+    if (enc->info_host)
+        (void)hipHostFree(enc->info_host);
+    delete enc;
+}
+
+TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int restart_mcus)
+{
+    TF_REQUIRE(out, "tf_jpeg_create: null pointer");
+    *out = nullptr;
+    TF_REQUIRE(height >= 1 && width >= 1 && height <= 65535 && width <= 65535, "tf_jpeg_create: bad size %dx%d (1 to 65535)",
+               width, height);
+    TF_REQUIRE(quality >= 1 && quality <= 100, "tf_jpeg_create: quality %d (1 to 100)", quality);
+    TF_REQUIRE(restart_mcus >= 0 && restart_mcus <= 65535, "tf_jpeg_create: restart interval %d (0 = default, 1 to 65535)",
+               restart_mcus);
+    TF_TRY(ensure_init());
+    tf_jpeg *enc = new (std::nothrow) tf_jpeg;
+    TF_REQUIRE(enc, "tf_jpeg_create: out of memory");
+    enc->H = height, enc->W = width, enc->quality = quality;
+    enc->restart_mcus = restart_mcus ? restart_mcus : DEFAULT_RESTART_MCUS;
+    enc->mcus_x = (width + 15) / 16;
+    enc->n_mcus = enc->mcus_x * ((height + 15) / 16);
+    enc->n_intervals = (enc->n_mcus + enc->restart_mcus - 1) / enc->restart_mcus;
+    // (an interval longer than the image codes n_mcus MCUs: its slot need not be larger than that)
+    enc->slot = (uint32_t)slot_bytes(enc->restart_mcus < enc->n_mcus ? enc->restart_mcus : enc->n_mcus);
+
+    Tables t;
+    uint8_t q[2][64];
+    quant_table(QUANT_LUMA, quality, q[0]);
+    quant_table(QUANT_CHROMA, quality, q[1]);
+    for (int k = 0; k < 64; k++) {
+        t.zz[k] = ZIGZAG[k];
+        t.q8[0][k] = (uint16_t)(8 * q[0][ZIGZAG[k]]), t.q8[1][k] = (uint16_t)(8 * q[1][ZIGZAG[k]]);
+    }
+    huff_entries(DC_LUMA_BITS, DC_LUMA_VALS, t.dc[0], 16);
+    huff_entries(DC_CHROMA_BITS, DC_CHROMA_VALS, t.dc[1], 16);
+    huff_entries(AC_LUMA_BITS, AC_LUMA_VALS, t.ac[0], 256);
+    huff_entries(AC_CHROMA_BITS, AC_CHROMA_VALS, t.ac[1], 256);
+    enc->header = make_header(height, width, q, enc->restart_mcus);
+
+    int rc = TF_OK;
+    for (int c = 0; c < 2; c++) // a lane's symbols: three ZRLs, a code, 10 value bits (11 with a DC code)
+        if (3 * (t.ac[c][0xF0] >> 16) + 16 + 10 > (uint32_t)LANE_MAX_BITS)
+            rc = set_error(TF_ERR_STATE, "tf_jpeg_create: a lane's symbols would not fit %d bits", LANE_MAX_BITS);
+    const size_t n = (size_t)enc->n_intervals;
+    if (rc == TF_OK)
+        rc = enc->tables.alloc(sizeof(Tables));
+    if (rc == TF_OK)
+        rc = enc->staging.alloc(n * enc->slot);
+    if (rc == TF_OK)
+        rc = enc->lengths.alloc(n * sizeof(uint32_t));
+    if (rc == TF_OK)
+        rc = enc->offsets.alloc(n * sizeof(uint32_t));
+    if (rc == TF_OK)
+        rc = enc->info.alloc(2 * sizeof(unsigned long long));
+    if (rc == TF_OK) // the worst case again: every slot full, a marker behind each
+        rc = enc->packed.alloc(n * enc->slot + 2 * n);
+    if (rc == TF_OK && hipHostMalloc((void **)&enc->info_host, 2 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
+        rc = set_error(TF_ERR_HIP, "tf_jpeg_create: hipHostMalloc failed");
+    if (rc == TF_OK && hipMemcpyAsync(enc->tables.p, &t, sizeof(Tables), hipMemcpyHostToDevice, stream()) != hipSuccess)
+        rc = set_error(TF_ERR_HIP, "tf_jpeg_create: table upload failed");
+    if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess) // `t` is on this stack
+        rc = set_error(TF_ERR_HIP, "tf_jpeg_create: hipStreamSynchronize failed");
+    if (rc != TF_OK) {
+        tf_jpeg_destroy(enc);
+        return rc;
+    }
+    *out = enc;
+    return TF_OK;
+}
+
+TF_API int tf_jpeg_header(tf_jpeg *enc, const uint8_t **bytes, size_t *n)
+{
+    TF_REQUIRE(enc && bytes && n, "tf_jpeg_header: null pointer");
+    *bytes = enc->header.data();
+    *n = enc->header.size();
+    return TF_OK;
+}
+
+// the slots to their places in the packed stream, as far as `dev_capacity` reaches
+static int pack(tf_jpeg *enc, size_t dev_capacity)
+{
+    return launch("jpeg_pack", k_jpeg_pack, dim3(cdiv(enc->n_intervals, PACK_BLOCK / WAVE)), dim3(PACK_BLOCK), 0,
+                  enc->staging.as<uint8_t>(), enc->slot, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(), enc->n_intervals,
+                  enc->packed.as<uint8_t>(), dev_capacity);
+}
+
+// header and packed stream to the caller, if they fit; *n_bytes either way
+static int copy_out(tf_jpeg *enc, const char *who, uint8_t *out, size_t capacity, size_t *n_bytes)
+{
+    const size_t hdr = enc->header.size(), scan = enc->last_scan;
+    *n_bytes = hdr + scan;
+    TF_REQUIRE(hdr + scan <= capacity, "%s: the file has %zu bytes, the buffer %zu", who, hdr + scan, capacity);
+    memcpy(out, enc->header.data(), hdr);
+    TF_HIP(hipMemcpyAsync(out + hdr, enc->packed.p, scan, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    return TF_OK;
+}
+
+TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, size_t capacity, size_t *n_bytes)
+{
+    TF_REQUIRE(enc && rgb_dev && n_bytes && (out || capacity == 0), "tf_jpeg_encode_dev: null pointer");
+    *n_bytes = 0;
+    const size_t hdr = enc->header.size();
+    // what the pack kernel may write: the caller's room behind the header, and never more than the packed buffer
+    const size_t room = capacity > hdr ? capacity - hdr : 0;
+    const size_t dev_capacity = room < enc->packed.bytes ? room : enc->packed.bytes;
+    TF_HIP(hipMemsetAsync(enc->info.p, 0, enc->info.bytes, stream()));
+    EncodeArgs a;
+    a.rgb = (const uint8_t *)rgb_dev, a.W = enc->W, a.H = enc->H;
+    a.mcus_x = enc->mcus_x, a.n_mcus = enc->n_mcus, a.restart_mcus = enc->restart_mcus;
+    a.lum_bx = (enc->W + 7) / 8, a.lum_by = (enc->H + 7) / 8, a.chroma_rows = (enc->H + 1) / 2;
+    a.tables = enc->tables.as<Tables>(), a.staging = enc->staging.as<uint8_t>(), a.slot_bytes = enc->slot;
+    a.lengths = enc->lengths.as<uint32_t>();
+    a.overflow = reinterpret_cast<uint32_t *>(enc->info.as<unsigned long long>() + 1);
+    TF_TRY(launch("jpeg_encode", k_jpeg_encode, dim3(enc->n_intervals), dim3(WAVE), 0, a, fast_div_setup((uint32_t)enc->mcus_x)));
+    TF_TRY(launch("jpeg_scan", k_jpeg_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
+                  enc->n_intervals, enc->info.as<unsigned long long>()));
+    TF_TRY(pack(enc, dev_capacity));
+    enc->last_scan = 0;
+    TF_HIP(hipMemcpyAsync(enc->info_host, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    if (enc->info_host[1])
+        return set_error(TF_ERR_STATE, "tf_jpeg_encode_dev: an interval outgrew its staging slot of %u bytes", enc->slot);
+    enc->last_scan = (size_t)enc->info_host[0];
+    return copy_out(enc, "tf_jpeg_encode_dev", out, capacity, n_bytes);
+}
+
+TF_API int tf_jpeg_copy_last(tf_jpeg *enc, uint8_t *out, size_t capacity, size_t *n_bytes)
+{
+    TF_REQUIRE(enc && n_bytes && (out || capacity == 0), "tf_jpeg_copy_last: null pointer");
+    *n_bytes = 0;
+    if (!enc->last_scan)
+        return set_error(TF_ERR_STATE, "tf_jpeg_copy_last: nothing has been encoded");
+    const size_t hdr = enc->header.size();
+    const size_t room = capacity > hdr ? capacity - hdr : 0;
+    TF_TRY(pack(enc, room < enc->packed.bytes ? room : enc->packed.bytes));
+    return copy_out(enc, "tf_jpeg_copy_last", out, capacity, n_bytes);
+}
+
+TF_API int tf_jpeg_default_restart_mcus(void) { return DEFAULT_RESTART_MCUS; }
+
+TF_API int tf_jpeg_encode(tf_jpeg *enc, const uint8_t *rgb_host, uint8_t *out, size_t capacity, size_t *n_bytes)
+{
+    TF_REQUIRE(enc && rgb_host && n_bytes, "tf_jpeg_encode: null pointer");
+    const size_t bytes = (size_t)enc->H * enc->W * 3;
+    if (!enc->upload.p)
+        TF_TRY(enc->upload.alloc(bytes));
+    TF_HIP(hipMemcpyAsync(enc->upload.p, rgb_host, bytes, hipMemcpyHostToDevice, stream()));
+    return tf_jpeg_encode_dev(enc, enc->upload.p, out, capacity, n_bytes);
+}

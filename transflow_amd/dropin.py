@@ -69,14 +69,27 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
     return classmethod(from_args)
 
 
-def _compositor_from_args(original, lazy_frames=False):
+def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None):
     from .compositor import LAYER_CLASSES, HipCompositor
 
     def from_args(cls, height, width, layer_configs, background_color="#ffffff"):
         if all(getattr(c, "classname", None) in LAYER_CLASSES for c in layer_configs):
             return HipCompositor.from_args(height, width, layer_configs, background_color=background_color,
-                                           lazy_frames=lazy_frames)
+                                           lazy_frames=lazy_frames, jpeg_frames=jpeg_frames)
         return original(height, width, layer_configs, background_color=background_color)
+
+    return classmethod(from_args)
+
+
+def _output_from_args(original, quality):
+    from .output import HipMjpegOutput, RawFramesOnly, mjpeg_address
+
+    def from_args(cls, path, width, height, framerate=None, vcodec="h264", execute=False, replace=False, initial_counter=0):
+        address = mjpeg_address(path)
+        if address is None:         # the reference's own output; it takes pixels, and says so if it is given a file
+            return RawFramesOnly(original(path, width, height, framerate=framerate, vcodec=vcodec, execute=execute,
+                                          replace=replace, initial_counter=initial_counter))
+        return HipMjpegOutput(address[0], address[1], width, height, 30 if framerate is None else framerate, quality)
 
     return classmethod(from_args)
 
@@ -96,7 +109,8 @@ def _pixmap_from_args(original):
 
 
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
-            lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False) -> None:
+            lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
+            jpeg_frames: int | None = None) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -108,7 +122,14 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     pickles the frame -- and waits for its download -- in the queue's feeder thread, beside the next update.
     pixmaps: still pixmap sources (colours, the noises, gradient, images, a video's first frame) are this backend's
     (transflow_amd/pixmap.py): made once, kept on the device, taken by the layers of a compositor of the same process by
-    address; across a process boundary they travel as host arrays.  By default they stay the reference's."""
+    address; across a process boundary they travel as host arrays.  By default they stay the reference's.
+    jpeg_frames: a JPEG quality -- the compositors built for the pipeline return JpegFrames from render()
+    (transflow_amd/jpeg.py: encoded on the device, only the file comes down and crosses to the output process), and
+    VideoOutput.from_args (pipeline.py's output process) builds a HipMjpegOutput (transflow_amd/output.py) for `mjpeg...`
+    paths; any other output is the reference's own and raises a TypeError that names this option when it is fed a
+    JpegFrame.  Not together with lazy_frames.  By default (None) nothing of this is touched."""
+    if jpeg_frames is not None and lazy_frames:
+        raise ValueError("jpeg_frames and lazy_frames exclude each other")
     if flow and "flow" not in _saved:
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
@@ -120,7 +141,11 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from .compositor import bind_reference_data_layer
         bind_reference_data_layer()    # extra/control.py:155 asks isinstance(layer, DataLayer) of checkpointed layers
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
-        RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames)
+        RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames)
+    if jpeg_frames is not None and "output" not in _saved:
+        from transflow.output.video_output import VideoOutput as RefVideoOutput
+        _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
+        RefVideoOutput.from_args = _output_from_args(RefVideoOutput.from_args, int(jpeg_frames))
     if pixmaps and "pixmaps" not in _saved:
         from transflow.pixmap.source import PixmapSource as RefPixmapSource
         _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])

@@ -1,0 +1,151 @@
+"""The MJPEG output for frames that arrive compressed (transflow/output/mjpeg.py:160-189 is the one it mirrors).
+
+The reference's MjpegOutput keeps the last raw frame and encodes it whenever a client's turn comes
+(mjpeg.py:54-65, :90-94).  `HipMjpegOutput` keeps the last frame as it came: a `JpegFrame` (transflow_amd/jpeg.py: the
+compositor encoded it on the device) is served as it is; a raw array is encoded on request, on the host, by Pillow at
+the same quality, subsampling and restart interval -- the same bytes by construction, and the output process never
+opens the GPU.  The reference's server and handler are used unchanged and imported only in `__enter__`: everything
+else here works without aiohttp, netifaces or cv2.
+"""
+from __future__ import annotations
+
+import re
+
+import numpy as np
+
+from .jpeg import JpegFrame, pillow_encode
+
+
+def default_restart_mcus() -> int:
+    """What a raw frame is encoded with on the host: the device encoder's default interval, asked of the library (the
+    call loads it and touches no GPU)."""
+    from . import _lib
+    return int(_lib.load().tf_jpeg_default_restart_mcus())
+
+
+class _Encoded:
+    """What the reference's handler asks of a processed frame: `.tobytes()` (mjpeg.py:94)."""
+
+    def __init__(self, data: bytes):
+        self._data = data
+
+    def tobytes(self) -> bytes:
+        return self._data
+
+    def __len__(self) -> int:
+        return len(self._data)
+
+
+class HipMjpegStream:
+    """MjpegStream's surface (mjpeg.py:26-73) for the reference's _StreamHandler and MjpegServer.add_stream:
+    `name`, `fps`, `set_frame`, `get_frame`, `get_frame_processed`, `get_bandwidth`."""
+
+    def __init__(self, name: str, size, quality: int = 50, fps: float = 30, restart_mcus: int | None = None):
+        self.name = name.lower().casefold().replace(" ", "_")
+        self.size = size                                   # (width, height)
+        self.quality = max(1, min(int(quality), 100))
+        self.fps = fps
+        self.restart_mcus = None if restart_mcus is None else int(restart_mcus)    # None: the library's default
+        self._frame = None
+        self._sizes = []
+
+    def set_frame(self, frame) -> None:
+        self._frame = frame
+
+    def processed(self) -> _Encoded:
+        frame = self._frame
+        if frame is None:                                  # nothing fed yet: a grey frame of the stream's size
+            frame = np.full((self.size[1], self.size[0], 3), 128, np.uint8)
+        if isinstance(frame, JpegFrame):
+            data = frame.tobytes()
+        else:
+            if self.restart_mcus is None:
+                self.restart_mcus = default_restart_mcus()
+            data = pillow_encode(np.asarray(frame), self.quality, self.restart_mcus)
+        self._sizes = (self._sizes + [len(data)])[-30:]
+        return _Encoded(data)
+
+    def get_bandwidth(self) -> float:
+        return sum(self._sizes)
+
+    async def get_frame(self):
+        return self._frame
+
+    async def get_frame_processed(self) -> _Encoded:
+        return self.processed()
+
+
+class HipMjpegOutput:
+    """Same constructor, context-manager protocol and `feed` as transflow's MjpegOutput."""
+
+    def __init__(self, host: str, port: int, width: int, height: int, framerate: float, quality: int = 50):
+        self.width, self.height = int(width), int(height)
+        self.host, self.port = host, port
+        self.framerate = framerate
+        self.quality = quality
+        self.stream = HipMjpegStream("transflow", (self.width, self.height), quality=quality, fps=framerate)
+        self.server = None
+
+    @property
+    def output_path(self):
+        """VideoOutput.output_path (video_output.py:62-64): pipeline.py:479-481 reads it of every output; no file."""
+        return None
+
+    def __enter__(self):
+        from transflow.output.mjpeg import MjpegServer     # aiohttp, netifaces, cv2: only a served stream needs them
+        self.server = MjpegServer(self.host, self.port)
+        self.server.add_stream(self.stream)
+        self.server.start()
+        return self
+
+    def feed(self, frame):
+        if isinstance(frame, tuple):                       # mjpeg.py:182-183
+            frame = frame[0]
+        if tuple(frame.shape[:2]) != (self.height, self.width):
+            raise ValueError(f"the stream is {self.height} x {self.width}, the frame {tuple(frame.shape[:2])}")
+        self.stream.set_frame(frame)
+
+    def __exit__(self, exc_type, exc_value, exc_traceback):
+        if self.server is not None:
+            self.server.stop()
+
+
+MJPEG_PATH = re.compile(r"^mjpeg(:[:a-z0-9A-Z\-]+)?$", re.IGNORECASE)        # video_output.py:37
+
+
+def mjpeg_address(path):
+    """(host, port) of an `mjpeg[:port[:host]]` output path (video_output.py:37-52), None for any other path."""
+    m = MJPEG_PATH.match(path) if isinstance(path, str) else None
+    if m is None:
+        return None
+    args = m.group(1)[1:].split(":") if m.group(1) else []
+    if len(args) > 2:
+        raise ValueError(f"Invalid number of MJPEG arguments: {len(args)}")
+    return (args[1] if len(args) == 2 else "localhost"), (int(args[0]) if args else 8080)
+
+
+class RawFramesOnly:
+    """Another output of the reference's, as it is, except that a JpegFrame fed to it is refused by name: those outputs
+    take pixels (`install(jpeg_frames=...)` is for the MJPEG output)."""
+
+    def __init__(self, output):
+        self._output = output
+
+    def __enter__(self):
+        self._output.__enter__()
+        return self
+
+    def __exit__(self, exc_type, exc_value, exc_traceback):
+        return self._output.__exit__(exc_type, exc_value, exc_traceback)
+
+    def feed(self, frame):
+        first = frame[0] if isinstance(frame, tuple) else frame
+        if isinstance(first, JpegFrame):
+            raise TypeError(f"{type(self._output).__name__} takes raw frames, not JPEG files: install(jpeg_frames=...) "
+                            "serves the mjpeg output only")
+        return self._output.feed(frame)
+
+    def __getattr__(self, name):
+        if name == "_output":       # not set yet (an instance being unpickled): no attribute, not a recursion
+            raise AttributeError(name)
+        return getattr(self._output, name)                  # output_path (pipeline.py:479-481) and whatever else it has
