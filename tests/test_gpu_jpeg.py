@@ -68,6 +68,24 @@ def test_one_encoder_keeps_no_state_between_images():
         enc.close()
 
 
+def test_fat_mcus_leave_nothing_behind_for_the_next_image():
+    """600-byte MCUs, then a flat image of a few bytes per MCU, then the first again: bits left in the LDS buffer past
+    the words a small MCU zeroes, or in the staging slots, would show in the second file."""
+    from transflow_amd.jpeg import JpegEncoder
+    a, quality, restart, want_a = _case("32x48_binary_q100")
+    b = np.empty((32, 48, 3), np.uint8)
+    b[:] = (90, 160, 30)
+    want_b = jpeg_ref.encode(b, quality, restart)
+    assert len(want_b) - 629 < (len(want_a) - 629) // 10                    # (the header is 629 bytes of each)
+    enc = JpegEncoder(32, 48, quality, restart)
+    try:
+        assert enc.encode(a) == want_a
+        assert enc.encode(b) == want_b
+        assert enc.encode(a) == want_a
+    finally:
+        enc.close()
+
+
 def test_device_inputs_give_the_host_arrays_bytes():
     from transflow_amd.jpeg import JpegEncoder, JpegFrame
     from transflow_amd.pixmap import DevicePixmap
@@ -123,6 +141,30 @@ def test_a_buffer_one_byte_short_is_refused_and_left_alone():
         enc.close()
 
 
+def test_a_buffer_one_byte_short_is_refused_past_the_first_scan_chunk():
+    """The same contract where k_jpeg_pack's offsets come from the second and third trips of k_jpeg_scan."""
+    from transflow_amd.jpeg import JpegEncoder
+    image, quality, restart, expected = _case("730x725_r1")
+    enc = JpegEncoder(730, 725, quality, restart)
+    try:
+        guard = 64
+        buf = np.full(len(expected) + guard, 0xA5, np.uint8)
+        short = buf[:len(expected) - 1]
+        with pytest.raises(ValueError):
+            enc.encode_into(image, short)
+        assert enc.last_needed == len(expected)                            # the library says what it takes
+        assert (buf == 0xA5).all()                                         # nothing written, within or beyond
+        for capacity in (0, 10, len(enc.header), len(enc.header) + 5, len(expected) // 2):
+            with pytest.raises(ValueError):
+                enc.encode_into(image, buf[:capacity])
+            assert enc.last_needed == len(expected) and (buf == 0xA5).all()
+        exact = buf[:len(expected)]
+        assert enc.encode_into(image, exact) == len(expected)
+        assert exact.tobytes() == expected and (buf[len(expected):] == 0xA5).all()
+    finally:
+        enc.close()
+
+
 def test_a_file_larger_than_the_encoders_buffer_is_packed_again_not_encoded_again():
     from transflow_amd import _lib
     from transflow_amd.jpeg import JpegEncoder
@@ -145,6 +187,65 @@ def test_a_file_larger_than_the_encoders_buffer_is_packed_again_not_encoded_agai
         assert enc._out.nbytes == len(expected) and (small[len(enc.header):] == 0).all()
         with pytest.raises(ValueError):                                    # a wrong shape is not mistaken for a short buffer
             enc.encode(np.zeros((33, 48, 3), np.uint8))
+    finally:
+        enc.close()
+
+
+def _intervals(scan: bytes):
+    """The scan (EOI stripped) split at its RST markers: (the intervals' bytes, the markers' low bytes).  An 0xFF of the
+    entropy-coded data has an 0x00 behind it, so FF D0 .. FF D7 is a marker wherever it stands."""
+    b = np.frombuffer(scan, np.uint8)
+    at = np.flatnonzero((b[:-1] == 0xFF) & (b[1:] >= 0xD0) & (b[1:] <= 0xD7))
+    starts, ends = np.concatenate([[0], at + 2]), np.concatenate([at, [len(b)]])
+    return [scan[s:e] for s, e in zip(starts, ends)], [int(b[i + 1]) for i in at]
+
+
+def test_every_interval_is_where_libjpeg_has_it_across_scan_chunks():
+    """2116 intervals: k_jpeg_scan carries its total over two chunk boundaries and ends on a partial chunk.  Through
+    the C ABI, interval by interval, so that a lost carry reads as `interval 1024`, not as a byte offset."""
+    from transflow_amd import _lib
+    from transflow_amd.device import DevBuffer
+    lib = _lib.load()
+    image, quality, restart, expected = _case("730x725_r1")
+    h = C.c_void_p()
+    _lib.check(lib.tf_jpeg_create(C.byref(h), 730, 725, quality, restart))
+    dev = DevBuffer.from_array(image)
+    try:
+        out = np.full(len(expected) + 4096, 0x5A, np.uint8)
+        n = C.c_size_t()
+        _lib.check(lib.tf_jpeg_encode_dev(h, C.c_void_p(dev.ptr), C.c_void_p(out.ctypes.data), out.nbytes, C.byref(n)))
+        got = out[:n.value].tobytes()
+        hdr = len(jpeg_ref.header(730, 725, quality, restart))
+        assert got[:hdr] == expected[:hdr] and got[-2:] == b"\xff\xd9"
+        want_iv, want_rst = _intervals(expected[hdr:-2])
+        got_iv, got_rst = _intervals(got[hdr:-2])
+        assert len(want_iv) == 2116
+        wrong = [i for i in range(min(len(got_iv), len(want_iv))) if got_iv[i] != want_iv[i]]
+        assert len(got_iv) == len(want_iv) and not wrong, (
+            f"{len(got_iv)} intervals against {len(want_iv)}; {len(wrong)} differ, the first is interval "
+            f"{wrong[0] if wrong else None} (chunk {wrong[0] // 1024 if wrong else None}); "
+            + _first_difference(got, expected))
+        assert got_rst == want_rst
+        assert n.value == len(expected) and got == expected
+        assert (out[n.value:] == 0x5A).all()
+    finally:
+        lib.tf_jpeg_destroy(h)
+        dev.close()
+
+
+@pytest.mark.parametrize("height,width", [(1, 65535), (65535, 1)], ids=["1x65535", "65535x1"])
+def test_the_largest_sizes_the_format_has(height, width):
+    """tf_jpeg_create admits the format's 65535; libjpeg stops at 65500 (JPEG_MAX_DIMENSION), where the fixtures
+    1x65500 and 65500x1 are its files.  Beyond it the restatement is the reference: 4096 MCUs in a row or a column,
+    512 intervals, every luma block below or beside the first a dummy."""
+    from transflow_amd.jpeg import JpegEncoder
+    image = jpeg_ref.formula_image(height, width)
+    enc = JpegEncoder(height, width, 50)
+    try:
+        want = jpeg_ref.encode(image, 50, enc.restart_mcus)
+        got = enc.encode(image)
+        assert len(_intervals(want[len(enc.header):-2])[0]) == 512
+        assert got == want, _first_difference(got, want)
     finally:
         enc.close()
 

@@ -71,6 +71,103 @@ def test_restatement_equals_live_pillow(shape, quality, restart):
         assert jpeg_ref.encode(image, quality, restart) == pillow_encode(image, quality, restart)
 
 
+@needs_pillow_restart
+@pytest.mark.parametrize("image,quality,restart", [
+    (lambda: jpeg_ref.directed_luma(96, 96, 3), 100, 3), (lambda: jpeg_ref.directed_luma(40, 56, 4), 90, 2),
+    (lambda: jpeg_ref.directed_chroma(96, 96, 3), 100, 4), (lambda: jpeg_ref.directed_chroma(50, 70, 4), 75, 1),
+    (lambda: jpeg_ref.binary_noise(32, 48, 5), 100, 2), (lambda: jpeg_ref.chroma_checker(48, 80), 100, 3),
+    (lambda: jpeg_ref.formula_image(16, 16400), 50, 1)],                  # 1025 intervals
+    ids=["directed_luma", "directed_luma_ragged", "directed_chroma", "directed_chroma_ragged", "binary_noise",
+         "chroma_checker", "1025_intervals"])
+def test_restatement_equals_live_pillow_on_directed_content(image, quality, restart):
+    """Seeds and sizes that no fixture has."""
+    from transflow_amd.jpeg import pillow_encode
+    image = image()
+    assert jpeg_ref.encode(image, quality, restart) == pillow_encode(image, quality, restart)
+
+
+# ---- what the fixtures reach, by the restatement's own account of what it coded -------------------------------------
+ALL_AC = {0x00, 0xF0} | {(run << 4) | size for run in range(16) for size in range(1, 11)}      # 162 per table
+_traced = {}
+
+
+def _trace(name):
+    """The trace of a fixture's image, whose file is the fixture's: made once."""
+    if name not in _traced:
+        image, quality, restart, expected = jpeg_ref.load_case(os.path.join(GOLDEN, f"jpeg_{name}.npz"))
+        _traced[name] = jpeg_ref.trace(image, quality, restart)
+        assert _traced[name].data == expected
+    return _traced[name]
+
+
+def _small_cases():
+    """Every case but the `formula` ones, which are there for their sizes and interval counts, not for their symbols."""
+    return [name for name, case in jpeg_ref.CASES.items() if case[2] != "formula"]
+
+
+def test_trace_is_encodes_own_account():
+    image, quality, restart, expected = jpeg_ref.load_case(os.path.join(GOLDEN, "jpeg_45x61_r3.npz"))
+    t = _trace("45x61_r3")
+    assert len(t.mcu_bits) == len(t.flushed) == len(t.interval_end) == 12
+    assert t.interval_end == [False, False, True] * 4
+    scan = expected[len(jpeg_ref.header(45, 61, quality, restart)):-2]
+    # the flushed bytes, stuffed and with a marker behind each interval but the last, are the scan
+    again = bytearray()
+    for n, (chunk, end) in enumerate(zip(t.flushed, t.interval_end)):
+        again += chunk.replace(b"\xff", b"\xff\x00")
+        if end and n != 11:
+            again += bytes([0xFF, 0xD0 + (n // 3) % 8])
+    assert bytes(again) == scan
+    # bits carried from MCU to MCU within an interval, padded at its end
+    for first in range(0, 12, 3):
+        assert sum(len(c) for c in t.flushed[first:first + 3]) == (sum(t.mcu_bits[first:first + 3]) + 7) // 8
+    assert t.most_zrls(0)[0] <= 3 and 0x00 in t.ac_symbols[0] and t.widest_lane[0] <= 59 and t.widest_lane[1] <= 56
+
+
+def test_fixtures_reach_the_symbols_and_widths_they_are_for():
+    """Conditions on the inputs, not on any kernel.  The floors are those of the issue that asked for the cases; what
+    the fixtures reach is in DESIGN.md section 15."""
+    total = jpeg_ref.Trace()
+    for name in _small_cases():
+        total.merge(_trace(name))
+    luma, chroma = total.ac_symbols
+    assert luma <= ALL_AC and chroma <= ALL_AC
+    print(f"AC symbols: luma {len(luma)}, missing {sorted(map(hex, ALL_AC - luma))}; "
+          f"chroma {len(chroma)}, missing {sorted(map(hex, ALL_AC - chroma))}")
+    print(f"ZRLs -> largest size: {total.zrl_sizes}; widest lanes {total.widest_lane}; fattest MCU {max(total.mcu_bits)} bits")
+    assert len(luma) >= 150 and len(chroma) >= 130
+    assert {(run << 4) | size for run in range(16) for size in range(1, 8)} <= luma
+    for table, lane_bits in ((0, 55), (1, 50)):
+        assert total.zrl_sizes[table].get(3, 0) >= 5                       # three ZRLs in front of a size of 5 or more
+        assert total.widest_lane[table] >= lane_bits
+        assert total.dc_categories[table] == set(range(12))
+    assert max(total.mcu_bits) >= 4600
+
+
+def test_fattest_case_puts_ff_at_the_edges_of_the_flush_loop():
+    """An MCU's bytes leave 64 at a time, a ballot placing the stuffed ones: an 0xFF in the last lane of a trip, in the
+    first lane of a later trip, and as the last byte of an interval (1-padding, then FF 00 FF Dn)."""
+    t = _trace("32x48_binary_q100")
+    assert max(t.mcu_bits) >= 4600 and max(len(c) for c in t.flushed) > 8 * 64
+    assert any(byte == 0xFF and j % 64 == 63 for chunk in t.flushed for j, byte in enumerate(chunk))
+    assert any(byte == 0xFF and j % 64 == 0 and j >= 64 for chunk in t.flushed for j, byte in enumerate(chunk))
+    ends = [chunk for chunk, end in zip(t.flushed, t.interval_end) if end]
+    assert len(ends) == 3 and any(chunk[-1] == 0xFF for chunk in ends[:-1])
+    expected = jpeg_ref.load_case(os.path.join(GOLDEN, "jpeg_32x48_binary_q100.npz"))[3]
+    assert any(bytes([0xFF, 0x00, 0xFF, 0xD0 + k]) in expected for k in range(2))
+
+
+@pytest.mark.parametrize("name,intervals", [("512x512_r1", 1024), ("16x16400_r1", 1025), ("730x725_r1", 2116),
+                                            ("1x65500", 512), ("65500x1", 512), ("40x4099", 97)])
+def test_interval_counts_are_the_ones_the_cases_are_for(name, intervals):
+    """Counted from the file: RST markers plus one.  (An 0xFF of the entropy-coded data has an 0x00 behind it.)"""
+    data = jpeg_ref.load_case(os.path.join(GOLDEN, f"jpeg_{name}.npz"))[3]
+    scan = data[data.index(b"\xff\xda") + 14:-2]
+    markers = [scan[i + 1] for i in range(len(scan) - 1) if scan[i] == 0xFF and 0xD0 <= scan[i + 1] <= 0xD7]
+    assert len(markers) + 1 == intervals
+    assert markers == [0xD0 + i % 8 for i in range(intervals - 1)]
+
+
 # ---- JpegFrame ---------------------------------------------------------------------------------------------------------
 def _frame(shape=(24, 40), quality=50, restart=4, seed=3):
     from transflow_amd.jpeg import JpegFrame
