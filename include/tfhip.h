@@ -366,6 +366,15 @@ int tf_hs_stage_derivatives(tf_hs *hs, const uint8_t *prev, const uint8_t *next,
 /* The device stages of the convergence test on a host field du [h][w] (float64 if is_f64, else float32):
    *decision 1 (sigma_max < delta), 0 (not), -1 (the host must decide); *stage 0 bounds, 1 power, 2 Gram, 3 host. */
 int tf_hs_stage_norm_test(const void *field, int w, int h, int is_f64, double delta, int *decision, int *stage);
+/* Every stage of that test without early exit, on du = u_new - u_old taken in the fields' type (u_old NULL: zeros):
+   out[3 + 16 + 3] = F, U, L of the cheap bounds; the 16 lower bounds of the 8 power-iteration steps (||du x||, then
+   ||du^T y||, per step); the Gram bounds of k = 1, 2, 4.  The stages after the bounds run through the host code of
+   the decision path; where that path does not run them (du not finite, or ||du||_F^2 below 2^-960) their values are
+   NaN, as are the Gram bounds when F is 0. */
+int tf_hs_stage_norm_values(const void *u_new, const void *u_old, int w, int h, int is_f64, double *out);
+/* out[3] = F, U, L of `pair`'s most recent convergence check in the last call, from the partial sums that the
+   iteration kernel wrote.  TF_ERR_ARG when that call made none for the pair (no delta, or no iteration). */
+int tf_hs_stage_last_bounds(tf_hs *hs, int pair, double *out);
 
 /* ---- Lucas-Kanade (transflow/flow/methods/lukas_kanade.py) ---------------------------
  * calc_optical_flow_lukas_kanade(prev, next, win_size, max_level, step): cv2.calcOpticalFlowPyrLK over the grid

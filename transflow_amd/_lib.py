@@ -142,6 +142,8 @@ PROTOTYPES = {
     "tf_hs_stats": (_I, [_P, _I, _PI]),
     "tf_hs_stage_derivatives": (_I, [_P, _P, _P, C.c_double, _P]),
     "tf_hs_stage_norm_test": (_I, [_P, _I, _I, _I, C.c_double, _PI, _PI]),
+    "tf_hs_stage_norm_values": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_double)]),
+    "tf_hs_stage_last_bounds": (_I, [_P, _I, C.POINTER(C.c_double)]),
     "tf_lk_create": (_I, [_PP, _I, _I, _I, _I]),
     "tf_lk_destroy": (None, [_P]),
     "tf_lk_set_frame": (_I, [_P, _I, _P, C.c_ssize_t]),

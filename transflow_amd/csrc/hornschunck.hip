@@ -360,13 +360,12 @@ static int hs_run(tf_hs *hs)
             for (int k = 0; k < 2; k++)
                 for (int i = 0; i < l[k].n; i++) {
                     const int p = l[k].p[i].pair;
-                    bool nonfinite = false;
-                    double F = 0.0;
-                    int dec = decide_bounds(hs->host_blocks.data() + (size_t)p * nbb * 4, hs->W, hs->H, hs->prm.delta, &nonfinite, &F);
+                    const Bounds b = bounds_of(hs->host_blocks.data() + (size_t)p * nbb * 4, hs->W, hs->H);
+                    int dec = decide_bounds(b, hs->prm.delta);
                     int stage = ST_BOUNDS;
-                    if (dec == UNDECIDED && !nonfinite)
+                    if (dec == UNDECIDED && b.device_stages())
                         TF_TRY(decide_device(hs->norm, hs->plane(p, hs->cur[p], 0), hs->plane(p, hs->cur[p] ^ 1, 0), k == 1,
-                                             hs->prm.delta, F, &dec, &stage));
+                                             hs->prm.delta, b.F, &dec, &stage));
                     if (dec == UNDECIDED)
                         stage = ST_HOST;
                     hs->stats[p][1 + stage]++;
@@ -492,6 +491,17 @@ TF_API int tf_hs_stats(tf_hs *hs, int pair, int *stats)
     TF_REQUIRE(pair >= 0 && pair < hs->n_pairs, "tf_hs_stats: pair %d out of range", pair);
     for (int k = 0; k < 5; k++)
         stats[k] = hs->stats[pair][k];
+    return TF_OK;
+}
+
+TF_API int tf_hs_stage_last_bounds(tf_hs *hs, int pair, double *out)
+{
+    TF_REQUIRE(hs && out, "tf_hs_stage_last_bounds: null pointer");
+    TF_REQUIRE(pair >= 0 && pair < hs->n_pairs, "tf_hs_stage_last_bounds: pair %d out of range", pair);
+    const std::array<int, 5> &st = hs->stats[pair];
+    TF_REQUIRE(st[1] + st[2] + st[3] + st[4] > 0, "tf_hs_stage_last_bounds: pair %d had no convergence check in the last call", pair);
+    const Bounds b = bounds_of(hs->host_blocks.data() + (size_t)pair * n_bound_blocks(hs->W, hs->H) * 4, hs->W, hs->H);
+    out[0] = b.F, out[1] = b.U, out[2] = b.L;
     return TF_OK;
 }
 

@@ -42,12 +42,28 @@ struct NormScratch {
     int init(int w, int h);
 };
 
-// cheap bounds from the reduced blocks of one pair -> decision (CONVERGED / NOT_CONVERGED / UNDECIDED);
-// *nonfinite set when du has a NaN or an inf (or a square that overflows): only the host can decide then
-// (*F_out: the Frobenius norm, for the Gram stage's scaling)
-int decide_bounds(const double *blocks, int W, int H, double delta, bool *nonfinite, double *F_out);
-// the device stages after the bounds for one pair: power iteration, then the Gram certificate.  Returns the decision
-// and the stage that made it (ST_HOST if neither could).
+// The cheap bounds of one pair, from its reduced blocks.  nonfinite: du has a NaN or an inf (or a square that
+// overflows).  tiny: ||du||_F^2 < TINY_F2, where the squares of du leave float64's normal range: F and L (sums of
+// squares) are not used then and U is sqrt(n1) sqrt(ninf), the sums of |du| being exact at any magnitude.  In both
+// cases the device stages after the bounds are not run: what the bounds cannot decide goes to the host.
+constexpr double TINY_F2 = 0x1p-960;
+struct Bounds {
+    double F, U, L;
+    bool nonfinite, tiny;
+    bool device_stages() const { return !nonfinite && !tiny; }
+};
+Bounds bounds_of(const double *blocks, int W, int H);
+// -> CONVERGED / NOT_CONVERGED / UNDECIDED
+int decide_bounds(const Bounds &b, double delta);
+// What the device stages after the bounds compute for one pair: the lower bounds of the power iteration (two per
+// step) and the upper bounds of the Gram certificate (k = 1, 2, 4; NaN where F is zero).
+struct StageValues {
+    double power[2 * POWER_STEPS], gram[3];
+};
+// every stage without early exit
+int device_values(NormScratch &s, const void *u_new, const void *u_old, bool f64, double F, StageValues *v);
+// the same stages, each decided as soon as its values are read back.  Returns the decision and the stage that made
+// it (ST_HOST if neither could).
 int decide_device(NormScratch &s, const void *u_new, const void *u_old, bool f64, double delta, double F, int *decision,
                   int *stage);
 // enqueue the reduction of a launch's partials into blocks[n_active][n_bound_blocks][4]

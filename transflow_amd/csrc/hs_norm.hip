@@ -11,6 +11,8 @@
 // Every sum runs in a fixed order (no atomics): the same field gets the same decision every time.
 #include "hs_common.h"
 
+#include <limits>
+
 namespace tf {
 namespace hs {
 
@@ -142,7 +144,7 @@ int launch_delta(const void *u_new, const void *u_old, bool f64, size_t n, void 
                   (float *)dst, n);
 }
 
-int decide_bounds(const double *blocks, int W, int H, double delta, bool *nonfinite, double *F_out)
+Bounds bounds_of(const double *blocks, int W, int H)
 {
     const int ncbw = (W + 255) / 256, nb = n_bound_blocks(W, H);
     double F2 = 0.0, L2 = 0.0, n1 = 0.0, ninf = 0.0, bad = 0.0;
@@ -157,16 +159,31 @@ int decide_bounds(const double *blocks, int W, int H, double delta, bool *nonfin
         }
         bad += q[3];
     }
-    *nonfinite = bad > 0 || !std::isfinite(F2) || !std::isfinite(n1 * ninf);
-    *F_out = std::sqrt(F2);
-    if (*nonfinite)
+    Bounds r;
+    r.nonfinite = bad > 0 || !std::isfinite(F2) || !std::isfinite(n1 * ninf);
+    // A square of du that is denormal or flushed to zero is wrong by up to 2^-1075: at most 2^-1044 over W * H < 2^31
+    // values.  From TINY_F2 up that is nothing beside a sum of squares that decides wrongly: such a sum is compared
+    // with a delta^2 near sigma^2 >= F^2 / min(W, H) > 2^-976.  Below it the squares cannot be trusted.
+    r.tiny = !r.nonfinite && F2 < TINY_F2;
+    r.F = std::sqrt(F2);
+    r.L = std::sqrt(L2);
+    r.U = r.tiny ? std::sqrt(n1) * std::sqrt(ninf) : std::sqrt(n1 * ninf);   // (the product underflows with the squares)
+    return r;
+}
+
+int decide_bounds(const Bounds &b, double delta)
+{
+    if (b.nonfinite)
         return UNDECIDED;        // NaN: numpy.linalg.norm raises; inf: it returns nan.  The host's call says which.
     if (!(delta > 0))
         return NOT_CONVERGED;    // sigma >= 0 is never below it
-    const double F = std::sqrt(F2), U = std::sqrt(n1 * ninf), L = std::sqrt(L2);
-    if ((F < U ? F : U) < delta * (1 - GUARD))
+    if (b.tiny) {                // F and L lost squares: U alone (zero, or normal: a denormal U is itself rounded coarsely),
+        const bool usable = b.U == 0 || b.U >= std::numeric_limits<double>::min();
+        return usable && b.U < delta * (1 - GUARD) ? CONVERGED : UNDECIDED;   // and it can only say CONVERGED
+    }
+    if ((b.F < b.U ? b.F : b.U) < delta * (1 - GUARD))
         return CONVERGED;
-    if (L >= delta * (1 + GUARD))
+    if (b.L >= delta * (1 + GUARD))
         return NOT_CONVERGED;
     return UNDECIDED;
 }
@@ -339,53 +356,95 @@ static int frobenius(NormScratch &s, const double *x, size_t n, double *out)
     return TF_OK;
 }
 
-template <typename T>
-static int decide_device_t(NormScratch &s, const T *un, const T *uo, double delta, double F, int *decision, int *stage)
+static_assert(POWER_STEPS % 2 == 0, "the power bounds are read back after every second step");
+
+// ---- the stages' steps: what decide_device and device_values both run ----------------------------------------
+// power iteration: x = the normalised ones vector
+static int power_start(NormScratch &s)
+{
+    double *x = s.pw_x.as<double>(), *scal = s.pw_scal.as<double>();
+    TF_TRY(launch("hs_power", k_fill, dim3(cdiv(s.W, 256)), dim3(256), 0, x, s.W, 1.0));
+    return launch("hs_power", k_norm, dim3(1), dim3(1024), 0, (const double *)x, s.W, scal, (double *)nullptr);
+}
+
+// steps `step` and `step + 1`; lbs[0 .. 2 * step + 4): every lower bound so far, ||du x|| and ||du^T y|| per step
+template <typename T> static int power_two_steps(NormScratch &s, const T *un, const T *uo, int step, double *lbs)
 {
     const int W = s.W, H = s.H;
-    const double hi = delta * (1 + GUARD), lo = delta * (1 - GUARD);
-    // 2. power iteration
     double *x = s.pw_x.as<double>(), *y = s.pw_y.as<double>(), *scal = s.pw_scal.as<double>();
-    TF_TRY(launch("hs_power", k_fill, dim3(cdiv(W, 256)), dim3(256), 0, x, W, 1.0));
-    TF_TRY(launch("hs_power", k_norm, dim3(1), dim3(1024), 0, (const double *)x, W, scal, (double *)nullptr));
-    double lbs[2 * POWER_STEPS];
-    for (int step = 0; step < POWER_STEPS; step++) {
+    for (int st = step; st < step + 2; st++) {
         TF_TRY(launch("hs_power", k_pw_rows<T>, dim3(H), dim3(256), 0, un, uo, W, (const double *)x, (const double *)scal, y));
-        TF_TRY(launch("hs_power", k_norm, dim3(1), dim3(1024), 0, (const double *)y, H, scal + 1, scal + 2 + 2 * step));
+        TF_TRY(launch("hs_power", k_norm, dim3(1), dim3(1024), 0, (const double *)y, H, scal + 1, scal + 2 + 2 * st));
         TF_TRY(launch("hs_power", k_pw_cols<T>, dim3(cdiv(W, 256), PW_CHUNKS), dim3(256), 0, un, uo, W, H, (const double *)y,
                       (const double *)(scal + 1), s.pw_xpart.as<double>()));
         TF_TRY(launch("hs_power", k_pw_combine, dim3(cdiv(W, 256)), dim3(256), 0, (const double *)s.pw_xpart.p, W, x));
-        TF_TRY(launch("hs_power", k_norm, dim3(1), dim3(1024), 0, (const double *)x, W, scal, scal + 3 + 2 * step));
-        if (step % 2 == 1 || step == POWER_STEPS - 1) {
-            TF_HIP(hipMemcpyAsync(lbs, scal + 2, (size_t)(2 * step + 2) * sizeof(double), hipMemcpyDeviceToHost, stream()));
-            TF_HIP(hipStreamSynchronize(stream()));
-            for (int k = 0; k < 2 * step + 2; k++)
-                if (lbs[k] >= hi) {
-                    *decision = NOT_CONVERGED, *stage = ST_POWER;
-                    return TF_OK;
-                }
-        }
+        TF_TRY(launch("hs_power", k_norm, dim3(1), dim3(1024), 0, (const double *)x, W, scal, scal + 3 + 2 * st));
+    }
+    TF_HIP(hipMemcpyAsync(lbs, scal + 2, (size_t)(2 * step + 4) * sizeof(double), hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    return TF_OK;
+}
+
+// Gram certificate: the walk over G, G^2, G^4, each in one of the two scratch buffers
+struct GramWalk {
+    int p = 0;
+    double *src = nullptr, *dst = nullptr;
+};
+
+static bool gram_usable(double F) { return F > 0 && std::isfinite(F); }
+
+// A = du / F, then G = A A^T
+template <typename T> static int gram_start(NormScratch &s, const T *un, const T *uo, double F, GramWalk &g)
+{
+    const int W = s.W, H = s.H, p = W < H ? W : H, m = W < H ? H : W;
+    if (s.gram_a.bytes < (size_t)p * m * sizeof(double))
+        TF_TRY(s.gram_a.alloc((size_t)p * m * sizeof(double)));
+    if (s.gram_g.bytes < (size_t)p * p * sizeof(double))
+        TF_TRY(s.gram_g.alloc((size_t)p * p * sizeof(double)));
+    double *A = s.gram_a.as<double>(), *G = s.gram_g.as<double>();
+    TF_TRY(launch("hs_gram_build", k_gram_build<T>, dim3(cdiv((size_t)W * H, 256)), dim3(256), 0, un, uo, W, H, 1.0 / F, A));
+    TF_TRY(launch("hs_gram_syrk", k_syrk, dim3(cdiv(p, 64), cdiv(p, 64)), dim3(256), 0, (const double *)A, p, m, G));
+    g.p = p, g.src = G, g.dst = A;
+    return TF_OK;
+}
+
+// the bound of k = 1, 2, 4 in turn: sigma <= F ||G^k||_F^(1 / (2k))
+static int gram_bound(NormScratch &s, GramWalk &g, int k, double F, double *bound)
+{
+    if (k > 1) { // G^k = G^(k/2) (G^(k/2))^T: the powers are symmetric
+        TF_TRY(launch("hs_gram_syrk", k_syrk, dim3(cdiv(g.p, 64), cdiv(g.p, 64)), dim3(256), 0, (const double *)g.src, g.p, g.p,
+                      g.dst));
+        std::swap(g.src, g.dst);
+    }
+    double fro;
+    TF_TRY(frobenius(s, g.src, (size_t)g.p * g.p, &fro));
+    *bound = F * std::pow(fro, 1.0 / (2 * k));
+    return TF_OK;
+}
+
+template <typename T>
+static int decide_device_t(NormScratch &s, const T *un, const T *uo, double delta, double F, int *decision, int *stage)
+{
+    const double hi = delta * (1 + GUARD), lo = delta * (1 - GUARD);
+    // 2. power iteration
+    double lbs[2 * POWER_STEPS];
+    TF_TRY(power_start(s));
+    for (int step = 0; step < POWER_STEPS; step += 2) {
+        TF_TRY(power_two_steps(s, un, uo, step, lbs));
+        for (int k = 0; k < 2 * step + 4; k++)
+            if (lbs[k] >= hi) {
+                *decision = NOT_CONVERGED, *stage = ST_POWER;
+                return TF_OK;
+            }
     }
     // 3. Gram certificate
-    if (F > 0 && std::isfinite(F)) {
-        const int p = W < H ? W : H, m = W < H ? H : W;
-        if (s.gram_a.bytes < (size_t)p * m * sizeof(double))
-            TF_TRY(s.gram_a.alloc((size_t)p * m * sizeof(double)));
-        if (s.gram_g.bytes < (size_t)p * p * sizeof(double))
-            TF_TRY(s.gram_g.alloc((size_t)p * p * sizeof(double)));
-        double *A = s.gram_a.as<double>(), *G = s.gram_g.as<double>();
-        TF_TRY(launch("hs_gram_build", k_gram_build<T>, dim3(cdiv((size_t)W * H, 256)), dim3(256), 0, un, uo, W, H, 1.0 / F, A));
-        const dim3 tiles(cdiv(p, 64), cdiv(p, 64));
-        TF_TRY(launch("hs_gram_syrk", k_syrk, tiles, dim3(256), 0, (const double *)A, p, m, G)); // G
-        double *src = G, *dst = A;
+    if (gram_usable(F)) {
+        GramWalk g;
+        TF_TRY(gram_start(s, un, uo, F, g));
         for (int k = 1; k <= 4; k *= 2) {
-            if (k > 1) { // G^k = G^(k/2) (G^(k/2))^T: the powers are symmetric
-                TF_TRY(launch("hs_gram_syrk", k_syrk, tiles, dim3(256), 0, (const double *)src, p, p, dst));
-                std::swap(src, dst);
-            }
-            double fro;
-            TF_TRY(frobenius(s, src, (size_t)p * p, &fro));
-            if (F * std::pow(fro, 1.0 / (2 * k)) < lo) {
+            double bound;
+            TF_TRY(gram_bound(s, g, k, F, &bound));
+            if (bound < lo) {
                 *decision = CONVERGED, *stage = ST_GRAM;
                 return TF_OK;
             }
@@ -402,40 +461,99 @@ int decide_device(NormScratch &s, const void *u_new, const void *u_old, bool f64
     return decide_device_t(s, (const float *)u_new, (const float *)u_old, delta, F, decision, stage);
 }
 
+template <typename T> static int device_values_t(NormScratch &s, const T *un, const T *uo, double F, StageValues *v)
+{
+    TF_TRY(power_start(s));
+    for (int step = 0; step < POWER_STEPS; step += 2)
+        TF_TRY(power_two_steps(s, un, uo, step, v->power));
+    v->gram[0] = v->gram[1] = v->gram[2] = std::numeric_limits<double>::quiet_NaN();
+    if (gram_usable(F)) {
+        GramWalk g;
+        TF_TRY(gram_start(s, un, uo, F, g));
+        for (int k = 1, i = 0; k <= 4; k *= 2, i++)
+            TF_TRY(gram_bound(s, g, k, F, &v->gram[i]));
+    }
+    return TF_OK;
+}
+
+int device_values(NormScratch &s, const void *u_new, const void *u_old, bool f64, double F, StageValues *v)
+{
+    if (f64)
+        return device_values_t(s, (const double *)u_new, (const double *)u_old, F, v);
+    return device_values_t(s, (const float *)u_new, (const float *)u_old, F, v);
+}
+
 } // namespace hs
 } // namespace tf
 
 using namespace tf;
 using namespace tf::hs;
 
+// A host field pair on the device and its cheap bounds, by the stage entry's partials kernel and the product's reduction
+struct StagedField {
+    NormScratch s;
+    DevBuf un, uo;
+    Bounds b;
+};
+
+static int stage_field(StagedField &f, const void *u_new, const void *u_old, int w, int h, bool f64)
+{
+    TF_TRY(ensure_init());
+    TF_TRY(f.s.init(w, h));
+    const size_t bytes = (size_t)w * h * (f64 ? 8 : 4);
+    TF_TRY(f.un.alloc(bytes));
+    TF_TRY(f.uo.alloc(bytes));
+    TF_HIP(hipMemcpyAsync(f.un.p, u_new, bytes, hipMemcpyHostToDevice, stream()));
+    if (u_old)
+        TF_HIP(hipMemcpyAsync(f.uo.p, u_old, bytes, hipMemcpyHostToDevice, stream()));
+    else
+        TF_HIP(hipMemsetAsync(f.uo.p, 0, bytes, stream()));   // du = u_new - 0 = u_new
+    TF_TRY(launch_delta_partials(f.un.p, f.uo.p, f64, w, h, f.s.partials.as<double>()));
+    PairList pl;
+    pl.n = 1;
+    pl.p[0] = PairDesc{0, 0};
+    TF_TRY(launch_bounds_reduce(f.s.partials.as<double>(), 0, pl, w, h, f.s.blocks.as<double>()));
+    TF_HIP(hipMemcpyAsync(f.s.host_blocks.data(), f.s.blocks.p, f.s.host_blocks.size() * sizeof(double), hipMemcpyDeviceToHost,
+                          stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    f.b = bounds_of(f.s.host_blocks.data(), w, h);
+    return TF_OK;
+}
+
 TF_API int tf_hs_stage_norm_test(const void *field, int w, int h, int is_f64, double delta, int *decision, int *stage)
 {
     TF_REQUIRE(field && decision && stage, "tf_hs_stage_norm_test: null pointer");
     TF_REQUIRE(w >= 1 && h >= 1 && (long long)w * h < (1ll << 31), "tf_hs_stage_norm_test: bad size %dx%d", w, h);
-    TF_TRY(ensure_init());
-    NormScratch s;
-    TF_TRY(s.init(w, h));
-    const size_t bytes = (size_t)w * h * (is_f64 ? 8 : 4);
-    DevBuf un, uo;
-    TF_TRY(un.alloc(bytes));
-    TF_TRY(uo.alloc(bytes));
-    TF_HIP(hipMemcpyAsync(un.p, field, bytes, hipMemcpyHostToDevice, stream()));
-    TF_HIP(hipMemsetAsync(uo.p, 0, bytes, stream()));   // du = field - 0 = field
-    TF_TRY(launch_delta_partials(un.p, uo.p, is_f64 != 0, w, h, s.partials.as<double>()));
-    PairList pl;
-    pl.n = 1;
-    pl.p[0] = PairDesc{0, 0};
-    TF_TRY(launch_bounds_reduce(s.partials.as<double>(), 0, pl, w, h, s.blocks.as<double>()));
-    TF_HIP(hipMemcpyAsync(s.host_blocks.data(), s.blocks.p, s.host_blocks.size() * sizeof(double), hipMemcpyDeviceToHost, stream()));
-    TF_HIP(hipStreamSynchronize(stream()));
-    bool nonfinite = false;
-    double F = 0.0;
-    *decision = decide_bounds(s.host_blocks.data(), w, h, delta, &nonfinite, &F);
+    StagedField f;
+    TF_TRY(stage_field(f, field, nullptr, w, h, is_f64 != 0));
+    *decision = decide_bounds(f.b, delta);
     *stage = ST_BOUNDS;
-    if (*decision == UNDECIDED && !nonfinite)
-        TF_TRY(decide_device(s, un.p, uo.p, is_f64 != 0, delta, F, decision, stage));
+    if (*decision == UNDECIDED && f.b.device_stages())
+        TF_TRY(decide_device(f.s, f.un.p, f.uo.p, is_f64 != 0, delta, f.b.F, decision, stage));
     if (*decision == UNDECIDED)
         *stage = ST_HOST;
+    TF_HIP(hipStreamSynchronize(stream()));
+    return TF_OK;
+}
+
+TF_API int tf_hs_stage_norm_values(const void *u_new, const void *u_old, int w, int h, int is_f64, double *out)
+{
+    TF_REQUIRE(u_new && out, "tf_hs_stage_norm_values: null pointer");
+    TF_REQUIRE(w >= 1 && h >= 1 && (long long)w * h < (1ll << 31), "tf_hs_stage_norm_values: bad size %dx%d", w, h);
+    StagedField f;
+    TF_TRY(stage_field(f, u_new, u_old, w, h, is_f64 != 0));
+    out[0] = f.b.F, out[1] = f.b.U, out[2] = f.b.L;
+    StageValues v;
+    for (double &x : v.power)
+        x = std::numeric_limits<double>::quiet_NaN();
+    for (double &x : v.gram)
+        x = std::numeric_limits<double>::quiet_NaN();
+    if (f.b.device_stages())
+        TF_TRY(device_values(f.s, f.un.p, f.uo.p, is_f64 != 0, f.b.F, &v));
+    for (int k = 0; k < 2 * POWER_STEPS; k++)
+        out[3 + k] = v.power[k];
+    for (int k = 0; k < 3; k++)
+        out[3 + 2 * POWER_STEPS + k] = v.gram[k];
     TF_HIP(hipStreamSynchronize(stream()));
     return TF_OK;
 }

@@ -145,6 +145,13 @@ class HornSchunck:
         check(self._lib.tf_hs_stage_derivatives(self._h, _ptr(p), _ptr(n), float(alpha ** 2), _ptr(out)))
         return out[..., 0], out[..., 1], out[..., 2], out[..., 3]
 
+    def last_bounds(self, pair: int = 0):
+        """F, U, L of `pair`'s most recent convergence check in the last call, from the iteration kernel's partial sums.
+        ValueError when the call made none (delta None, or no iteration)."""
+        out = (C.c_double * 3)()
+        check(self._lib.tf_hs_stage_last_bounds(self._h, int(pair), out))
+        return tuple(out)
+
 
 def stage_norm_test(field: np.ndarray, delta: float):
     """The device's stages of `numpy.linalg.norm(field, 2) < delta` -> (decision, stage): decision 1 / 0, or -1 when only
@@ -156,3 +163,25 @@ def stage_norm_test(field: np.ndarray, delta: float):
     check(_lib.load().tf_hs_stage_norm_test(_ptr(f), f.shape[1], f.shape[0], int(f.dtype == np.float64), float(delta),
                                             C.byref(dec), C.byref(st)))
     return dec.value, st.value
+
+
+POWER_STEPS = 8
+
+
+def stage_norm_values(u_new: np.ndarray, u_old: np.ndarray | None = None) -> dict:
+    """Every stage of the test without early exit, on du = u_new - u_old in the fields' dtype (u_old None: zeros):
+    {"F", "U", "L", "power": the 2 * POWER_STEPS lower bounds in the device's order, "gram": the bounds of k = 1, 2, 4},
+    float64."""
+    f = np.ascontiguousarray(u_new)
+    if f.dtype not in (np.float32, np.float64) or f.ndim != 2:
+        raise ValueError("a 2-D float32 or float64 field")
+    o = None
+    if u_old is not None:
+        o = np.ascontiguousarray(u_old)
+        if o.dtype != f.dtype or o.shape != f.shape:
+            raise ValueError("u_old must have u_new's dtype and shape")
+    out = (C.c_double * (3 + 2 * POWER_STEPS + 3))()
+    check(_lib.load().tf_hs_stage_norm_values(_ptr(f), None if o is None else _ptr(o), f.shape[1], f.shape[0],
+                                              int(f.dtype == np.float64), out))
+    v = np.array(out)
+    return {"F": v[0], "U": v[1], "L": v[2], "power": v[3:3 + 2 * POWER_STEPS], "gram": v[3 + 2 * POWER_STEPS:]}
