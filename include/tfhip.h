@@ -688,6 +688,33 @@ int tf_jpeg_copy_last(tf_jpeg *enc, uint8_t *out, size_t capacity, size_t *n_byt
    settings (transflow_amd/output.py) asks here. */
 int tf_jpeg_default_restart_mcus(void);
 
+/* ---- PNG of a frame in device memory (transflow/output/frames.py: `-o out/%05d.png`) -----------------------------------
+ * 8-bit RGB (colour type 2, no interlace): lossless.  Every row is filtered with the type -- None, Sub, Up, Average,
+ * Paeth -- of the smallest sum of min(b, 256 - b); the zlib stream is cut into bands of `band_rows` rows that are coded
+ * side by side, each a dynamic-Huffman block over a literal/length code that is a constant of the library
+ * (tf_png_code_lengths), with run-length matches (distance 1) only, closed by an empty stored block; one IDAT per band.
+ * DESIGN.md section 16 has the rules; any PNG decoder returns the frame's pixels exactly.
+ * band_rows: 1 or more (more than the height: one band), 0 = the library's default.  The handle owns its filtered,
+ * staging, scan and packed-stream buffers, sized for the worst case at creation. */
+typedef struct tf_png tf_png;
+int tf_png_create(tf_png **out, int height, int width, int band_rows);
+void tf_png_destroy(tf_png *enc);
+int tf_png_band_rows(tf_png *enc); /* the rows of a band of this handle */
+/* rgb_dev: uint8 [H][W][3] in device memory.  Queues its kernels on the calling thread's stream and waits; the file is
+   then copied to `out` (host) and *n_bytes is its size.  A file larger than `capacity` returns TF_ERR_ARG with *n_bytes
+   the size needed; `out` is then not written at all, and in no case is anything written at or beyond out + capacity. */
+int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, size_t capacity, size_t *n_bytes);
+/* The same for an image in host memory: uploaded to a buffer of the handle first. */
+int tf_png_encode(tf_png *enc, const uint8_t *rgb_host, uint8_t *out, size_t capacity, size_t *n_bytes);
+/* The file of the handle's last encode again, for a caller whose buffer was too small: the bands are still in the
+   handle's staging slots, so only the packing runs again, up to the new capacity.  Same return values; TF_ERR_STATE if
+   nothing has been encoded. */
+int tf_png_copy_last(tf_png *enc, uint8_t *out, size_t capacity, size_t *n_bytes);
+/* No GPU call in these two.  The rows band_rows = 0 stands for at this size: max(1, ceil(8192 / (3 W + 1))), at most H
+   (0 for a size that is none).  The lengths of the literal/length code's 286 symbols. */
+int tf_png_default_band_rows(int height, int width);
+int tf_png_code_lengths(uint8_t *out /* [286] */);
+
 /* ---- batch-of-frames mode over the GPUs of one node ----------------------
  * With flags == 0 every Farnebäck pair is independent (transflow/flow/sources/cv.py:478-490: the
  * `flow=` argument is an output buffer only), so ranks take contiguous ranges of pairs and the path

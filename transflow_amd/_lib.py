@@ -222,6 +222,14 @@ PROTOTYPES = {
     "tf_jpeg_encode": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_jpeg_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_jpeg_default_restart_mcus": (_I, []),
+    "tf_png_create": (_I, [_PP, _I, _I, _I]),
+    "tf_png_destroy": (None, [_P]),
+    "tf_png_band_rows": (_I, [_P]),
+    "tf_png_encode_dev": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_png_encode": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_png_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_png_default_band_rows": (_I, [_I, _I]),
+    "tf_png_code_lengths": (_I, [_P]),
     "tf_batch_unique_id": (_I, [_P]),
     "tf_batch_init": (_I, [_PP, _I, _I, _P]),
     "tf_batch_destroy": (None, [_P]),

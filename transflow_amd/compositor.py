@@ -310,13 +310,17 @@ class HipCompositor:
     """Same constructor, methods and attributes as transflow.compositor.Compositor."""
 
     def __init__(self, height: int, width: int, layers, background_color: str = "#ffffff", lazy_frames: bool = False,
-                 jpeg_frames: int | None = None):
+                 jpeg_frames: int | None = None, png_frames: bool = False):
         """lazy_frames: render() returns a DeviceFrame (transflow_amd/deviceframe.py) -- the uint8 (H, W, 3) array to
         everything numpy, its download started but not waited for, so that frame t comes down (pipeline.py:518,
         output/ffmpeg.py:32-54) beside frame t + 1's uploads and kernels (pipeline.py:565).  Default: a plain ndarray.
         jpeg_frames: a quality, 1 to 100 -- render() returns a JpegFrame (transflow_amd/jpeg.py): the frame is encoded
         where it is, the deferred one-launch frame included, and only the file comes down (an output whose product is
-        a compressed frame: output/mjpeg.py:58-60).  Not together with lazy_frames."""
+        a compressed frame: output/mjpeg.py:58-60).  Not together with lazy_frames.
+        png_frames: render() returns a PngFrame (transflow_amd/png.py): the same for the lossless frame-sequence output
+        (output/frames.py).  Not together with lazy_frames or jpeg_frames."""
+        if png_frames and (lazy_frames or jpeg_frames is not None):
+            raise ValueError("png_frames excludes lazy_frames and jpeg_frames: a frame leaves in one form")
         if jpeg_frames is not None:
             if lazy_frames:
                 raise ValueError("jpeg_frames and lazy_frames exclude each other: the encode is not overlapped")
@@ -329,7 +333,9 @@ class HipCompositor:
         self.layers = list(layers)
         self.lazy_frames = bool(lazy_frames)
         self.jpeg_frames = None if jpeg_frames is None else int(jpeg_frames)
+        self.png_frames = bool(png_frames)
         self._jpeg = None           # the encoder, made at the first render
+        self._png = None
         self._comp = None
         self._comp2 = None          # lazy frames: the second image (frame t downloads from one while t + 1 is rendered into the other)
         self._flip = False
@@ -368,6 +374,11 @@ class HipCompositor:
                 from .jpeg import JpegEncoder
                 self._jpeg = JpegEncoder(self.height, self.width, self.jpeg_frames)
             return self._jpeg.frame(comp)
+        if self.png_frames:
+            if self._png is None:
+                from .png import PngEncoder
+                self._png = PngEncoder(self.height, self.width)
+            return self._png.frame(comp)
         if self._frame_pool is None:
             from .device import ArrayPool
             self._frame_pool = ArrayPool((self.height, self.width, 3), np.uint8, pinned=True)
@@ -380,7 +391,7 @@ class HipCompositor:
 
     @classmethod
     def from_args(cls, height: int, width: int, layer_configs, background_color: str = "#ffffff", rng: str = "numpy",
-                  lazy_frames: bool = False, jpeg_frames: int | None = None):
+                  lazy_frames: bool = False, jpeg_frames: int | None = None, png_frames: bool = False):
         layers = []
         for config in layer_configs:
             classname = getattr(config, "classname", "moveref")
@@ -388,20 +399,22 @@ class HipCompositor:
                 raise ValueError(f"Unknown layer classname {classname}")                # layer.py:56
             layers.append(LAYER_CLASSES[classname](config, height, width, [], rng=rng))
         return cls(height, width, layers, background_color=background_color, lazy_frames=lazy_frames,
-                   jpeg_frames=jpeg_frames)
+                   jpeg_frames=jpeg_frames, png_frames=png_frames)
 
     def set_sources(self, pixmap_interfaces: dict):
         for i, layer in enumerate(self.layers):
             layer.set_sources(pixmap_interfaces.get(i, []))
 
     def __getstate__(self):
-        return {k: v for k, v in self.__dict__.items() if k not in ("_comp", "_comp2", "_frame_pool", "_jpeg")}
+        return {k: v for k, v in self.__dict__.items() if k not in ("_comp", "_comp2", "_frame_pool", "_jpeg", "_png")}
 
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.lazy_frames = bool(state.get("lazy_frames", False))
         self.jpeg_frames = state.get("jpeg_frames")
+        self.png_frames = bool(state.get("png_frames", False))
         self._jpeg = None
+        self._png = None
         self._comp = None
         self._comp2 = None
         self._flip = False
@@ -418,3 +431,6 @@ class HipCompositor:
         if getattr(self, "_jpeg", None) is not None:
             self._jpeg.close()
             self._jpeg = None
+        if getattr(self, "_png", None) is not None:
+            self._png.close()
+            self._png = None

@@ -1,0 +1,765 @@
+// PNG of a device-resident RGB frame: 8-bit colour type 2, no interlace, every row filtered with the type of the
+// smallest sum of min(b, 256 - b), and a zlib stream cut into bands that are coded side by side (tests/png_ref.py is
+// the numpy statement of the same rules).
+//
+// A band is `band_rows` rows of the filtered stream.  Its deflate data is one dynamic-Huffman block -- the table header
+// is a constant of the library: a fixed literal/length code, a distance alphabet of the single code 0 -- and an empty
+// stored block that brings the stream to a byte boundary, so a band's bytes depend on nothing but its own rows and the
+// bands concatenate into one valid stream.  Matches are runs: distance 1, never across the band's first byte.
+//
+//   k_png_filter   one work-group per row: the five candidates' sums, the choice, the filtered row to HBM, and the
+//                  row's two Adler sums (the plain sum and the sum weighted by the bytes behind, 64-bit, reduced once).
+//   k_png_deflate  one wave per band, 64 bytes a trip.  A lane compares its byte with its left neighbour's; the ballot
+//                  of equal lanes and the count carried from the trip before give it its place in a run.  A run leaves
+//                  a match of 258 at the lane where the count reaches it, and what is left -- a match, or one or two
+//                  literals -- at the lane behind its end, in front of that lane's own literal; the position one past
+//                  the band is a lane too and its own symbol is end-of-block.  A wave prefix sum of the bit counts
+//                  places the tokens in an LDS bit buffer that starts out holding the table header; after every trip
+//                  its whole bytes go to the band's staging slot and the bits left over to its front.
+//   k_png_scan     exclusive sum of the bands' chunk sizes, data + 12 (one work-group).
+//   k_png_pack     one wave per band writes length, "IDAT", the data and the chunk's CRC-32 at the band's offset: the
+//                  lanes take contiguous slices through the byte table and the slices' CRCs are combined by
+//                  multiplying with x^(8 * bytes behind) modulo the polynomial.  No byte at or past `capacity` is
+//                  written.
+#include "png_common.h"
+
+#include <cstring>
+
+namespace tf {
+namespace png {
+
+constexpr int WAVE = 64;
+constexpr uint32_t ADLER_BASE = 65521, CRC_POLY = 0xEDB88320u;
+
+// ---- filter ----------------------------------------------------------------------------------------------------------
+constexpr int FILTER_BLOCK = 256;
+
+__device__ __forceinline__ int paeth(int a, int b, int c)
+{
+    const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+}
+
+__device__ __forceinline__ int filter_byte(int type, int x, int a, int b, int c)
+{
+    const int pred = type == 0 ? 0 : type == 1 ? a : type == 2 ? b : type == 3 ? (a + b) >> 1 : paeth(a, b, c);
+    return (x - pred) & 0xFF;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int d = WAVE / 2; d; d >>= 1)
+        v += __shfl_xor(v, d, WAVE);
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+#pragma unroll
+    for (int d = WAVE / 2; d; d >>= 1)
+        v += __shfl_xor(v, d, WAVE);
+    return v;
+}
+
+// rowsums[2 r], [2 r + 1]: sum of the filtered row's L = 1 + 3 W bytes, and sum of (L - j) byte[j], both mod 65521.
+// Largest values: 255 L < 2^26 and 255 L (L + 1) / 2 < 2^43 for W = 65535, so nothing is reduced before the end.
+__global__ __launch_bounds__(FILTER_BLOCK) void k_png_filter(const uint8_t *__restrict__ rgb, int W, uint8_t *__restrict__ filtered,
+                                                             uint32_t *__restrict__ rowsums)
+{
+    __shared__ uint32_t s_cost[FILTER_BLOCK / WAVE][5];
+    __shared__ unsigned long long s_adler[FILTER_BLOCK / WAVE][2];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int row = blockIdx.x, n = 3 * W;
+    const uint8_t *cur = rgb + (size_t)row * n;
+    const uint8_t *prev = row ? cur - n : nullptr;
+    uint32_t cost[5] = {0, 0, 0, 0, 0};
+    for (int i = tid; i < n; i += FILTER_BLOCK) {
+        const int x = cur[i], a = i >= 3 ? cur[i - 3] : 0, b = prev ? prev[i] : 0, c = (prev && i >= 3) ? prev[i - 3] : 0;
+#pragma unroll
+        for (int t = 0; t < 5; t++) {
+            const int v = filter_byte(t, x, a, b, c);
+            cost[t] += (uint32_t)min(v, 256 - v);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 5; t++) {
+        const uint32_t s = wave_sum(cost[t]);
+        if (lane == 0)
+            s_cost[wave][t] = s;
+    }
+    __syncthreads();
+    int type = 0;
+    uint32_t best = 0;
+#pragma unroll
+    for (int t = 0; t < 5; t++) {
+        uint32_t s = 0;
+        for (int w = 0; w < FILTER_BLOCK / WAVE; w++)
+            s += s_cost[w][t];
+        if (t == 0 || s < best) // ties stay with the lowest type
+            best = s, type = t;
+    }
+    const size_t L = (size_t)n + 1;
+    uint8_t *out = filtered + (size_t)row * L;
+    unsigned long long s1 = 0, s2 = 0;
+    if (tid == 0) {
+        out[0] = (uint8_t)type;
+        s1 = (unsigned long long)type, s2 = (unsigned long long)type * L;
+    }
+    for (int i = tid; i < n; i += FILTER_BLOCK) {
+        const int x = cur[i], a = i >= 3 ? cur[i - 3] : 0, b = prev ? prev[i] : 0, c = (prev && i >= 3) ? prev[i - 3] : 0;
+        const int v = filter_byte(type, x, a, b, c);
+        out[1 + i] = (uint8_t)v;
+        s1 += (unsigned long long)v;
+        s2 += (unsigned long long)v * (L - 1 - (size_t)i);
+    }
+    s1 = wave_sum64(s1), s2 = wave_sum64(s2);
+    if (lane == 0)
+        s_adler[wave][0] = s1, s_adler[wave][1] = s2;
+    __syncthreads();
+    if (tid == 0) {
+        s1 = s2 = 0;
+        for (int w = 0; w < FILTER_BLOCK / WAVE; w++)
+            s1 += s_adler[w][0], s2 += s_adler[w][1];
+        rowsums[2 * row] = (uint32_t)(s1 % ADLER_BASE);
+        rowsums[2 * row + 1] = (uint32_t)(s2 % ADLER_BASE);
+    }
+}
+
+// ---- deflate ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wave_inclusive_sum(int v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const int up = __shfl_up(v, d, WAVE);
+        if (lane >= d)
+            v += up;
+    }
+    return v;
+}
+
+struct DeflateArgs {
+    const uint8_t *filtered; // H rows of row_bytes
+    uint32_t row_bytes;
+    int H, band_rows;
+    const Tables *tables;
+    uint8_t *staging;        // n_bands slots of slot_bytes
+    uint32_t slot_bytes;
+    uint32_t *lengths;       // per band: the bytes it wrote
+    uint32_t *overflow;      // set if a band had more bytes than its slot (the bound of png_common.h says: never)
+};
+
+constexpr int TRIPS = 4;
+
+__device__ __forceinline__ void put_token(unsigned long long &bits, int &len, uint32_t entry)
+{
+    bits |= (unsigned long long)(entry & 0xFFFFFFu) << len;
+    len += (int)(entry >> 24);
+}
+
+__global__ __launch_bounds__(WAVE) void k_png_deflate(const DeflateArgs a)
+{
+    __shared__ uint32_t s_bits[BIT_WORDS]; // the trip's bits, stream bit 32 w + k in bit k of word w
+    __shared__ uint32_t s_lit[END_OF_BLOCK + 1];
+    __shared__ uint32_t s_match[MAX_MATCH + 1];
+    const int lane = threadIdx.x;
+    const Tables &t = *a.tables;
+    for (int w = lane; w < BIT_WORDS; w += WAVE)
+        s_bits[w] = w < HEADER_WORDS ? t.header[w] : 0;
+    for (int w = lane; w <= END_OF_BLOCK; w += WAVE)
+        s_lit[w] = t.lit[w];
+    for (int w = lane; w <= MAX_MATCH; w += WAVE)
+        s_match[w] = t.match[w];
+    const int first_row = blockIdx.x * a.band_rows; // (n_bands * band_rows < H + band_rows <= 2^17)
+    const int rows = min(a.band_rows, a.H - first_row);
+    const uint32_t N = (uint32_t)rows * a.row_bytes; // (at most 2^28: tf_png_create)
+    const uint8_t *src = a.filtered + (size_t)first_row * a.row_bytes;
+    uint8_t *slot = a.staging + (size_t)blockIdx.x * a.slot_bytes;
+    uint32_t bitpos = HEADER_BITS; // bits in s_bits
+    uint32_t outpos = 0;           // bytes in the slot
+    int carry = 0;                 // the run the last trip ended in, counted from its last match of 258
+    int prev_last = 0;             // the last trip's last byte
+    int cur[TRIPS], next[TRIPS]; // a block of TRIPS trips: its bytes are loaded while the block before is coded
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+        const uint32_t j = (uint32_t)(k * WAVE + lane);
+        cur[k] = j < N ? src[j] : 0;
+    }
+    __syncthreads();
+    for (uint32_t block = 0; block <= N; block += TRIPS * WAVE) {
+#pragma unroll
+        for (int k = 0; k < TRIPS; k++) {
+            const uint32_t j = block + (uint32_t)((TRIPS + k) * WAVE + lane);
+            next[k] = j < N ? src[j] : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < TRIPS; k++) {
+        const uint32_t base = block + (uint32_t)(k * WAVE);
+        if (base > N)
+            break;
+        const uint32_t i = base + lane;
+        const int byte = cur[k];
+        int left = __shfl_up(byte, 1, WAVE);
+        if (lane == 0)
+            left = prev_last;
+        const bool eq = i < N && i > 0 && byte == left;
+        const unsigned long long differ = ~__ballot(eq) & ((1ull << lane) - 1); // the lanes below that end a run
+        const int last_differ = differ ? 63 - __clzll((long long)differ) : -1;
+        unsigned long long bits = 0;
+        int len = 0, run = 0;
+        if (eq) {
+            run = differ ? lane - last_differ : carry + lane + 1; // < 258 + 64: it reaches 258 once at the most
+            if (run == MAX_MATCH)
+                put_token(bits, len, s_match[MAX_MATCH]);
+        } else if (i <= N) {
+            int pending = differ ? lane - 1 - last_differ : carry + lane; // the run that ended at the byte before
+            if (pending >= MAX_MATCH)
+                pending -= MAX_MATCH; // a lane below has emitted that match
+            if (pending >= MIN_MATCH) {
+                put_token(bits, len, s_match[pending]);
+            } else {
+                for (int k = 0; k < pending; k++)
+                    put_token(bits, len, s_lit[left]);
+            }
+            put_token(bits, len, s_lit[i < N ? byte : END_OF_BLOCK]);
+        }
+        carry = __shfl(eq ? (run >= MAX_MATCH ? run - MAX_MATCH : run) : 0, WAVE - 1, WAVE);
+        prev_last = __shfl(byte, WAVE - 1, WAVE);
+        len = min(len, LANE_MAX_BITS); // (never: the host checked the table)
+        const int incl = wave_inclusive_sum(len, lane);
+        if (len) {
+            const uint32_t p = bitpos + (uint32_t)(incl - len);
+            const uint32_t word = p >> 5, sh = p & 31;
+            const uint32_t w0 = (uint32_t)(bits << sh), w1 = (uint32_t)((bits >> 1) >> (31 - sh));
+            const uint32_t w2 = (uint32_t)((bits >> 33) >> (31 - sh));
+            if (word + 2 < BIT_WORDS) {
+                if (w0)
+                    atomicOr(&s_bits[word], w0);
+                if (w1)
+                    atomicOr(&s_bits[word + 1], w1);
+                if (w2)
+                    atomicOr(&s_bits[word + 2], w2);
+            }
+        }
+        bitpos += (uint32_t)__shfl(incl, WAVE - 1, WAVE);
+        // ---- behind end-of-block: three zero bits, zeros to the byte boundary, 00 00 FF FF
+        if (base + WAVE > N) {
+            bitpos = (bitpos + 3 + 7) & ~7u;
+            const uint32_t q = bitpos + 16 + 8 * (uint32_t)lane;
+            if (lane < 2 && (q >> 5) < BIT_WORDS)
+                atomicOr(&s_bits[q >> 5], 0xFFu << (q & 31));
+            bitpos += 32;
+        }
+        __syncthreads();
+        // ---- the trip's whole bytes to the slot
+        const uint32_t n_bytes = bitpos >> 3;
+        for (uint32_t j = lane; j < n_bytes; j += WAVE)
+            if (outpos + j < a.slot_bytes)
+                slot[outpos + j] = (uint8_t)(s_bits[j >> 2] >> (8 * (j & 3)));
+        outpos += n_bytes;
+        // ---- the bits left over go to the front of a zeroed buffer
+        const uint32_t rem = bitpos & 7;
+        const uint32_t left_over = rem ? (s_bits[n_bytes >> 2] >> (8 * (n_bytes & 3))) & 0xFF : 0;
+        const uint32_t used = (bitpos >> 5) + 3;
+        __syncthreads();
+        for (uint32_t w = lane; w < used && w < BIT_WORDS; w += WAVE)
+            s_bits[w] = w == 0 ? left_over : 0;
+        bitpos = rem;
+        __syncthreads();
+        }
+#pragma unroll
+        for (int k = 0; k < TRIPS; k++)
+            cur[k] = next[k];
+    }
+    if (lane == 0) {
+        a.lengths[blockIdx.x] = min(outpos, a.slot_bytes);
+        if (outpos > a.slot_bytes)
+            *a.overflow = 1;
+    }
+}
+
+// ---- scan: lengths[n] -> offsets[n], exclusive sums of the chunk sizes lengths[i] + 12; info[0] = their total
+constexpr int SCAN_BLOCK = 1024;
+__global__ __launch_bounds__(SCAN_BLOCK) void k_png_scan(const uint32_t *__restrict__ lengths, uint32_t *__restrict__ offsets, int n,
+                                                         unsigned long long *__restrict__ info)
+{
+    __shared__ unsigned long long s_wave[SCAN_BLOCK / WAVE];
+    __shared__ unsigned long long s_carry;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    if (tid == 0)
+        s_carry = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += SCAN_BLOCK) {
+        const int i = base + tid;
+        const unsigned long long v = i < n ? (unsigned long long)lengths[i] + 12 : 0;
+        unsigned long long incl = v;
+#pragma unroll
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const unsigned long long up = __shfl_up(incl, d, WAVE);
+            if (lane >= d)
+                incl += up;
+        }
+        if (lane == WAVE - 1)
+            s_wave[wave] = incl;
+        __syncthreads();
+        unsigned long long before = s_carry;
+        for (int w = 0; w < wave; w++)
+            before += s_wave[w];
+        if (i < n)
+            offsets[i] = (uint32_t)(before + incl - v);
+        __syncthreads();
+        if (tid == SCAN_BLOCK - 1)
+            s_carry = before + incl;
+        __syncthreads();
+    }
+    if (tid == 0)
+        info[0] = s_carry;
+}
+
+// ---- pack ------------------------------------------------------------------------------------------------------------
+// a(x) b(x) mod the polynomial, bit 31 the coefficient of x^0 (zlib's multmodp)
+__host__ __device__ inline uint32_t multmodp(uint32_t a, uint32_t b)
+{
+    uint32_t m = 1u << 31, p = 0;
+    for (;;) {
+        if (a & m) {
+            p ^= b;
+            if ((a & (m - 1)) == 0)
+                break;
+        }
+        m >>= 1;
+        b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
+    }
+    return p;
+}
+
+// x^(8 n) mod the polynomial
+__device__ __forceinline__ uint32_t x8nmodp(uint32_t n, const uint32_t *__restrict__ x2n)
+{
+    uint32_t p = 1u << 31;
+    for (int k = 3; n; n >>= 1, k++)
+        if (n & 1)
+            p = multmodp(x2n[k & 31], p);
+    return p;
+}
+
+constexpr uint32_t IDAT_CRC = 0x35AF061Eu; // crc32("IDAT"); checked against the table when a handle is made
+
+constexpr int PACK_BLOCK = 256;
+__global__ __launch_bounds__(PACK_BLOCK) void k_png_pack(const uint8_t *__restrict__ staging, uint32_t slot_bytes,
+                                                         const uint32_t *__restrict__ lengths, const uint32_t *__restrict__ offsets, int n,
+                                                         const Tables *__restrict__ tables, uint8_t *__restrict__ out, size_t capacity)
+{
+    __shared__ uint32_t s_crc[256];
+    __shared__ uint32_t s_x2n[32];
+    s_crc[threadIdx.x] = tables->crc[threadIdx.x];
+    if (threadIdx.x < 32)
+        s_x2n[threadIdx.x] = tables->x2n[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * (PACK_BLOCK / WAVE) + threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    if (i >= n)
+        return;
+    const uint8_t *src = staging + (size_t)i * slot_bytes;
+    const uint32_t len = min(lengths[i], slot_bytes);
+    const size_t dst = (size_t)offsets[i];
+    if (lane < 8 && dst + lane < capacity)
+        out[dst + lane] = lane < 4 ? (uint8_t)(len >> (24 - 8 * lane)) : (uint8_t)"IDAT"[lane - 4];
+    // (slots are dword-aligned and a multiple of four bytes: a dword that holds a byte below len lies inside the slot)
+    const uint32_t *src4 = reinterpret_cast<const uint32_t *>(src);
+#pragma unroll 4
+    for (uint32_t j = 4 * (uint32_t)lane; j < len; j += 4 * WAVE) {
+        const uint32_t v = src4[j >> 2];
+#pragma unroll
+        for (uint32_t b = 0; b < 4; b++)
+            if (j + b < len && dst + 8 + j + b < capacity)
+                out[dst + 8 + j + b] = (uint8_t)(v >> (8 * b));
+    }
+    // the CRC of "IDAT" and the data: lane l takes bytes [l slice, (l + 1) slice); lane 0 goes on from "IDAT"
+    const uint32_t slice = ((len + WAVE - 1) / WAVE + 3) & ~3u; // whole dwords
+    const uint32_t begin = min((uint32_t)lane * slice, len), end = min(begin + slice, len);
+    uint32_t c = lane == 0 ? ~IDAT_CRC : 0xFFFFFFFFu;
+#pragma unroll 4
+    for (uint32_t j = begin; j < end; j += 4) {
+        const uint32_t v = src4[j >> 2];
+#pragma unroll
+        for (uint32_t b = 0; b < 4; b++)
+            if (j + b < end)
+                c = s_crc[(c ^ (v >> (8 * b))) & 0xFF] ^ (c >> 8);
+    }
+    c = ~c; // the slice's own CRC-32 (of no bytes: 0)
+    if (c && end < len)
+        c = multmodp(x8nmodp(len - end, s_x2n), c);
+#pragma unroll
+    for (int d = WAVE / 2; d; d >>= 1)
+        c ^= __shfl_xor(c, d, WAVE);
+    if (lane < 4 && dst + 8 + len + lane < capacity)
+        out[dst + 8 + len + lane] = (uint8_t)(c >> (24 - 8 * lane));
+}
+
+// ---- host: the code, the tables, the chunks the host writes ------------------------------------------------------------
+// The literal/length code: Huffman over model weights, the two smallest merged on the key (weight, order) -- a leaf's
+// order is its symbol, the k-th internal node's 1000 + k -- until one is left; a symbol's length is its leaf's depth.
+static void make_code_lengths(uint8_t lengths[N_SYMBOLS])
+{
+    struct Node {
+        uint64_t weight;
+        int order, parent;
+        bool live;
+    };
+    std::vector<Node> nodes;
+    for (int v = 0; v < 256; v++) {
+        const uint64_t m = (uint64_t)(v < 256 - v ? v : 256 - v) + 1, cube = m * m * m;
+        uint64_t root = 0;
+        while ((root + 1) * (root + 1) <= cube)
+            root++;
+        const uint64_t w = 65536 / root;
+        nodes.push_back({w < 128 ? 128 : w, v, -1, true});
+    }
+    nodes.push_back({128, END_OF_BLOCK, -1, true});
+    for (int k = 0; k < N_LENGTH_SYMBOLS; k++)
+        nodes.push_back({k == N_LENGTH_SYMBOLS - 1 ? 4096u : 512u, 257 + k, -1, true});
+    for (int k = 0;; k++) {
+        int lo[2] = {-1, -1};
+        for (int pick = 0; pick < 2; pick++)
+            for (int i = 0; i < (int)nodes.size(); i++) {
+                if (!nodes[i].live || i == lo[0])
+                    continue;
+                const int j = lo[pick];
+                if (j < 0 || nodes[i].weight < nodes[j].weight || (nodes[i].weight == nodes[j].weight && nodes[i].order < nodes[j].order))
+                    lo[pick] = i;
+            }
+        if (lo[1] < 0)
+            break;
+        nodes[lo[0]].live = nodes[lo[1]].live = false;
+        nodes[lo[0]].parent = nodes[lo[1]].parent = (int)nodes.size();
+        nodes.push_back({nodes[lo[0]].weight + nodes[lo[1]].weight, 1000 + k, -1, true});
+    }
+    for (int s = 0; s < N_SYMBOLS; s++) {
+        int depth = 0;
+        for (int i = s; nodes[i].parent >= 0; i = nodes[i].parent)
+            depth++;
+        lengths[s] = (uint8_t)(depth > 255 ? 255 : depth);
+    }
+}
+
+static uint32_t reverse_bits(uint32_t code, int n)
+{
+    uint32_t r = 0;
+    for (int i = 0; i < n; i++)
+        r |= ((code >> i) & 1) << (n - 1 - i);
+    return r;
+}
+
+struct HeaderBits {
+    uint32_t words[HEADER_WORDS] = {};
+    int n = 0;
+    void put(uint32_t value, int bits)
+    {
+        for (int i = 0; i < bits; i++, n++)
+            if ((value >> i) & 1)
+                words[n >> 5] |= 1u << (n & 31);
+    }
+};
+
+// Everything the kernels read; byte_bits and eob_bits for the bound.  TF_ERR_STATE if the code is not what the kernels
+// are written for (complete, at most 15 bits, a lane's tokens within 64).
+static int make_tables(Tables &t, int *byte_bits, int *eob_bits)
+{
+    uint8_t len[N_SYMBOLS];
+    make_code_lengths(len);
+    // RFC 1951 3.2.2
+    int count[17] = {}, longest = 0;
+    uint64_t kraft = 0; // in units of 2^-16
+    for (int s = 0; s < N_SYMBOLS; s++) {
+        if (len[s] < 1 || len[s] > 15)
+            return set_error(TF_ERR_STATE, "png: symbol %d has a code of %d bits", s, len[s]);
+        count[len[s]]++, kraft += 1ull << (16 - len[s]);
+        longest = len[s] > longest ? len[s] : longest;
+    }
+    if (kraft != 1ull << 16)
+        return set_error(TF_ERR_STATE, "png: the literal/length code is not complete");
+    uint32_t next_code[17] = {}, code = 0, codes[N_SYMBOLS];
+    for (int bits = 1; bits <= 15; bits++) {
+        code = (code + count[bits - 1]) << 1;
+        next_code[bits] = code;
+    }
+    for (int s = 0; s < N_SYMBOLS; s++)
+        codes[s] = next_code[len[s]]++;
+    int worst = 0, longest_lit = 0, longest_match = 0;
+    for (int s = 0; s <= END_OF_BLOCK; s++) {
+        t.lit[s] = ((uint32_t)len[s] << 24) | reverse_bits(codes[s], len[s]);
+        if (s < END_OF_BLOCK)
+            longest_lit = len[s] > longest_lit ? len[s] : longest_lit;
+    }
+    worst = longest_lit;
+    for (int n = 0; n <= MAX_MATCH; n++)
+        t.match[n] = 0;
+    for (int k = 0; k < N_LENGTH_SYMBOLS; k++) {
+        const int s = 257 + k, last = k + 1 < N_LENGTH_SYMBOLS ? LENGTH_BASE[k + 1] - 1 : MAX_MATCH;
+        for (int n = LENGTH_BASE[k]; n <= last && (k == N_LENGTH_SYMBOLS - 1 || n < MAX_MATCH); n++) {
+            const int bits = len[s] + LENGTH_EXTRA[k] + 1; // the code, the extra bits, the distance code 0
+            t.match[n] = ((uint32_t)bits << 24) | reverse_bits(codes[s], len[s]) | ((uint32_t)(n - LENGTH_BASE[k]) << len[s]);
+            const int per_byte = (bits + n - 1) / n;
+            worst = per_byte > worst ? per_byte : worst;
+            longest_match = bits > longest_match ? bits : longest_match;
+        }
+    }
+    // a lane's tokens: a match or two literals, then its own literal or end-of-block
+    const int own = longest_lit > len[END_OF_BLOCK] ? longest_lit : len[END_OF_BLOCK];
+    if (2 * longest_lit + own > LANE_MAX_BITS || longest_match + own > LANE_MAX_BITS || longest_match > 24)
+        return set_error(TF_ERR_STATE, "png: a lane's tokens would not fit %d bits", LANE_MAX_BITS);
+    *byte_bits = worst, *eob_bits = len[END_OF_BLOCK];
+
+    for (uint32_t n = 0; n < 256; n++) {
+        uint32_t c = n;
+        for (int k = 0; k < 8; k++)
+            c = (c & 1) ? (c >> 1) ^ CRC_POLY : c >> 1;
+        t.crc[n] = c;
+    }
+    uint32_t p = 1u << 30; // x^1
+    t.x2n[0] = p;
+    for (int k = 1; k < 32; k++)
+        t.x2n[k] = p = multmodp(p, p);
+
+    HeaderBits h;
+    h.put(0, 1), h.put(2, 2), h.put(N_SYMBOLS - 257, 5), h.put(0, 5), h.put(19 - 4, 4);
+    for (int k = 0; k < 19; k++)
+        h.put(CLEN_ORDER[k] >= 16 ? 0 : 4, 3);
+    for (int s = 0; s <= N_SYMBOLS; s++) // the lengths' 4-bit codes are the lengths; the last is the distance code's
+        h.put(reverse_bits(s < N_SYMBOLS ? len[s] : 1, 4), 4);
+    if (h.n != HEADER_BITS)
+        return set_error(TF_ERR_STATE, "png: the table header has %d bits, not %d", h.n, HEADER_BITS);
+    memcpy(t.header, h.words, sizeof(t.header));
+    return TF_OK;
+}
+
+static uint32_t host_crc(const Tables &t, const uint8_t *p, size_t n)
+{
+    uint32_t c = 0xFFFFFFFFu;
+    for (size_t i = 0; i < n; i++)
+        c = t.crc[(c ^ p[i]) & 0xFF] ^ (c >> 8);
+    return ~c;
+}
+
+static void put_be32(std::vector<uint8_t> &out, uint32_t v)
+{
+    for (int k = 0; k < 4; k++)
+        out.push_back((uint8_t)(v >> (24 - 8 * k)));
+}
+
+static void put_chunk(std::vector<uint8_t> &out, const Tables &t, const char *kind, const std::vector<uint8_t> &payload)
+{
+    put_be32(out, (uint32_t)payload.size());
+    const size_t at = out.size();
+    out.insert(out.end(), kind, kind + 4);
+    out.insert(out.end(), payload.begin(), payload.end());
+    put_be32(out, host_crc(t, out.data() + at, out.size() - at));
+}
+
+static int default_band_rows(int height, int width)
+{
+    const long row = 3L * width + 1;
+    const long rows = (DEFAULT_BAND_BYTES + row - 1) / row;
+    return (int)(rows < 1 ? 1 : (rows > height ? height : rows));
+}
+
+} // namespace png
+} // namespace tf
+
+using namespace tf;
+using namespace tf::png;
+
+struct tf_png {
+    int H = 0, W = 0, band_rows = 0, n_bands = 0;
+    uint32_t row_bytes = 0, slot = 0;
+    Tables tables;
+    std::vector<uint8_t> head, tail; // what the host writes in front of the bands' chunks and behind them
+    DevBuf dev_tables, filtered, rowsums, staging, lengths, offsets, info, packed, upload;
+    unsigned long long *info_host = nullptr; // page-locked: [0] the chunks' bytes, [1] the overflow flag
+    uint32_t *rowsums_host = nullptr;        // page-locked: the rows' Adler sums
+    size_t last_chunks = 0;                  // the chunks' bytes of the last encode that ran; 0: none to copy again
+};
+
+TF_API void tf_png_destroy(tf_png *enc)
+{
+    if (!enc)
+        return;
+    if (enc->info_host)
+        (void)hipHostFree(enc->info_host);
+    if (enc->rowsums_host)
+        (void)hipHostFree(enc->rowsums_host);
+    delete enc;
+}
+
+TF_API int tf_png_default_band_rows(int height, int width)
+{
+    if (height < 1 || width < 1)
+        return 0;
+    return default_band_rows(height, width);
+}
+
+TF_API int tf_png_code_lengths(uint8_t *out)
+{
+    TF_REQUIRE(out, "tf_png_code_lengths: null pointer");
+    make_code_lengths(out);
+    return TF_OK;
+}
+
+TF_API int tf_png_create(tf_png **out, int height, int width, int band_rows)
+{
+    TF_REQUIRE(out, "tf_png_create: null pointer");
+    *out = nullptr;
+    TF_REQUIRE(height >= 1 && width >= 1 && height <= 65535 && width <= 65535, "tf_png_create: bad size %dx%d (1 to 65535)", width,
+               height);
+    TF_REQUIRE(band_rows >= 0, "tf_png_create: band_rows %d (0 = default, 1 or more)", band_rows);
+    const int rows = band_rows == 0 ? default_band_rows(height, width) : (band_rows > height ? height : band_rows);
+    const size_t row_bytes = 3 * (size_t)width + 1;
+    TF_REQUIRE(rows * row_bytes <= (size_t)1 << 28, "tf_png_create: a band of %d rows has %zu bytes (at most 2^28)", rows,
+               rows * row_bytes);
+    TF_TRY(ensure_init());
+    tf_png *enc = new (std::nothrow) tf_png;
+    TF_REQUIRE(enc, "tf_png_create: out of memory");
+    enc->H = height, enc->W = width, enc->band_rows = rows, enc->row_bytes = (uint32_t)row_bytes;
+    enc->n_bands = (height + rows - 1) / rows;
+    int byte_bits = 0, eob_bits = 0;
+    int rc = make_tables(enc->tables, &byte_bits, &eob_bits);
+    const size_t n = (size_t)enc->n_bands;
+    size_t slot = 0;
+    if (rc == TF_OK) {
+        slot = slot_bytes(rows * row_bytes, byte_bits, eob_bits);
+        if (n * (slot + 12) >= (size_t)1 << 32) // offsets are 32-bit
+            rc = set_error(TF_ERR_ARG, "tf_png_create: %dx%d in bands of %d rows could take %zu bytes (less than 2^32)", width, height,
+                           rows, n * (slot + 12));
+    }
+    if (rc == TF_OK && host_crc(enc->tables, (const uint8_t *)"IDAT", 4) != IDAT_CRC)
+        rc = set_error(TF_ERR_STATE, "tf_png_create: the CRC table is wrong");
+    enc->slot = (uint32_t)slot;
+    if (rc == TF_OK) {
+        enc->head = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+        std::vector<uint8_t> ihdr;
+        put_be32(ihdr, (uint32_t)width), put_be32(ihdr, (uint32_t)height);
+        ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});
+        put_chunk(enc->head, enc->tables, "IHDR", ihdr);
+        put_chunk(enc->head, enc->tables, "IDAT", {0x78, 0x01});
+    }
+    if (rc == TF_OK)
+        rc = enc->dev_tables.alloc(sizeof(Tables));
+    if (rc == TF_OK)
+        rc = enc->filtered.alloc((size_t)height * row_bytes);
+    if (rc == TF_OK)
+        rc = enc->rowsums.alloc((size_t)height * 2 * sizeof(uint32_t));
+    if (rc == TF_OK)
+        rc = enc->staging.alloc(n * slot);
+    if (rc == TF_OK)
+        rc = enc->lengths.alloc(n * sizeof(uint32_t));
+    if (rc == TF_OK)
+        rc = enc->offsets.alloc(n * sizeof(uint32_t));
+    if (rc == TF_OK)
+        rc = enc->info.alloc(2 * sizeof(unsigned long long));
+    if (rc == TF_OK) // the worst case again: every slot full, 12 bytes of chunk around each
+        rc = enc->packed.alloc(n * (slot + 12));
+    if (rc == TF_OK && hipHostMalloc((void **)&enc->info_host, 2 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
+        rc = set_error(TF_ERR_HIP, "tf_png_create: hipHostMalloc failed");
+    if (rc == TF_OK && hipHostMalloc((void **)&enc->rowsums_host, enc->rowsums.bytes, hipHostMallocDefault) != hipSuccess)
+        rc = set_error(TF_ERR_HIP, "tf_png_create: hipHostMalloc failed");
+    if (rc == TF_OK && hipMemcpyAsync(enc->dev_tables.p, &enc->tables, sizeof(Tables), hipMemcpyHostToDevice, stream()) != hipSuccess)
+        rc = set_error(TF_ERR_HIP, "tf_png_create: table upload failed");
+    if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
+        rc = set_error(TF_ERR_HIP, "tf_png_create: hipStreamSynchronize failed");
+    if (rc != TF_OK) {
+        tf_png_destroy(enc);
+        return rc;
+    }
+    *out = enc;
+    return TF_OK;
+}
+
+TF_API int tf_png_band_rows(tf_png *enc)
+{
+    return enc ? enc->band_rows : 0;
+}
+
+// the slots to their chunks in the packed stream, as far as `dev_capacity` reaches
+static int pack(tf_png *enc, size_t dev_capacity)
+{
+    return launch("png_pack", k_png_pack, dim3(cdiv(enc->n_bands, PACK_BLOCK / WAVE)), dim3(PACK_BLOCK), 0, enc->staging.as<uint8_t>(),
+                  enc->slot, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(), enc->n_bands, enc->dev_tables.as<Tables>(),
+                  enc->packed.as<uint8_t>(), dev_capacity);
+}
+
+// what the pack kernel may write: the caller's room behind the head, and never more than the packed buffer
+static size_t dev_room(const tf_png *enc, size_t capacity)
+{
+    const size_t room = capacity > enc->head.size() ? capacity - enc->head.size() : 0;
+    return room < enc->packed.bytes ? room : enc->packed.bytes;
+}
+
+// head, the bands' chunks and tail to the caller, if they fit; *n_bytes either way
+static int copy_out(tf_png *enc, const char *who, uint8_t *out, size_t capacity, size_t *n_bytes)
+{
+    const size_t head = enc->head.size(), chunks = enc->last_chunks, tail = enc->tail.size();
+    *n_bytes = head + chunks + tail;
+    TF_REQUIRE(*n_bytes <= capacity, "%s: the file has %zu bytes, the buffer %zu", who, *n_bytes, capacity);
+    memcpy(out, enc->head.data(), head);
+    TF_HIP(hipMemcpyAsync(out + head, enc->packed.p, chunks, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    memcpy(out + head + chunks, enc->tail.data(), tail);
+    return TF_OK;
+}
+
+TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, size_t capacity, size_t *n_bytes)
+{
+    TF_REQUIRE(enc && rgb_dev && n_bytes && (out || capacity == 0), "tf_png_encode_dev: null pointer");
+    *n_bytes = 0;
+    TF_HIP(hipMemsetAsync(enc->info.p, 0, enc->info.bytes, stream()));
+    TF_TRY(launch("png_filter", k_png_filter, dim3(enc->H), dim3(FILTER_BLOCK), 0, (const uint8_t *)rgb_dev, enc->W,
+                  enc->filtered.as<uint8_t>(), enc->rowsums.as<uint32_t>()));
+    DeflateArgs a;
+    a.filtered = enc->filtered.as<uint8_t>(), a.row_bytes = enc->row_bytes, a.H = enc->H, a.band_rows = enc->band_rows;
+    a.tables = enc->dev_tables.as<Tables>(), a.staging = enc->staging.as<uint8_t>(), a.slot_bytes = enc->slot;
+    a.lengths = enc->lengths.as<uint32_t>();
+    a.overflow = reinterpret_cast<uint32_t *>(enc->info.as<unsigned long long>() + 1);
+    TF_TRY(launch("png_deflate", k_png_deflate, dim3(enc->n_bands), dim3(WAVE), 0, a));
+    TF_TRY(launch("png_scan", k_png_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
+                  enc->n_bands, enc->info.as<unsigned long long>()));
+    TF_TRY(pack(enc, dev_room(enc, capacity)));
+    enc->last_chunks = 0;
+    TF_HIP(hipMemcpyAsync(enc->info_host, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(enc->rowsums_host, enc->rowsums.p, enc->rowsums.bytes, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    if (enc->info_host[1])
+        return set_error(TF_ERR_STATE, "tf_png_encode_dev: a band outgrew its staging slot of %u bytes", enc->slot);
+    // Adler-32 of the whole stream from the rows' sums: a row of L bytes moves s2 by L s1 + its weighted sum
+    uint64_t s1 = 1, s2 = 0;
+    for (int r = 0; r < enc->H; r++) {
+        s2 = (s2 + (enc->row_bytes % ADLER_BASE) * s1 + enc->rowsums_host[2 * r + 1]) % ADLER_BASE;
+        s1 = (s1 + enc->rowsums_host[2 * r]) % ADLER_BASE;
+    }
+    enc->tail.clear();
+    std::vector<uint8_t> last{0x01, 0x00, 0x00, 0xFF, 0xFF};
+    put_be32(last, (uint32_t)((s2 << 16) | s1));
+    put_chunk(enc->tail, enc->tables, "IDAT", last);
+    put_chunk(enc->tail, enc->tables, "IEND", {});
+    enc->last_chunks = (size_t)enc->info_host[0];
+    return copy_out(enc, "tf_png_encode_dev", out, capacity, n_bytes);
+}
+
+TF_API int tf_png_copy_last(tf_png *enc, uint8_t *out, size_t capacity, size_t *n_bytes)
+{
+    TF_REQUIRE(enc && n_bytes && (out || capacity == 0), "tf_png_copy_last: null pointer");
+    *n_bytes = 0;
+    if (!enc->last_chunks)
+        return set_error(TF_ERR_STATE, "tf_png_copy_last: nothing has been encoded");
+    TF_TRY(pack(enc, dev_room(enc, capacity)));
+    return copy_out(enc, "tf_png_copy_last", out, capacity, n_bytes);
+}
+
+TF_API int tf_png_encode(tf_png *enc, const uint8_t *rgb_host, uint8_t *out, size_t capacity, size_t *n_bytes)
+{
+    TF_REQUIRE(enc && rgb_host && n_bytes, "tf_png_encode: null pointer");
+    const size_t bytes = (size_t)enc->H * enc->W * 3;
+    if (!enc->upload.p)
+        TF_TRY(enc->upload.alloc(bytes));
+    TF_HIP(hipMemcpyAsync(enc->upload.p, rgb_host, bytes, hipMemcpyHostToDevice, stream()));
+    return tf_png_encode_dev(enc, enc->upload.p, out, capacity, n_bytes);
+}

@@ -69,13 +69,13 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
     return classmethod(from_args)
 
 
-def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None):
+def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_frames=False):
     from .compositor import LAYER_CLASSES, HipCompositor
 
     def from_args(cls, height, width, layer_configs, background_color="#ffffff"):
         if all(getattr(c, "classname", None) in LAYER_CLASSES for c in layer_configs):
             return HipCompositor.from_args(height, width, layer_configs, background_color=background_color,
-                                           lazy_frames=lazy_frames, jpeg_frames=jpeg_frames)
+                                           lazy_frames=lazy_frames, jpeg_frames=jpeg_frames, png_frames=png_frames)
         return original(height, width, layer_configs, background_color=background_color)
 
     return classmethod(from_args)
@@ -90,6 +90,18 @@ def _output_from_args(original, quality):
             return RawFramesOnly(original(path, width, height, framerate=framerate, vcodec=vcodec, execute=execute,
                                           replace=replace, initial_counter=initial_counter))
         return HipMjpegOutput(address[0], address[1], width, height, 30 if framerate is None else framerate, quality)
+
+    return classmethod(from_args)
+
+
+def _png_output_from_args(original):
+    from .output import HipFramesOutput, RawFramesOnly, png_template
+
+    def from_args(cls, path, width, height, framerate=None, vcodec="h264", execute=False, replace=False, initial_counter=0):
+        if not png_template(path):  # the reference's own output; it takes pixels, and says so if it is given a file
+            return RawFramesOnly(original(path, width, height, framerate=framerate, vcodec=vcodec, execute=execute,
+                                          replace=replace, initial_counter=initial_counter))
+        return HipFramesOutput(path, width, height, initial_counter, execute)
 
     return classmethod(from_args)
 
@@ -110,7 +122,7 @@ def _pixmap_from_args(original):
 
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
-            jpeg_frames: int | None = None) -> None:
+            jpeg_frames: int | None = None, png_frames: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -127,9 +139,16 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     (transflow_amd/jpeg.py: encoded on the device, only the file comes down and crosses to the output process), and
     VideoOutput.from_args (pipeline.py's output process) builds a HipMjpegOutput (transflow_amd/output.py) for `mjpeg...`
     paths; any other output is the reference's own and raises a TypeError that names this option when it is fed a
-    JpegFrame.  Not together with lazy_frames.  By default (None) nothing of this is touched."""
+    JpegFrame.  Not together with lazy_frames.  By default (None) nothing of this is touched.
+    png_frames: the compositors built for the pipeline return PngFrames from render() (transflow_amd/png.py: the
+    lossless file, made on the device), and VideoOutput.from_args builds a HipFramesOutput (transflow_amd/output.py) for
+    `%d` templates that end in `.png`; any other output is the reference's own and raises a TypeError that names this
+    option when it is fed a PngFrame.  Not together with jpeg_frames or lazy_frames.  By default nothing of this is
+    touched."""
     if jpeg_frames is not None and lazy_frames:
         raise ValueError("jpeg_frames and lazy_frames exclude each other")
+    if png_frames and (jpeg_frames is not None or lazy_frames):
+        raise ValueError("png_frames excludes jpeg_frames and lazy_frames")
     if flow and "flow" not in _saved:
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
@@ -141,11 +160,15 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from .compositor import bind_reference_data_layer
         bind_reference_data_layer()    # extra/control.py:155 asks isinstance(layer, DataLayer) of checkpointed layers
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
-        RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames)
+        RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames, bool(png_frames))
     if jpeg_frames is not None and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
         RefVideoOutput.from_args = _output_from_args(RefVideoOutput.from_args, int(jpeg_frames))
+    if png_frames and "output" not in _saved:
+        from transflow.output.video_output import VideoOutput as RefVideoOutput
+        _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
+        RefVideoOutput.from_args = _png_output_from_args(RefVideoOutput.from_args)
     if pixmaps and "pixmaps" not in _saved:
         from transflow.pixmap.source import PixmapSource as RefPixmapSource
         _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])

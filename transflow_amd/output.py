@@ -6,14 +6,20 @@ compositor encoded it on the device) is served as it is; a raw array is encoded 
 the same quality, subsampling and restart interval -- the same bytes by construction, and the output process never
 opens the GPU.  The reference's server and handler are used unchanged and imported only in `__enter__`: everything
 else here works without aiohttp, netifaces or cv2.
+
+`HipFramesOutput` is the same for the frame-sequence output (transflow/output/frames.py, `-o out/%05d.png`): a `PngFrame`
+(transflow_amd/png.py) is written to its file as it is, a raw array is encoded by Pillow on the host.
 """
 from __future__ import annotations
 
+import os
+import pathlib
 import re
 
 import numpy as np
 
 from .jpeg import JpegFrame, pillow_encode
+from .png import PngFrame, pillow_encode_png
 
 
 def default_restart_mcus() -> int:
@@ -124,9 +130,58 @@ def mjpeg_address(path):
     return (args[1] if len(args) == 2 else "localhost"), (int(args[0]) if args else 8080)
 
 
+FRAMES_PATH = re.compile(r"%(\d+)?d")                                         # video_output.py:55
+
+
+def png_template(path) -> bool:
+    """Whether an output path is a frame-sequence template (video_output.py:55-58) whose files are PNGs."""
+    return isinstance(path, str) and FRAMES_PATH.search(path) is not None and path.lower().endswith(".png")
+
+
+class HipFramesOutput:
+    """Same constructor, context-manager protocol and `feed` as transflow's FramesVideoOutput (frames.py:15-36): frame
+    n goes to `template % (initial_counter + n)`.  A PngFrame's bytes are the file; a raw array (what the pipeline
+    feeds when the output is a flow rendering) is encoded by Pillow here.  Never opens the GPU."""
+
+    def __init__(self, template: str, width: int, height: int, initial_counter: int = 0, execute: bool = False):
+        self.width, self.height = int(width), int(height)
+        self.template = template
+        self.directory = pathlib.Path(self.template).parent
+        self.execute = execute
+        self.counter = initial_counter
+
+    @property
+    def output_path(self):
+        """VideoOutput.output_path (video_output.py:62-64), which FramesVideoOutput inherits: no single file."""
+        return None
+
+    def __enter__(self):
+        if not os.path.isdir(self.directory):                # frames.py:25-26
+            os.makedirs(self.directory)
+        return self
+
+    def feed(self, frame):
+        if isinstance(frame, tuple):
+            frame = frame[0]
+        if tuple(frame.shape[:2]) != (self.height, self.width):
+            raise ValueError(f"the output is {self.height} x {self.width}, the frame {tuple(frame.shape[:2])}")
+        if isinstance(frame, JpegFrame):
+            raise TypeError("HipFramesOutput writes PNG files, not JPEG files: install(jpeg_frames=...) serves the mjpeg output only")
+        data = frame.tobytes() if isinstance(frame, PngFrame) else pillow_encode_png(np.asarray(frame))
+        with open(self.template % self.counter, "wb") as f:
+            f.write(data)
+        self.counter += 1
+
+    def __exit__(self, exc_type, exc_value, exc_traceback):
+        if self.execute:                                     # frames.py:35-36
+            from transflow.utils import startfile
+            startfile(self.directory.as_posix())
+
+
 class RawFramesOnly:
-    """Another output of the reference's, as it is, except that a JpegFrame fed to it is refused by name: those outputs
-    take pixels (`install(jpeg_frames=...)` is for the MJPEG output)."""
+    """Another output of the reference's, as it is, except that a JpegFrame or a PngFrame fed to it is refused by name:
+    those outputs take pixels (`install(jpeg_frames=...)` is for the MJPEG output, `install(png_frames=True)` for
+    `%d ... .png` templates)."""
 
     def __init__(self, output):
         self._output = output
@@ -143,6 +198,9 @@ class RawFramesOnly:
         if isinstance(first, JpegFrame):
             raise TypeError(f"{type(self._output).__name__} takes raw frames, not JPEG files: install(jpeg_frames=...) "
                             "serves the mjpeg output only")
+        if isinstance(first, PngFrame):
+            raise TypeError(f"{type(self._output).__name__} takes raw frames, not PNG files: install(png_frames=True) "
+                            "serves %d ... .png frame templates only")
         return self._output.feed(frame)
 
     def __getattr__(self, name):
