@@ -45,6 +45,11 @@ __global__ void __launch_bounds__(64) k_rate(float *out, int n, float seed)
             if (MODE == 22) asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(f[i]) : "v"(f[(i + 1) & 7]));
             if (MODE == 23) asm volatile("v_lshl_add_u64 %0, %0, 1, %1" : "+v"(d[i]) : "v"(d[(i + 1) & 7]));
             if (MODE == 24) asm volatile("v_cmp_gt_f32_e64 %1, %0, %0" : "+v"(f[i]), "=s"(mask));
+            // Philox's round (remap_common.h): both halves of a 32 x 32 product from one instruction (the carry-out pair is
+            // written and unused); a three-input xor as one v_bitop3_b32 (gfx950 has no v_xor3_b32) against two v_xor_b32
+            if (MODE == 25) asm volatile("v_mad_u64_u32 %0, %1, %2, %2, 0" : "+v"(d[i]), "=s"(mask) : "v"(f[(i + 1) & 7]));
+            if (MODE == 26) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(f[i]) : "v"(f[(i + 1) & 7]), "s"(n));
+            if (MODE == 27) asm volatile("v_xor_b32 %0, %0, %1\n\tv_xor_b32 %0, %2, %0" : "+v"(f[i]) : "v"(f[(i + 1) & 7]), "s"(n));
         }
     }
     float s = 0;
@@ -103,6 +108,9 @@ int main()
         run<22>("v_mul_lo_u32", out, w);
         run<23>("v_lshl_add_u64", out, w);
         run<24>("v_cmp_gt_f32 -> sgpr", out, w);
+        run<25>("v_mad_u64_u32", out, w);
+        run<26>("v_bitop3_b32 (xor3)", out, w);
+        run<27>("v_xor_b32 (x2)", out, w);
     }
     return 0;
 }

@@ -367,6 +367,284 @@ k_remap_step_px(const float2 *__restrict__ flow, const S *__restrict__ old, S *_
     }
 }
 
+// The layer state of a lane's four adjacent pixels in registers, and of one gathered pixel.  int32 x 4 and int16 x 4 are
+// unpacked to the reference's four integers; the one-word form stays the word: the step only ever copies a state, sets
+// its alpha to 1, or writes row, column and alpha 1 over it (and, with reset_source, a source index), and each of these
+// is the same statement on the word's fields (row and column below 8192, alpha one bit, source index below 32: what
+// state_can_pack admits), so nothing is unpacked but the row and column the pixmap gather needs.
+struct QuadInt {
+    using Reg = int4;
+    static __device__ __forceinline__ int alpha(Reg r) { return r.z; }
+    static __device__ __forceinline__ Reg with_alpha_one(Reg r)
+    {
+        r.z = 1;
+        return r;
+    }
+    static __device__ __forceinline__ Reg reset_to(Reg r, int i, int j)
+    {
+        r.x = i;
+        r.y = j;
+        r.z = 1;
+        return r;
+    }
+    static __device__ __forceinline__ Reg with_source(Reg r, int q)
+    {
+        r.w = q;
+        return r;
+    }
+    static __device__ __forceinline__ bool selected(Reg r) { return r.w == 0 && r.z != 0; }
+    static __device__ __forceinline__ int row(Reg r) { return r.x; }
+    static __device__ __forceinline__ int col(Reg r) { return r.y; }
+};
+struct QuadWord {
+    using Reg = unsigned;
+    static __device__ __forceinline__ int alpha(Reg r) { return (int)((r >> 26) & 1u); }
+    static __device__ __forceinline__ Reg with_alpha_one(Reg r) { return r | (1u << 26); }
+    static __device__ __forceinline__ Reg reset_to(Reg r, int i, int j)
+    {
+        return (r & 0xf8000000u) | (1u << 26) | ((unsigned)j << 13) | (unsigned)i; // 0 <= i, j < 8192
+    }
+    static __device__ __forceinline__ Reg with_source(Reg r, int q) { return (r & 0x07ffffffu) | ((unsigned)q << 27); }
+    static __device__ __forceinline__ bool selected(Reg r) { return (r >> 26) == 1u; } // alpha 1, source index 0
+    static __device__ __forceinline__ int row(Reg r) { return (int)(r & 0x1fffu); }
+    static __device__ __forceinline__ int col(Reg r) { return (int)((r >> 13) & 0x1fffu); }
+};
+template <typename S>
+struct Quad;
+template <>
+struct Quad<int4> : QuadInt {
+    static __device__ __forceinline__ Reg load1(const int4 *p, size_t t) { return p[t]; }
+    static __device__ __forceinline__ void load4(const int4 *p, size_t t, Reg r[4])
+    {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            r[k] = p[t + k];
+    }
+    static __device__ __forceinline__ void store4(int4 *p, size_t t, const Reg r[4])
+    {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            p[t + k] = r[k];
+    }
+};
+template <>
+struct Quad<short4s> : QuadInt {
+    static __device__ __forceinline__ Reg unpack(unsigned a, unsigned b)
+    {
+        return make_int4((short)(a & 0xffff), (short)(a >> 16), (short)(b & 0xffff), (short)(b >> 16));
+    }
+    static __device__ __forceinline__ uint2 pack(Reg d)
+    {
+        return make_uint2(((unsigned)d.x & 0xffffu) | ((unsigned)d.y << 16), ((unsigned)d.z & 0xffffu) | ((unsigned)d.w << 16));
+    }
+    static __device__ __forceinline__ Reg load1(const short4s *p, size_t t) { return state_load(p, t); }
+    static __device__ __forceinline__ void load4(const short4s *p, size_t t, Reg r[4]) // t a multiple of 4: 32 bytes, 16-aligned
+    {
+        const uint4 a = reinterpret_cast<const uint4 *>(p + t)[0], b = reinterpret_cast<const uint4 *>(p + t)[1];
+        r[0] = unpack(a.x, a.y);
+        r[1] = unpack(a.z, a.w);
+        r[2] = unpack(b.x, b.y);
+        r[3] = unpack(b.z, b.w);
+    }
+    static __device__ __forceinline__ void store4(short4s *p, size_t t, const Reg r[4])
+    {
+        const uint2 a = pack(r[0]), b = pack(r[1]), c = pack(r[2]), d = pack(r[3]);
+        reinterpret_cast<uint4 *>(p + t)[0] = make_uint4(a.x, a.y, b.x, b.y);
+        reinterpret_cast<uint4 *>(p + t)[1] = make_uint4(c.x, c.y, d.x, d.y);
+    }
+};
+template <>
+struct Quad<packed32> : QuadWord {
+    static __device__ __forceinline__ Reg load1(const packed32 *p, size_t t) { return p[t].v; }
+    static __device__ __forceinline__ void load4(const packed32 *p, size_t t, Reg r[4]) // t a multiple of 4: 16 bytes
+    {
+        const uint4 a = *reinterpret_cast<const uint4 *>(p + t);
+        r[0] = a.x;
+        r[1] = a.y;
+        r[2] = a.z;
+        r[3] = a.w;
+    }
+    static __device__ __forceinline__ void store4(packed32 *p, size_t t, const Reg r[4])
+    {
+        *reinterpret_cast<uint4 *>(p + t) = make_uint4(r[0], r[1], r[2], r[3]);
+    }
+};
+
+struct rgb12 { // four RGB pixels: 12 bytes at a 4-byte boundary
+    uint32_t a, b, c;
+};
+
+// The same step with FOUR ADJACENT pixels per lane: lane l of block b owns pixels 4 (b BLOCK + l) .. + 3 of a frame whose
+// width is a multiple of 4, so the four share a row.  What the pixel itself addresses then comes in 16-byte accesses
+// (flow: two; the one-word state, the reset mask, the alpha mask, the winner map: one each), the state leaves in one
+// store, and the four RGB pixels are 12 bytes at a 4-byte boundary: one store straight from registers, no LDS and no
+// barrier.  The row / column split and the row's clip bounds are computed once per lane.  What the SOURCE addresses --
+// the moved state, the source mask, the pixmap -- stays one gather per pixel.  Same statements per pixel, in the same
+// order, as k_remap_step_px, and the same phases.
+template <int C, typename S>
+__global__ void __launch_bounds__(BLOCK)
+k_remap_step_quad(const float2 *__restrict__ flow, const S *__restrict__ old, S *__restrict__ neu,
+                  const uint8_t *__restrict__ msrc, const uint8_t *__restrict__ mdst, const double *__restrict__ u,
+                  const float *__restrict__ reset_mask, const uint8_t *__restrict__ intro, uchar4 *__restrict__ rgba,
+                  const uint8_t *__restrict__ pixmap, const float *__restrict__ mask_alpha, uint8_t *__restrict__ image,
+                  int N, int H, int W, StepParams sp, int *err)
+{
+    using Q = Quad<S>;
+    using Reg = typename Q::Reg;
+    // (the XCD-aware renumbering of k_remap_step_px)
+    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7, qn = nb >> 3, rn = nb & 7;
+    const unsigned bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const int t = (int)(bid * BLOCK + threadIdx.x) * 4;
+    const bool live = t < N; // N is a multiple of 4: a lane's four pixels are all inside the frame or all outside
+    const int tc = live ? t : N - 4; // a dead lane of the last block reads a valid quad and stores nothing
+    // --- phase 1: what the pixels themselves address
+    float fx[4], fy[4];
+    int wv[4];
+    Reg me[4];
+    float rm[4] = {1.f, 1.f, 1.f, 1.f}, ma[4] = {0.f, 0.f, 0.f, 0.f};
+    double uv[4] = {0.0, 0.0, 0.0, 0.0};
+    uint32_t mdv = 0x01010101u;
+    if (sp.clip_flow == 2) {
+        const int4 w4 = *reinterpret_cast<const int4 *>(reinterpret_cast<const int *>(flow) + tc);
+        wv[0] = w4.x, wv[1] = w4.y, wv[2] = w4.z, wv[3] = w4.w;
+    } else {
+        const float4 a = reinterpret_cast<const float4 *>(flow + tc)[0], b = reinterpret_cast<const float4 *>(flow + tc)[1];
+        fx[0] = a.x, fy[0] = a.y, fx[1] = a.z, fy[1] = a.w;
+        fx[2] = b.x, fy[2] = b.y, fx[3] = b.z, fy[3] = b.w;
+    }
+    Q::load4(old, (size_t)tc, me);
+    if (sp.reset_random && reset_mask) {
+        const float4 a = *reinterpret_cast<const float4 *>(reset_mask + tc);
+        rm[0] = a.x, rm[1] = a.y, rm[2] = a.z, rm[3] = a.w;
+    }
+    if (sp.reset_random && u) {
+        const double2 a = reinterpret_cast<const double2 *>(u + tc)[0], b = reinterpret_cast<const double2 *>(u + tc)[1];
+        uv[0] = a.x, uv[1] = a.y, uv[2] = b.x, uv[3] = b.y;
+    }
+    if (mask_alpha) {
+        const float4 a = *reinterpret_cast<const float4 *>(mask_alpha + tc);
+        ma[0] = a.x, ma[1] = a.y, ma[2] = a.z, ma[3] = a.w;
+    }
+    if (mdst)
+        mdv = *reinterpret_cast<const uint32_t *>(mdst + tc);
+    // --- phase 2: the source pixels of the move (movement.py:20-48); one row / column split and one pair of row bounds per lane
+    const int i = (int)fast_div((uint32_t)tc, sp.div), j0 = tc - i * W;
+    const float ylo = (float)(-i), yhi = (float)(H - 1 - i);
+    bool moved[4];
+    int sidx[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        const int j = j0 + p;
+        float2 g;
+        if (sp.clip_flow == 2) {
+            const int src = wv[p] >= 0 ? wv[p] : tc + p;
+            const int si = (int)fast_div((uint32_t)src, sp.div);
+            g = make_float2((float)(src - si * W - j), (float)(si - i)); // source.py:359-360
+        } else {
+            g = make_float2(fx[p], fy[p]);
+        }
+        if (sp.clip_flow) {
+            g.x = clip_nan(g.x, (float)(-j), (float)(W - 1 - j));
+            g.y = clip_nan(g.y, ylo, yhi);
+        }
+        const long long off = flow_offset(g, W);
+        const long long s = tc + p + off;
+        const bool inside = s >= 0 && s < N;
+        if (off != 0 && !inside && live)
+            atomicOr(err, 1);
+        moved[p] = off != 0 && inside;
+        sidx[p] = moved[p] ? (int)s : tc + p;
+    }
+    // --- phase 3: what the sources address
+    Reg so[4];
+    uint8_t msv[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++)
+        so[p] = Q::load1(old, (size_t)sidx[p]);
+    if (msrc) {
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+            msv[p] = msrc[sidx[p]];
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+            msv[p] = 1;
+    }
+    // --- phase 4: the new states (move, then the random reset of reference.py:58-67), the gather addresses
+    Reg d[4];
+    bool sel[4];
+    size_t gidx[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        d[p] = me[p];
+        const bool me_filled = Q::alpha(me[p]) != 0, src_filled = Q::alpha(so[p]) != 0;
+        const bool ms = msv[p] != 0 && (sp.fl.transparent_can_move || src_filled);
+        const bool md = ((mdv >> (8 * p)) & 0xffu) != 0 && (sp.fl.to_empty || me_filled) && (sp.fl.to_filled || !me_filled);
+        if (moved[p] && ms && md) {
+            d[p] = so[p];
+            if (!sp.fl.transparent_can_move || src_filled)
+                d[p] = Q::with_alpha_one(d[p]);
+        }
+        if (sp.reset_random) {
+            const float thr = sp.factor * rm[p]; // factor * 1.f == factor where no mask is set
+            const double uu = u ? uv[p] : philox_uniform((uint32_t)(tc + p), sp.frame, sp.seed);
+            if (uu < (double)thr) {
+                d[p] = Q::reset_to(d[p], i, j0 + p);
+                if (sp.reset_source)
+                    for (int q = 0; q < sp.n_sources; q++)
+                        if (intro[(size_t)q * N + tc + p])
+                            d[p] = Q::with_source(d[p], q);
+            }
+        }
+        sel[p] = Q::selected(d[p]);
+        const int gi = min(max(Q::row(d[p]), 0), H - 1), gj = min(max(Q::col(d[p]), 0), W - 1);
+        gidx[p] = sel[p] ? (size_t)gi * W + gj : 0;
+    }
+    if (live)
+        Q::store4(neu, (size_t)t, d);
+    // --- phase 5: gather of source 0 (reference.py:94-105); pixels not selected keep their previous colour
+    const bool store_rgba = !(sp.rgba_dead && *sp.rgba_dead);
+    uchar4 px[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        if (C == 4) {
+            px[p] = reinterpret_cast<const uchar4 *>(pixmap)[gidx[p]];
+        } else {
+            const uint8_t *q = pixmap + gidx[p] * 3;
+            px[p] = make_uchar4(q[0], q[1], q[2], 1);
+        }
+    }
+    if (!(sel[0] && sel[1] && sel[2] && sel[3])) {
+        const uint4 prev = *reinterpret_cast<const uint4 *>(rgba + tc);
+        const uint32_t pv[4] = {prev.x, prev.y, prev.z, prev.w};
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+            if (!sel[p]) {
+                px[p] = make_uchar4(pv[p] & 0xff, (pv[p] >> 8) & 0xff, (pv[p] >> 16) & 0xff, C == 3 ? 0 : pv[p] >> 24);
+            }
+    }
+    uint32_t out[4], rgb[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        // --- Layer.render (layer.py:32-34)
+        if (mask_alpha)
+            px[p].w = (unsigned char)(int)(ma[p] * (float)px[p].w);
+        out[p] = (uint32_t)px[p].x | ((uint32_t)px[p].y << 8) | ((uint32_t)px[p].z << 16) | ((uint32_t)px[p].w << 24);
+        // --- Compositor.render over the background (compositor.py:35-39)
+        const uchar4 o = px[p].w != 0 ? px[p] : sp.bg;
+        rgb[p] = (uint32_t)o.x | ((uint32_t)o.y << 8) | ((uint32_t)o.z << 16);
+    }
+    if (live) {
+        if (store_rgba)
+            *reinterpret_cast<uint4 *>(rgba + t) = make_uint4(out[0], out[1], out[2], out[3]);
+        rgb12 v;
+        v.a = rgb[0] | (rgb[1] << 24);
+        v.b = (rgb[1] >> 8) | (rgb[2] << 16);
+        v.c = (rgb[2] >> 16) | (rgb[3] << 8);
+        *reinterpret_cast<rgb12 *>(image + (size_t)t * 3) = v;
+    }
+}
+
 __global__ void k_remap_clip_flow(float2 *flow, int W, int H)
 {
     int t = blockIdx.x * BLOCK + threadIdx.x;
@@ -503,6 +781,12 @@ static int step_dev_impl(tf_remap *L, tf_comp *comp, const void *flow_dev, int c
     sp.bg = comp->bg;
     sp.rgba_dead = rgba_dead;
     const int px_per_thread = (int)option(OPT_REMAP_PX);
+    // four adjacent pixels per thread (k_remap_step_quad): rows of whole quads, and every array a lane reads or writes
+    // 16 bytes of at once on a 16-byte boundary (the destination mask and the RGB frame: 4 bytes)
+    auto aligned = [](const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+    const bool quad = px_per_thread >= 4 && option(OPT_REMAP_QUAD) == 1 && L->W % 4 == 0 && aligned(flow_dev, 16) &&
+                      aligned(uniform_dev, 16) && aligned(L->reset_mask.p, 16) && aligned(L->mask_alpha.p, 16) &&
+                      aligned(L->mask_dst.p, 4) && aligned(L->rgba.p, 16) && aligned(comp->image.p, 4);
     dim3 block(BLOCK);
     auto run = [&](auto *old, auto *neu) {
         using S = typename std::remove_const<typename std::remove_pointer<decltype(old)>::type>::type;
@@ -514,6 +798,8 @@ static int step_dev_impl(tf_remap *L, tf_comp *comp, const void *flow_dev, int c
                           (const float *)L->mask_alpha.as<float>(), comp->image.as<uint8_t>(), L->N, L->H, L->W, sp,
                           L->err.as<int>());
         };
+        if (quad && aligned(old, 16) && aligned(neu, 16))
+            return channels == 4 ? go(k_remap_step_quad<4, S>, "remap_step_rgba", 4) : go(k_remap_step_quad<3, S>, "remap_step_rgb", 4);
         if (px_per_thread >= 4)
             return channels == 4 ? go(k_remap_step_px<4, S, 4>, "remap_step_rgba", 4)
                                  : go(k_remap_step_px<3, S, 4>, "remap_step_rgb", 4);

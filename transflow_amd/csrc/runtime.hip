@@ -44,6 +44,7 @@ static OptDef g_opts[OPT_COUNT] = {
     {"fb_exact_sums", 0, 0, 1},                // 1: the box window's sums in OpenCV's own order (bit-identical flow, ~5x slower; read per call)
     {"fb_chain", -1, -1, 1},                   // how a segmented march gets OpenCV's column sums: -1 the cheaper way per launch; 0 a pre-pass; 1 handed down inside the launch
     {"fb_segs", 0, 0, 64},                     // > 0: row segments per column of the marching kernels (0: chosen per launch)
+    {"remap_quad", 1, 0, 1},                   // 1: with remap_px = 4 and a frame width that is a multiple of 4, the remap step's four pixels per thread are adjacent (16-byte accesses, no LDS); 0: a block apart
 };
 long option(Opt which) { return g_opts[which].value; }
 
