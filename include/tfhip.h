@@ -718,6 +718,42 @@ int tf_png_copy_last(tf_png *enc, uint8_t *out, size_t capacity, size_t *n_bytes
 int tf_png_default_band_rows(int height, int width);
 int tf_png_code_lengths(uint8_t *out /* [286] */);
 
+/* ---- flow archive members deflated on the device (transflow_amd/csrc/flowzip.hip) --------
+ * The reference's flow export (transflow/pipeline.py:363-377, 505-506, output/numpy.py, output/zip.py) writes
+ * numpy.save(flow) into a deflated zip member.  tf_flowzip makes that member's raw deflate stream -- no zlib header, no
+ * Adler-32: what a zip holds -- and the CRC-32 of the uncompressed bytes where the flow is, so that only the member
+ * comes down.  The uncompressed stream is S = prefix ‖ data: the `.npy` header (host; a multiple of 64 bytes, as numpy
+ * aligns it, at most 4096; 0 for none) and the array's C-order bytes.  S is cut into bands of `band_bytes` that are
+ * coded side by side: "the same byte `distance` back" matches only (1 to 64), one literal/length code per member built
+ * on the device from the member's own token counts, a band stored where coding it would not make it smaller.
+ * DESIGN.md section 17 has the rules; any inflater returns S.
+ * band_bytes: a multiple of 64, 0 = the library's default.  The handle owns its count, scan and stream buffers, sized
+ * at creation for streams of up to max_stream_bytes (at most 2^31): the stream is never longer than
+ * N + 5 per stored block of 65535 bytes + 5. */
+typedef struct tf_flowzip tf_flowzip;
+int tf_flowzip_create(tf_flowzip **out, size_t max_stream_bytes, int band_bytes);
+void tf_flowzip_destroy(tf_flowzip *enc);
+int tf_flowzip_band_bytes(tf_flowzip *enc); /* the bytes of a band of this handle */
+int tf_flowzip_default_band_bytes(void);    /* what band_bytes = 0 stands for; no GPU call */
+/* data_dev: data_bytes in device memory, read where they are.  Queues its kernels on the calling thread's stream and
+   waits; the stream is then copied to `out` (host), *n_bytes is its size and *crc32 the CRC-32 of S.  A stream larger
+   than `capacity` returns TF_ERR_ARG with *n_bytes the size needed; `out` is then not written at all, and in no case is
+   anything written at or beyond out + capacity. */
+int tf_flowzip_encode_dev(tf_flowzip *enc, const uint8_t *prefix_host, size_t prefix_len, const void *data_dev, size_t data_bytes,
+                          int distance, uint8_t *out, size_t capacity, size_t *n_bytes, uint32_t *crc32);
+/* The same for data in host memory: uploaded to a buffer of the handle first. */
+int tf_flowzip_encode(tf_flowzip *enc, const uint8_t *prefix_host, size_t prefix_len, const void *data_host, size_t data_bytes,
+                      int distance, uint8_t *out, size_t capacity, size_t *n_bytes, uint32_t *crc32);
+/* The stream of the handle's last encode again, for a caller whose buffer was too small: it is still in the handle, no
+   kernel runs.  Same return values; TF_ERR_STATE if nothing has been encoded. */
+int tf_flowzip_copy_last(tf_flowzip *enc, uint8_t *out, size_t capacity, size_t *n_bytes);
+/* The lengths of the last member's literal/length code, 286 symbols (0: unused). */
+int tf_flowzip_last_lengths(tf_flowzip *enc, uint8_t *out /* [286] */);
+/* numpy.round(flow).astype(int) of n_values float32 (wide = 0) or float64 (wide = 1) values in device memory: rounded
+   half to even in the input's type, then converted; a value that does not fit, or a NaN, gives 0x8000000000000000 (what
+   numpy gives on x86-64).  out_dev: n_values int64.  Queued on the calling thread's stream; does not wait. */
+int tf_flow_round_i64_dev(const void *flow_dev, size_t n_values, int wide, void *out_dev);
+
 /* ---- batch-of-frames mode over the GPUs of one node ----------------------
  * With flags == 0 every Farnebäck pair is independent (transflow/flow/sources/cv.py:478-490: the
  * `flow=` argument is an output buffer only), so ranks take contiguous ranges of pairs and the path

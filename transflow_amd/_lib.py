@@ -230,6 +230,17 @@ PROTOTYPES = {
     "tf_png_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_png_default_band_rows": (_I, [_I, _I]),
     "tf_png_code_lengths": (_I, [_P]),
+    "tf_flowzip_create": (_I, [_PP, C.c_size_t, _I]),
+    "tf_flowzip_destroy": (None, [_P]),
+    "tf_flowzip_band_bytes": (_I, [_P]),
+    "tf_flowzip_default_band_bytes": (_I, []),
+    "tf_flowzip_encode_dev": (_I, [_P, _P, C.c_size_t, _P, C.c_size_t, _I, _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                   C.POINTER(C.c_uint32)]),
+    "tf_flowzip_encode": (_I, [_P, _P, C.c_size_t, _P, C.c_size_t, _I, _P, C.c_size_t, C.POINTER(C.c_size_t),
+                               C.POINTER(C.c_uint32)]),
+    "tf_flowzip_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_flowzip_last_lengths": (_I, [_P, _P]),
+    "tf_flow_round_i64_dev": (_I, [_P, C.c_size_t, _I, _P]),
     "tf_batch_unique_id": (_I, [_P]),
     "tf_batch_init": (_I, [_PP, _I, _I, _P]),
     "tf_batch_destroy": (None, [_P]),

@@ -266,6 +266,13 @@ class FlowRing:
             pass
 
 
+# While this is on, numpy.round / numpy.around of a DeviceFlow whose device copy is current (decimals 0, no `out`) is a
+# lazy flowzip.RoundedFlow: its `.astype(int)` is computed on the device and stays there for the archive writer
+# (transflow/pipeline.py:506), any other use of it gives what numpy.round gives.  Off by default:
+# dropin.install(device_flow_export=True) turns it on.
+DEVICE_ROUND = False
+
+
 class DeviceFlow(NDArrayOperatorsMixin):
     """float32 (H, W, 2) flow in HBM; see the module text."""
 
@@ -366,6 +373,12 @@ class DeviceFlow(NDArrayOperatorsMixin):
         return out[0] if isinstance(out[0], DeviceFlow) else res
 
     def __array_function__(self, func, types, args, kwargs):
+        if DEVICE_ROUND and func in (np.round, np.around) and not self._dirty and args and args[0] is self:
+            decimals = args[1] if len(args) > 1 else kwargs.get("decimals", 0)
+            if len(args) <= 2 and decimals == 0 and kwargs.get("out") is None and set(kwargs) <= {"decimals", "out"}:
+                from .flowzip import RoundedFlow
+                return RoundedFlow(self)
+
         def down(x):
             if isinstance(x, DeviceFlow):
                 return x._read()

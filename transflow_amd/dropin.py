@@ -27,6 +27,7 @@ import os
 import re
 
 _saved = {}
+_saved_export = []      # (the reference's pipeline module, its NumpyOutput, deviceflow.DEVICE_ROUND) while device_flow_export is on
 
 
 def _served_config(cv_config, horn_schunck: bool, lucas_kanade: bool = False, liteflownet=None) -> bool:
@@ -122,7 +123,7 @@ def _pixmap_from_args(original):
 
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
-            jpeg_frames: int | None = None, png_frames: bool = False) -> None:
+            jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -144,7 +145,11 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     lossless file, made on the device), and VideoOutput.from_args builds a HipFramesOutput (transflow_amd/output.py) for
     `%d` templates that end in `.png`; any other output is the reference's own and raises a TypeError that names this
     option when it is fed a PngFrame.  Not together with jpeg_frames or lazy_frames.  By default nothing of this is
-    touched."""
+    touched.
+    device_flow_export: the flow export (`--export-flow`, `--export-rounded-flow`) writes its `.flow.zip` through
+    archive.DeviceFlowArchiveWriter, put where pipeline.py:369 finds NumpyOutput: a DeviceFlow is deflated on the device
+    (transflow_amd/flowzip.py) and only the member comes down; and `numpy.round(flow).astype(int)` (pipeline.py:506) of a
+    DeviceFlow is computed on the device too (deviceflow.DEVICE_ROUND).  Host arrays are written as before."""
     if jpeg_frames is not None and lazy_frames:
         raise ValueError("jpeg_frames and lazy_frames exclude each other")
     if png_frames and (jpeg_frames is not None or lazy_frames):
@@ -169,6 +174,14 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
         RefVideoOutput.from_args = _png_output_from_args(RefVideoOutput.from_args)
+    if device_flow_export and not _saved_export:
+        import transflow.pipeline as ref_pipeline
+
+        from . import deviceflow
+        from .archive import DeviceFlowArchiveWriter
+        _saved_export.append((ref_pipeline, ref_pipeline.NumpyOutput, deviceflow.DEVICE_ROUND))
+        ref_pipeline.NumpyOutput = DeviceFlowArchiveWriter
+        deviceflow.DEVICE_ROUND = True
     if pixmaps and "pixmaps" not in _saved:
         from transflow.pixmap.source import PixmapSource as RefPixmapSource
         _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])
@@ -179,3 +192,8 @@ def uninstall() -> None:
     for key in list(_saved):
         cls, original = _saved.pop(key)
         cls.from_args = original
+    while _saved_export:
+        from . import deviceflow
+        module, original, switch = _saved_export.pop()
+        module.NumpyOutput = original
+        deviceflow.DEVICE_ROUND = switch
