@@ -57,9 +57,10 @@ def bound(n: int, band_bytes: int) -> int:
 
 
 # ---- the code --------------------------------------------------------------------------------------------------------------
-def huffman_lengths(weights) -> list:
+def huffman_lengths(weights, first_node: int = 1000) -> list:
     """Two-smallest merge on (weight, order) over the symbols of weight > 0: a leaf's order is its symbol, the k-th
-    internal node's 1000 + k.  The others get 0."""
+    internal node's 1000 + k.  The others get 0.  (`first_node` = -1000 is the other rule, internal nodes before leaves
+    of their weight: the tests use it to show that a case depends on the rule.)"""
     heap = [(int(w), s, (s,)) for s, w in enumerate(weights) if w > 0]
     heapq.heapify(heap)
     depth = [0] * len(weights)
@@ -69,17 +70,17 @@ def huffman_lengths(weights) -> list:
         b = heapq.heappop(heap)
         for s in a[2] + b[2]:
             depth[s] += 1
-        heapq.heappush(heap, (a[0] + b[0], 1000 + k, a[2] + b[2]))
+        heapq.heappush(heap, (a[0] + b[0], first_node + k, a[2] + b[2]))
         k += 1
     return depth
 
 
-def build_lengths(counts):
+def build_lengths(counts, first_node: int = 1000):
     """(lengths, repairs): while a length exceeds 15 every used weight becomes max(1, w >> 1) and the code is rebuilt."""
     weights = [int(c) for c in counts]
     repairs = 0
     while True:
-        lengths = huffman_lengths(weights)
+        lengths = huffman_lengths(weights, first_node)
         if max(lengths) <= 15:
             return lengths, repairs
         weights = [max(1, w >> 1) if w > 0 else 0 for w in weights]
@@ -199,6 +200,34 @@ class Trace:
     @property
     def stretch_lengths(self):
         return {n for _, _, n in self.stretches}
+
+    def _coded_stretches(self):
+        return [(start, n) for band, start, n in self.stretches if self.band_coded[band]]
+
+    @property
+    def phase_lengths(self):
+        """{(the place in its trip where a stretch starts, its length)}, over the bands k_fz_emit tokenises."""
+        return {(start % TRIP, n) for start, n in self._coded_stretches()}
+
+    @property
+    def match_258_lanes(self):
+        """The lanes that emit a match of 258: where the count reaches it."""
+        return {(start + 258 * j - 1) % TRIP for start, n in self._coded_stretches() for j in range(1, n // 258 + 1)}
+
+    @property
+    def pending_literals(self):
+        """{(lane, count)}: the one or two literals a stretch leaves, emitted at the lane behind its end."""
+        return {((start + n) % TRIP, n % 258) for start, n in self._coded_stretches() if n % 258 in (1, 2)}
+
+    @property
+    def ends_at_band_end(self):
+        """{(the band's bytes, the stretch's length)} of the stretches whose last byte is a coded band's last."""
+        out = set()
+        for band, start, n in self.stretches:
+            size = min(self.band_bytes, self.n - band * self.band_bytes)
+            if self.band_coded[band] and start + n == size:
+                out.add((size, n))
+        return out
 
     @property
     def across_trip(self):
@@ -415,6 +444,58 @@ def fibonacci_bytes(symbols: int) -> np.ndarray:
     return values[(np.arange(n, dtype=np.int64) * step) % n]
 
 
+def sweep_bytes(lengths, distance: int, seed: int) -> np.ndarray:
+    """For every n of `lengths` and every phase p of 0 .. 63: bytes that each differ from the byte `distance` before
+    until the position is p (mod 64), n bytes that equal it, and one that differs -- a stretch of exactly n that starts
+    at every place of a trip.  Sixteen byte values, so that a band of nothing but padding is still coded, not stored."""
+    out = [int(v) & 15 for v in noise_bytes(distance, seed)]
+    h = _hash(seed + 1, len(lengths) * TRIP * (TRIP + 1))
+    k = 0
+    for n in lengths:
+        for p in range(TRIP):
+            while len(out) % TRIP != p:
+                out.append((out[-distance] + 1 + int(h[k]) % 15) & 15)
+                k += 1
+            out.extend((out[-distance:] * (n // distance + 1))[:n])
+            out.append((out[-distance] + 1 + int(h[k]) % 15) & 15)
+            k += 1
+    return np.array(out, np.uint8)
+
+
+def band_end_bytes(length: int, n: int, gap: int, distance: int, seed: int) -> np.ndarray:
+    """`length` bytes of four values: bytes that differ from the byte `distance` before, then a stretch of n (none for
+    n = 0) that ends `gap` bytes before the last one."""
+    assert length - n - gap >= (distance if n else 0)
+    out = [int(v) & 3 for v in noise_bytes(distance, seed)][:length]
+    h = [int(v) % 3 for v in _hash(seed + 1, length)]
+    while len(out) < length - n - gap:
+        out.append((out[-distance] + 1 + h.pop()) & 3)
+    out.extend((out[-distance:] * (n // distance + 1))[:n])
+    while len(out) < length:
+        out.append((out[-distance] + 1 + h.pop()) & 3)
+    return np.array(out, np.uint8)
+
+
+BAND_END_STRETCHES = (1, 2, 3, 258, 259)
+
+
+def band_ends_bytes(band_bytes: int, last: int, last_n: int, last_gap: int, distance: int, seed: int) -> np.ndarray:
+    """Bands of exactly `band_bytes`: for each n of BAND_END_STRETCHES one whose stretch of n ends at its last byte, one
+    whose stretch ends a byte before, and one without a stretch; then a last band of `last` bytes whose stretch of
+    `last_n` ends `last_gap` bytes before its end."""
+    bands = [band_end_bytes(band_bytes, n, gap, distance, seed + 10 * i + gap)
+             for gap in (0, 1) for i, n in enumerate(BAND_END_STRETCHES)]
+    bands.append(band_end_bytes(band_bytes, 0, 0, distance, seed + 100))
+    bands.append(band_end_bytes(last, last_n, last_gap, distance, seed + 101))
+    return np.concatenate(bands)
+
+
+def equal_counts_bytes(times: int) -> np.ndarray:
+    """The 256 byte values `times` times each, in an order in which no byte equals its predecessor: every merge of the
+    code's construction is between equal weights."""
+    return np.tile(((np.arange(256) * 167 + 13) % 256).astype(np.uint8), times)
+
+
 def periodic_bytes(n: int, period: int, seed: int) -> np.ndarray:
     """`period` hashed bytes repeated: with that distance every band is one long stretch behind its first bytes."""
     return np.resize(noise_bytes(period, seed), n)
@@ -428,6 +509,29 @@ def npy_prefix(array: np.ndarray) -> bytes:
 
 
 EDGES = (2, 3, 258, 259, 260, 261, 516)
+SWEEP = (1, 2, 3, 4, 257, 258, 259, 260, 261, 515, 516, 517, 518, 774)
+SWEEP_DISTANCES = (1, 2, 3, 16, 63, 64)
+LAST_BAND = {"end": (2, 0), "before": (3, 1), "none": (0, 0)}          # the last band's stretch and the bytes behind it
+SWEEP_BAND = 5007 * 64                 # a multiple of 64 that holds a whole sweep: its phases are the band's
+FIBONACCI_DEEP = 20                    # the smallest fibonacci_bytes whose code, in one band, is halved three times
+
+_sweeps = {}
+
+
+def _sweep(distance: int) -> np.ndarray:
+    """sweep_bytes(SWEEP, distance, 50 + distance): made once, never written to."""
+    if distance not in _sweeps:
+        _sweeps[distance] = sweep_bytes(SWEEP, distance, 50 + distance)
+        _sweeps[distance].setflags(write=False)
+    return _sweeps[distance]
+
+
+def every_distance(distance: int) -> np.ndarray:
+    """The EDGES stretches at this distance: a few KB, one band of EVERY_DISTANCE_BAND."""
+    return stretch_bytes(EDGES, distance, 100 + distance)
+
+
+EVERY_DISTANCE_BAND = 4096
 
 # name: (the array's maker, band_bytes, distance, whether the stream is numpy.save's bytes or the array's alone)
 CASES = {
@@ -453,6 +557,16 @@ CASES = {
     "empty_npy_b64": (lambda: np.zeros(0, np.uint8), 64, 1, True),                           # two bands, both stored
     "noise_1025_bands_b64": (lambda: noise_bytes(1025 * 64 - 128 - 9, 17), 64, 1, True),
     "zeros_2049_bands_b64": (lambda: np.zeros(2049 * 64 - 128, np.uint8), 64, 1, True),
+    # every stretch length of SWEEP at every place of a trip, in one band and in bands that cut the stretches
+    **{f"sweep_d{d}": ((lambda d=d: _sweep(d)), SWEEP_BAND, d, False) for d in SWEEP_DISTANCES},
+    **{f"sweep_d{d}_b4096": ((lambda d=d: _sweep(d)), 4096, d, False) for d in SWEEP_DISTANCES},
+    # bands of 64 (mod 256) and of 0 (mod 256) bytes that end in a stretch, a byte behind one, or in none
+    **{f"ends_b320_last64_{v}": ((lambda n=n, g=g: band_ends_bytes(320, 64, n, g, 1, 30)), 320, 1, False)
+       for v, (n, g) in LAST_BAND.items()},
+    **{f"ends_b512_last256_{v}": ((lambda n=n, g=g: band_ends_bytes(512, 256, n, g, 16, 40)), 512, 16, False)
+       for v, (n, g) in LAST_BAND.items()},
+    "fibonacci_deep": (lambda: fibonacci_bytes(FIBONACCI_DEEP), 65536, 1, False),            # three repairs
+    "equal_counts": (lambda: equal_counts_bytes(16), 4096, 1, False),                        # every merge a tie
 }
 
 

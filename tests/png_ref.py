@@ -267,6 +267,27 @@ class Trace:
         self.bands = 0
         self.row_bytes = 0
         self.band_rows = 0
+        self.band_bytes = []            # per band
+
+    @property
+    def phase_lengths(self):
+        """{(the place in its trip where a stretch starts, its length)}."""
+        return {(start % TRIP, n) for _, start, n in self.runs}
+
+    @property
+    def match_258_lanes(self):
+        """The lanes that emit a match of 258: where the count reaches it."""
+        return {(start + 258 * j - 1) % TRIP for _, start, n in self.runs for j in range(1, n // 258 + 1)}
+
+    @property
+    def pending_literals(self):
+        """{(lane, count)}: the one or two literals a stretch leaves, emitted at the lane behind its end."""
+        return {((start + n) % TRIP, n % 258) for _, start, n in self.runs if n % 258 in (1, 2)}
+
+    @property
+    def ends_at_band_end(self):
+        """{(the band's bytes, the stretch's length)} of the stretches whose last byte is their band's last."""
+        return {(self.band_bytes[band], n) for band, start, n in self.runs if start + n == self.band_bytes[band]}
 
 
 def encode(image: np.ndarray, band_rows: int = 0, trace: Trace | None = None) -> bytes:
@@ -297,6 +318,7 @@ def encode(image: np.ndarray, band_rows: int = 0, trace: Trace | None = None) ->
         trace.longest_run = max((n for _, _, n in trace.runs), default=0)
         trace.bands = -(-h // rows)
         trace.row_bytes, trace.band_rows = 1 + 3 * w, rows
+        trace.band_bytes = [min(rows, h - first) * (1 + 3 * w) for first in range(0, h, rows)]
     return bytes(out)
 
 
@@ -369,6 +391,43 @@ def edge_image() -> np.ndarray:
     return row.reshape(1, -1, 3)
 
 
+SWEEP = (1, 2, 3, 4, 257, 258, 259, 260, 261, 515, 516, 517, 518, 774)
+SWEEP_PARTS = {"a": SWEEP[:8], "b": SWEEP[8:11], "c": SWEEP[11:]}     # a row holds at most 3 * 65535 + 1 bytes
+
+
+def sweep_image(lengths) -> np.ndarray:
+    """One row of bytes 0 and 1 whose filtered stream (None: a 0 and the row) holds, for every n of `lengths` and every
+    phase p of 0 .. 63, a stretch of exactly n that starts at a stream position p (mod 64): a 1, a 0 and n more zeros.
+    Between them 1 and 0 alternate; where the next phase has the other parity a single 2 takes the place of a 1.  Behind
+    a stretch that leaves one or two literals to lane 0 of the next trip, that trip is padded to its end, with a 1 last."""
+    s = [0, 1]                                                    # the filter type, the first byte of the row
+    for n in lengths:
+        for p in range(TRIP):
+            start = len(s) + 1 + (p - len(s) - 1) % TRIP          # the first place of phase p with room for the 0 before it
+            if (start - 1 - len(s)) % 2:
+                s.append(2)
+            while len(s) < start:
+                s.append(0 if s[-1] else 1)
+            assert s[-1] == 0 and s[-2] != 0
+            s.extend([0] * n + [1])
+            if len(s) % TRIP == 1 and n % 258 in (1, 2):          # lane 0 emits the pending zeros: they are prev_last's,
+                s.append(2)                                       # so this trip's last byte is made a 1
+                while len(s) % TRIP:
+                    s.append(0 if s[-1] else 1)
+                assert s[-1] == 1
+    while (len(s) - 1) % 3:
+        s.append(0 if s[-1] else 1)
+    return np.array(s[1:], np.uint8).reshape(1, -1, 3)
+
+
+def grey_tail_image(height: int, width: int, seed: int) -> np.ndarray:
+    """Noise whose row r ends in 1 + r % 3 pixels of the grey 90: whichever filter wins, the row ends in a stretch."""
+    image = noise_image(height, width, seed)
+    for r in range(height):
+        image[r, width - 1 - r % 3:] = 90
+    return image
+
+
 NOISE_SEED = 11
 
 # name: (the image's maker, band_rows)
@@ -386,6 +445,18 @@ CASES = {
     "2049x2_b1": (lambda: noise_image(2049, 2, 7), 1),
     "40x300_smear": (lambda: smear_image(40, 300, 8, 50, 8), 0),
     "1x523_edges": (edge_image, 0),
+    # every stretch length of SWEEP at every place of a trip
+    **{f"sweep_{part}": ((lambda part=part: sweep_image(SWEEP_PARTS[part])), 1) for part in SWEEP_PARTS},
+    # bands of 256 and 512 bytes: rows of 256 one and two to a band, four rows of 64 in one band
+    **{f"4x85_{kind}_b{b}": (maker, b) for b in (1, 2) for kind, maker in
+       (("noise", lambda: noise_image(4, 85, 21)), ("black", lambda: black_image(4, 85)),
+        ("tail", lambda: grey_tail_image(4, 85, 22)))},
+    "4x21_noise_b4": (lambda: noise_image(4, 21, 23), 4),
+    "4x21_black_b4": (lambda: black_image(4, 21), 4),
+    "4x21_tail_b4": (lambda: grey_tail_image(4, 21, 24), 4),
+    # rows of 65524 bytes, more than Adler-32's 65521
+    "2x21841_noise_b1": (lambda: noise_image(2, 21841, 25), 1),
+    "3x21841_black": (lambda: black_image(3, 21841), 0),
 }
 # the cases whose image is all noise: the staging bound is asserted on their files
 NOISE_CASES = [name for name in CASES if "noise" in name or name in ("1x1", "1x21", "1x22", "7x1", "1025x1_b1", "2049x2_b1")]

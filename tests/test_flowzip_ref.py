@@ -105,6 +105,126 @@ def test_merge_order_decides_between_equal_weights():
     assert lengths[:2] == [1, 1] and repairs == 0
 
 
+# ---- the sweeps: what the new cases reach (these are the conditions of the GPU tests) --------------------------------------
+def test_sweep_puts_every_length_at_every_phase_in_coded_bands():
+    """Per distance: every (phase, length) pair exactly once and nothing else, in one coded band whose phases are the
+    stream's; a match of 258 from each of the 64 lanes; one and two pending literals at lane 0 and at lane 1, where they
+    are the trip before's bytes.  Cut into bands of 4096 every band is still coded: k_fz_emit tokenises all of them."""
+    pairs = {(p, n) for n in R.SWEEP for p in range(R.TRIP)}
+    assert R.SWEEP_BAND % 64 == 0
+    for d in R.SWEEP_DISTANCES:
+        _, t = _trace(f"sweep_d{d}")
+        assert t.band_bytes == R.SWEEP_BAND >= t.n and t.bands == 1 and t.band_coded == [True], d
+        assert sorted((start % R.TRIP, n) for _, start, n in t.stretches) == sorted(pairs), d
+        assert t.phase_lengths == pairs and t.match_258_lanes == set(range(64)), d
+        assert {(0, 1), (0, 2), (1, 1), (1, 2)} <= t.pending_literals, d
+        S, cut = _trace(f"sweep_d{d}_b4096")
+        assert S == _trace(f"sweep_d{d}")[0] and cut.band_bytes == 4096 and cut.bands == -(-len(S) // 4096)
+        assert all(cut.band_coded), d
+        assert cut.cut_by_band >= 20 and cut.match_258_lanes == set(range(64)), d
+        assert {(0, 1), (0, 2), (1, 1), (1, 2)} <= cut.pending_literals, d
+    assert set(R.SWEEP_DISTANCES) == {1, 2, 3, 16, 63, 64}
+    assert R.SWEEP == (1, 2, 3, 4, 257, 258, 259, 260, 261, 515, 516, 517, 518, 774)
+
+
+def test_pending_literals_at_lane_0_differ_from_this_trips():
+    """A coder that took lane 0's pending literals from its own trip's lane 63 and 62 would go unnoticed where those
+    bytes are equal: at every distance some stretch that ends at a trip's last byte has them different."""
+    for d in R.SWEEP_DISTANCES:
+        S, t = _trace(f"sweep_d{d}")
+        found = 0
+        for _, start, n in t.stretches:
+            end = start + n
+            if end % R.TRIP == 0 and n % 258 in (1, 2) and end + R.TRIP <= len(S):
+                found += S[end - 1] != S[end + R.TRIP - 1]
+        assert found >= 1, d
+
+
+def test_every_distance_reaches_every_distance_symbol():
+    assert {R.distance_symbol(d) for d in range(1, 65)} == set(range(12))
+    extra = set()
+    for d in range(1, 65):
+        member = R.every_distance(d).tobytes()
+        assert len(member) <= R.EVERY_DISTANCE_BAND
+        t = R.trace(b"", member, R.EVERY_DISTANCE_BAND, d)
+        assert t.band_coded == [True] and set(R.EDGES) <= t.stretch_lengths, d
+        assert zlib.decompressobj(-15).decompress(t.stream) == member, d
+        hdist = (int.from_bytes(t.stream[:4], "little") >> 8) & 31        # behind BFINAL, BTYPE and HLIT
+        assert hdist == R.distance_symbol(d), d
+        extra.add((hdist, d - R.DIST_BASE[hdist]))
+    assert len(extra) == 64 and max(e for _, e in extra) == 15            # every value of every symbol's extra bits
+
+
+def test_golden_every_distance_streams_are_the_restatements():
+    with np.load(os.path.join(GOLDEN, "flowzip_every_distance.npz")) as z:
+        streams, ends = z["streams"].tobytes(), [0] + list(z["ends"])
+        assert int(z["band_bytes"]) == R.EVERY_DISTANCE_BAND and len(ends) == 65
+        for d in range(1, 65):
+            member = R.every_distance(d).tobytes()
+            stream, crc, _ = R.encode_stream(b"", member, R.EVERY_DISTANCE_BAND, d)
+            assert streams[ends[d - 1]:ends[d]] == stream, d
+            assert int(z["crcs"][d - 1]) == crc and int(z["sizes"][d - 1]) == len(member)
+
+
+def test_band_end_cases_end_stretches_at_and_before_the_last_byte():
+    """Bands of 320 (64 mod 256) and 512 (0 mod 256) bytes, all coded: a stretch of each of 1, 2, 3, 258 and 259 that
+    ends at the band's last byte -- end-of-block's lane then emits what it left -- one that ends a byte before, and a
+    band with no stretch.  The last band of 256 is coded too; one of 64 never is (the table header alone is 154 bytes),
+    so there it is k_fz_count whose end-of-block lane is alone in its trip."""
+    for band_bytes, last, d in ((320, 64, 1), (512, 256, 16)):
+        streams = set()
+        for variant, (last_n, last_gap) in R.LAST_BAND.items():
+            S, t = _trace(f"ends_b{band_bytes}_last{last}_{variant}")
+            streams.add(t.stream)
+            assert (t.band_bytes, t.distance, t.bands) == (band_bytes, d, 12) and t.n == 11 * band_bytes + last
+            assert all(t.band_coded[:11]) and t.band_coded[11] == (last == 256)
+            behind = {}                                                   # bytes behind a band's stretch: its lengths
+            for band, start, n in t.stretches:
+                size = min(band_bytes, t.n - band * band_bytes)
+                behind.setdefault(size - start - n, set()).add((size, n))
+            assert {(band_bytes, n) for n in R.BAND_END_STRETCHES} <= behind[0]
+            assert {(band_bytes, n) for n in R.BAND_END_STRETCHES} <= behind[1]
+            assert {(band_bytes, n) for n in R.BAND_END_STRETCHES} <= t.ends_at_band_end
+            assert [n for band, _, n in t.stretches if band == 10] == []
+            in_last = [(start, n) for band, start, n in t.stretches if band == 11]
+            assert in_last == ([(last - last_n - last_gap, last_n)] if last_n else []), variant
+            if last == 256 and variant == "end":
+                assert (256, 2) in t.ends_at_band_end
+        assert len(streams) == 3
+    assert 320 % 64 == 0 and 320 % 256 and 512 % 256 == 0
+
+
+def test_deep_fibonacci_needs_three_repairs_and_the_tie_rule():
+    """FIBONACCI_DEEP is the smallest fibonacci_bytes(k) whose code, in one band, is halved three times; on those passes
+    equal weights meet, and the other tie rule (internal node before leaf) would give other lengths."""
+    for k in range(16, R.FIBONACCI_DEEP + 1):
+        counts = np.bincount(R.fibonacci_bytes(k), minlength=R.N_SYMBOLS)
+        for start, n in R.stretches(R.fibonacci_bytes(k), 1):             # a stretch of one or two is literals
+            assert n <= 2
+        counts[R.END_OF_BLOCK] = 1
+        assert (R.build_lengths(counts)[1] >= 3) == (k == R.FIBONACCI_DEEP), k
+    S, t = _trace("fibonacci_deep")
+    assert t.repairs == 3 and t.band_coded == [True] and 10000 < len(S) < 100000 and max(t.lengths) <= 15
+    assert _trace("edges_d1")[1].repairs == 0 and _trace("edges_d1")[1].band_bytes == t.band_bytes   # its neighbour on the GPU
+    counts = np.bincount(np.frombuffer(S, np.uint8), minlength=R.N_SYMBOLS)
+    counts[R.END_OF_BLOCK] = 1
+    assert R.build_lengths(counts)[0] == t.lengths
+    other, other_repairs = R.build_lengths(counts, first_node=-1000)
+    assert other_repairs == 3 and other != t.lengths
+    weights = [int(c) for c in counts]
+    for _ in range(2):                                                     # the second pass alone already depends on it
+        weights = [max(1, w >> 1) if w else 0 for w in weights]
+    assert R.huffman_lengths(weights) != R.huffman_lengths(weights, first_node=-1000)
+
+
+def test_equal_counts_are_all_ties():
+    S, t = _trace("equal_counts")
+    assert np.bincount(np.frombuffer(S, np.uint8)).tolist() == [16] * 256 and t.stretches == [] and t.repairs == 0
+    assert sorted(set(t.lengths[:256])) == [8, 9] and t.lengths[256] == 9
+    assert t.lengths[:256] == sorted(t.lengths[:256], reverse=True)        # lower symbols merge first and sink deeper
+    assert t.band_coded == [False]                                         # 8 bits a byte: the table is what is compared
+
+
 @pytest.mark.parametrize("name", list(R.CASES))
 def test_golden_streams_are_the_restatements(name):
     """tools/capture_golden_flowzip.py wrote these from the restatement: a change of either shows here."""

@@ -54,9 +54,30 @@ def test_device_writes_the_restatements_stream_and_zlib_inflates_the_member(name
     assert again == got and crc_again == crc                               # integer counts: the same table every time
 
 
+def test_every_distance_codes_its_symbol_and_extra_bits():
+    """The EDGES stretches at each distance of 1 .. 64 through one encoder: all 12 distance symbols, every value of their
+    extra bits in the match entries, and the header's HDIST."""
+    from transflow_amd.flowzip import FlowZipEncoder
+    enc = FlowZipEncoder(R.EVERY_DISTANCE_BAND)
+    try:
+        for distance in range(1, 65):
+            array = R.every_distance(distance)
+            member = array.tobytes()
+            want, want_crc, want_lengths = R.encode_stream(b"", member, R.EVERY_DISTANCE_BAND, distance)
+            got, crc = enc.encode_host(b"", array, distance)
+            d = zlib.decompressobj(-15)                                    # whatever the restatement says
+            assert d.decompress(got) == member and d.eof and d.unused_data == b"", distance
+            assert crc == zlib.crc32(member), distance
+            assert got == want, f"distance {distance}: " + _first_difference(got, want)
+            assert crc == want_crc and enc.last_lengths() == want_lengths, distance
+    finally:
+        enc.close()
+
+
 def test_one_encoder_keeps_no_state_between_members():
     """A member of many coded bands, a short one at another distance, the first again: counts, tables or stream bytes left
-    in the handle would show."""
+    in the handle would show.  Then a member whose code is halved three times, one that needs no repair, the first again:
+    weights, ranks or parents left from the repair passes would show."""
     from transflow_amd.flowzip import FlowZipEncoder
     a, b = _case("i64_33x31_b256_d16"), _case("f64_7x9_b128_d16")
     enc = FlowZipEncoder(256)
@@ -68,11 +89,21 @@ def test_one_encoder_keeps_no_state_between_members():
         assert enc.encode_host(a[0], a[1], 16) == (a[4], a[5])
     finally:
         enc.close()
+    deep, plain = _case("fibonacci_deep"), _case("edges_d1")
+    assert deep[2] == plain[2] == 65536 and deep[3] == plain[3] == 1
+    enc = FlowZipEncoder(65536)
+    try:
+        for prefix, array, _, distance, want, want_crc, want_lengths in (deep, plain, deep):
+            assert enc.encode_host(prefix, array, distance) == (want, want_crc)
+            assert enc.last_lengths() == want_lengths
+    finally:
+        enc.close()
 
 
-@pytest.mark.parametrize("name", ["i64_33x31_b256_d16", "zeros_2049_bands_b64"])
+@pytest.mark.parametrize("name", ["i64_33x31_b256_d16", "zeros_2049_bands_b64", "ends_b512_last256_end"])
 def test_a_buffer_one_byte_short_is_refused_and_left_alone(name):
-    """2049 bands: the same contract where the offsets come from the second and third trips of k_fz_scan."""
+    """2049 bands: the same contract where the offsets come from the second and third trips of k_fz_scan.  A last band of
+    256 bytes: where end-of-block's lane is alone in its block of trips."""
     from transflow_amd import _lib
     lib = _lib.load()
     prefix, array, band_bytes, distance, want, want_crc, _ = _case(name)

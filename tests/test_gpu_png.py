@@ -2,6 +2,7 @@
 independently of the restatement -- against Pillow's decoder: the file holds the frame's pixels exactly."""
 import ctypes as C
 import io
+import zlib
 
 import numpy as np
 import pytest
@@ -45,6 +46,10 @@ def test_encoder_writes_the_restatements_file_and_pillow_reads_the_pixels(name):
     finally:
         enc.close()
     np.testing.assert_array_equal(_decode(got), image)                    # whatever the restatement says
+    chunks = png_ref.chunks(got)
+    assert all(crc == zlib.crc32(kind + payload) for kind, payload, crc in chunks)
+    idat = b"".join(payload for kind, payload, _ in chunks if kind == b"IDAT")
+    assert len(zlib.decompress(idat)) == image.shape[0] * (3 * image.shape[1] + 1)      # zlib checks the Adler-32
     assert got == want, _first_difference(got, want)
     if name in png_ref.NOISE_CASES:                                        # staging is sized by the bound: no file exceeds it
         bound = png_ref.file_bound(image.shape[0], image.shape[1], band_rows)
@@ -103,9 +108,10 @@ def test_bad_arguments_are_refused():
             PngEncoder(*args)
 
 
-@pytest.mark.parametrize("name", ["24x40_noise_b5", "2049x2_b1"])
+@pytest.mark.parametrize("name", ["24x40_noise_b5", "2049x2_b1", "4x85_tail_b1"])
 def test_a_buffer_one_byte_short_is_refused_and_left_alone(name):
-    """2049 bands: the same contract where k_png_pack's offsets come from the second and third trips of k_png_scan."""
+    """2049 bands: the same contract where k_png_pack's offsets come from the second and third trips of k_png_scan.
+    Bands of 256 bytes: where end-of-block's lane is alone in its block of trips."""
     from transflow_amd.png import PngEncoder
     image, band_rows, want = _case(name)
     enc = PngEncoder(image.shape[0], image.shape[1], band_rows)

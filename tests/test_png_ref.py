@@ -149,6 +149,64 @@ def test_cases_reach_the_edges_of_trips_rows_and_bands():
     assert widest > 64 * 8                                                 # costlier than stored bytes: noise does that
 
 
+# ---- the sweep, the band ends and the wide rows: the conditions of the GPU tests ----------------------------------------
+def test_sweep_images_are_filtered_with_none_and_hold_every_pair():
+    """A row of 0, 1 and a few 2: Up equals None, None wins, and the filtered stream is the designed one -- a 0 and the
+    row.  Over the three images every length of SWEEP starts at every stream position mod 64, exactly once; a match of
+    258 comes from each of the 64 lanes, one and two pending literals from lane 0 (prev_last's byte) and lane 1."""
+    assert sum(png_ref.SWEEP_PARTS.values(), ()) == png_ref.SWEEP
+    assert png_ref.SWEEP == (1, 2, 3, 4, 257, 258, 259, 260, 261, 515, 516, 517, 518, 774)
+    lanes, pending, at_lane_0 = set(), set(), set()
+    for part, lengths in png_ref.SWEEP_PARTS.items():
+        image, band_rows, t = _trace(f"sweep_{part}")
+        assert image.shape[0] == 1 and image.shape[1] <= 65535 and band_rows == 1 and t.bands == 1
+        assert t.filter_types == [0]
+        stream = png_ref.filtered(image)
+        assert stream == b"\x00" + image.tobytes()
+        values = np.bincount(np.frombuffer(stream, np.uint8))
+        assert len(values) == 3 and values[2] <= 65 * len(lengths)         # bytes 0 and 1; a 2 where the parity turns
+        assert sorted((s % png_ref.TRIP, n) for _, s, n in t.runs) == sorted((p, n) for n in lengths for p in range(64))
+        assert t.phase_lengths == {(p, n) for n in lengths for p in range(64)}
+        lanes |= t.match_258_lanes
+        pending |= t.pending_literals
+        if part != "a":
+            assert t.match_258_lanes == set(range(64))
+        for _, start, n in t.runs:                                         # lane 0's pending literals are the trip before's
+            if (start + n) % 64 == 0 and n % 258 in (1, 2):
+                assert stream[start + n - 1] == 0 and stream[start + n + 63] == 1
+                at_lane_0.add(n % 258)
+    assert lanes == set(range(64)) and at_lane_0 == {1, 2}
+    assert {(0, 1), (0, 2), (1, 1), (1, 2)} <= pending
+    assert {(0, 1), (0, 2), (1, 1), (1, 2)} <= _trace("sweep_a")[2].pending_literals
+
+
+def test_band_end_cases_have_bands_of_256_and_512_that_end_in_a_stretch():
+    """N % 256 == 0: end-of-block's lane is alone in a fresh block of four trips.  The black bands carry a stretch of
+    N - 1 into it (a match), the grey tails one of 2 (two pending literals of prev_last's byte) and of 5; the noise
+    bands end in no stretch."""
+    sizes = {"4x85_%s_b1": [256] * 4, "4x85_%s_b2": [512] * 2, "4x21_%s_b4": [256]}
+    for pattern, want in sizes.items():
+        for kind in ("noise", "black", "tail"):
+            assert _trace(pattern % kind)[2].band_bytes == want
+        assert _trace(pattern % "noise")[2].ends_at_band_end == set()
+        assert _trace(pattern % "black")[2].ends_at_band_end == {(want[0], want[0] - 1)}
+        assert (want[0], 2) in _trace(pattern % "tail")[2].ends_at_band_end
+    assert (256, 5) in _trace("4x85_tail_b1")[2].ends_at_band_end
+    assert _trace("4x85_black_b2")[2].runs == [(0, 1, 511), (1, 1, 511)] and 511 - 258 >= 3
+
+
+def test_wide_rows_are_longer_than_adlers_base():
+    """A row of 65524 bytes: the rows' sums are combined with row_bytes mod 65521 = 3, not with row_bytes."""
+    for name, bands in (("2x21841_noise_b1", 2), ("3x21841_black", 3)):
+        image, band_rows, t = _trace(name)
+        assert t.row_bytes == 65524 > 65521 and t.band_rows == 1 and t.bands == bands
+        stream = png_ref.filtered(image)
+        idat = b"".join(p for k, p, _ in png_ref.chunks(t.data) if k == b"IDAT")
+        assert zlib.decompress(idat) == stream
+        assert int.from_bytes(idat[-4:], "big") == zlib.adler32(stream) == png_ref.adler32(stream)
+    assert zlib.adler32(png_ref.filtered(_trace("3x21841_black")[0])) == (3 * 65524 % 65521) << 16 | 1
+
+
 # ---- the regression pin ---------------------------------------------------------------------------------------------------
 def test_golden_files_are_the_restatements():
     """tools/capture_golden_png.py wrote them: the code-length table, and per case its parameters and file."""
