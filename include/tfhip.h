@@ -749,10 +749,48 @@ int tf_flowzip_encode(tf_flowzip *enc, const uint8_t *prefix_host, size_t prefix
 int tf_flowzip_copy_last(tf_flowzip *enc, uint8_t *out, size_t capacity, size_t *n_bytes);
 /* The lengths of the last member's literal/length code, 286 symbols (0: unused). */
 int tf_flowzip_last_lengths(tf_flowzip *enc, uint8_t *out /* [286] */);
+/* The compressed bytes of each band of the handle's last encode, in stream order (they sum, with the five bytes of the
+   final block, to the stream's size): what a reader needs to inflate the bands side by side.  Read from the handle's
+   size words; no kernel runs.  The handle keeps no band count: it is inferred as the number of leading size words that sum
+   to the stream's size without the final block (every band has at least six bytes).  *n_bands is the band count; TF_ERR_STATE before the first encode, TF_ERR_ARG (with
+   *n_bands set) if `capacity` is smaller. */
+int tf_flowzip_last_band_sizes(tf_flowzip *enc, uint32_t *out, size_t capacity, size_t *n_bands);
 /* numpy.round(flow).astype(int) of n_values float32 (wide = 0) or float64 (wide = 1) values in device memory: rounded
    half to even in the input's type, then converted; a value that does not fit, or a NaN, gives 0x8000000000000000 (what
    numpy gives on x86-64).  out_dev: n_values int64.  Queued on the calling thread's stream; does not wait. */
 int tf_flow_round_i64_dev(const void *flow_dev, size_t n_values, int wide, void *out_dev);
+
+/* ---- flow archive members inflated on the device (transflow_amd/csrc/flowunzip.hip) --------
+ * The inverse of tf_flowzip for a member whose bands' compressed sizes are known (the archive's band index, DESIGN.md
+ * section 18): band b is bytes [offset_b, offset_b + size_b) of the member's raw deflate stream and must inflate, on its
+ * own, to exactly bytes [b * band_bytes, min(usize, (b + 1) * band_bytes)) of S = the `.npy` header ‖ the array.  A band
+ * is any sequence of RFC 1951 blocks with BFINAL 0 -- stored, fixed, dynamic -- whose matches stay inside the band's own
+ * output and whose last block ends on the range's last bit: tf_flowzip's bands and zlib's Z_FULL_FLUSH bands are such.
+ * Anything else is rejected per band with no access outside the band's ranges.  What follows the last band (the final
+ * block) is not decoded: the caller checks it.
+ * Bytes of S below `split` (a multiple of 64, at most 4096, 0 for none) come down to head_out_host; bytes from `split`
+ * on go to data + (index - split).  *crc32 is the CRC-32 of S, computed on the device. */
+typedef struct tf_flowunzip tf_flowunzip;
+int tf_flowunzip_create(tf_flowunzip **out, size_t max_stream_bytes, size_t max_bands);
+void tf_flowunzip_destroy(tf_flowunzip *h);
+/* stream_host: the compressed bytes (page-locked memory is copied at the link's rate); band_sizes_host: n_bands sizes.
+   data_dev: usize - split bytes of device memory, 4-byte aligned.  Queues on the calling thread's stream and waits.
+   TF_ERR_ARG (nothing is launched): split or band_bytes no multiple of 64 or out of range, sizes that sum past
+   stream_bytes, n_bands != ceil(usize / band_bytes), more than the handle was made for.  TF_ERR_STATE: a band was
+   rejected; *bad_band is the first such (0xFFFFFFFF otherwise) and the destination's contents are undefined.
+   A band's decoding time is bounded by its compressed bits, not by its output: every dynamic block costs three table
+   constructions in one lane, however little it holds.  A caller with untrusted input bounds the bands' sizes first
+   (transflow_amd/archive.py: at most 2 * band_bytes + 1024 bytes a band, band_bytes at most 1 MiB). */
+int tf_flowunzip_decode_dev(tf_flowunzip *h, const uint8_t *stream_host, size_t stream_bytes, const uint32_t *band_sizes_host,
+                            size_t n_bands, size_t band_bytes, size_t usize, size_t split, uint8_t *head_out_host, void *data_dev,
+                            uint32_t *crc32, uint32_t *bad_band);
+/* The same into host memory (through a buffer of the handle). */
+int tf_flowunzip_decode(tf_flowunzip *h, const uint8_t *stream_host, size_t stream_bytes, const uint32_t *band_sizes_host,
+                        size_t n_bands, size_t band_bytes, size_t usize, size_t split, uint8_t *head_out_host, void *data_host,
+                        uint32_t *crc32, uint32_t *bad_band);
+/* astype(float32) of n_values int64 in device memory: to nearest, ties to even, as numpy converts.  Queued on the
+   calling thread's stream; does not wait. */
+int tf_flow_i64_to_f32_dev(const void *src_dev, size_t n_values, void *dst_dev);
 
 /* ---- batch-of-frames mode over the GPUs of one node ----------------------
  * With flags == 0 every Farnebäck pair is independent (transflow/flow/sources/cv.py:478-490: the

@@ -240,7 +240,15 @@ PROTOTYPES = {
                                C.POINTER(C.c_uint32)]),
     "tf_flowzip_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_flowzip_last_lengths": (_I, [_P, _P]),
+    "tf_flowzip_last_band_sizes": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_flow_round_i64_dev": (_I, [_P, C.c_size_t, _I, _P]),
+    "tf_flowunzip_create": (_I, [_PP, C.c_size_t, C.c_size_t]),
+    "tf_flowunzip_destroy": (None, [_P]),
+    "tf_flowunzip_decode_dev": (_I, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tf_flowunzip_decode": (_I, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
+                                 C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tf_flow_i64_to_f32_dev": (_I, [_P, C.c_size_t, _P]),
     "tf_batch_unique_id": (_I, [_P]),
     "tf_batch_init": (_I, [_PP, _I, _I, _P]),
     "tf_batch_destroy": (None, [_P]),

@@ -792,6 +792,37 @@ TF_API int tf_flowzip_last_lengths(tf_flowzip *enc, uint8_t *out)
     return TF_OK;
 }
 
+TF_API int tf_flowzip_last_band_sizes(tf_flowzip *enc, uint32_t *out, size_t capacity, size_t *n_bands)
+{
+    TF_REQUIRE(enc && n_bands && (out || capacity == 0), "tf_flowzip_last_band_sizes: null pointer");
+    *n_bands = 0;
+    if (!enc->last_bytes)
+        return set_error(TF_ERR_STATE, "tf_flowzip_last_band_sizes: nothing has been encoded");
+    // the handle keeps no band count: the bands are those whose sizes sum to the stream without its final block (a band
+    // has at least six bytes, so the sum reaches that value once)
+    // (a block of the handle's size words at a time, so that nothing here allocates)
+    constexpr size_t CHUNK = 1024;
+    uint32_t words[CHUNK];
+    const size_t max_bands = (size_t)enc->max_bands;
+    size_t n = 0, sum = 0;
+    for (size_t base = 0; base < max_bands && sum + 5 < enc->last_bytes; base += CHUNK) {
+        const size_t count = max_bands - base < CHUNK ? max_bands - base : CHUNK;
+        TF_HIP(hipMemcpyAsync(words, enc->sizes.as<uint32_t>() + base, count * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
+        TF_HIP(hipStreamSynchronize(stream()));
+        for (size_t k = 0; k < count && sum + 5 < enc->last_bytes; k++, n++) {
+            const uint32_t size = words[k] & ~CODED_FLAG;
+            sum += size;
+            if (n < capacity)
+                out[n] = size;
+        }
+    }
+    if (sum + 5 != enc->last_bytes)
+        return set_error(TF_ERR_STATE, "tf_flowzip_last_band_sizes: the bands' sizes do not sum to the stream's");
+    *n_bands = n;
+    TF_REQUIRE(n <= capacity, "tf_flowzip_last_band_sizes: %zu bands, room for %zu", n, capacity);
+    return TF_OK;
+}
+
 TF_API int tf_flow_round_i64_dev(const void *flow_dev, size_t n_values, int wide, void *out_dev)
 {
     TF_REQUIRE((flow_dev && out_dev) || n_values == 0, "tf_flow_round_i64_dev: null pointer");

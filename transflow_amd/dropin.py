@@ -41,7 +41,8 @@ def _served_config(cv_config, horn_schunck: bool, lucas_kanade: bool = False, li
     return horn_schunck or not isinstance(cfg, HornSchunckConfig)
 
 
-def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None, motion_vectors=False):
+def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None, motion_vectors=False,
+                    device_flow_replay=False):
     from .flow import HipFlowSource
 
     def from_args(cls, flow_path, use_mvs=False, mask_path=None, kernel_path=None, cv_config=None,
@@ -65,7 +66,8 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
                             lock_expr=lock_expr, lock_mode=lock_mode)
         return HipFlowSource.from_args(flow_path, use_mvs, mask_path, kernel_path, cv_config, flow_filters, size,
                                        direction, seek_ckpt, seek_time, duration_time, repeat, lock_expr, lock_mode,
-                                       lucas_kanade=lucas_kanade, liteflownet=liteflownet)
+                                       lucas_kanade=lucas_kanade, liteflownet=liteflownet,
+                                       archive_device_inflate=device_flow_replay)
 
     return classmethod(from_args)
 
@@ -123,7 +125,8 @@ def _pixmap_from_args(original):
 
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
-            jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export: bool = False) -> None:
+            jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
+            device_flow_replay: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -149,7 +152,13 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     device_flow_export: the flow export (`--export-flow`, `--export-rounded-flow`) writes its `.flow.zip` through
     archive.DeviceFlowArchiveWriter, put where pipeline.py:369 finds NumpyOutput: a DeviceFlow is deflated on the device
     (transflow_amd/flowzip.py) and only the member comes down; and `numpy.round(flow).astype(int)` (pipeline.py:506) of a
-    DeviceFlow is computed on the device too (deviceflow.DEVICE_ROUND).  Host arrays are written as before."""
+    DeviceFlow is computed on the device too (deviceflow.DEVICE_ROUND).  Host arrays are written as before.
+    device_flow_export="indexed": the same, and the writer leaves a band index in the archive
+    (DeviceFlowArchiveWriter(index=True)); plain True keeps writing the bytes it wrote before.
+    device_flow_replay: the archive source FlowSource.from_args builds for a `.flow.zip` path is
+    archive.ArchiveFlowSource(device_inflate=True): members with a band index are inflated on the device
+    (transflow_amd/flowunzip.py) straight into the flow that is post-processed there; members without one, and every
+    member while a lock expression or a polar filter needs the raw flow on the host, are read as before."""
     if jpeg_frames is not None and lazy_frames:
         raise ValueError("jpeg_frames and lazy_frames exclude each other")
     if png_frames and (jpeg_frames is not None or lazy_frames):
@@ -158,7 +167,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
         RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet,
-                                                     motion_vectors)
+                                                     motion_vectors, bool(device_flow_replay))
     if compositor and "compositor" not in _saved:
         from transflow.compositor.compositor import Compositor as RefCompositor
 
@@ -180,7 +189,11 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from . import deviceflow
         from .archive import DeviceFlowArchiveWriter
         _saved_export.append((ref_pipeline, ref_pipeline.NumpyOutput, deviceflow.DEVICE_ROUND))
-        ref_pipeline.NumpyOutput = DeviceFlowArchiveWriter
+        if device_flow_export == "indexed":
+            import functools
+            ref_pipeline.NumpyOutput = functools.partial(DeviceFlowArchiveWriter, index=True)
+        else:
+            ref_pipeline.NumpyOutput = DeviceFlowArchiveWriter
         deviceflow.DEVICE_ROUND = True
     if pixmaps and "pixmaps" not in _saved:
         from transflow.pixmap.source import PixmapSource as RefPixmapSource

@@ -902,10 +902,11 @@ class HipFlowSource(FlowSource):
     def from_args(cls, flow_path, use_mvs: bool = False, mask_path=None, kernel_path=None, cv_config=None,
                   flow_filters=None, size=None, direction=None, seek_ckpt=None, seek_time=None,
                   duration_time=None, repeat: int = 1, lock_expr=None, lock_mode="stay", lucas_kanade: bool = False,
-                  liteflownet=None):
+                  liteflownet=None, archive_device_inflate: bool = False):
         """Same signature as FlowSource.from_args (source.py:365-411); `flow_path` may also be
         a frame provider object.  lucas_kanade: a config naming "lukas-kanade" is served (else it raises ValueError);
-        liteflownet: the network's weights (a path or a dict of arrays), with which a config naming "liteflownet" is.  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399);
+        liteflownet: the network's weights (a path or a dict of arrays), with which a config naming "liteflownet" is.  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399), with archive_device_inflate to its
+        device_inflate form (indexed members are inflated on the device, DESIGN.md section 18);
         use_mvs: codec motion vectors (source.py:400-402) go to MotionVectorFlowSource (transflow_amd/motionvectors.py),
         `flow_path` being a video path for PyAV (`avformat::path` as the reference splits it) or a vector provider."""
         common = dict(direction=direction, mask_path=mask_path, kernel_path=kernel_path, flow_filters=flow_filters,
@@ -913,7 +914,7 @@ class HipFlowSource(FlowSource):
                       lock_expr=lock_expr, lock_mode=lock_mode)
         if isinstance(flow_path, str) and flow_path.split("::")[-1].endswith(".flow.zip"):
             from .archive import ArchiveFlowSource
-            return ArchiveFlowSource.Builder(flow_path.split("::")[-1], **common)
+            return ArchiveFlowSource.Builder(flow_path.split("::")[-1], device_inflate=archive_device_inflate, **common)
         if use_mvs:                                        # source.py:381-384, 400-402
             from .motionvectors import MotionVectorFlowSource
             avformat = None

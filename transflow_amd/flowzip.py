@@ -11,7 +11,11 @@ An encoder is anything with
     encode_host(prefix: bytes, array: numpy.ndarray, distance: int) -> (stream: bytes, crc32: int)
     encode_device(prefix: bytes, dev_ptr: int, nbytes: int, distance: int) -> (stream: bytes, crc32: int)
 
-(and `close()`): tests/flowzip_ref.py has one in numpy, for writing whole archives without a GPU.
+(and `close()`): tests/flowzip_ref.py has one in numpy, for writing whole archives without a GPU.  An encoder may also have
+
+    last_band_sizes() -> [int]      the compressed bytes of each band of the last encode, in stream order
+
+which is what `DeviceFlowArchiveWriter(index=True)` writes into the archive's band index.
 
 `RoundedFlow` and `DeviceInt64Flow` are what `numpy.round(flow)` and `numpy.round(flow).astype(int)` are while
 `deviceflow.DEVICE_ROUND` is on: the rounding runs on the device (tf_flow_round_i64_dev) and its int64 values stay there
@@ -104,6 +108,15 @@ class FlowZipEncoder:
         out = (C.c_uint8 * 286)()
         self._check(self._lib.tf_flowzip_last_lengths(self._h, out))
         return list(out)
+
+    def last_band_sizes(self) -> list:
+        """The compressed bytes of each band of the last encode (tf_flowzip_last_band_sizes: read from the handle, no
+        kernel runs); with the final block's five bytes they sum to the stream's length."""
+        n = C.c_size_t()
+        room = max(1, -(-max(1, self._room) // self.band_bytes))
+        out = (C.c_uint32 * room)()
+        self._check(self._lib.tf_flowzip_last_band_sizes(self._h, out, room, C.byref(n)))
+        return list(out[:n.value])
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
