@@ -457,7 +457,7 @@ CASES = {
     "chroma_s0_q50": (96, 96, ("directed_chroma", 0), 50, 4),
     "32x48_binary_q100": (32, 48, ("binary_noise", 129), 100, 2),      # the fattest MCUs: 600 bytes, ten trips of the flush
     "32x64_chroma_checker_q100": (32, 64, "chroma_checker", 100, 4),   # chroma DC categories 10 and 11
-    # interval counts around k_jpeg_scan's 1024 per trip
+    # interval counts around k_slot_scan's 1024 per trip
     "512x512_r1": (512, 512, "formula", 50, 1),                         # 1024: one full trip
     "16x16400_r1": (16, 16400, "formula", 50, 1),                       # 1025: one element in the second
     "730x725_r1": (730, 725, "formula", 50, 1),                         # 46 x 46 = 2116: three trips, ragged edges

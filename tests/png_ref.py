@@ -20,7 +20,7 @@ import numpy as np
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 BAND_BYTES = 8192                      # the default band holds at least this much of the filtered stream
 TRIP = 64                              # the bytes a wave of the device's coder takes at a time
-SCAN_CHUNK = 1024                      # the bands k_png_scan sums per trip
+SCAN_CHUNK = 1024                      # the bands k_slot_scan sums per trip
 
 # RFC 1951 3.2.5: length symbol 257 + k stands for LENGTH_BASE[k] .. with LENGTH_EXTRA[k] extra bits
 LENGTH_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]

@@ -1,7 +1,7 @@
 """The Python restatement of the band inflater (tests/flowunzip_ref.py) against zlib, band by band;
 what its cases reach, by its own trace; the band index in archives written without a GPU; and the decoder's shared
-host/device core (transflow_amd/csrc/flowunzip_common.h) run on the CPU under the sanitizers, verdict by verdict.  No GPU:
-tests/test_gpu_flowunzip.py holds the device to the restatement."""
+host/device core (transflow_amd/csrc/flowunzip_common.h) run on the CPU under the sanitizers, verdict by verdict, and the
+codecs' shared CRC-32 (crc32_common.h) likewise.  No GPU: tests/test_gpu_flowunzip.py holds the device to the restatement."""
 import io
 import os
 import shutil
@@ -210,11 +210,10 @@ def _corpus():
     return cases
 
 
-def test_host_check_program(tmp_path):
-    """tools/flowunzip_host_check.cpp -- the machine the device's lane 0 runs, with every buffer a heap block of the size
-    the decoder is entitled to -- over the whole valid and malformed corpus: no sanitizer report, and every verdict and
-    CRC-32 the restatement's."""
-    source = os.path.join(ROOT, "tools", "flowunzip_host_check.cpp")
+def _run_host_check(tmp_path, source_name, corpus_lines):
+    """tools/<source_name> built with the sanitizers by the first host compiler whose program runs, and run over the
+    corpus: its output, after no sanitizer report."""
+    source = os.path.join(ROOT, "tools", source_name)
     flags = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
     program = None
     for compiler in ("g++", "clang++", "c++"):
@@ -228,15 +227,23 @@ def test_host_check_program(tmp_path):
             break
     if program is None:
         pytest.skip("no host compiler here builds a program that runs with -fsanitize=address,undefined")
-    cases = _corpus()
     corpus = tmp_path / "corpus.txt"
-    corpus.write_text("\n".join(U.corpus_lines(cases)) + "\n")
+    corpus.write_text("\n".join(corpus_lines) + "\n")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     run = subprocess.run([program, str(corpus)], capture_output=True, text=True, env=env)
     assert run.returncode == 0, run.stderr[-4000:]
     assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-4000:]
+    return run.stdout
+
+
+def test_host_check_program(tmp_path):
+    """tools/flowunzip_host_check.cpp -- the machine the device's lane 0 runs, with every buffer a heap block of the size
+    the decoder is entitled to -- over the whole valid and malformed corpus: no sanitizer report, and every verdict and
+    CRC-32 the restatement's."""
+    cases = _corpus()
+    stdout = _run_host_check(tmp_path, "flowunzip_host_check.cpp", U.corpus_lines(cases))
     got = {}
-    for line in run.stdout.splitlines():
+    for line in stdout.splitlines():
         name, verdict, crc = line.split()
         got[name] = (int(verdict), int(crc))
     want = {}
@@ -245,6 +252,29 @@ def test_host_check_program(tmp_path):
         for band, n in enumerate(sizes):
             data, reason, _ = _inflate(stream, offs[band], n, min(band_bytes, usize - band * band_bytes))
             want["%s/%d" % (name, band)] = (0, zlib.crc32(data)) if data is not None else (U.REJECT_NUMBER[reason], 0)
+    assert len(got) == len(want)
+    wrong = {k: (got.get(k), v) for k, v in want.items() if got.get(k) != v}
+    assert not wrong, sorted(wrong.items())[:10]
+
+
+CRC_LENGTHS = [0, 1, 2, 3, 4, 5, 63, 64, 65, 127, 128, 129, *range(252, 261), 4095, 4096, 4097, 65535, 65539]
+
+
+def test_crc32_host_check_program(tmp_path):
+    """tools/crc32_host_check.cpp -- the CRC-32 the device codecs share (transflow_amd/csrc/crc32_common.h), a wave's lanes
+    done by a loop -- over random and all-zero messages of the lengths where the slices change shape: no sanitizer
+    report, and the table's value, the 64 plain slices', the 64 whole-dword slices' and the two bands' all zlib's."""
+    rng = np.random.default_rng(20)
+    cases = {}
+    for n in CRC_LENGTHS:
+        cases["random.%d" % n] = rng.integers(0, 256, n, dtype=np.uint8).tobytes()
+        cases["zeros.%d" % n] = bytes(n)
+    stdout = _run_host_check(tmp_path, "crc32_host_check.cpp", ["%s %s" % (name, data.hex() or "-") for name, data in cases.items()])
+    got = {}
+    for line in stdout.splitlines():
+        name, *values = line.split()
+        got[name] = [int(v) for v in values]
+    want = {name: [zlib.crc32(data)] * 4 for name, data in cases.items()}
     assert len(got) == len(want)
     wrong = {k: (got.get(k), v) for k, v in want.items() if got.get(k) != v}
     assert not wrong, sorted(wrong.items())[:10]

@@ -142,7 +142,7 @@ def test_a_buffer_one_byte_short_is_refused_and_left_alone():
 
 
 def test_a_buffer_one_byte_short_is_refused_past_the_first_scan_chunk():
-    """The same contract where k_jpeg_pack's offsets come from the second and third trips of k_jpeg_scan."""
+    """The same contract where k_jpeg_pack's offsets come from the second and third trips of k_slot_scan."""
     from transflow_amd.jpeg import JpegEncoder
     image, quality, restart, expected = _case("730x725_r1")
     enc = JpegEncoder(730, 725, quality, restart)
@@ -201,7 +201,7 @@ def _intervals(scan: bytes):
 
 
 def test_every_interval_is_where_libjpeg_has_it_across_scan_chunks():
-    """2116 intervals: k_jpeg_scan carries its total over two chunk boundaries and ends on a partial chunk.  Through
+    """2116 intervals: k_slot_scan carries its total over two chunk boundaries and ends on a partial chunk.  Through
     the C ABI, interval by interval, so that a lost carry reads as `interval 1024`, not as a byte offset."""
     from transflow_amd import _lib
     from transflow_amd.device import DevBuffer

@@ -110,7 +110,7 @@ def test_bad_arguments_are_refused():
 
 @pytest.mark.parametrize("name", ["24x40_noise_b5", "2049x2_b1", "4x85_tail_b1"])
 def test_a_buffer_one_byte_short_is_refused_and_left_alone(name):
-    """2049 bands: the same contract where k_png_pack's offsets come from the second and third trips of k_png_scan.
+    """2049 bands: the same contract where k_png_pack's offsets come from the second and third trips of k_slot_scan.
     Bands of 256 bytes: where end-of-block's lane is alone in its block of trips."""
     from transflow_amd.png import PngEncoder
     image, band_rows, want = _case(name)

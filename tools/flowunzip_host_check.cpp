@@ -9,6 +9,7 @@
 // CORPUS: one case per line, `name out_bytes hex-of-the-band's-compressed-bytes` (`-` for no bytes).  Prints one line
 // per case: `name verdict crc32`, the verdict being the Reject number (0: inflated whole), the CRC-32 that of the
 // output (0 for a rejected band).
+#include "../transflow_amd/csrc/crc32_common.h"
 #include "../transflow_amd/csrc/flowunzip_common.h"
 
 #include <cstdio>
@@ -21,17 +22,6 @@
 #include <vector>
 
 using namespace tf::flowunzip;
-
-static uint32_t crc32_of(const uint8_t *p, size_t n)
-{
-    uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; i++) {
-        c ^= p[i];
-        for (int k = 0; k < 8; k++)
-            c = (c & 1) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-    }
-    return ~c;
-}
 
 // the whole band: its verdict; out: out_bytes
 static uint32_t inflate_band(const uint8_t *stream, uint32_t size, uint8_t *out, uint32_t out_bytes)
@@ -93,6 +83,8 @@ int main(int argc, char **argv)
         fprintf(stderr, "cannot read %s\n", argv[1]);
         return 2;
     }
+    tf::Crc32Consts consts;
+    tf::make_crc32_consts(consts);
     std::string line;
     while (std::getline(in, line)) {
         std::istringstream fields(line);
@@ -107,7 +99,7 @@ int main(int argc, char **argv)
         for (size_t i = 0; i < size; i++)
             stream[i] = (uint8_t)strtoul(hex.substr(2 * i, 2).c_str(), nullptr, 16);
         const uint32_t verdict = inflate_band(stream, (uint32_t)size, out, (uint32_t)out_bytes);
-        printf("%s %u %u\n", name.c_str(), verdict, verdict == R_OK ? crc32_of(out, out_bytes) : 0u);
+        printf("%s %u %u\n", name.c_str(), verdict, verdict == R_OK ? tf::crc32_bytes(consts, out, out_bytes) : 0u);
         free(stream), free(out);
     }
     return 0;

@@ -18,19 +18,14 @@
 #include "flowunzip_common.h"
 
 #include "common.h"
+#include "crc32_common.h"
 
 namespace tf {
 namespace flowunzip {
 
 constexpr int WAVE = 64;
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
 constexpr uint32_t MAX_SPLIT = 4096;
 constexpr uint32_t NO_BAND = 0xFFFFFFFFu;
-
-struct Consts {
-    uint32_t crc[256]; // CRC-32, reflected
-    uint32_t x2n[32];  // x^(2^k) mod the polynomial
-};
 
 struct Member {
     const uint8_t *stream;   // the compressed bytes, stream_bytes of them
@@ -140,41 +135,13 @@ __global__ __launch_bounds__(WAVE) void k_fu_inflate(const Member m, uint32_t *_
 }
 
 // ---- CRC-32 ------------------------------------------------------------------------------------------------------------
-// a(x) b(x) mod the polynomial, bit 31 the coefficient of x^0
-__host__ __device__ inline uint32_t multmodp(uint32_t a, uint32_t b)
-{
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0)
-                break;
-        }
-        m >>= 1;
-        b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-
-// x^(8 n) mod the polynomial
-__device__ __forceinline__ uint32_t x8nmodp(uint32_t n, const uint32_t *__restrict__ x2n)
-{
-    uint32_t p = 1u << 31;
-    for (int k = 3; n; n >>= 1, k++)
-        if (n & 1)
-            p = multmodp(x2n[k & 31], p);
-    return p;
-}
-
-__global__ __launch_bounds__(WAVE) void k_fu_crc(const Member m, const Consts *__restrict__ consts, uint32_t *__restrict__ band_crc)
+__global__ __launch_bounds__(WAVE) void k_fu_crc(const Member m, const Crc32Consts *__restrict__ consts, uint32_t *__restrict__ band_crc)
 {
     __shared__ uint32_t s_crc[256];
     __shared__ uint32_t s_x2n[32];
     const int lane = threadIdx.x;
-    for (int w = lane; w < 256; w += WAVE)
-        s_crc[w] = consts->crc[w];
-    if (lane < 32)
-        s_x2n[lane] = consts->x2n[lane];
+    crc32_stage_table(s_crc, consts, lane, WAVE);
+    crc32_stage_x2n(s_x2n, consts, lane);
     __syncthreads();
     const uint32_t first = blockIdx.x * m.band_bytes;
     const uint32_t n = min(m.band_bytes, m.usize - first);
@@ -185,16 +152,11 @@ __global__ __launch_bounds__(WAVE) void k_fu_crc(const Member m, const Consts *_
         uint32_t v = *reinterpret_cast<const uint32_t *>(place(m, first + j));
 #pragma unroll
         for (int k = 0; k < 4; k++, v >>= 8)
-            c = s_crc[(c ^ v) & 0xFF] ^ (c >> 8);
+            c = crc32_update(c, v, s_crc);
     }
     for (; j < end; j++)
-        c = s_crc[(c ^ *place(m, first + j)) & 0xFF] ^ (c >> 8);
-    c = ~c; // the slice's own CRC-32 (of no bytes: 0)
-    if (c && end < n)
-        c = multmodp(x8nmodp(n - end, s_x2n), c);
-#pragma unroll
-    for (int d = WAVE / 2; d; d >>= 1)
-        c ^= __shfl_xor(c, d, WAVE);
+        c = crc32_update(c, *place(m, first + j), s_crc);
+    c = crc32_wave_xor(crc32_shift(~c, n - end, s_x2n)); // ~c: the slice's own CRC-32 (of no bytes: 0)
     if (lane == 0)
         band_crc[blockIdx.x] = c;
 }
@@ -203,21 +165,19 @@ constexpr int FINISH_BLOCK = 1024;
 // info[0]: the CRC-32 of S, info[1]: the first rejected band (NO_BAND: none), info[2]: why
 __global__ __launch_bounds__(FINISH_BLOCK) void k_fu_finish(const uint32_t *__restrict__ band_crc, const uint32_t *__restrict__ status,
                                                             uint32_t n_bands, uint32_t band_bytes, uint32_t usize,
-                                                            const Consts *__restrict__ consts, uint32_t *__restrict__ info)
+                                                            const Crc32Consts *__restrict__ consts, uint32_t *__restrict__ info)
 {
     __shared__ uint32_t s_x2n[32];
     __shared__ uint32_t s_crc, s_bad;
     const int tid = threadIdx.x;
-    if (tid < 32)
-        s_x2n[tid] = consts->x2n[tid];
+    crc32_stage_x2n(s_x2n, consts, tid);
     if (tid == 0)
         s_crc = 0, s_bad = NO_BAND;
     __syncthreads();
     uint32_t crc = 0, bad = NO_BAND;
     for (uint32_t i = tid; i < n_bands; i += FINISH_BLOCK) {
         const unsigned long long end = min((unsigned long long)usize, ((unsigned long long)i + 1) * band_bytes);
-        const uint32_t c = band_crc[i];
-        crc ^= (c && end < usize) ? multmodp(x8nmodp(usize - (uint32_t)end, s_x2n), c) : c;
+        crc ^= crc32_shift(band_crc[i], usize - (uint32_t)end, s_x2n);
         if (status[i] != R_OK)
             bad = min(bad, i);
     }
@@ -239,20 +199,6 @@ __global__ __launch_bounds__(CONVERT_BLOCK) void k_fu_i64_f32(const long long *_
     const size_t i = (size_t)blockIdx.x * CONVERT_BLOCK + threadIdx.x;
     if (i < n)
         out[i] = (float)in[i]; // to nearest, ties to even: the conversion numpy's astype compiles to
-}
-
-static void make_consts(Consts &c)
-{
-    for (uint32_t n = 0; n < 256; n++) {
-        uint32_t v = n;
-        for (int k = 0; k < 8; k++)
-            v = (v & 1) ? (v >> 1) ^ CRC_POLY : v >> 1;
-        c.crc[n] = v;
-    }
-    uint32_t p = 1u << 30; // x^1
-    c.x2n[0] = p;
-    for (int k = 1; k < 32; k++)
-        c.x2n[k] = p = multmodp(p, p);
 }
 
 } // namespace flowunzip
@@ -290,9 +236,9 @@ TF_API int tf_flowunzip_create(tf_flowunzip **out, size_t max_stream_bytes, size
     tf_flowunzip *h = new (std::nothrow) tf_flowunzip;
     TF_REQUIRE(h, "tf_flowunzip_create: out of memory");
     h->max_stream = max_stream_bytes, h->max_bands = max_bands;
-    Consts consts;
-    make_consts(consts);
-    int rc = h->consts.alloc(sizeof(Consts));
+    Crc32Consts consts;
+    make_crc32_consts(consts);
+    int rc = h->consts.alloc(sizeof(Crc32Consts));
     if (rc == TF_OK)
         rc = h->stream.alloc(max_stream_bytes);
     if (rc == TF_OK)
@@ -309,7 +255,7 @@ TF_API int tf_flowunzip_create(tf_flowunzip **out, size_t max_stream_bytes, size
         rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: hipHostMalloc failed");
     if (rc == TF_OK && hipHostMalloc((void **)&h->info_host, 4 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipMemcpyAsync(h->consts.p, &consts, sizeof(Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
+    if (rc == TF_OK && hipMemcpyAsync(h->consts.p, &consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: table upload failed");
     if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: hipStreamSynchronize failed");
@@ -352,9 +298,9 @@ TF_API int tf_flowunzip_decode_dev(tf_flowunzip *h, const uint8_t *stream_host, 
     TF_HIP(hipMemcpyAsync(h->stream.p, stream_host, stream_bytes, hipMemcpyHostToDevice, stream()));
     TF_HIP(hipMemcpyAsync(h->offsets.p, h->offsets_host, (n_bands + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream()));
     TF_TRY(launch("fu_inflate", k_fu_inflate, dim3((unsigned)n_bands), dim3(WAVE), 0, m, h->status.as<uint32_t>()));
-    TF_TRY(launch("fu_crc", k_fu_crc, dim3((unsigned)n_bands), dim3(WAVE), 0, m, h->consts.as<Consts>(), h->band_crc.as<uint32_t>()));
+    TF_TRY(launch("fu_crc", k_fu_crc, dim3((unsigned)n_bands), dim3(WAVE), 0, m, h->consts.as<Crc32Consts>(), h->band_crc.as<uint32_t>()));
     TF_TRY(launch("fu_finish", k_fu_finish, dim3(1), dim3(FINISH_BLOCK), 0, h->band_crc.as<uint32_t>(), h->status.as<uint32_t>(),
-                  (uint32_t)n_bands, (uint32_t)band_bytes, (uint32_t)usize, h->consts.as<Consts>(), h->info.as<uint32_t>()));
+                  (uint32_t)n_bands, (uint32_t)band_bytes, (uint32_t)usize, h->consts.as<Crc32Consts>(), h->info.as<uint32_t>()));
     TF_HIP(hipMemcpyAsync(h->info_host, h->info.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
     if (split)
         TF_HIP(hipMemcpyAsync(head_out_host, h->head.p, split, hipMemcpyDeviceToHost, stream()));

@@ -15,6 +15,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "deflate_tables.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define FU_HD __host__ __device__ inline
@@ -24,6 +26,8 @@
 
 namespace tf {
 namespace flowunzip {
+
+using namespace deflate;
 
 // why a band was rejected (0: it was not); the names are tests/flowunzip_ref.py's
 enum Reject : uint32_t {
@@ -55,13 +59,6 @@ constexpr int N_LITLEN = 288, N_DIST = 32, MAX_LENGTHS = 320;
 constexpr uint32_t HEADER_WINDOW = 600;
 static_assert(HEADER_WINDOW + 8 <= WINDOW_BYTES, "a dynamic header must fit the window");
 static_assert(FLUSH_AT + STORED_CHUNK + 258 < RING_BYTES, "the ring must hold what is not flushed");
-
-constexpr uint16_t LEN_BASE[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
-constexpr uint8_t LEN_EXTRA[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-constexpr uint16_t DST_BASE[30] = {1,   2,   3,   4,   5,   7,    9,    13,   17,   25,   33,   49,   65,    97,    129,
-                                   193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-constexpr uint8_t DST_EXTRA[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
-constexpr uint8_t CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
 // ---- the bit reader: bytes [0, size) of the band's range, of which win[0 .. win_len) holds those from win_base on -------
 struct Bits {
@@ -278,7 +275,7 @@ FU_HD uint32_t read_dynamic(Bits &b, Code &lit, Code &dist, uint8_t *lengths)
     for (uint32_t i = 0; i < ncode; i++) {
         if (!take(b, 3, v))
             return R_EXHAUSTED;
-        lengths[CL_ORDER[i]] = (uint8_t)v;
+        lengths[CLEN_ORDER[i]] = (uint8_t)v;
     }
     if (build_code(lit, lengths, 19) != 0) // the code-length code, in the literal code's place for now
         return R_BAD_CODE;
@@ -357,17 +354,17 @@ FU_HD uint32_t step(Bits &b, const Code &lit, const Code &dist, uint32_t produce
     if (sym >= 286)
         return R_BAD_SYMBOL;
     const uint32_t k = sym - 257;
-    if (!take(b, LEN_EXTRA[k], v))
+    if (!take(b, LENGTH_EXTRA[k], v))
         return R_EXHAUSTED;
-    const uint32_t len = LEN_BASE[k] + v;
+    const uint32_t len = LENGTH_BASE[k] + v;
     rc = decode(b, dist, sym);
     if (rc != R_OK)
         return rc;
     if (sym >= 30)
         return R_BAD_SYMBOL;
-    if (!take(b, DST_EXTRA[sym], v))
+    if (!take(b, DIST_EXTRA[sym], v))
         return R_EXHAUSTED;
-    const uint32_t d = DST_BASE[sym] + v;
+    const uint32_t d = DIST_BASE[sym] + v;
     if (d > produced)
         return R_DISTANCE;
     if (len > out_bytes - produced) // (produced <= out_bytes always)

@@ -23,14 +23,12 @@
 //                checked against the buffer's capacity.
 //   k_fz_round   numpy.round(flow).astype(int): half to even in the input's type, int64 out.
 #include "flowzip_common.h"
+#include "stream_common.h"
 
 #include <cstring>
 
 namespace tf {
 namespace flowzip {
-
-constexpr int WAVE = 64;
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
 
 struct Stream {
     const uint8_t *prefix; // prefix_len bytes, a multiple of 64
@@ -103,36 +101,10 @@ __device__ __forceinline__ int length_symbol(int n) // k of 257 + k
     return k;
 }
 
-// a(x) b(x) mod the polynomial, bit 31 the coefficient of x^0 (zlib's multmodp)
-__host__ __device__ inline uint32_t multmodp(uint32_t a, uint32_t b)
-{
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0)
-                break;
-        }
-        m >>= 1;
-        b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-
-// x^(8 n) mod the polynomial
-__device__ __forceinline__ uint32_t x8nmodp(uint32_t n, const uint32_t *__restrict__ x2n)
-{
-    uint32_t p = 1u << 31;
-    for (int k = 3; n; n >>= 1, k++)
-        if (n & 1)
-            p = multmodp(x2n[k & 31], p);
-    return p;
-}
-
 constexpr int TRIPS = 4; // a block of trips: its bytes are loaded while the block before is coded
 
 // ---- count -------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(WAVE) void k_fz_count(const Stream s, const Consts *__restrict__ consts, uint32_t *__restrict__ counts,
+__global__ __launch_bounds__(WAVE) void k_fz_count(const Stream s, const Crc32Consts *__restrict__ consts, uint32_t *__restrict__ counts,
                                                    uint32_t *__restrict__ totals, uint32_t *__restrict__ band_crc)
 {
     __shared__ uint32_t s_cnt[N_SYMBOLS];
@@ -379,9 +351,8 @@ __global__ __launch_bounds__(SIZES_BLOCK) void k_fz_sizes(const uint32_t *__rest
 }
 
 // ---- scan: sizes[n] -> offsets[n], exclusive; info[0] = the stream's bytes, info[2] = the member's CRC-32 --------------
-constexpr int SCAN_BLOCK = 1024;
 __global__ __launch_bounds__(SCAN_BLOCK) void k_fz_scan(const uint32_t *__restrict__ sizes, unsigned long long *__restrict__ offsets, int n,
-                                                        const uint32_t *__restrict__ band_crc, const Consts *__restrict__ consts, uint32_t N,
+                                                        const uint32_t *__restrict__ band_crc, const Crc32Consts *__restrict__ consts, uint32_t N,
                                                         uint32_t band_bytes, uint8_t *__restrict__ out, size_t capacity,
                                                         unsigned long long *__restrict__ info)
 {
@@ -392,20 +363,13 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_fz_scan(const uint32_t *__restri
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
     if (tid == 0)
         s_carry = 0, s_crc = 0;
-    if (tid < 32)
-        s_x2n[tid] = consts->x2n[tid];
+    crc32_stage_x2n(s_x2n, consts, tid);
     __syncthreads();
     uint32_t crc = 0;
     for (int base = 0; base < n; base += SCAN_BLOCK) {
         const int i = base + tid;
         const unsigned long long v = i < n ? (unsigned long long)(sizes[i] & ~CODED_FLAG) : 0;
-        unsigned long long incl = v;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const unsigned long long up = __shfl_up(incl, d, WAVE);
-            if (lane >= d)
-                incl += up;
-        }
+        const unsigned long long incl = wave_inclusive_sum(v, lane);
         if (lane == WAVE - 1)
             s_wave[wave] = incl;
         __syncthreads();
@@ -416,17 +380,14 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_fz_scan(const uint32_t *__restri
             offsets[i] = before + incl - v;
             // the band's CRC moved in front of the bytes behind it
             const unsigned long long end = min((unsigned long long)N, ((unsigned long long)i + 1) * band_bytes);
-            const uint32_t c = band_crc[i];
-            crc ^= (c && end < N) ? multmodp(x8nmodp(N - (uint32_t)end, s_x2n), c) : c;
+            crc ^= crc32_shift(band_crc[i], N - (uint32_t)end, s_x2n);
         }
         __syncthreads();
         if (tid == SCAN_BLOCK - 1)
             s_carry = before + incl;
         __syncthreads();
     }
-#pragma unroll
-    for (int d = WAVE / 2; d; d >>= 1)
-        crc ^= __shfl_xor(crc, d, WAVE);
+    crc = crc32_wave_xor(crc);
     if (lane == 0 && crc)
         atomicXor(&s_crc, crc);
     __syncthreads();
@@ -442,17 +403,6 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_fz_scan(const uint32_t *__restri
 }
 
 // ---- emit ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int up = __shfl_up(v, d, WAVE);
-        if (lane >= d)
-            v += up;
-    }
-    return v;
-}
-
 __device__ __forceinline__ void put_token(unsigned long long &bits, int &len, uint32_t entry)
 {
     bits |= (unsigned long long)(entry & ENTRY_MASK) << len;
@@ -602,20 +552,6 @@ __global__ __launch_bounds__(ROUND_BLOCK) void k_fz_round(const T *__restrict__ 
     out[i] = (r >= -edge && r < edge) ? (long long)r : (long long)0x8000000000000000ull;
 }
 
-static void make_consts(Consts &c)
-{
-    for (uint32_t n = 0; n < 256; n++) {
-        uint32_t v = n;
-        for (int k = 0; k < 8; k++)
-            v = (v & 1) ? (v >> 1) ^ CRC_POLY : v >> 1;
-        c.crc[n] = v;
-    }
-    uint32_t p = 1u << 30; // x^1
-    c.x2n[0] = p;
-    for (int k = 1; k < 32; k++)
-        c.x2n[k] = p = multmodp(p, p);
-}
-
 } // namespace flowzip
 } // namespace tf
 
@@ -667,9 +603,9 @@ TF_API int tf_flowzip_create(tf_flowzip **out, size_t max_stream_bytes, int band
     enc->band_bytes = band_bytes ? (uint32_t)band_bytes : (uint32_t)DEFAULT_BAND_BYTES;
     enc->max_bands = (int)((max_stream_bytes + enc->band_bytes - 1) / enc->band_bytes);
     const size_t n = (size_t)enc->max_bands;
-    Consts consts;
-    make_consts(consts);
-    int rc = enc->consts.alloc(sizeof(Consts));
+    Crc32Consts consts;
+    make_crc32_consts(consts);
+    int rc = enc->consts.alloc(sizeof(Crc32Consts));
     if (rc == TF_OK)
         rc = enc->tables.alloc(sizeof(Tables));
     if (rc == TF_OK)
@@ -692,7 +628,7 @@ TF_API int tf_flowzip_create(tf_flowzip **out, size_t max_stream_bytes, int band
         rc = set_error(TF_ERR_HIP, "tf_flowzip_create: hipHostMalloc failed");
     if (rc == TF_OK && hipHostMalloc((void **)&enc->tables_host, sizeof(Tables), hipHostMallocDefault) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_flowzip_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipMemcpyAsync(enc->consts.p, &consts, sizeof(Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
+    if (rc == TF_OK && hipMemcpyAsync(enc->consts.p, &consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_flowzip_create: table upload failed");
     if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_flowzip_create: hipStreamSynchronize failed");
@@ -739,13 +675,13 @@ TF_API int tf_flowzip_encode_dev(tf_flowzip *enc, const uint8_t *prefix_host, si
         TF_HIP(hipMemcpyAsync(enc->prefix.p, prefix_host, prefix_len, hipMemcpyHostToDevice, stream()));
     TF_HIP(hipMemsetAsync(enc->info.p, 0, enc->info.bytes, stream()));
     TF_HIP(hipMemsetAsync(enc->totals.p, 0, enc->totals.bytes, stream()));
-    TF_TRY(launch("fz_count", k_fz_count, dim3(n_bands), dim3(WAVE), 0, s, enc->consts.as<Consts>(), enc->counts.as<uint32_t>(),
+    TF_TRY(launch("fz_count", k_fz_count, dim3(n_bands), dim3(WAVE), 0, s, enc->consts.as<Crc32Consts>(), enc->counts.as<uint32_t>(),
                   enc->totals.as<uint32_t>(), enc->band_crc.as<uint32_t>()));
     TF_TRY(launch("fz_table", k_fz_table, dim3(1), dim3(TABLE_BLOCK), 0, enc->totals.as<uint32_t>(), distance, enc->tables.as<Tables>()));
     TF_TRY(launch("fz_sizes", k_fz_sizes, dim3(cdiv(n_bands, SIZES_BLOCK / WAVE)), dim3(SIZES_BLOCK), 0, enc->counts.as<uint32_t>(),
                   enc->tables.as<Tables>(), s.N, s.band_bytes, n_bands, enc->sizes.as<uint32_t>()));
     TF_TRY(launch("fz_scan", k_fz_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->sizes.as<uint32_t>(), enc->offsets.as<unsigned long long>(),
-                  n_bands, enc->band_crc.as<uint32_t>(), enc->consts.as<Consts>(), s.N, s.band_bytes, enc->packed.as<uint8_t>(),
+                  n_bands, enc->band_crc.as<uint32_t>(), enc->consts.as<Crc32Consts>(), s.N, s.band_bytes, enc->packed.as<uint8_t>(),
                   enc->packed.bytes, enc->info.as<unsigned long long>()));
     TF_TRY(launch("fz_emit", k_fz_emit, dim3(n_bands), dim3(WAVE), 0, s, enc->tables.as<Tables>(), enc->sizes.as<uint32_t>(),
                   enc->offsets.as<unsigned long long>(), enc->packed.as<uint8_t>(), enc->packed.bytes,

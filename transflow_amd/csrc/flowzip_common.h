@@ -1,24 +1,19 @@
-// Flow archive members deflated on the device (flowzip.hip): deflate's alphabets, the layout of the table buffer the
-// table kernel writes and the other kernels read, the bound on a member's stream.
+// Flow archive members deflated on the device (flowzip.hip): the layout of the table buffer the table kernel writes and
+// the other kernels read, the bound on a member's stream.
 #pragma once
 #include "common.h"
+#include "crc32_common.h"
+#include "deflate_tables.h"
 
 namespace tf {
 namespace flowzip {
 
-// ---- RFC 1951 3.2.5: length symbol 257 + k codes LENGTH_BASE[k] .. with LENGTH_EXTRA[k] extra bits, distance symbol k
-// DIST_BASE[k] .. with DIST_EXTRA[k] (as far as 64); 3.2.7: the order of the code-length code's lengths
-constexpr int N_SYMBOLS = 286, N_LENGTH_SYMBOLS = 29, END_OF_BLOCK = 256, MAX_MATCH = 258, MIN_MATCH = 3;
+using namespace deflate;
+
+// distances as far as 64: the first twelve distance symbols
 constexpr int MAX_DISTANCE = 64, N_DIST_SYMBOLS = 12, MAX_CODE_BITS = 15;
-constexpr uint16_t LENGTH_BASE[N_LENGTH_SYMBOLS] = {
-    3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258,
-};
-constexpr uint8_t LENGTH_EXTRA[N_LENGTH_SYMBOLS] = {
-    0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0,
-};
-constexpr uint8_t DIST_BASE[N_DIST_SYMBOLS] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49};
-constexpr uint8_t DIST_EXTRA[N_DIST_SYMBOLS] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4};
-constexpr uint8_t CLEN_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+static_assert(DIST_BASE[N_DIST_SYMBOLS - 1] + (1 << DIST_EXTRA[N_DIST_SYMBOLS - 1]) - 1 == MAX_DISTANCE,
+              "the last distance symbol in use must end at MAX_DISTANCE");
 
 // ---- the start of every coded band's block: BFINAL 0, BTYPE 10, HLIT 29, HDIST, HCLEN 15, nineteen 3-bit lengths of
 // the code-length code (4 for the symbols 0 - 15, none for the repeat codes), then 286 + HDIST + 1 lengths of 4 bits
@@ -40,12 +35,6 @@ struct Tables {
     uint32_t header_bits;
     uint32_t repairs;               // how often the weights were halved to bring the code within 15 bits
     uint8_t lengths[N_SYMBOLS + 2];
-};
-
-// ---- constants of the library, made on the host
-struct Consts {
-    uint32_t crc[256]; // CRC-32, reflected, polynomial EDB88320
-    uint32_t x2n[32];  // x^(2^k) mod the polynomial (zlib's x2n_table)
 };
 
 // The LDS bit buffer of a wave holds the header or the 7 bits carried into a trip, what 64 lanes can OR into it per

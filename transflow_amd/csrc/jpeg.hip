@@ -15,7 +15,8 @@
 //                  buffer go to the interval's staging slot, an 0x00 after every 0xFF (a ballot counts the 0xFFs
 //                  before a lane's byte), and the bits left over are carried to the front.  The buffer is zeroed by
 //                  the kernel before it is used and behind every flush.
-//   k_jpeg_scan    exclusive sum of the intervals' byte counts (one work-group).
+//   k_slot_scan    exclusive sum of the intervals' byte counts, each with its marker's two (one work-group;
+//                  stream_common.h).
 //   k_jpeg_pack    one wave per interval copies its slot to its place in the packed stream and puts RSTn behind it, EOI
 //                  behind the last; no byte at or past `capacity` is written.
 //
@@ -25,13 +26,12 @@
 // is then padded with its last row -- a chroma row below the image averages rows H - 2 and H - 1 of an image of even
 // height, not H - 1 twice.
 #include "jpeg_common.h"
+#include "stream_common.h"
 
 #include <cstring>
 
 namespace tf {
 namespace jpeg {
-
-constexpr int WAVE = 64;
 
 // jfdctint.c (CONST_BITS 13, PASS1_BITS 2)
 constexpr int CONST_BITS = 13, PASS1_BITS = 2;
@@ -88,17 +88,6 @@ __device__ __forceinline__ Px load_px(const uint8_t *__restrict__ rgb, int W, in
 __device__ __forceinline__ int ycc_y(Px p) { return (19595 * p.r + 38470 * p.g + 7471 * p.b + 32768) >> 16; }
 __device__ __forceinline__ int ycc_cb(Px p) { return (-11059 * p.r - 21709 * p.g + 32768 * p.b + (128 << 16) + 32767) >> 16; }
 __device__ __forceinline__ int ycc_cr(Px p) { return (32768 * p.r - 27439 * p.g - 5329 * p.b + (128 << 16) + 32767) >> 16; }
-
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int up = __shfl_up(v, d, WAVE);
-        if (lane >= d)
-            v += up;
-    }
-    return v;
-}
 
 struct EncodeArgs {
     const uint8_t *rgb;
@@ -260,45 +249,8 @@ __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const EncodeArgs a, const 
     }
 }
 
-// lengths[n] -> offsets[n] (exclusive sums); info[0] = the scan's bytes: all intervals, a marker behind each
-constexpr int SCAN_BLOCK = 1024;
-__global__ __launch_bounds__(SCAN_BLOCK) void k_jpeg_scan(const uint32_t *__restrict__ lengths, uint32_t *__restrict__ offsets,
-                                                          int n, unsigned long long *__restrict__ info)
-{
-    __shared__ unsigned long long s_wave[SCAN_BLOCK / WAVE];
-    __shared__ unsigned long long s_carry;
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    if (tid == 0)
-        s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += SCAN_BLOCK) {
-        const int i = base + tid;
-        const unsigned long long v = i < n ? lengths[i] : 0;
-        unsigned long long incl = v;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const unsigned long long up = __shfl_up(incl, d, WAVE);
-            if (lane >= d)
-                incl += up;
-        }
-        if (lane == WAVE - 1)
-            s_wave[wave] = incl;
-        __syncthreads();
-        unsigned long long before = s_carry;
-        for (int w = 0; w < wave; w++)
-            before += s_wave[w];
-        if (i < n)
-            offsets[i] = (uint32_t)(before + incl - v);
-        __syncthreads();
-        if (tid == SCAN_BLOCK - 1)
-            s_carry = before + incl;
-        __syncthreads();
-    }
-    if (tid == 0)
-        info[0] = s_carry + 2ull * (unsigned long long)n;
-}
-
-// interval i: its bytes to out + offsets[i] + 2 i, then FF D0+(i mod 8), or FF D9 behind the last one
+// interval i: its bytes to out + offsets[i] (the markers before it are counted in), then FF D0+(i mod 8), or FF D9
+// behind the last one
 constexpr int PACK_BLOCK = 256;
 __global__ __launch_bounds__(PACK_BLOCK) void k_jpeg_pack(const uint8_t *__restrict__ staging, uint32_t slot_bytes,
                                                           const uint32_t *__restrict__ lengths, const uint32_t *__restrict__ offsets,
@@ -309,7 +261,7 @@ __global__ __launch_bounds__(PACK_BLOCK) void k_jpeg_pack(const uint8_t *__restr
         return;
     const uint8_t *src = staging + (size_t)i * slot_bytes;
     const uint32_t len = min(lengths[i], slot_bytes);
-    const size_t dst = (size_t)offsets[i] + 2 * (size_t)i;
+    const size_t dst = (size_t)offsets[i];
     for (uint32_t j = lane; j < len; j += WAVE)
         if (dst + j < capacity)
             out[dst + j] = src[j];
@@ -521,8 +473,8 @@ TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, s
     a.lengths = enc->lengths.as<uint32_t>();
     a.overflow = reinterpret_cast<uint32_t *>(enc->info.as<unsigned long long>() + 1);
     TF_TRY(launch("jpeg_encode", k_jpeg_encode, dim3(enc->n_intervals), dim3(WAVE), 0, a, fast_div_setup((uint32_t)enc->mcus_x)));
-    TF_TRY(launch("jpeg_scan", k_jpeg_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
-                  enc->n_intervals, enc->info.as<unsigned long long>()));
+    TF_TRY(launch("jpeg_scan", k_slot_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
+                  enc->n_intervals, 2u, enc->info.as<unsigned long long>())); // a marker behind each interval
     TF_TRY(pack(enc, dev_capacity));
     enc->last_scan = 0;
     TF_HIP(hipMemcpyAsync(enc->info_host, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));

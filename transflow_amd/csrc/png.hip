@@ -16,20 +16,20 @@
 //                  the band is a lane too and its own symbol is end-of-block.  A wave prefix sum of the bit counts
 //                  places the tokens in an LDS bit buffer that starts out holding the table header; after every trip
 //                  its whole bytes go to the band's staging slot and the bits left over to its front.
-//   k_png_scan     exclusive sum of the bands' chunk sizes, data + 12 (one work-group).
+//   k_slot_scan    exclusive sum of the bands' chunk sizes, data + 12 (one work-group; stream_common.h).
 //   k_png_pack     one wave per band writes length, "IDAT", the data and the chunk's CRC-32 at the band's offset: the
 //                  lanes take contiguous slices through the byte table and the slices' CRCs are combined by
-//                  multiplying with x^(8 * bytes behind) modulo the polynomial.  No byte at or past `capacity` is
-//                  written.
+//                  multiplying with x^(8 * bytes behind) modulo the polynomial (crc32_common.h).  No byte at or past
+//                  `capacity` is written.
 #include "png_common.h"
+#include "stream_common.h"
 
 #include <cstring>
 
 namespace tf {
 namespace png {
 
-constexpr int WAVE = 64;
-constexpr uint32_t ADLER_BASE = 65521, CRC_POLY = 0xEDB88320u;
+constexpr uint32_t ADLER_BASE = 65521;
 
 // ---- filter ----------------------------------------------------------------------------------------------------------
 constexpr int FILTER_BLOCK = 256;
@@ -127,17 +127,6 @@ __global__ __launch_bounds__(FILTER_BLOCK) void k_png_filter(const uint8_t *__re
 }
 
 // ---- deflate ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int up = __shfl_up(v, d, WAVE);
-        if (lane >= d)
-            v += up;
-    }
-    return v;
-}
-
 struct DeflateArgs {
     const uint8_t *filtered; // H rows of row_bytes
     uint32_t row_bytes;
@@ -278,71 +267,7 @@ __global__ __launch_bounds__(WAVE) void k_png_deflate(const DeflateArgs a)
     }
 }
 
-// ---- scan: lengths[n] -> offsets[n], exclusive sums of the chunk sizes lengths[i] + 12; info[0] = their total
-constexpr int SCAN_BLOCK = 1024;
-__global__ __launch_bounds__(SCAN_BLOCK) void k_png_scan(const uint32_t *__restrict__ lengths, uint32_t *__restrict__ offsets, int n,
-                                                         unsigned long long *__restrict__ info)
-{
-    __shared__ unsigned long long s_wave[SCAN_BLOCK / WAVE];
-    __shared__ unsigned long long s_carry;
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    if (tid == 0)
-        s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += SCAN_BLOCK) {
-        const int i = base + tid;
-        const unsigned long long v = i < n ? (unsigned long long)lengths[i] + 12 : 0;
-        unsigned long long incl = v;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const unsigned long long up = __shfl_up(incl, d, WAVE);
-            if (lane >= d)
-                incl += up;
-        }
-        if (lane == WAVE - 1)
-            s_wave[wave] = incl;
-        __syncthreads();
-        unsigned long long before = s_carry;
-        for (int w = 0; w < wave; w++)
-            before += s_wave[w];
-        if (i < n)
-            offsets[i] = (uint32_t)(before + incl - v);
-        __syncthreads();
-        if (tid == SCAN_BLOCK - 1)
-            s_carry = before + incl;
-        __syncthreads();
-    }
-    if (tid == 0)
-        info[0] = s_carry;
-}
-
 // ---- pack ------------------------------------------------------------------------------------------------------------
-// a(x) b(x) mod the polynomial, bit 31 the coefficient of x^0 (zlib's multmodp)
-__host__ __device__ inline uint32_t multmodp(uint32_t a, uint32_t b)
-{
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0)
-                break;
-        }
-        m >>= 1;
-        b = (b & 1) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-
-// x^(8 n) mod the polynomial
-__device__ __forceinline__ uint32_t x8nmodp(uint32_t n, const uint32_t *__restrict__ x2n)
-{
-    uint32_t p = 1u << 31;
-    for (int k = 3; n; n >>= 1, k++)
-        if (n & 1)
-            p = multmodp(x2n[k & 31], p);
-    return p;
-}
-
 constexpr uint32_t IDAT_CRC = 0x35AF061Eu; // crc32("IDAT"); checked against the table when a handle is made
 
 constexpr int PACK_BLOCK = 256;
@@ -352,9 +277,8 @@ __global__ __launch_bounds__(PACK_BLOCK) void k_png_pack(const uint8_t *__restri
 {
     __shared__ uint32_t s_crc[256];
     __shared__ uint32_t s_x2n[32];
-    s_crc[threadIdx.x] = tables->crc[threadIdx.x];
-    if (threadIdx.x < 32)
-        s_x2n[threadIdx.x] = tables->x2n[threadIdx.x];
+    s_crc[threadIdx.x] = tables->crc.crc[threadIdx.x]; // (PACK_BLOCK is the table's 256)
+    crc32_stage_x2n(s_x2n, &tables->crc, threadIdx.x);
     __syncthreads();
     const int i = blockIdx.x * (PACK_BLOCK / WAVE) + threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
     if (i >= n)
@@ -384,14 +308,9 @@ __global__ __launch_bounds__(PACK_BLOCK) void k_png_pack(const uint8_t *__restri
 #pragma unroll
         for (uint32_t b = 0; b < 4; b++)
             if (j + b < end)
-                c = s_crc[(c ^ (v >> (8 * b))) & 0xFF] ^ (c >> 8);
+                c = crc32_update(c, v >> (8 * b), s_crc);
     }
-    c = ~c; // the slice's own CRC-32 (of no bytes: 0)
-    if (c && end < len)
-        c = multmodp(x8nmodp(len - end, s_x2n), c);
-#pragma unroll
-    for (int d = WAVE / 2; d; d >>= 1)
-        c ^= __shfl_xor(c, d, WAVE);
+    c = crc32_wave_xor(crc32_shift(~c, len - end, s_x2n)); // ~c: the slice's own CRC-32 (of no bytes: 0)
     if (lane < 4 && dst + 8 + len + lane < capacity)
         out[dst + 8 + len + lane] = (uint8_t)(c >> (24 - 8 * lane));
 }
@@ -510,16 +429,7 @@ static int make_tables(Tables &t, int *byte_bits, int *eob_bits)
         return set_error(TF_ERR_STATE, "png: a lane's tokens would not fit %d bits", LANE_MAX_BITS);
     *byte_bits = worst, *eob_bits = len[END_OF_BLOCK];
 
-    for (uint32_t n = 0; n < 256; n++) {
-        uint32_t c = n;
-        for (int k = 0; k < 8; k++)
-            c = (c & 1) ? (c >> 1) ^ CRC_POLY : c >> 1;
-        t.crc[n] = c;
-    }
-    uint32_t p = 1u << 30; // x^1
-    t.x2n[0] = p;
-    for (int k = 1; k < 32; k++)
-        t.x2n[k] = p = multmodp(p, p);
+    make_crc32_consts(t.crc);
 
     HeaderBits h;
     h.put(0, 1), h.put(2, 2), h.put(N_SYMBOLS - 257, 5), h.put(0, 5), h.put(19 - 4, 4);
@@ -531,14 +441,6 @@ static int make_tables(Tables &t, int *byte_bits, int *eob_bits)
         return set_error(TF_ERR_STATE, "png: the table header has %d bits, not %d", h.n, HEADER_BITS);
     memcpy(t.header, h.words, sizeof(t.header));
     return TF_OK;
-}
-
-static uint32_t host_crc(const Tables &t, const uint8_t *p, size_t n)
-{
-    uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; i++)
-        c = t.crc[(c ^ p[i]) & 0xFF] ^ (c >> 8);
-    return ~c;
 }
 
 static void put_be32(std::vector<uint8_t> &out, uint32_t v)
@@ -553,7 +455,7 @@ static void put_chunk(std::vector<uint8_t> &out, const Tables &t, const char *ki
     const size_t at = out.size();
     out.insert(out.end(), kind, kind + 4);
     out.insert(out.end(), payload.begin(), payload.end());
-    put_be32(out, host_crc(t, out.data() + at, out.size() - at));
+    put_be32(out, crc32_bytes(t.crc, out.data() + at, out.size() - at));
 }
 
 static int default_band_rows(int height, int width)
@@ -631,7 +533,7 @@ TF_API int tf_png_create(tf_png **out, int height, int width, int band_rows)
             rc = set_error(TF_ERR_ARG, "tf_png_create: %dx%d in bands of %d rows could take %zu bytes (less than 2^32)", width, height,
                            rows, n * (slot + 12));
     }
-    if (rc == TF_OK && host_crc(enc->tables, (const uint8_t *)"IDAT", 4) != IDAT_CRC)
+    if (rc == TF_OK && crc32_bytes(enc->tables.crc, (const uint8_t *)"IDAT", 4) != IDAT_CRC)
         rc = set_error(TF_ERR_STATE, "tf_png_create: the CRC table is wrong");
     enc->slot = (uint32_t)slot;
     if (rc == TF_OK) {
@@ -720,8 +622,8 @@ TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, siz
     a.lengths = enc->lengths.as<uint32_t>();
     a.overflow = reinterpret_cast<uint32_t *>(enc->info.as<unsigned long long>() + 1);
     TF_TRY(launch("png_deflate", k_png_deflate, dim3(enc->n_bands), dim3(WAVE), 0, a));
-    TF_TRY(launch("png_scan", k_png_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
-                  enc->n_bands, enc->info.as<unsigned long long>()));
+    TF_TRY(launch("png_scan", k_slot_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
+                  enc->n_bands, 12u, enc->info.as<unsigned long long>())); // a chunk: length, type, data, CRC
     TF_TRY(pack(enc, dev_room(enc, capacity)));
     enc->last_chunks = 0;
     TF_HIP(hipMemcpyAsync(enc->info_host, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));

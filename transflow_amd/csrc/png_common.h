@@ -1,21 +1,13 @@
-// PNG on the device (png.hip): deflate's length alphabet, the layout of the table buffer the kernels read, and the
-// bound on what a band can emit.
+// PNG on the device (png.hip): the layout of the table buffer the kernels read, and the bound on what a band can emit.
 #pragma once
 #include "common.h"
+#include "crc32_common.h"
+#include "deflate_tables.h"
 
 namespace tf {
 namespace png {
 
-// ---- RFC 1951 3.2.5: length symbol 257 + k codes LENGTH_BASE[k] .. with LENGTH_EXTRA[k] extra bits; 3.2.7: the order
-// in which a dynamic block sends the lengths of its code-length code
-constexpr int N_SYMBOLS = 286, N_LENGTH_SYMBOLS = 29, END_OF_BLOCK = 256, MAX_MATCH = 258, MIN_MATCH = 3;
-constexpr uint16_t LENGTH_BASE[N_LENGTH_SYMBOLS] = {
-    3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258,
-};
-constexpr uint8_t LENGTH_EXTRA[N_LENGTH_SYMBOLS] = {
-    0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0,
-};
-constexpr uint8_t CLEN_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+using namespace deflate;
 
 // ---- the constant start of every band's block: BFINAL 0, BTYPE 10, HLIT 29, HDIST 0, HCLEN 15, nineteen 3-bit lengths
 // of the code-length code (4 for the symbols 0 - 15, none for the repeat codes), then 286 + 1 code lengths of 4 bits
@@ -28,8 +20,7 @@ constexpr int HEADER_WORDS = (HEADER_BITS + 31) / 32;
 struct Tables {
     uint32_t lit[END_OF_BLOCK + 1]; // the literals and end-of-block
     uint32_t match[MAX_MATCH + 1];  // [n], n = 3 .. 258
-    uint32_t crc[256];              // CRC-32, reflected, polynomial EDB88320
-    uint32_t x2n[32];               // x^(2^k) mod the polynomial (zlib's x2n_table)
+    Crc32Consts crc;                // (crc32_common.h)
     uint32_t header[HEADER_WORDS];  // the HEADER_BITS above, stream bit 32 w + k in bit k of word w
 };
 

@@ -12,6 +12,8 @@ import io
 
 import numpy as np
 
+from .framecodec import EncodedFrame, FrameEncoder
+
 
 def pillow_encode_png(image: np.ndarray) -> bytes:
     """A PNG of the same pixels made on the host by Pillow (zlib level 1): what a process without a GPU does with a
@@ -37,114 +39,29 @@ def code_lengths() -> list:
     return list(out)
 
 
-class PngFrame:
+class PngFrame(EncodedFrame):
     """A frame as a PNG file: `data`, the `shape` (H, W, 3) of the image it decodes to, `band_rows`."""
 
-    __slots__ = ("data", "shape", "band_rows")
+    __slots__ = ("band_rows",)
 
     def __init__(self, data: bytes, shape, band_rows: int):
-        self.data = bytes(data)
-        self.shape = tuple(int(v) for v in shape)
+        super().__init__(data, shape)
         self.band_rows = int(band_rows)
 
-    def __bytes__(self) -> bytes:
-        return self.data
 
-    def tobytes(self) -> bytes:
-        return self.data
-
-    def __len__(self) -> int:
-        return len(self.data)
-
-    def decode(self) -> np.ndarray:
-        """The uint8 (H, W, 3) RGB array the file holds (Pillow's decoder)."""
-        import PIL.Image
-        with PIL.Image.open(io.BytesIO(self.data)) as im:
-            return np.asarray(im.convert("RGB"))
-
-    def __reduce__(self):
-        return (PngFrame, (self.data, self.shape, self.band_rows))
-
-    def __eq__(self, other):
-        return isinstance(other, PngFrame) and (self.data, self.shape, self.band_rows) == (
-            other.data, other.shape, other.band_rows)
-
-    __hash__ = None
-
-    def __repr__(self):
-        return f"PngFrame({len(self.data)} bytes, shape={self.shape}, band_rows={self.band_rows})"
-
-
-class PngEncoder:
+class PngEncoder(FrameEncoder):
     """tf_png: one size, one band height; its device buffers are allocated once."""
 
+    ENCODE_DEV, ENCODE, COPY_LAST, DESTROY = "tf_png_encode_dev", "tf_png_encode", "tf_png_copy_last", "tf_png_destroy"
+
     def __init__(self, height: int, width: int, band_rows: int | None = None):
-        from . import _lib
-        self._lib = _lib.load()
-        self._check = _lib.check
-        self.height, self.width = int(height), int(width)
-        self._h = C.c_void_p()
+        super().__init__(height, width)
         self._check(self._lib.tf_png_create(C.byref(self._h), self.height, self.width,
                                             0 if band_rows is None else int(band_rows)))
         self.band_rows = int(self._lib.tf_png_band_rows(self._h))
-        self.last_needed = 0        # the size the last encode() reported, also when the buffer was too small
-        self._out = None
 
-    def _source(self, image):
-        """(device address or None, host array or None) of an ndarray, a DevicePixmap or a CompImage."""
-        shape = (self.height, self.width, 3)
-        if hasattr(image, "image_ptr"):                              # CompImage
-            if (image.height, image.width) != shape[:2]:
-                raise ValueError(f"the encoder is for {shape[:2]} frames, the image is {(image.height, image.width)}")
-            return image.image_ptr(), None
-        if tuple(image.shape) != shape:
-            raise ValueError(f"the encoder is for {shape} frames, the image is {tuple(image.shape)}")
-        if getattr(image, "dev_ptr", None) is not None:              # DevicePixmap
-            image.wait_on_stream()
-            return image.dev_ptr, None
-        return None, np.ascontiguousarray(image, dtype=np.uint8)
-
-    def encode_into(self, image, out: np.ndarray) -> int:
-        """The file into `out` (uint8, C-contiguous); returns its size.  ValueError if it does not fit: `last_needed`
-        then says how much room it takes, and `out` is as it was."""
-        self.last_needed = 0
-        dev, host = self._source(image)
-        n = C.c_size_t()
-        dst = C.c_void_p(out.ctypes.data)
-        if dev is not None:
-            rc = self._lib.tf_png_encode_dev(self._h, C.c_void_p(dev), dst, out.nbytes, C.byref(n))
-        else:
-            rc = self._lib.tf_png_encode(self._h, C.c_void_p(host.ctypes.data), dst, out.nbytes, C.byref(n))
-        self.last_needed = n.value
-        self._check(rc)
-        return n.value
-
-    def encode(self, image) -> bytes:
-        """The PNG file of `image`: a uint8 (H, W, 3) ndarray, a DevicePixmap or a CompImage."""
-        if self._out is None:       # rendered frames are a part of this; one that is not makes the buffer grow
-            self._out = np.empty(self.height * self.width * 3 // 2 + 4096, np.uint8)
-        try:
-            n = self.encode_into(image, self._out)
-        except ValueError:
-            if self.last_needed <= self._out.nbytes:
-                raise
-            self._out = np.empty(self.last_needed, np.uint8)      # the bands are still in the handle: pack and copy
-            size = C.c_size_t()
-            self._check(self._lib.tf_png_copy_last(self._h, C.c_void_p(self._out.ctypes.data), self._out.nbytes,
-                                                   C.byref(size)))
-            n = size.value
-        return self._out[:n].tobytes()
+    def _first_capacity(self) -> int:   # rendered frames are a part of this
+        return self.height * self.width * 3 // 2 + 4096
 
     def frame(self, image) -> PngFrame:
         return PngFrame(self.encode(image), (self.height, self.width, 3), self.band_rows)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.tf_png_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
