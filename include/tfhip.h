@@ -197,6 +197,10 @@ int tf_fb_set_frame(tf_fb *fb, int slot, const uint8_t *grey, ptrdiff_t stride);
    (row stride in bytes) is uploaded as it is and cv2.resize(INTER_NEAREST) to the handle's size +
    cv2.cvtColor(COLOR_BGR2GRAY) run on the device (tf_frame_grey_dev) straight into the slot. */
 int tf_fb_set_frame_bgr(tf_fb *fb, int slot, const uint8_t *bgr, int src_width, int src_height, ptrdiff_t stride);
+/* tf_fb_set_frame_bgr without the upload: bgr_dev is a complete, packed uint8 [src_height][src_width][3] frame in
+   device memory (tf_jpegdec_decode_dev's output ...).  Ordered inside the library like the two above: it returns with
+   the frame in place, so the caller needs no tf_sync(). */
+int tf_fb_set_frame_bgr_dev(tf_fb *fb, int slot, const void *bgr_dev, int src_width, int src_height);
 /* Resident path with TF_OPTFLOW_USE_INITIAL_FLOW: the initial flow of `pair` for the next tf_fb_calc_slots
    (float32 [height][width][2]; kept until written again, zero at creation), from the host or -- through
    its device address -- filled on the GPU (e.g. copied from a previous result). */
@@ -791,6 +795,28 @@ int tf_flowunzip_decode(tf_flowunzip *h, const uint8_t *stream_host, size_t stre
 /* astype(float32) of n_values int64 in device memory: to nearest, ties to even, as numpy converts.  Queued on the
    calling thread's stream; does not wait. */
 int tf_flow_i64_to_f32_dev(const void *src_dev, size_t n_values, void *dst_dev);
+
+/* ---- baseline JPEG decoded on the device (transflow_amd/csrc/jpegdec.hip) ----------------
+ * The inverse of tf_jpeg for more than its own files: SOF0, 8-bit, one scan that interleaves all components, three
+ * components (luma sampled 2x2, 2x1 or 1x1, chroma 1x1) or one, 8-bit DQT, any valid DHT, any restart interval or
+ * none.  The pixels are libjpeg's (islow IDCT, fancy upsampling), bit for bit.  The compressed bytes go up; the restart
+ * intervals are decoded side by side, one wave each, so a file without DRI is decoded by one wave.
+ * Every other file is rejected whole, with a reason (tf_jpegdec_reject_name; the enum is jpegdec_common.h's Reject).
+ * A rejection is a status, not an error: the call returns TF_OK and *reject != 0.  Nothing is then promised about
+ * the output buffer except that nothing outside it was written. */
+typedef struct tf_jpegdec tf_jpegdec;
+typedef struct { int width, height, components, h_samp, v_samp, restart_mcus, intervals; uint32_t reject; } tf_jpegdec_info;
+/* The header alone (host only, no GPU call): the geometry, or why the header is rejected. */
+int tf_jpegdec_probe(const uint8_t *file, size_t n, tf_jpegdec_info *info);
+int tf_jpegdec_create(tf_jpegdec **out, int max_width, int max_height, size_t max_file_bytes);
+void tf_jpegdec_destroy(tf_jpegdec *dec);
+/* order: 0 RGB, 1 BGR.  out_dev: uint8 [height][width][3].  Queues on the calling thread's stream and waits for the
+   status.  Returns TF_OK with *reject != 0 for a file the device does not take; TF_ERR_ARG for a frame larger than
+   the handle was made for or a NULL pointer. */
+int tf_jpegdec_decode_dev(tf_jpegdec *dec, const uint8_t *file, size_t n, void *out_dev, int order, uint32_t *reject);
+/* The same into host memory (through a buffer of the handle); out_host is written only when *reject == 0. */
+int tf_jpegdec_decode(tf_jpegdec *dec, const uint8_t *file, size_t n, uint8_t *out_host, int order, uint32_t *reject);
+const char *tf_jpegdec_reject_name(uint32_t reject);
 
 /* ---- batch-of-frames mode over the GPUs of one node ----------------------
  * With flags == 0 every Farnebäck pair is independent (transflow/flow/sources/cv.py:478-490: the

@@ -38,6 +38,11 @@ class TfMvVector(C.Structure):
                                                "motion_scale")]
 
 
+class TfJpegdecInfo(C.Structure):
+    _fields_ = [(name, C.c_int) for name in ("width", "height", "components", "h_samp", "v_samp", "restart_mcus",
+                                             "intervals")] + [("reject", C.c_uint32)]
+
+
 class TfPolarStep(C.Structure):
     _fields_ = [("op", C.c_int), ("wide", C.c_int), ("imm", C.c_double)]
 
@@ -106,6 +111,7 @@ PROTOTYPES = {
     "tf_fb_calc": (_I, [_P, _P, C.c_ssize_t, _P, C.c_ssize_t, _P]),
     "tf_fb_set_frame": (_I, [_P, _I, _P, C.c_ssize_t]),
     "tf_fb_set_frame_bgr": (_I, [_P, _I, _P, _I, _I, C.c_ssize_t]),
+    "tf_fb_set_frame_bgr_dev": (_I, [_P, _I, _P, _I, _I]),
     "tf_fb_frame_ptr": (_I, [_P, _I, _PP]),
     "tf_fb_set_initial_flow": (_I, [_P, _I, _P]),
     "tf_fb_initial_flow_ptr": (_I, [_P, _I, _PP]),
@@ -249,6 +255,12 @@ PROTOTYPES = {
     "tf_flowunzip_decode": (_I, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _P, _P,
                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tf_flow_i64_to_f32_dev": (_I, [_P, C.c_size_t, _P]),
+    "tf_jpegdec_probe": (_I, [_P, C.c_size_t, C.POINTER(TfJpegdecInfo)]),
+    "tf_jpegdec_create": (_I, [_PP, _I, _I, C.c_size_t]),
+    "tf_jpegdec_destroy": (None, [_P]),
+    "tf_jpegdec_decode_dev": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
+    "tf_jpegdec_decode": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
+    "tf_jpegdec_reject_name": (C.c_char_p, [C.c_uint32]),
     "tf_batch_unique_id": (_I, [_P]),
     "tf_batch_init": (_I, [_PP, _I, _I, _P]),
     "tf_batch_destroy": (None, [_P]),

@@ -503,6 +503,24 @@ TF_API int tf_fb_set_frame_bgr(tf_fb *fb, int slot, const uint8_t *bgr, int src_
     return TF_OK;
 }
 
+// the same for a frame that is in device memory already (a decoder's output): no upload, no staging
+TF_API int tf_fb_set_frame_bgr_dev(tf_fb *fb, int slot, const void *bgr_dev, int src_width, int src_height)
+{
+    TF_REQUIRE(fb && bgr_dev, "tf_fb_set_frame_bgr_dev: null pointer");
+    TF_REQUIRE(slot >= 0 && slot < fb->slots, "tf_fb_set_frame_bgr_dev: slot %d out of range (%d slots)", slot, fb->slots);
+    TF_REQUIRE(src_width >= 1 && src_height >= 1 && (long long)src_width * src_height < (1ll << 31),
+               "tf_fb_set_frame_bgr_dev: bad source size %dx%d", src_width, src_height);
+    TF_TRY(ensure_init());
+    uint8_t *dst = fb->frames.as<uint8_t>() + (size_t)slot * fb->W * fb->H;
+    if (fb->keep)
+        fb->expanded[slot] = 0;
+    TF_TRY(fb_upload_scope_begin(fb, slot));
+    StreamScope up(fb->async_io ? fb->up_stream : stream());
+    TF_TRY(tf_frame_grey_dev(bgr_dev, src_width, src_height, dst, fb->W, fb->H));
+    TF_HIP(hipStreamSynchronize(stream())); // returns with the frame in place, as tf_fb_set_frame does
+    return TF_OK;
+}
+
 TF_API int tf_fb_frame_ptr(tf_fb *fb, int slot, void **dev)
 {
     TF_REQUIRE(fb && dev, "tf_fb_frame_ptr: null pointer");

@@ -27,6 +27,7 @@ import os
 import re
 
 _saved = {}
+_pixmap_options = {"stills": False, "mjpeg": False}   # what the installed pixmap factory serves
 _saved_export = []      # (the reference's pipeline module, its NumpyOutput, deviceflow.DEVICE_ROUND) while device_flow_export is on
 
 
@@ -41,8 +42,13 @@ def _served_config(cv_config, horn_schunck: bool, lucas_kanade: bool = False, li
     return horn_schunck or not isinstance(cfg, HornSchunckConfig)
 
 
+def _is_mjpeg(path) -> bool:
+    from .jpegdec import MJPEG_EXTS
+    return isinstance(path, str) and os.path.splitext(path)[1].lower() in MJPEG_EXTS and os.path.isfile(path)
+
+
 def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None, motion_vectors=False,
-                    device_flow_replay=False):
+                    device_flow_replay=False, mjpeg_inputs=False):
     from .flow import HipFlowSource
 
     def from_args(cls, flow_path, use_mvs=False, mask_path=None, kernel_path=None, cv_config=None,
@@ -64,6 +70,9 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
                             cv_config=cv_config, flow_filters=flow_filters, size=size, direction=direction,
                             seek_ckpt=seek_ckpt, seek_time=seek_time, duration_time=duration_time, repeat=repeat,
                             lock_expr=lock_expr, lock_mode=lock_mode)
+        if mjpeg_inputs and not use_mvs and _is_mjpeg(flow_path):   # a raw MJPEG stream: its frames are decoded on the device
+            from .jpegdec import MjpegFrameProvider
+            flow_path = MjpegFrameProvider(flow_path, size=size)
         return HipFlowSource.from_args(flow_path, use_mvs, mask_path, kernel_path, cv_config, flow_filters, size,
                                        direction, seek_ckpt, seek_time, duration_time, repeat, lock_expr, lock_mode,
                                        lucas_kanade=lucas_kanade, liteflownet=liteflownet,
@@ -109,13 +118,13 @@ def _png_output_from_args(original):
     return classmethod(from_args)
 
 
-def _pixmap_from_args(original):
+def _pixmap_from_args(original, stills=True, mjpeg_inputs=False):
     from .pixmap import HipPixmapSource
 
     def from_args(cls, path, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat=1, flow_path=None):
-        still = re.match(HipPixmapSource.STILL_RE, path.lower().strip()) is not None
-        image = os.path.isfile(path) and os.path.splitext(path)[1].lower() in HipPixmapSource.IMAGE_EXTS
-        if not (still or image):               # a video: the reference's CvPixmapSource
+        still = stills and re.match(HipPixmapSource.STILL_RE, path.lower().strip()) is not None
+        image = stills and os.path.isfile(path) and os.path.splitext(path)[1].lower() in HipPixmapSource.IMAGE_EXTS
+        if not (still or image or (mjpeg_inputs and _is_mjpeg(path))):     # a video: the reference's CvPixmapSource
             return original(path, size, seek=seek, seed=seed, seek_time=seek_time, alteration_path=alteration_path,
                             repeat=repeat, flow_path=flow_path)
         return HipPixmapSource.from_args(path, size, seek, seed, seek_time, alteration_path, repeat, flow_path)
@@ -126,7 +135,7 @@ def _pixmap_from_args(original):
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
-            device_flow_replay: bool = False) -> None:
+            device_flow_replay: bool = False, mjpeg_inputs: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -158,7 +167,10 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     device_flow_replay: the archive source FlowSource.from_args builds for a `.flow.zip` path is
     archive.ArchiveFlowSource(device_inflate=True): members with a band index are inflated on the device
     (transflow_amd/flowunzip.py) straight into the flow that is post-processed there; members without one, and every
-    member while a lock expression or a polar filter needs the raw flow on the host, are read as before."""
+    member while a lock expression or a polar filter needs the raw flow on the host, are read as before.
+    mjpeg_inputs: an existing file with extension .mjpeg / .mjpg (a raw MJPEG stream) is decoded on the device
+    (transflow_amd/jpegdec.py), as a flow source's video (a MjpegFrameProvider under the HipFlowSource) and as a pixmap
+    source (HipMjpegPixmapSource); by default such paths stay the reference's, like every other video."""
     if jpeg_frames is not None and lazy_frames:
         raise ValueError("jpeg_frames and lazy_frames exclude each other")
     if png_frames and (jpeg_frames is not None or lazy_frames):
@@ -167,7 +179,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
         RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet,
-                                                     motion_vectors, bool(device_flow_replay))
+                                                     motion_vectors, bool(device_flow_replay), bool(mjpeg_inputs))
     if compositor and "compositor" not in _saved:
         from transflow.compositor.compositor import Compositor as RefCompositor
 
@@ -195,16 +207,24 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         else:
             ref_pipeline.NumpyOutput = DeviceFlowArchiveWriter
         deviceflow.DEVICE_ROUND = True
-    if pixmaps and "pixmaps" not in _saved:
+    if pixmaps or mjpeg_inputs:
+        # one factory serves both options: a later call that asks for the other one adds it to what is installed
         from transflow.pixmap.source import PixmapSource as RefPixmapSource
-        _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])
-        RefPixmapSource.from_args = _pixmap_from_args(RefPixmapSource.from_args)
+        if "pixmaps" not in _saved:
+            _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])
+            _pixmap_options.update(stills=False, mjpeg=False)
+        wanted = dict(stills=_pixmap_options["stills"] or bool(pixmaps), mjpeg=_pixmap_options["mjpeg"] or bool(mjpeg_inputs))
+        if wanted != _pixmap_options:
+            _pixmap_options.update(wanted)
+            RefPixmapSource.from_args = _saved["pixmaps"][1]              # the reference's own, to be wrapped once
+            RefPixmapSource.from_args = _pixmap_from_args(RefPixmapSource.from_args, wanted["stills"], wanted["mjpeg"])
 
 
 def uninstall() -> None:
     for key in list(_saved):
         cls, original = _saved.pop(key)
         cls.from_args = original
+    _pixmap_options.update(stills=False, mjpeg=False)
     while _saved_export:
         from . import deviceflow
         module, original, switch = _saved_export.pop()

@@ -124,6 +124,14 @@ class Farneback:
             a = np.ascontiguousarray(a)   # (a vertically flipped view, frame[::-1], or a broadcast row: rows that do not advance)
         check(self._lib.tf_fb_set_frame_bgr(self._h, int(slot), _ptr(a), a.shape[1], a.shape[0], a.strides[0]))
 
+    def set_frame_bgr_dev(self, slot: int, pixmap) -> None:
+        """The same for a BGR frame that is in device memory already (a `DevicePixmap`: a decoder's output): no
+        upload; the call returns with the grey frame in the slot."""
+        if pixmap.dtype != np.uint8 or len(pixmap.shape) != 3 or pixmap.shape[2] != 3:
+            raise ValueError(f"expected a uint8 BGR frame (H, W, 3), got {pixmap.shape}")
+        pixmap.synchronize()
+        check(self._lib.tf_fb_set_frame_bgr_dev(self._h, int(slot), C.c_void_p(pixmap.dev_ptr), pixmap.shape[1], pixmap.shape[0]))
+
     def set_initial_flow(self, pair: int, flow) -> None:
         """Resident path, OPTFLOW_USE_INITIAL_FLOW: the initial flow of `pair` for the next calc_slots."""
         f = np.ascontiguousarray(flow, dtype=np.float32)

@@ -758,6 +758,12 @@ class HipFlowSource(FlowSource):
         self._batch_left = self._batch_pos = 0     # flows of a hip_batch call made before the seek are not handed out after it
 
     def _ingest(self, slot: int, frame) -> None:
+        from .pixmap import DevicePixmap
+        # A frame decoded on the device stays there.  A provider hands BGR, as every provider's host frames are
+        # (MjpegFrameProvider.read's default order): a three-channel DevicePixmap is read as BGR, whatever made it.
+        if isinstance(frame, DevicePixmap) and hasattr(self._handle(), "set_frame_bgr_dev") and frame.shape[2] == 3:
+            self._handle().set_frame_bgr_dev(slot, frame)
+            return
         a = np.asarray(frame)
         if self._method.colour and a.ndim != 3:
             raise ValueError(f"the {self.config.method} method needs colour (BGR) frames; the frame provider gives grey ones")

@@ -30,6 +30,7 @@ import re
 import numpy as np
 from numpy.lib.mixins import NDArrayOperatorsMixin
 
+MJPEG_EXTS = (".mjpeg", ".mjpg")       # the extensions a raw MJPEG stream file is known by, here and in jpegdec.py
 NODE_I, NODE_J, NODE_RGB, NODE_MIX, NODE_TRIPLE, NODE_Z, NODE_B = range(7)     # still.py:86-92
 MAX_NODES = 40                                                                 # TF_PX_MAX_NODES
 
@@ -105,6 +106,11 @@ class DevicePixmap(NDArrayOperatorsMixin):
         """The calling thread's library stream waits, on the device, for the image to be complete."""
         if self._ready is not None:
             self._ready.stream_wait()
+
+    def synchronize(self) -> None:
+        """The host waits for the image to be complete: for a reader on a stream of its own."""
+        if self._ready is not None:
+            self._ready.synchronize()
 
     # ---- the array it stands for --------------------------------------------------------------------------------
     @property
@@ -234,6 +240,7 @@ class HipPixmapSource:
     """transflow/pixmap/source.py:15-120."""
 
     IMAGE_EXTS = {".jpg", ".jpeg", ".png", ".webp", ".bmp", ".ico", ".tiff"}
+    MJPEG_EXTS = MJPEG_EXTS               # raw MJPEG streams: decoded on the device (HipMjpegPixmapSource)
     STILL_RE = r"^(color:[a-z0-9\(\)#, ]+|color|#?[0-9a-f]{6}|noise|bwnoise|cnoise|gradient|first)$"   # source.py:83
 
     def __init__(self, alteration_path: str | None, length: int | None = None):
@@ -283,7 +290,7 @@ class HipPixmapSource:
     @classmethod
     def from_args(cls, path: str, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat: int = 1,
                   flow_path=None):
-        """source.py:71-120; a video path (CvPixmapSource there) is not served."""
+        """source.py:71-120; of the video paths (CvPixmapSource there) only a raw MJPEG stream file is served."""
         ext = os.path.splitext(path)[1]
         still_match = re.match(cls.STILL_RE, path.lower().strip())
         if still_match is not None:
@@ -310,6 +317,8 @@ class HipPixmapSource:
             raise ValueError(f"Unknown pixmap source '{still_match.group(1)}'")
         if os.path.isfile(path) and ext.lower() in cls.IMAGE_EXTS:
             return HipImagePixmapSource(path, alteration_path)
+        if os.path.isfile(path) and ext.lower() in cls.MJPEG_EXTS:
+            return HipMjpegPixmapSource(path, seek, seek_time, alteration_path, repeat)
         raise NotImplementedError(f"video pixmap source '{path}': not served by this backend (CvPixmapSource)")
 
 
@@ -455,6 +464,70 @@ class HipVideoStillPixmapSource(HipImagePixmapSource):
         array = np.ascontiguousarray(np.asarray(frame)[:, :, ::-1])                     # cv2.COLOR_BGR2RGB
         provider.release()
         return array
+
+
+class HipMjpegPixmapSource(HipPixmapSource):
+    """CvPixmapSource (pixmap/cv.py:11-66) over a raw MJPEG stream file (.mjpeg / .mjpg), a `%0Nd.jpg` pattern or a
+    sequence of JPEG files in memory: the same rewind, seek, `repeat` and `length`, every frame decoded on the device
+    (transflow_amd/jpegdec.py) and handed out as an RGB `DevicePixmap` -- the compressed bytes go up and the pixels never
+    exist on the host.  With an alteration the frame comes down, is altered by numpy.put and goes up again, as the
+    stills' overlay does.  (The overlay is loaded once the size is known; the reference loads it before, cv.py:33.)"""
+
+    def __init__(self, path, seek: int | None = None, seek_time: float | None = None, alteration_path: str | None = None,
+                 repeat: int = 1, framerate: float = 25.0):
+        HipPixmapSource.__init__(self, alteration_path)
+        self.path = path
+        self.capture = None                          # the frame provider, under the reference's name for it
+        self.seek = seek
+        self.seek_time = seek_time
+        self.repeat = repeat
+        self.loop_index = 1
+        self._framerate = framerate
+
+    def rewind(self):
+        if self.capture is None:
+            raise ValueError("Capture not initialized")
+        self.capture.seek_start()
+        if self.seek is not None:                    # cv.py:28-30 reads and drops the frames: nothing to decode for that
+            self.capture.pos = min(max(0, int(self.seek)), self.capture.frame_count)
+
+    def __enter__(self):
+        from .jpegdec import MjpegFrameProvider
+        self.capture = MjpegFrameProvider(self.path, framerate=self._framerate)
+        self.width = int(self.capture.width)
+        self.height = int(self.capture.height)
+        self.framerate = round(self.capture.framerate)
+        self.setup()
+        frame_count = self.capture.frame_count
+        if self.repeat > 0 and frame_count > 0:
+            self.length = int(frame_count) * self.repeat
+        if self.seek_time is not None:
+            self.seek = int(self.seek_time * self.framerate)
+            if self.length is not None:
+                self.length -= self.seek * self.repeat
+        self.rewind()
+        return self
+
+    def __next__(self) -> DevicePixmap:
+        assert self.capture is not None
+        while True:
+            frame = self.capture.read("rgb")
+            if frame is not None:
+                break
+            if self.repeat == 0 or self.loop_index < self.repeat:
+                self.loop_index += 1
+                self.rewind()
+                continue
+            raise StopIteration
+        if self.alteration is not None:              # numpy's put on the host: down, altered, up again
+            host = np.array(frame.host())
+            frame.close()
+            frame = DevicePixmap.from_host(self.alter(host))
+        return frame
+
+    def __exit__(self, exc_type, exc_value, exc_traceback):
+        if self.capture is not None:
+            self.capture.release()
 
 
 class EndOfPixmap(StopIteration):
