@@ -707,6 +707,12 @@ typedef struct tf_png tf_png;
 int tf_png_create(tf_png **out, int height, int width, int band_rows);
 void tf_png_destroy(tf_png *enc);
 int tf_png_band_rows(tf_png *enc); /* the rows of a band of this handle */
+/* on != 0: the files of the handle's later encodes carry the band index, the ancillary chunk tfBX between IHDR and the
+   first IDAT (payload, big-endian: uint8 version 1, uint8 flags 0, uint16 0, uint32 band_rows, uint32 n_bands), which
+   tells tf_pngdec that, and how, the IDATs are bands.  Off (the default) the file is what it always was, byte for
+   byte.  No GPU call; tf_png_copy_last has nothing to copy until the next encode.  No counterpart in the reference:
+   cv2.imwrite (transflow/output/frames.py:31) writes one zlib stream and has no such option. */
+int tf_png_set_index(tf_png *enc, int on);
 /* rgb_dev: uint8 [H][W][3] in device memory.  Queues its kernels on the calling thread's stream and waits; the file is
    then copied to `out` (host) and *n_bytes is its size.  A file larger than `capacity` returns TF_ERR_ARG with *n_bytes
    the size needed; `out` is then not written at all, and in no case is anything written at or beyond out + capacity. */
@@ -817,6 +823,55 @@ int tf_jpegdec_decode_dev(tf_jpegdec *dec, const uint8_t *file, size_t n, void *
 /* The same into host memory (through a buffer of the handle); out_host is written only when *reject == 0. */
 int tf_jpegdec_decode(tf_jpegdec *dec, const uint8_t *file, size_t n, uint8_t *out_host, int order, uint32_t *reject);
 const char *tf_jpegdec_reject_name(uint32_t reject);
+
+/* ---- banded PNG frames decoded on the device (transflow_amd/csrc/pngdec.hip) --------------
+ * The inverse of tf_png for the files it writes with tf_png_set_index, and for any file of that shape: 8-bit RGB, colour
+ * type 2, not interlaced; IHDR, tfBX, an IDAT with a two-byte zlib header, one IDAT per band of band_rows rows, an
+ * IDAT with an empty final block and the Adler-32, IEND.  A band is any sequence of non-final deflate blocks that ends
+ * on a byte and whose matches stay inside the band's own output (tf_png's bands, zlib's Z_FULL_FLUSH bands).  It stands
+ * where the reference decodes a frame of an image sequence on the host and the pixels go up: cv2.VideoCapture.read()
+ * in transflow/pixmap/cv.py:54 (a moving pixmap) and transflow/flow/sources/cv.py:451, 461 (the video a flow is
+ * computed from).  The compressed file goes up; chunk CRCs, inflate (one wave per band), Adler-32 and the row filters
+ * are done on the device and the pixels are written once, where the caller wants them.
+ * A reject word is reason | where << 8: `where` is the chunk (chunk_crc; IHDR is chunk 0), the row (filter_type) or the
+ * band (band_*), else 0; tf_pngdec_reject_name names the reason (pngdec_common.h's Reject).
+ * A band's decoding time is bounded by its compressed bits, as tf_flowunzip's: a direct caller with untrusted files sets
+ * a bound on the bands first, as transflow_amd/pngdec.py does (a band of at most 1 MiB of output and of at most
+ * 2 * that + 1024 compressed bytes; other files are decoded on the host). */
+typedef struct tf_pngdec tf_pngdec;
+typedef struct {
+    int width, height, band_rows, n_bands;
+    int indexed;             /* 1: a file for the device */
+    int why_not;             /* a well-formed file that is not: 1 no index, 2 not 8-bit RGB, 3 interlaced, 4 an index of an unknown version */
+    uint32_t reject;         /* a malformed file: the reject word (then neither of the above) */
+    uint32_t max_band_bytes; /* the largest band's compressed bytes */
+    uint32_t *band_offsets, *band_sizes; /* in: arrays of band_capacity entries (or NULL, 0); out: where each band's
+                                            compressed bytes begin in the file, and how many they are */
+    size_t band_capacity;
+} tf_pngdec_info;
+/* The chunks alone, walked on the host (no GPU call; CRCs are not looked at): every length is checked against the file
+   before it is used.  Always TF_OK for non-null arguments; info->reject, info->indexed and info->why_not say which of
+   the three a file is: rejected, for the device, or a PNG of another kind (which is no error).
+   Replaces the container probing of cv2.VideoCapture(path) (transflow/pixmap/cv.py:34, flow/sources/cv.py:421). */
+int tf_pngdec_probe(const uint8_t *file, size_t n, tf_pngdec_info *info);
+/* Frames of up to max_width x max_height (each at most 2^24 - 1, together at most 2^31 filtered bytes) in files of up to
+   max_file_bytes; the staging buffer (page-locked) and every device buffer are allocated here.  Stands where the
+   reference opens its capture: cv2.VideoCapture(path) (transflow/pixmap/cv.py:34, transflow/flow/sources/cv.py:421). */
+int tf_pngdec_create(tf_pngdec **out, int max_width, int max_height, size_t max_file_bytes);
+/* Replaces capture.release() (transflow/pixmap/cv.py:66, transflow/flow/sources/cv.py:524). */
+void tf_pngdec_destroy(tf_pngdec *dec);
+/* file_host: the file; pix_dev: uint8 [height][width][3] in device memory, RGB, or BGR with bgr = 1 (what a flow source
+   wants); nothing outside these bytes is written.  Queues on the calling thread's stream and waits for the status.
+   TF_ERR_ARG (nothing is launched): a NULL pointer, a file larger than the handle's, a file that is not for the device.
+   TF_ERR_STATE with *reject set: a file the walk rejects (a frame beyond the handle's size is `size`), a chunk whose
+   CRC differs, a band that is no valid band, a filter type above 4, an Adler-32 that differs; the pixels are then
+   undefined.  Replaces capture.read() (transflow/pixmap/cv.py:54, transflow/flow/sources/cv.py:451, 461). */
+int tf_pngdec_decode_dev(tf_pngdec *dec, const uint8_t *file_host, size_t n, void *pix_dev, int bgr, uint32_t *reject);
+/* The same into host memory (through a buffer of the handle); pix_host is written only when the file is accepted. */
+int tf_pngdec_decode(tf_pngdec *dec, const uint8_t *file_host, size_t n, uint8_t *pix_host, int bgr, uint32_t *reject);
+/* The name of a reject word's reason ("ok" for 0, "unknown" for a number that is none).  No counterpart in the
+   reference, whose capture.read() says only success or not (transflow/pixmap/cv.py:54-55). */
+const char *tf_pngdec_reject_name(uint32_t reject);
 
 /* ---- batch-of-frames mode over the GPUs of one node ----------------------
  * With flags == 0 every Farnebäck pair is independent (transflow/flow/sources/cv.py:478-490: the

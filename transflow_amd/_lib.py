@@ -43,6 +43,12 @@ class TfJpegdecInfo(C.Structure):
                                              "intervals")] + [("reject", C.c_uint32)]
 
 
+class TfPngdecInfo(C.Structure):
+    _fields_ = [(name, C.c_int) for name in ("width", "height", "band_rows", "n_bands", "indexed", "why_not")] + [
+        ("reject", C.c_uint32), ("max_band_bytes", C.c_uint32), ("band_offsets", C.POINTER(C.c_uint32)),
+        ("band_sizes", C.POINTER(C.c_uint32)), ("band_capacity", C.c_size_t)]
+
+
 class TfPolarStep(C.Structure):
     _fields_ = [("op", C.c_int), ("wide", C.c_int), ("imm", C.c_double)]
 
@@ -234,6 +240,7 @@ PROTOTYPES = {
     "tf_png_encode_dev": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_png_encode": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_png_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_png_set_index": (_I, [_P, _I]),
     "tf_png_default_band_rows": (_I, [_I, _I]),
     "tf_png_code_lengths": (_I, [_P]),
     "tf_flowzip_create": (_I, [_PP, C.c_size_t, _I]),
@@ -261,6 +268,12 @@ PROTOTYPES = {
     "tf_jpegdec_decode_dev": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
     "tf_jpegdec_decode": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
     "tf_jpegdec_reject_name": (C.c_char_p, [C.c_uint32]),
+    "tf_pngdec_probe": (_I, [_P, C.c_size_t, C.POINTER(TfPngdecInfo)]),
+    "tf_pngdec_create": (_I, [_PP, _I, _I, C.c_size_t]),
+    "tf_pngdec_destroy": (None, [_P]),
+    "tf_pngdec_decode_dev": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
+    "tf_pngdec_decode": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
+    "tf_pngdec_reject_name": (C.c_char_p, [C.c_uint32]),
     "tf_batch_unique_id": (_I, [_P]),
     "tf_batch_init": (_I, [_PP, _I, _I, _P]),
     "tf_batch_destroy": (None, [_P]),

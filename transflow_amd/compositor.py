@@ -318,7 +318,9 @@ class HipCompositor:
         where it is, the deferred one-launch frame included, and only the file comes down (an output whose product is
         a compressed frame: output/mjpeg.py:58-60).  Not together with lazy_frames.
         png_frames: render() returns a PngFrame (transflow_amd/png.py): the same for the lossless frame-sequence output
-        (output/frames.py).  Not together with lazy_frames or jpeg_frames."""
+        (output/frames.py).  Not together with lazy_frames or jpeg_frames.  png_frames="indexed": the files also carry
+        the band index that lets transflow_amd/pngdec.py decode them on the device (PngEncoder(index=True)); True keeps
+        writing the bytes it wrote before."""
         if png_frames and (lazy_frames or jpeg_frames is not None):
             raise ValueError("png_frames excludes lazy_frames and jpeg_frames: a frame leaves in one form")
         if jpeg_frames is not None:
@@ -334,6 +336,7 @@ class HipCompositor:
         self.lazy_frames = bool(lazy_frames)
         self.jpeg_frames = None if jpeg_frames is None else int(jpeg_frames)
         self.png_frames = bool(png_frames)
+        self.png_index = isinstance(png_frames, str) and png_frames == "indexed"
         self._jpeg = None           # the encoder, made at the first render
         self._png = None
         self._comp = None
@@ -377,7 +380,7 @@ class HipCompositor:
         if self.png_frames:
             if self._png is None:
                 from .png import PngEncoder
-                self._png = PngEncoder(self.height, self.width)
+                self._png = PngEncoder(self.height, self.width, index=self.png_index)
             return self._png.frame(comp)
         if self._frame_pool is None:
             from .device import ArrayPool
@@ -413,6 +416,7 @@ class HipCompositor:
         self.lazy_frames = bool(state.get("lazy_frames", False))
         self.jpeg_frames = state.get("jpeg_frames")
         self.png_frames = bool(state.get("png_frames", False))
+        self.png_index = bool(state.get("png_index", False))
         self._jpeg = None
         self._png = None
         self._comp = None

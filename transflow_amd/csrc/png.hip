@@ -482,6 +482,31 @@ struct tf_png {
     size_t last_chunks = 0;                  // the chunks' bytes of the last encode that ran; 0: none to copy again
 };
 
+// What the host writes in front of the bands' chunks: the signature, IHDR, with `index` the band index tfBX (version 1,
+// flags 0, 0, band_rows, n_bands), and the IDAT of the zlib header.
+static void make_head(tf_png *enc, bool index)
+{
+    enc->head = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+    std::vector<uint8_t> ihdr;
+    put_be32(ihdr, (uint32_t)enc->W), put_be32(ihdr, (uint32_t)enc->H);
+    ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});
+    put_chunk(enc->head, enc->tables, "IHDR", ihdr);
+    if (index) {
+        std::vector<uint8_t> bands{1, 0, 0, 0};
+        put_be32(bands, (uint32_t)enc->band_rows), put_be32(bands, (uint32_t)enc->n_bands);
+        put_chunk(enc->head, enc->tables, "tfBX", bands);
+    }
+    put_chunk(enc->head, enc->tables, "IDAT", {0x78, 0x01});
+}
+
+TF_API int tf_png_set_index(tf_png *enc, int on)
+{
+    TF_REQUIRE(enc, "tf_png_set_index: null pointer");
+    make_head(enc, on != 0);
+    enc->last_chunks = 0; // the head of the last encode is gone: nothing to copy again
+    return TF_OK;
+}
+
 TF_API void tf_png_destroy(tf_png *enc)
 {
     if (!enc)
@@ -536,14 +561,8 @@ TF_API int tf_png_create(tf_png **out, int height, int width, int band_rows)
     if (rc == TF_OK && crc32_bytes(enc->tables.crc, (const uint8_t *)"IDAT", 4) != IDAT_CRC)
         rc = set_error(TF_ERR_STATE, "tf_png_create: the CRC table is wrong");
     enc->slot = (uint32_t)slot;
-    if (rc == TF_OK) {
-        enc->head = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
-        std::vector<uint8_t> ihdr;
-        put_be32(ihdr, (uint32_t)width), put_be32(ihdr, (uint32_t)height);
-        ihdr.insert(ihdr.end(), {8, 2, 0, 0, 0});
-        put_chunk(enc->head, enc->tables, "IHDR", ihdr);
-        put_chunk(enc->head, enc->tables, "IDAT", {0x78, 0x01});
-    }
+    if (rc == TF_OK)
+        make_head(enc, false);
     if (rc == TF_OK)
         rc = enc->dev_tables.alloc(sizeof(Tables));
     if (rc == TF_OK)

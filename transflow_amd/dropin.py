@@ -27,7 +27,7 @@ import os
 import re
 
 _saved = {}
-_pixmap_options = {"stills": False, "mjpeg": False}   # what the installed pixmap factory serves
+_pixmap_options = {"stills": False, "mjpeg": False, "png": False}   # what the installed pixmap factory serves
 _saved_export = []      # (the reference's pipeline module, its NumpyOutput, deviceflow.DEVICE_ROUND) while device_flow_export is on
 
 
@@ -47,8 +47,13 @@ def _is_mjpeg(path) -> bool:
     return isinstance(path, str) and os.path.splitext(path)[1].lower() in MJPEG_EXTS and os.path.isfile(path)
 
 
+def _is_png_sequence(path) -> bool:
+    from .pngdec import is_png_sequence
+    return is_png_sequence(path)
+
+
 def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None, motion_vectors=False,
-                    device_flow_replay=False, mjpeg_inputs=False):
+                    device_flow_replay=False, mjpeg_inputs=False, png_inputs=False):
     from .flow import HipFlowSource
 
     def from_args(cls, flow_path, use_mvs=False, mask_path=None, kernel_path=None, cv_config=None,
@@ -73,6 +78,9 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
         if mjpeg_inputs and not use_mvs and _is_mjpeg(flow_path):   # a raw MJPEG stream: its frames are decoded on the device
             from .jpegdec import MjpegFrameProvider
             flow_path = MjpegFrameProvider(flow_path, size=size)
+        elif png_inputs and not use_mvs and _is_png_sequence(flow_path):   # a PNG frame sequence: likewise
+            from .pngdec import PngSequenceFrameProvider
+            flow_path = PngSequenceFrameProvider(flow_path, size=size)
         return HipFlowSource.from_args(flow_path, use_mvs, mask_path, kernel_path, cv_config, flow_filters, size,
                                        direction, seek_ckpt, seek_time, duration_time, repeat, lock_expr, lock_mode,
                                        lucas_kanade=lucas_kanade, liteflownet=liteflownet,
@@ -118,13 +126,14 @@ def _png_output_from_args(original):
     return classmethod(from_args)
 
 
-def _pixmap_from_args(original, stills=True, mjpeg_inputs=False):
+def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=False):
     from .pixmap import HipPixmapSource
 
     def from_args(cls, path, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat=1, flow_path=None):
         still = stills and re.match(HipPixmapSource.STILL_RE, path.lower().strip()) is not None
         image = stills and os.path.isfile(path) and os.path.splitext(path)[1].lower() in HipPixmapSource.IMAGE_EXTS
-        if not (still or image or (mjpeg_inputs and _is_mjpeg(path))):     # a video: the reference's CvPixmapSource
+        video = (mjpeg_inputs and _is_mjpeg(path)) or (png_inputs and _is_png_sequence(path))
+        if not (still or image or video):                                  # a video: the reference's CvPixmapSource
             return original(path, size, seek=seek, seed=seed, seek_time=seek_time, alteration_path=alteration_path,
                             repeat=repeat, flow_path=flow_path)
         return HipPixmapSource.from_args(path, size, seek, seed, seek_time, alteration_path, repeat, flow_path)
@@ -135,7 +144,7 @@ def _pixmap_from_args(original, stills=True, mjpeg_inputs=False):
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
-            device_flow_replay: bool = False, mjpeg_inputs: bool = False) -> None:
+            device_flow_replay: bool = False, mjpeg_inputs: bool = False, png_inputs: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -157,7 +166,8 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     lossless file, made on the device), and VideoOutput.from_args builds a HipFramesOutput (transflow_amd/output.py) for
     `%d` templates that end in `.png`; any other output is the reference's own and raises a TypeError that names this
     option when it is fed a PngFrame.  Not together with jpeg_frames or lazy_frames.  By default nothing of this is
-    touched.
+    touched.  png_frames="indexed": the same, and the files carry the band index (PngEncoder(index=True), DESIGN.md
+    section 20) that lets `png_inputs` decode them on the device; plain True keeps writing the bytes it wrote before.
     device_flow_export: the flow export (`--export-flow`, `--export-rounded-flow`) writes its `.flow.zip` through
     archive.DeviceFlowArchiveWriter, put where pipeline.py:369 finds NumpyOutput: a DeviceFlow is deflated on the device
     (transflow_amd/flowzip.py) and only the member comes down; and `numpy.round(flow).astype(int)` (pipeline.py:506) of a
@@ -170,7 +180,11 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     member while a lock expression or a polar filter needs the raw flow on the host, are read as before.
     mjpeg_inputs: an existing file with extension .mjpeg / .mjpg (a raw MJPEG stream) is decoded on the device
     (transflow_amd/jpegdec.py), as a flow source's video (a MjpegFrameProvider under the HipFlowSource) and as a pixmap
-    source (HipMjpegPixmapSource); by default such paths stay the reference's, like every other video."""
+    source (HipMjpegPixmapSource); by default such paths stay the reference's, like every other video.
+    png_inputs: a path with a `%...d` field that ends in .png and whose first frame (0 or 1) exists -- a PNG frame
+    sequence -- is read by transflow_amd/pngdec.py, as a flow source's video (a PngSequenceFrameProvider under the
+    HipFlowSource) and as a pixmap source (HipPngSequencePixmapSource): frames with a band index are decoded on the
+    device, the others by Pillow; by default such paths stay the reference's."""
     if jpeg_frames is not None and lazy_frames:
         raise ValueError("jpeg_frames and lazy_frames exclude each other")
     if png_frames and (jpeg_frames is not None or lazy_frames):
@@ -179,14 +193,16 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
         RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet,
-                                                     motion_vectors, bool(device_flow_replay), bool(mjpeg_inputs))
+                                                     motion_vectors, bool(device_flow_replay), bool(mjpeg_inputs),
+                                                     bool(png_inputs))
     if compositor and "compositor" not in _saved:
         from transflow.compositor.compositor import Compositor as RefCompositor
 
         from .compositor import bind_reference_data_layer
         bind_reference_data_layer()    # extra/control.py:155 asks isinstance(layer, DataLayer) of checkpointed layers
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
-        RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames, bool(png_frames))
+        RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames,
+                                                        "indexed" if png_frames == "indexed" else bool(png_frames))
     if jpeg_frames is not None and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
@@ -207,24 +223,26 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         else:
             ref_pipeline.NumpyOutput = DeviceFlowArchiveWriter
         deviceflow.DEVICE_ROUND = True
-    if pixmaps or mjpeg_inputs:
+    if pixmaps or mjpeg_inputs or png_inputs:
         # one factory serves both options: a later call that asks for the other one adds it to what is installed
         from transflow.pixmap.source import PixmapSource as RefPixmapSource
         if "pixmaps" not in _saved:
             _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])
-            _pixmap_options.update(stills=False, mjpeg=False)
-        wanted = dict(stills=_pixmap_options["stills"] or bool(pixmaps), mjpeg=_pixmap_options["mjpeg"] or bool(mjpeg_inputs))
+            _pixmap_options.update(stills=False, mjpeg=False, png=False)
+        wanted = dict(stills=_pixmap_options["stills"] or bool(pixmaps), mjpeg=_pixmap_options["mjpeg"] or bool(mjpeg_inputs),
+                      png=_pixmap_options["png"] or bool(png_inputs))
         if wanted != _pixmap_options:
             _pixmap_options.update(wanted)
             RefPixmapSource.from_args = _saved["pixmaps"][1]              # the reference's own, to be wrapped once
-            RefPixmapSource.from_args = _pixmap_from_args(RefPixmapSource.from_args, wanted["stills"], wanted["mjpeg"])
+            RefPixmapSource.from_args = _pixmap_from_args(RefPixmapSource.from_args, wanted["stills"], wanted["mjpeg"],
+                                                          wanted["png"])
 
 
 def uninstall() -> None:
     for key in list(_saved):
         cls, original = _saved.pop(key)
         cls.from_args = original
-    _pixmap_options.update(stills=False, mjpeg=False)
+    _pixmap_options.update(stills=False, mjpeg=False, png=False)
     while _saved_export:
         from . import deviceflow
         module, original, switch = _saved_export.pop()

@@ -290,7 +290,8 @@ class HipPixmapSource:
     @classmethod
     def from_args(cls, path: str, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat: int = 1,
                   flow_path=None):
-        """source.py:71-120; of the video paths (CvPixmapSource there) only a raw MJPEG stream file is served."""
+        """source.py:71-120; of the video paths (CvPixmapSource there) a raw MJPEG stream file and a `%0Nd.png` frame
+        sequence are served."""
         ext = os.path.splitext(path)[1]
         still_match = re.match(cls.STILL_RE, path.lower().strip())
         if still_match is not None:
@@ -319,6 +320,9 @@ class HipPixmapSource:
             return HipImagePixmapSource(path, alteration_path)
         if os.path.isfile(path) and ext.lower() in cls.MJPEG_EXTS:
             return HipMjpegPixmapSource(path, seek, seek_time, alteration_path, repeat)
+        from .pngdec import is_png_sequence
+        if is_png_sequence(path):
+            return HipPngSequencePixmapSource(path, seek, seek_time, alteration_path, repeat)
         raise NotImplementedError(f"video pixmap source '{path}': not served by this backend (CvPixmapSource)")
 
 
@@ -491,9 +495,13 @@ class HipMjpegPixmapSource(HipPixmapSource):
         if self.seek is not None:                    # cv.py:28-30 reads and drops the frames: nothing to decode for that
             self.capture.pos = min(max(0, int(self.seek)), self.capture.frame_count)
 
-    def __enter__(self):
+    def _open(self):
+        """The frame provider over `path` (a subclass has another)."""
         from .jpegdec import MjpegFrameProvider
-        self.capture = MjpegFrameProvider(self.path, framerate=self._framerate)
+        return MjpegFrameProvider(self.path, framerate=self._framerate)
+
+    def __enter__(self):
+        self.capture = self._open()
         self.width = int(self.capture.width)
         self.height = int(self.capture.height)
         self.framerate = round(self.capture.framerate)
@@ -528,6 +536,16 @@ class HipMjpegPixmapSource(HipPixmapSource):
     def __exit__(self, exc_type, exc_value, exc_traceback):
         if self.capture is not None:
             self.capture.release()
+
+
+class HipPngSequencePixmapSource(HipMjpegPixmapSource):
+    """CvPixmapSource (pixmap/cv.py:11-66) over a `%0Nd.png` pattern or a sequence of PNG files in memory: the same
+    rewind, seek, `repeat`, `length` and alteration as `HipMjpegPixmapSource`, every frame that carries a band index
+    decoded on the device (transflow_amd/pngdec.py) and handed out as an RGB `DevicePixmap`."""
+
+    def _open(self):
+        from .pngdec import PngSequenceFrameProvider
+        return PngSequenceFrameProvider(self.path, framerate=self._framerate)
 
 
 class EndOfPixmap(StopIteration):

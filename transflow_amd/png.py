@@ -54,11 +54,16 @@ class PngEncoder(FrameEncoder):
 
     ENCODE_DEV, ENCODE, COPY_LAST, DESTROY = "tf_png_encode_dev", "tf_png_encode", "tf_png_copy_last", "tf_png_destroy"
 
-    def __init__(self, height: int, width: int, band_rows: int | None = None):
+    def __init__(self, height: int, width: int, band_rows: int | None = None, index: bool = False):
+        """index: the files carry the band index (the ancillary chunk tfBX) that lets
+        transflow_amd/pngdec.py decode them on the device; without it they are the bytes they always were."""
         super().__init__(height, width)
         self._check(self._lib.tf_png_create(C.byref(self._h), self.height, self.width,
                                             0 if band_rows is None else int(band_rows)))
         self.band_rows = int(self._lib.tf_png_band_rows(self._h))
+        self.index = bool(index)
+        if self.index:
+            self._check(self._lib.tf_png_set_index(self._h, 1))
 
     def _first_capacity(self) -> int:   # rendered frames are a part of this
         return self.height * self.width * 3 // 2 + 4096
