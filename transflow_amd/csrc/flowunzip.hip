@@ -210,20 +210,11 @@ using namespace tf::flowunzip;
 struct tf_flowunzip {
     size_t max_stream = 0, max_bands = 0;
     DevBuf consts, stream, offsets, status, band_crc, head, info, out;
-    uint32_t *offsets_host = nullptr; // page-locked: max_bands + 1
-    uint32_t *info_host = nullptr;    // page-locked: the CRC-32, the first rejected band, why
+    PinnedBuf offsets_host; // page-locked uint32_t: max_bands + 1
+    PinnedBuf info_host;    // page-locked uint32_t: the CRC-32, the first rejected band, why
 };
 
-TF_API void tf_flowunzip_destroy(tf_flowunzip *h)
-{
-    if (!h)
-        return;
-    if (h->offsets_host)
-        (void)hipHostFree(h->offsets_host);
-    if (h->info_host)
-        (void)hipHostFree(h->info_host);
-    delete h;
-}
+TF_API void tf_flowunzip_destroy(tf_flowunzip *h) { delete h; }
 
 TF_API int tf_flowunzip_create(tf_flowunzip **out, size_t max_stream_bytes, size_t max_bands)
 {
@@ -251,10 +242,10 @@ TF_API int tf_flowunzip_create(tf_flowunzip **out, size_t max_stream_bytes, size
         rc = h->head.alloc(MAX_SPLIT);
     if (rc == TF_OK)
         rc = h->info.alloc(4 * sizeof(uint32_t));
-    if (rc == TF_OK && hipHostMalloc((void **)&h->offsets_host, (max_bands + 1) * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipHostMalloc((void **)&h->info_host, 4 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: hipHostMalloc failed");
+    if (rc == TF_OK)
+        rc = h->offsets_host.alloc((max_bands + 1) * sizeof(uint32_t));
+    if (rc == TF_OK)
+        rc = h->info_host.alloc(4 * sizeof(uint32_t));
     if (rc == TF_OK && hipMemcpyAsync(h->consts.p, &consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: table upload failed");
     if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
@@ -284,32 +275,34 @@ TF_API int tf_flowunzip_decode_dev(tf_flowunzip *h, const uint8_t *stream_host, 
                "tf_flowunzip_decode_dev: %zu bands, a stream of %zu bytes; the handle is for %zu and %zu", n_bands, stream_bytes, h->max_bands,
                h->max_stream);
     TF_REQUIRE((data_dev && (uintptr_t)data_dev % 4 == 0) || usize == split, "tf_flowunzip_decode_dev: the destination is null or not 4-byte aligned");
+    uint32_t *offsets_host = h->offsets_host.as<uint32_t>();
     size_t at = 0;
     for (size_t b = 0; b < n_bands; b++) {
-        h->offsets_host[b] = (uint32_t)at;
+        offsets_host[b] = (uint32_t)at;
         at += band_sizes_host[b];
         TF_REQUIRE(at <= stream_bytes, "tf_flowunzip_decode_dev: the bands' sizes pass the stream's %zu bytes at band %zu", stream_bytes, b);
     }
-    h->offsets_host[n_bands] = (uint32_t)at;
+    offsets_host[n_bands] = (uint32_t)at;
     Member m;
     m.stream = h->stream.as<uint8_t>(), m.offsets = h->offsets.as<uint32_t>();
     m.stream_bytes = (uint32_t)stream_bytes, m.band_bytes = (uint32_t)band_bytes, m.usize = (uint32_t)usize, m.split = (uint32_t)split;
     m.head = h->head.as<uint8_t>(), m.data = (uint8_t *)data_dev;
     TF_HIP(hipMemcpyAsync(h->stream.p, stream_host, stream_bytes, hipMemcpyHostToDevice, stream()));
-    TF_HIP(hipMemcpyAsync(h->offsets.p, h->offsets_host, (n_bands + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipMemcpyAsync(h->offsets.p, h->offsets_host.p, (n_bands + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream()));
     TF_TRY(launch("fu_inflate", k_fu_inflate, dim3((unsigned)n_bands), dim3(WAVE), 0, m, h->status.as<uint32_t>()));
     TF_TRY(launch("fu_crc", k_fu_crc, dim3((unsigned)n_bands), dim3(WAVE), 0, m, h->consts.as<Crc32Consts>(), h->band_crc.as<uint32_t>()));
     TF_TRY(launch("fu_finish", k_fu_finish, dim3(1), dim3(FINISH_BLOCK), 0, h->band_crc.as<uint32_t>(), h->status.as<uint32_t>(),
                   (uint32_t)n_bands, (uint32_t)band_bytes, (uint32_t)usize, h->consts.as<Crc32Consts>(), h->info.as<uint32_t>()));
-    TF_HIP(hipMemcpyAsync(h->info_host, h->info.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(h->info_host.p, h->info.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
     if (split)
         TF_HIP(hipMemcpyAsync(head_out_host, h->head.p, split, hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
-    if (h->info_host[1] != NO_BAND) {
-        *bad_band = h->info_host[1];
-        return set_error(TF_ERR_STATE, "tf_flowunzip_decode_dev: band %u is no valid band (reason %u)", h->info_host[1], h->info_host[2]);
+    const uint32_t *info = h->info_host.as<uint32_t>();
+    if (info[1] != NO_BAND) {
+        *bad_band = info[1];
+        return set_error(TF_ERR_STATE, "tf_flowunzip_decode_dev: band %u is no valid band (reason %u)", info[1], info[2]);
     }
-    *crc32 = h->info_host[0];
+    *crc32 = info[0];
     return TF_OK;
 }
 

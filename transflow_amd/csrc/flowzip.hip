@@ -562,21 +562,12 @@ struct tf_flowzip {
     uint32_t max_stream = 0, band_bytes = 0;
     int max_bands = 0;
     DevBuf consts, tables, prefix, counts, totals, band_crc, sizes, offsets, info, packed, upload;
-    unsigned long long *info_host = nullptr; // page-locked: [0] the stream's bytes, [1] the overrun flag, [2] the CRC-32
-    Tables *tables_host = nullptr;           // page-locked: the last member's tables
+    PinnedBuf info_host;   // page-locked unsigned long long: [0] the stream's bytes, [1] the overrun flag, [2] the CRC-32
+    PinnedBuf tables_host; // page-locked Tables: the last member's tables
     size_t last_bytes = 0;                   // the stream of the last encode that ran; 0: none to copy again
 };
 
-TF_API void tf_flowzip_destroy(tf_flowzip *enc)
-{
-    if (!enc)
-        return;
-    if (enc->info_host)
-        (void)hipHostFree(enc->info_host);
-    if (enc->tables_host)
-        (void)hipHostFree(enc->tables_host);
-    delete enc;
-}
+TF_API void tf_flowzip_destroy(tf_flowzip *enc) { delete enc; }
 
 TF_API int tf_flowzip_default_band_bytes(void)
 {
@@ -624,10 +615,10 @@ TF_API int tf_flowzip_create(tf_flowzip **out, size_t max_stream_bytes, int band
         rc = enc->info.alloc(4 * sizeof(unsigned long long));
     if (rc == TF_OK) // the bound: every band stored
         rc = enc->packed.alloc((size_t)stream_bound(max_stream_bytes, enc->band_bytes));
-    if (rc == TF_OK && hipHostMalloc((void **)&enc->info_host, 4 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_flowzip_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipHostMalloc((void **)&enc->tables_host, sizeof(Tables), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_flowzip_create: hipHostMalloc failed");
+    if (rc == TF_OK)
+        rc = enc->info_host.alloc(4 * sizeof(unsigned long long));
+    if (rc == TF_OK)
+        rc = enc->tables_host.alloc(sizeof(Tables));
     if (rc == TF_OK && hipMemcpyAsync(enc->consts.p, &consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_flowzip_create: table upload failed");
     if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
@@ -686,13 +677,14 @@ TF_API int tf_flowzip_encode_dev(tf_flowzip *enc, const uint8_t *prefix_host, si
     TF_TRY(launch("fz_emit", k_fz_emit, dim3(n_bands), dim3(WAVE), 0, s, enc->tables.as<Tables>(), enc->sizes.as<uint32_t>(),
                   enc->offsets.as<unsigned long long>(), enc->packed.as<uint8_t>(), enc->packed.bytes,
                   enc->info.as<unsigned long long>()));
-    TF_HIP(hipMemcpyAsync(enc->info_host, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
-    TF_HIP(hipMemcpyAsync(enc->tables_host, enc->tables.p, sizeof(Tables), hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(enc->info_host.p, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(enc->tables_host.p, enc->tables.p, sizeof(Tables), hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
-    if (enc->info_host[1] || enc->info_host[0] > enc->packed.bytes)
+    const unsigned long long *info = enc->info_host.as<unsigned long long>();
+    if (info[1] || info[0] > enc->packed.bytes)
         return set_error(TF_ERR_STATE, "tf_flowzip_encode_dev: the stream outgrew its buffer of %zu bytes", enc->packed.bytes);
-    enc->last_bytes = (size_t)enc->info_host[0];
-    *crc32 = (uint32_t)enc->info_host[2];
+    enc->last_bytes = (size_t)info[0];
+    *crc32 = (uint32_t)info[2];
     return copy_out(enc, "tf_flowzip_encode_dev", out, capacity, n_bytes);
 }
 
@@ -724,7 +716,7 @@ TF_API int tf_flowzip_last_lengths(tf_flowzip *enc, uint8_t *out)
     TF_REQUIRE(enc && out, "tf_flowzip_last_lengths: null pointer");
     if (!enc->last_bytes)
         return set_error(TF_ERR_STATE, "tf_flowzip_last_lengths: nothing has been encoded");
-    memcpy(out, enc->tables_host->lengths, N_SYMBOLS);
+    memcpy(out, enc->tables_host.as<Tables>()->lengths, N_SYMBOLS);
     return TF_OK;
 }
 

@@ -350,18 +350,11 @@ struct tf_jpeg {
     uint32_t slot = 0;
     std::vector<uint8_t> header;
     DevBuf tables, staging, lengths, offsets, info, packed, upload;
-    unsigned long long *info_host = nullptr; // page-locked: [0] the scan's bytes, [1] the overflow flag
+    PinnedBuf info_host; // page-locked unsigned long long: [0] the scan's bytes, [1] the overflow flag
     size_t last_scan = 0;                    // the scan's bytes of the last encode that ran; 0: none to copy again
 };
 
-TF_API void tf_jpeg_destroy(tf_jpeg *enc)
-{
-    if (!enc)
-        return;
-    if (enc->info_host)
-        (void)hipHostFree(enc->info_host);
-    delete enc;
-}
+TF_API void tf_jpeg_destroy(tf_jpeg *enc) { delete enc; }
 
 TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int restart_mcus)
 {
@@ -414,8 +407,8 @@ TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int
         rc = enc->info.alloc(2 * sizeof(unsigned long long));
     if (rc == TF_OK) // the worst case again: every slot full, a marker behind each
         rc = enc->packed.alloc(n * enc->slot + 2 * n);
-    if (rc == TF_OK && hipHostMalloc((void **)&enc->info_host, 2 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_jpeg_create: hipHostMalloc failed");
+    if (rc == TF_OK)
+        rc = enc->info_host.alloc(2 * sizeof(unsigned long long));
     if (rc == TF_OK && hipMemcpyAsync(enc->tables.p, &t, sizeof(Tables), hipMemcpyHostToDevice, stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_jpeg_create: table upload failed");
     if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess) // `t` is on this stack
@@ -477,11 +470,11 @@ TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, s
                   enc->n_intervals, 2u, enc->info.as<unsigned long long>())); // a marker behind each interval
     TF_TRY(pack(enc, dev_capacity));
     enc->last_scan = 0;
-    TF_HIP(hipMemcpyAsync(enc->info_host, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(enc->info_host.p, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
-    if (enc->info_host[1])
+    if (enc->info_host.as<unsigned long long>()[1])
         return set_error(TF_ERR_STATE, "tf_jpeg_encode_dev: an interval outgrew its staging slot of %u bytes", enc->slot);
-    enc->last_scan = (size_t)enc->info_host[0];
+    enc->last_scan = (size_t)enc->info_host.as<unsigned long long>()[0];
     return copy_out(enc, "tf_jpeg_encode_dev", out, capacity, n_bytes);
 }
 

@@ -287,9 +287,9 @@ struct tf_jpegdec {
     int max_w = 0, max_h = 0;
     size_t max_file = 0, max_chunks = 0, max_intervals = 0, plane_room = 0;
     DevBuf tables, scan, counts, offsets, total, markers, status, planes, out;
-    uint8_t *stage = nullptr;       // page-locked: the scan's bytes on their way up
-    DevTables *tables_host = nullptr; // page-locked
-    uint32_t *status_host = nullptr;  // page-locked: the two status words
+    PinnedBuf stage;       // page-locked uint8_t: the scan's bytes on their way up
+    PinnedBuf tables_host; // page-locked DevTables
+    PinnedBuf status_host; // page-locked uint32_t: the two status words
     Header header;
     Raw raw;
 };
@@ -311,18 +311,7 @@ TF_API int tf_jpegdec_probe(const uint8_t *file, size_t n, tf_jpegdec_info *info
     return TF_OK;
 }
 
-TF_API void tf_jpegdec_destroy(tf_jpegdec *dec)
-{
-    if (!dec)
-        return;
-    if (dec->stage)
-        (void)hipHostFree(dec->stage);
-    if (dec->tables_host)
-        (void)hipHostFree(dec->tables_host);
-    if (dec->status_host)
-        (void)hipHostFree(dec->status_host);
-    delete dec;
-}
+TF_API void tf_jpegdec_destroy(tf_jpegdec *dec) { delete dec; }
 
 TF_API int tf_jpegdec_create(tf_jpegdec **out, int max_width, int max_height, size_t max_file_bytes)
 {
@@ -355,12 +344,12 @@ TF_API int tf_jpegdec_create(tf_jpegdec **out, int max_width, int max_height, si
         rc = dec->status.alloc(2 * sizeof(uint32_t));
     if (rc == TF_OK)
         rc = dec->planes.alloc(3 * dec->plane_room);
-    if (rc == TF_OK && hipHostMalloc((void **)&dec->stage, max_file_bytes, hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_jpegdec_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipHostMalloc((void **)&dec->tables_host, sizeof(DevTables), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_jpegdec_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipHostMalloc((void **)&dec->status_host, 2 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_jpegdec_create: hipHostMalloc failed");
+    if (rc == TF_OK)
+        rc = dec->stage.alloc(max_file_bytes);
+    if (rc == TF_OK)
+        rc = dec->tables_host.alloc(sizeof(DevTables));
+    if (rc == TF_OK)
+        rc = dec->status_host.alloc(2 * sizeof(uint32_t));
     if (rc != TF_OK) {
         tf_jpegdec_destroy(dec);
         return rc;
@@ -399,18 +388,18 @@ TF_API int tf_jpegdec_decode_dev(tf_jpegdec *dec, const uint8_t *file, size_t n,
                "tf_jpegdec_decode_dev: planes of %zu bytes, %d intervals: beyond the handle", y_bytes, hd.intervals);
     for (int c = 0; c < 3; c++)
         f.planes[c] = dec->planes.as<uint8_t>() + (size_t)c * dec->plane_room;
-    DevTables &t = *dec->tables_host;
+    DevTables &t = *dec->tables_host.as<DevTables>();
     for (int c = 0; c < 3; c++) {
         const int s = c < hd.components ? c : 0;
         t.dc[c] = hd.dc[s], t.ac[c] = hd.ac[s];
         memcpy(t.quant[c], hd.quant[s], sizeof(t.quant[c]));
     }
-    memcpy(dec->stage, file + hd.scan_offset, scan_bytes);
+    memcpy(dec->stage.p, file + hd.scan_offset, scan_bytes);
     const uint32_t n_chunks = (uint32_t)((scan_bytes + CHUNK - 1) / CHUNK);
     const uint32_t expected = (uint32_t)hd.intervals - 1;
     uint32_t *status = dec->status.as<uint32_t>();
-    TF_HIP(hipMemcpyAsync(dec->scan.p, dec->stage, scan_bytes, hipMemcpyHostToDevice, stream()));
-    TF_HIP(hipMemcpyAsync(dec->tables.p, dec->tables_host, sizeof(DevTables), hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipMemcpyAsync(dec->scan.p, dec->stage.p, scan_bytes, hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipMemcpyAsync(dec->tables.p, dec->tables_host.p, sizeof(DevTables), hipMemcpyHostToDevice, stream()));
     TF_HIP(hipMemsetAsync(dec->status.p, 0xFF, 2 * sizeof(uint32_t), stream()));
     TF_TRY(launch("jd_count", k_jd_count, dim3(cdiv(n_chunks, COUNT_BLOCK)), dim3(COUNT_BLOCK), 0, f.scan, f.scan_bytes, n_chunks,
                   dec->counts.as<uint32_t>(), status));
@@ -423,12 +412,13 @@ TF_API int tf_jpegdec_decode_dev(tf_jpegdec *dec, const uint8_t *file, size_t n,
     const size_t n_px = (size_t)hd.width * hd.height;
     TF_TRY(launch("jd_colour", k_jd_colour, dim3(cdiv(n_px, (size_t)COLOUR_BLOCK * PX_PER_LANE)), dim3(COLOUR_BLOCK), 0, f, (uint8_t *)out_dev, order,
                   (int)((uintptr_t)out_dev % 4 == 0), status, fast_div_setup((uint32_t)hd.width)));
-    TF_HIP(hipMemcpyAsync(dec->status_host, dec->status.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(dec->status_host.p, dec->status.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
-    if (dec->status_host[0] != ST_NONE)
-        *reject = dec->status_host[0];
-    else if (dec->status_host[1] != ST_NONE)
-        *reject = dec->status_host[1] & ((1u << REASON_BITS) - 1);
+    const uint32_t *st = dec->status_host.as<uint32_t>();
+    if (st[0] != ST_NONE)
+        *reject = st[0];
+    else if (st[1] != ST_NONE)
+        *reject = st[1] & ((1u << REASON_BITS) - 1);
     return TF_OK;
 }
 

@@ -477,8 +477,8 @@ struct tf_png {
     Tables tables;
     std::vector<uint8_t> head, tail; // what the host writes in front of the bands' chunks and behind them
     DevBuf dev_tables, filtered, rowsums, staging, lengths, offsets, info, packed, upload;
-    unsigned long long *info_host = nullptr; // page-locked: [0] the chunks' bytes, [1] the overflow flag
-    uint32_t *rowsums_host = nullptr;        // page-locked: the rows' Adler sums
+    PinnedBuf info_host;    // page-locked unsigned long long: [0] the chunks' bytes, [1] the overflow flag
+    PinnedBuf rowsums_host; // page-locked uint32_t: the rows' Adler sums
     size_t last_chunks = 0;                  // the chunks' bytes of the last encode that ran; 0: none to copy again
 };
 
@@ -507,16 +507,7 @@ TF_API int tf_png_set_index(tf_png *enc, int on)
     return TF_OK;
 }
 
-TF_API void tf_png_destroy(tf_png *enc)
-{
-    if (!enc)
-        return;
-    if (enc->info_host)
-        (void)hipHostFree(enc->info_host);
-    if (enc->rowsums_host)
-        (void)hipHostFree(enc->rowsums_host);
-    delete enc;
-}
+TF_API void tf_png_destroy(tf_png *enc) { delete enc; }
 
 TF_API int tf_png_default_band_rows(int height, int width)
 {
@@ -579,10 +570,10 @@ TF_API int tf_png_create(tf_png **out, int height, int width, int band_rows)
         rc = enc->info.alloc(2 * sizeof(unsigned long long));
     if (rc == TF_OK) // the worst case again: every slot full, 12 bytes of chunk around each
         rc = enc->packed.alloc(n * (slot + 12));
-    if (rc == TF_OK && hipHostMalloc((void **)&enc->info_host, 2 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_png_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipHostMalloc((void **)&enc->rowsums_host, enc->rowsums.bytes, hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_png_create: hipHostMalloc failed");
+    if (rc == TF_OK)
+        rc = enc->info_host.alloc(2 * sizeof(unsigned long long));
+    if (rc == TF_OK)
+        rc = enc->rowsums_host.alloc(enc->rowsums.bytes);
     if (rc == TF_OK && hipMemcpyAsync(enc->dev_tables.p, &enc->tables, sizeof(Tables), hipMemcpyHostToDevice, stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_png_create: table upload failed");
     if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
@@ -645,23 +636,23 @@ TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, siz
                   enc->n_bands, 12u, enc->info.as<unsigned long long>())); // a chunk: length, type, data, CRC
     TF_TRY(pack(enc, dev_room(enc, capacity)));
     enc->last_chunks = 0;
-    TF_HIP(hipMemcpyAsync(enc->info_host, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
-    TF_HIP(hipMemcpyAsync(enc->rowsums_host, enc->rowsums.p, enc->rowsums.bytes, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(enc->info_host.p, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(enc->rowsums_host.p, enc->rowsums.p, enc->rowsums.bytes, hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
-    if (enc->info_host[1])
+    if (enc->info_host.as<unsigned long long>()[1])
         return set_error(TF_ERR_STATE, "tf_png_encode_dev: a band outgrew its staging slot of %u bytes", enc->slot);
     // Adler-32 of the whole stream from the rows' sums: a row of L bytes moves s2 by L s1 + its weighted sum
     uint64_t s1 = 1, s2 = 0;
     for (int r = 0; r < enc->H; r++) {
-        s2 = (s2 + (enc->row_bytes % ADLER_BASE) * s1 + enc->rowsums_host[2 * r + 1]) % ADLER_BASE;
-        s1 = (s1 + enc->rowsums_host[2 * r]) % ADLER_BASE;
+        s2 = (s2 + (enc->row_bytes % ADLER_BASE) * s1 + enc->rowsums_host.as<uint32_t>()[2 * r + 1]) % ADLER_BASE;
+        s1 = (s1 + enc->rowsums_host.as<uint32_t>()[2 * r]) % ADLER_BASE;
     }
     enc->tail.clear();
     std::vector<uint8_t> last{0x01, 0x00, 0x00, 0xFF, 0xFF};
     put_be32(last, (uint32_t)((s2 << 16) | s1));
     put_chunk(enc->tail, enc->tables, "IDAT", last);
     put_chunk(enc->tail, enc->tables, "IEND", {});
-    enc->last_chunks = (size_t)enc->info_host[0];
+    enc->last_chunks = (size_t)enc->info_host.as<unsigned long long>()[0];
     return copy_out(enc, "tf_png_encode_dev", out, capacity, n_bytes);
 }
 

@@ -383,10 +383,10 @@ struct tf_pngdec {
     size_t max_file = 0, filt_bytes = 0;
     Crc32Consts consts;
     DevBuf dev_consts, file, bands, filt, rowsums, status, out;
-    uint8_t *stage = nullptr;         // page-locked: the file on its way up
-    uint32_t *bands_host = nullptr;   // page-locked: max_h offsets, then max_h sizes
-    uint32_t *rowsums_host = nullptr; // page-locked
-    uint32_t *status_host = nullptr;  // page-locked
+    PinnedBuf stage;        // page-locked uint8_t: the file on its way up
+    PinnedBuf bands_host;   // page-locked uint32_t: max_h offsets, then max_h sizes
+    PinnedBuf rowsums_host; // page-locked uint32_t
+    PinnedBuf status_host;  // page-locked uint32_t
     Layout layout;
     flowunzip::Code lit, dist; // the walk's working space (the tail's block)
     uint8_t lengths[flowunzip::MAX_LENGTHS];
@@ -414,20 +414,7 @@ TF_API int tf_pngdec_probe(const uint8_t *file, size_t n, tf_pngdec_info *info)
     return TF_OK;
 }
 
-TF_API void tf_pngdec_destroy(tf_pngdec *dec)
-{
-    if (!dec)
-        return;
-    if (dec->stage)
-        (void)hipHostFree(dec->stage);
-    if (dec->bands_host)
-        (void)hipHostFree(dec->bands_host);
-    if (dec->rowsums_host)
-        (void)hipHostFree(dec->rowsums_host);
-    if (dec->status_host)
-        (void)hipHostFree(dec->status_host);
-    delete dec;
-}
+TF_API void tf_pngdec_destroy(tf_pngdec *dec) { delete dec; }
 
 TF_API int tf_pngdec_create(tf_pngdec **out, int max_width, int max_height, size_t max_file_bytes)
 {
@@ -457,14 +444,14 @@ TF_API int tf_pngdec_create(tf_pngdec **out, int max_width, int max_height, size
         rc = dec->rowsums.alloc(2 * h * sizeof(uint32_t));
     if (rc == TF_OK)
         rc = dec->status.alloc(ST_WORDS * sizeof(uint32_t));
-    if (rc == TF_OK && hipHostMalloc((void **)&dec->stage, max_file_bytes, hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_pngdec_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipHostMalloc((void **)&dec->bands_host, 2 * h * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_pngdec_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipHostMalloc((void **)&dec->rowsums_host, 2 * h * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_pngdec_create: hipHostMalloc failed");
-    if (rc == TF_OK && hipHostMalloc((void **)&dec->status_host, ST_WORDS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_pngdec_create: hipHostMalloc failed");
+    if (rc == TF_OK)
+        rc = dec->stage.alloc(max_file_bytes);
+    if (rc == TF_OK)
+        rc = dec->bands_host.alloc(2 * h * sizeof(uint32_t));
+    if (rc == TF_OK)
+        rc = dec->rowsums_host.alloc(2 * h * sizeof(uint32_t));
+    if (rc == TF_OK)
+        rc = dec->status_host.alloc(ST_WORDS * sizeof(uint32_t));
     if (rc == TF_OK && hipMemcpyAsync(dec->dev_consts.p, &dec->consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
         rc = set_error(TF_ERR_HIP, "tf_pngdec_create: table upload failed");
     if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
@@ -490,7 +477,7 @@ TF_API int tf_pngdec_decode_dev(tf_pngdec *dec, const uint8_t *file, size_t n, v
     *reject = R_OK;
     TF_REQUIRE(n <= dec->max_file, "tf_pngdec_decode_dev: a file of %zu bytes, the handle is for %zu", n, dec->max_file);
     Layout &l = dec->layout;
-    uint32_t *band_off = dec->bands_host, *band_size = dec->bands_host + dec->max_h;
+    uint32_t *band_off = dec->bands_host.as<uint32_t>(), *band_size = band_off + dec->max_h;
     uint32_t r = walk(file, n, (uint32_t)dec->max_w, (uint32_t)dec->max_h, l, band_off, band_size, (size_t)dec->max_h, dec->lit, dec->dist,
                       dec->lengths);
     if (r != R_OK)
@@ -514,26 +501,26 @@ TF_API int tf_pngdec_decode_dev(tf_pngdec *dec, const uint8_t *file, size_t n, v
     f.filt_bytes = (size_t)(l.n_bands - 1) * f.slot_stride + (size_t)(band_row_count(l, l.n_bands - 1) * L) + FILT_PAD;
     TF_REQUIRE(f.filt_bytes <= dec->filt_bytes && l.n_bands <= (uint32_t)dec->max_h, "tf_pngdec_decode_dev: %u bands of %u bytes: beyond the handle",
                l.n_bands, f.slot_stride); // (never: the frame is within the handle's size)
-    memcpy(dec->stage, file, n);
+    memcpy(dec->stage.p, file, n);
     uint32_t *status = dec->status.as<uint32_t>();
-    TF_HIP(hipMemcpyAsync(dec->file.p, dec->stage, n, hipMemcpyHostToDevice, stream()));
-    TF_HIP(hipMemcpyAsync(dec->bands.p, dec->bands_host, 2 * (size_t)dec->max_h * sizeof(uint32_t), hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipMemcpyAsync(dec->file.p, dec->stage.p, n, hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipMemcpyAsync(dec->bands.p, dec->bands_host.p, 2 * (size_t)dec->max_h * sizeof(uint32_t), hipMemcpyHostToDevice, stream()));
     TF_HIP(hipMemsetAsync(dec->status.p, 0xFF, ST_WORDS * sizeof(uint32_t), stream()));
     TF_TRY(launch("pd_crc", k_pd_crc, dim3(l.n_bands), dim3(WAVE), 0, f, dec->dev_consts.as<Crc32Consts>(), status));
     TF_TRY(launch("pd_inflate", k_pd_inflate, dim3(l.n_bands), dim3(WAVE), 0, f, status));
     TF_TRY(launch("pd_rows", k_pd_rows, dim3(l.height), dim3(ROWS_BLOCK), 0, f, dec->rowsums.as<uint32_t>(), status));
     TF_TRY(launch("pd_unfilter", k_pd_unfilter, dim3(l.height), dim3(WAVE), 0, f, (uint8_t *)pix_dev, bgr, (const uint32_t *)status));
-    TF_HIP(hipMemcpyAsync(dec->status_host, dec->status.p, ST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
-    TF_HIP(hipMemcpyAsync(dec->rowsums_host, dec->rowsums.p, 2 * (size_t)l.height * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(dec->status_host.p, dec->status.p, ST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipMemcpyAsync(dec->rowsums_host.p, dec->rowsums.p, 2 * (size_t)l.height * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
-    const uint32_t *st = dec->status_host;
+    const uint32_t *st = dec->status_host.as<uint32_t>();
     if (st[ST_CRC] != ST_NONE)
         return rejected(reject, make_reject(R_CHUNK_CRC, st[ST_CRC]));
     if (st[ST_BAND] != ST_NONE)
         return rejected(reject, make_reject(R_BAND + (st[ST_BAND] & 0xFFu), st[ST_BAND] >> 8));
     if (st[ST_FILTER] != ST_NONE)
         return rejected(reject, make_reject(R_FILTER_TYPE, st[ST_FILTER]));
-    if (adler_of_rows(dec->rowsums_host, l.height, L) != l.adler)
+    if (adler_of_rows(dec->rowsums_host.as<uint32_t>(), l.height, L) != l.adler)
         return rejected(reject, R_ADLER);
     return TF_OK;
 }

@@ -144,6 +144,20 @@ void DevBuf::release()
     borrowed = false;
 }
 
+int PinnedBuf::alloc(size_t n)
+{
+    release();
+    TF_HIP(hipHostMalloc(&p, n, hipHostMallocDefault));
+    return TF_OK;
+}
+
+void PinnedBuf::release()
+{
+    if (p)
+        (void)hipHostFree(p);
+    p = nullptr;
+}
+
 // ---- profiler ---------------------------------------------------------------------
 struct ProfRec {
     const char *name;

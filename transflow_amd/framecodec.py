@@ -1,11 +1,16 @@
-"""What the device's frame codecs (transflow_amd/jpeg.py, transflow_amd/png.py) have in common on the Python side: the
-frame that travels as a compressed file, and the wrapper of a handle that encodes frames of one size."""
+"""What the device's frame codecs have in common on the Python side.  For the encoders (transflow_amd/jpeg.py,
+transflow_amd/png.py): the frame that travels as a compressed file, and the wrapper of a handle that encodes frames of
+one size.  For the decoders (transflow_amd/jpegdec.py, transflow_amd/pngdec.py): the host's way to the same pixels, the
+wrapper of a handle that decodes frames up to a size, and the frame provider over a sequence of compressed files."""
 from __future__ import annotations
 
 import ctypes as C
 import io
+import os
 
 import numpy as np
+
+from .pixmap import DevicePixmap, _dev_alloc, _recorded_event
 
 
 class EncodedFrame:
@@ -120,3 +125,156 @@ class FrameEncoder:
             self.close()
         except Exception:
             pass
+
+
+def bytes_of(data) -> bytes:
+    return data.data if hasattr(data, "data") and isinstance(getattr(data, "data"), (bytes, bytearray)) else bytes(data)
+
+
+def pillow_decode(data, order: str = "rgb") -> np.ndarray:
+    """The host's way: Pillow (libjpeg, zlib)."""
+    import PIL.Image
+    rgb = np.array(PIL.Image.open(io.BytesIO(bytes_of(data))).convert("RGB"))
+    return np.ascontiguousarray(rgb[:, :, ::-1]) if order == "bgr" else rgb
+
+
+class FrameDecoder:
+    """A handle of the library that decodes frames of up to max_width x max_height; its staging and device buffers are
+    allocated once (and again for a file larger than any before it).  A subclass names its C entry points (CREATE,
+    DECODE_DEV, DESTROY) and has `_verdict(rc, reject)`, which raises what a failed call means, and `decode`."""
+
+    CREATE = DECODE_DEV = DESTROY = None
+    ORDERS = {"rgb": 0, "bgr": 1}
+
+    def __init__(self, max_width: int, max_height: int, device: int | None = None, max_file_bytes: int | None = None):
+        from . import _lib
+        self._lib = _lib.load()
+        self._check = _lib.check
+        self._state = _lib.TF_ERR_STATE
+        if device is not None:
+            self._check(self._lib.tf_init(int(device)))
+        self.max_width, self.max_height = int(max_width), int(max_height)
+        self._file_room = int(max_file_bytes) if max_file_bytes else self.max_width * self.max_height * 3 // 2 + 65536
+        self._h = C.c_void_p()
+        self._create()
+        self.fallbacks = 0
+
+    def _create(self) -> None:
+        self._check(getattr(self._lib, self.CREATE)(C.byref(self._h), self.max_width, self.max_height, self._file_room))
+
+    def _room_for(self, nbytes: int) -> None:
+        if nbytes > self._file_room:
+            self.close()
+            self._file_room = int(nbytes) * 2
+            self._create()
+
+    def _decode(self, raw: bytes, order: str, info) -> DevicePixmap:
+        """What every `decode` ends with: `raw`, whose header says `info`, into a new device buffer."""
+        if info.width > self.max_width or info.height > self.max_height:
+            raise ValueError(f"a frame of {info.width}x{info.height}; the decoder is for {self.max_width}x{self.max_height}")
+        self._room_for(len(raw))
+        buf = _dev_alloc(info.height * info.width * 3)
+        reject = C.c_uint32()
+        rc = getattr(self._lib, self.DECODE_DEV)(self._h, raw, len(raw), C.c_void_p(buf.ptr), self.ORDERS[order], C.byref(reject))
+        try:
+            self._verdict(rc, reject.value)
+        except Exception:
+            buf.close()
+            raise
+        return DevicePixmap((info.height, info.width, 3), buf, _recorded_event())
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(self._lib, self.DESTROY)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CompressedFrameProvider:
+    """A frame provider (transflow_amd/flow.py: `width`, `height`, `framerate`, `frame_count`, `seek_start`, `read`,
+    `release`) whose frames are compressed files decoded on the device: a `%0Nd` pattern (numbered from the first of 0
+    or 1 that exists) or a sequence of `bytes` / `EncodedFrame`.  `read()` returns a BGR `DevicePixmap`: `HipFlowSource`
+    hands it to a Farnebäck handle by its device address, and `np.asarray` of it is the host frame for everything else.
+    `fallbacks` counts the frames Pillow decoded.  A subclass names its DECODER and what an EMPTY source is told, and
+    has `_first_size(raw)` -- (width, height) of the first frame -- and `decode_frame(index, order)`."""
+
+    DECODER = EMPTY = None
+
+    def __init__(self, source, framerate: float, size, device_decode: bool, device: int | None):
+        self.framerate = float(framerate)
+        self.device_decode, self.device = bool(device_decode), device
+        if isinstance(source, (str, os.PathLike)):
+            self.frame_count = self._open_path(os.fspath(source))
+        else:
+            self._frames = list(source)
+            self.frame_count = len(self._frames)
+        if self.frame_count == 0:
+            raise ValueError(self.EMPTY)
+        self._frame_size = self._first_size(self._get(0))
+        self.width, self.height = self._frame_size if size is None else (int(size[0]), int(size[1]))
+        self._decoder = None
+        self._host_fallbacks = 0
+        self.pos = 0
+
+    def _open_path(self, path: str) -> int:
+        first = next((k for k in (0, 1) if os.path.isfile(path % k)), None)
+        if first is None:
+            raise FileNotFoundError(f"no frame {path % 0} or {path % 1}")
+        self._files = []
+        while os.path.isfile(path % (first + len(self._files))):
+            self._files.append(path % (first + len(self._files)))
+        return len(self._files)
+
+    def _get(self, i: int) -> bytes:
+        if hasattr(self, "_files"):
+            with open(self._files[i], "rb") as f:
+                return f.read()
+        return bytes_of(self._frames[i])
+
+    def __getstate__(self):                          # a decoder's handle belongs to its process
+        state = dict(self.__dict__)
+        if state.get("_decoder") is not None:
+            state["_host_fallbacks"] = self.fallbacks
+            state["_decoder"] = None
+        return state
+
+    @property
+    def fallbacks(self) -> int:
+        return self._host_fallbacks + (self._decoder.fallbacks if self._decoder is not None else 0)
+
+    def _host_frame(self, raw: bytes, order: str) -> DevicePixmap:
+        self._host_fallbacks += 1
+        return DevicePixmap.from_host(pillow_decode(raw, order))
+
+    def _decoder_for(self, info) -> FrameDecoder:
+        if self._decoder is None or info.width > self._decoder.max_width or info.height > self._decoder.max_height:
+            room = (max(info.width, self._frame_size[0]), max(info.height, self._frame_size[1]))
+            if self._decoder is not None:            # a larger frame: the old handle's buffers go now, not with the collector
+                room = (max(room[0], self._decoder.max_width), max(room[1], self._decoder.max_height))
+                self._drop_decoder()
+            self._decoder = self.DECODER(room[0], room[1], self.device)
+        return self._decoder
+
+    def seek_start(self):
+        self.pos = 0
+
+    def read(self, order: str = "bgr"):
+        if self.pos >= self.frame_count:
+            return None
+        frame = self.decode_frame(self.pos, order)
+        self.pos += 1
+        return frame
+
+    def _drop_decoder(self):                        # its count stays
+        if self._decoder is not None:
+            self._host_fallbacks += self._decoder.fallbacks
+            self._decoder.close()
+            self._decoder = None
+
+    def release(self):
+        self._drop_decoder()

@@ -12,12 +12,10 @@ transflow_amd/flow.py) over a `%0Nd.png` pattern or a sequence of files in memor
 from __future__ import annotations
 
 import ctypes as C
-import io
 import os
 
-import numpy as np
-
-from .pixmap import DevicePixmap, _recorded_event
+from .framecodec import CompressedFrameProvider, FrameDecoder, bytes_of as _bytes_of, pillow_decode
+from .pixmap import DevicePixmap
 
 # pngdec_common.h's Reject (tests/pngdec_ref.py has the same names)
 REJECT_NAMES = {0: "ok", 1: "signature", 2: "truncated", 3: "ihdr", 4: "size", 5: "index", 6: "zlib_header", 7: "tail",
@@ -80,10 +78,6 @@ class PngInfo:
         return "PngInfo(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.__slots__[:-1]) + ")"
 
 
-def _bytes_of(data) -> bytes:
-    return data.data if hasattr(data, "data") and isinstance(getattr(data, "data"), (bytes, bytearray)) else bytes(data)
-
-
 def reject_name(reject: int) -> str:
     from . import _lib
     return _lib.load().tf_pngdec_reject_name(int(reject)).decode()
@@ -109,37 +103,15 @@ def probe(data) -> PngInfo:
     return PngInfo(info, bands)
 
 
-def pillow_decode(data, order: str = "rgb") -> np.ndarray:
-    """The host's way: Pillow."""
-    import PIL.Image
-    rgb = np.array(PIL.Image.open(io.BytesIO(_bytes_of(data))).convert("RGB"))
-    return np.ascontiguousarray(rgb[:, :, ::-1]) if order == "bgr" else rgb
+class PngDecoder(FrameDecoder):
+    """tf_pngdec: frames of up to max_width x max_height."""
 
+    CREATE, DECODE_DEV, DESTROY = "tf_pngdec_create", "tf_pngdec_decode_dev", "tf_pngdec_destroy"
 
-class PngDecoder:
-    """tf_pngdec: frames of up to max_width x max_height; its staging and device buffers are allocated once (and again
-    for a file larger than any before it)."""
-
-    ORDERS = {"rgb": 0, "bgr": 1}
-
-    def __init__(self, max_width: int, max_height: int, device: int | None = None, max_file_bytes: int | None = None):
-        from . import _lib
-        self._lib = _lib.load()
-        self._check = _lib.check
-        self._state = _lib.TF_ERR_STATE
-        if device is not None:
-            self._check(self._lib.tf_init(int(device)))
-        self.max_width, self.max_height = int(max_width), int(max_height)
-        self._file_room = int(max_file_bytes) if max_file_bytes else self.max_width * self.max_height * 3 // 2 + 65536
-        self._h = C.c_void_p()
-        self._check(self._lib.tf_pngdec_create(C.byref(self._h), self.max_width, self.max_height, self._file_room))
-        self.fallbacks = 0
-
-    def _room_for(self, nbytes: int) -> None:
-        if nbytes > self._file_room:
-            self.close()
-            self._file_room = int(nbytes) * 2
-            self._check(self._lib.tf_pngdec_create(C.byref(self._h), self.max_width, self.max_height, self._file_room))
+    def _verdict(self, rc: int, reject: int) -> None:
+        if rc == self._state and reject:
+            raise _rejected(reject)
+        self._check(rc)
 
     def decode(self, data, order: str = "rgb", info: PngInfo | None = None) -> DevicePixmap:
         """The file's pixels, uint8 (H, W, 3) in `order`, in device memory.  `PngRejected` for a malformed file and for
@@ -148,7 +120,6 @@ class PngDecoder:
         and of at most twice that and 1024 compressed bytes) and for a frame larger than the decoder was made for.
         `decode_or_host` takes the first two the host's way.  info: `probe(data)`, from a caller that has looked
         already."""
-        from .pixmap import _dev_alloc
         raw = _bytes_of(data)
         if info is None:
             info = probe(raw)
@@ -157,18 +128,7 @@ class PngDecoder:
         if not info.within_bound:
             raise ValueError(f"a band of {info.band_bytes} bytes in up to {info.max_band_bytes} compressed: beyond the bound on "
                              f"what goes to the device ({MAX_BAND_BYTES}, {max_band_compressed(info.band_bytes)})")
-        if info.width > self.max_width or info.height > self.max_height:
-            raise ValueError(f"a frame of {info.width}x{info.height}; the decoder is for {self.max_width}x{self.max_height}")
-        self._room_for(len(raw))
-        buf = _dev_alloc(info.height * info.width * 3)
-        reject = C.c_uint32()
-        rc = self._lib.tf_pngdec_decode_dev(self._h, raw, len(raw), C.c_void_p(buf.ptr), self.ORDERS[order], C.byref(reject))
-        if rc != 0:
-            buf.close()
-            if rc == self._state and reject.value:
-                raise _rejected(reject.value)
-            self._check(rc)
-        return DevicePixmap((info.height, info.width, 3), buf, _recorded_event())
+        return self._decode(raw, order, info)
 
     def decode_or_host(self, data, order: str = "rgb", info: PngInfo | None = None) -> DevicePixmap:
         """`decode`, or Pillow's pixels sent up for a file that is not for the device or asks more of it than an
@@ -180,17 +140,6 @@ class PngDecoder:
             self.fallbacks += 1
             return DevicePixmap.from_host(pillow_decode(raw, order))
         return self.decode(raw, order, info)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.tf_pngdec_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def is_png_sequence(path) -> bool:
@@ -204,92 +153,31 @@ def is_png_sequence(path) -> bool:
         return False
 
 
-class PngSequenceFrameProvider:
-    """A frame provider (transflow_amd/flow.py: `width`, `height`, `framerate`, `frame_count`, `seek_start`, `read`,
-    `release`) whose frames are PNG files decoded on the device.
+class PngSequenceFrameProvider(CompressedFrameProvider):
+    """A `CompressedFrameProvider` of PNG files.
 
-    source: a `%0Nd.png` pattern (numbered from the first of 0 or 1 that exists) or a sequence of `bytes` /
-    `PngFrame`.  `read()` returns a BGR `DevicePixmap`: `HipFlowSource` hands it to a Farnebäck handle by its device
-    address, and `np.asarray` of it is the host frame for everything else.  A frame without a band index, or of another
+    source: a `%0Nd.png` pattern or a sequence of `bytes` / `PngFrame`.  A frame without a band index, or of another
     kind of PNG, is decoded by Pillow; `fallbacks` counts the frames that went that way.  A malformed or corrupt frame
     raises `PngRejected` with the frame's number.  `device_decode=False` decodes every frame with Pillow."""
 
+    DECODER, EMPTY = PngDecoder, "the PNG sequence holds no frame"
+
     def __init__(self, source, framerate: float = 25.0, size=None, device_decode: bool = True, device: int | None = None):
-        self.framerate = float(framerate)
-        self.device_decode, self.device = bool(device_decode), device
-        if isinstance(source, (str, os.PathLike)):
-            path = os.fspath(source)
-            first = next((k for k in (0, 1) if os.path.isfile(path % k)), None)
-            if first is None:
-                raise FileNotFoundError(f"no frame {path % 0} or {path % 1}")
-            self._files = []
-            k = first
-            while os.path.isfile(path % k):
-                self._files.append(path % k)
-                k += 1
-            self.frame_count = len(self._files)
-        else:
-            self._frames = list(source)
-            self.frame_count = len(self._frames)
-        if self.frame_count == 0:
-            raise ValueError("the PNG sequence holds no frame")
+        CompressedFrameProvider.__init__(self, source, framerate, size, device_decode, device)
+
+    def _first_size(self, raw: bytes):
         try:
-            info = probe(self._get(0))
+            info = probe(raw)
         except PngRejected as err:
             raise PngRejected(err.reason, err.where, 0) from None
-        self._frame_size = (info.width, info.height)
-        self.width, self.height = self._frame_size if size is None else (int(size[0]), int(size[1]))
-        self._decoder = None
-        self._host_fallbacks = 0
-        self.pos = 0
-
-    def _get(self, i: int) -> bytes:
-        if hasattr(self, "_files"):
-            with open(self._files[i], "rb") as f:
-                return f.read()
-        return _bytes_of(self._frames[i])
-
-    def __getstate__(self):                          # a decoder's handle belongs to its process
-        state = dict(self.__dict__)
-        if state.get("_decoder") is not None:
-            state["_host_fallbacks"] = self.fallbacks
-            state["_decoder"] = None
-        return state
-
-    @property
-    def fallbacks(self) -> int:
-        return self._host_fallbacks + (self._decoder.fallbacks if self._decoder is not None else 0)
-
-    def seek_start(self):
-        self.pos = 0
+        return info.width, info.height
 
     def decode_frame(self, index: int, order: str = "bgr") -> DevicePixmap:
         raw = self._get(index)
         try:
             info = probe(raw)
             if not self.device_decode or not info.indexed:
-                self._host_fallbacks += 1
-                return DevicePixmap.from_host(pillow_decode(raw, order))
-            if self._decoder is None or info.width > self._decoder.max_width or info.height > self._decoder.max_height:
-                room = (max(info.width, self._frame_size[0]), max(info.height, self._frame_size[1]))
-                if self._decoder is not None:        # a larger frame: the old handle's buffers go now, not with the collector
-                    room = (max(room[0], self._decoder.max_width), max(room[1], self._decoder.max_height))
-                    self._host_fallbacks += self._decoder.fallbacks
-                    self._decoder.close()
-                self._decoder = PngDecoder(room[0], room[1], self.device)
-            return self._decoder.decode_or_host(raw, order, info)
+                return self._host_frame(raw, order)
+            return self._decoder_for(info).decode_or_host(raw, order, info)
         except PngRejected as err:
             raise PngRejected(err.reason, err.where, index) from None
-
-    def read(self, order: str = "bgr"):
-        if self.pos >= self.frame_count:
-            return None
-        frame = self.decode_frame(self.pos, order)
-        self.pos += 1
-        return frame
-
-    def release(self):
-        if self._decoder is not None:
-            self._host_fallbacks += self._decoder.fallbacks
-            self._decoder.close()
-            self._decoder = None
