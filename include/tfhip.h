@@ -71,6 +71,11 @@ int tf_device_count(int *count);
                           for bit), 0 = a pre-pass computes the values (equal up to the association of double
                           additions, ~1e-16), -1 = whichever is cheaper for the launch (read per call)
      "fb_segs"        0   > 0: that many row segments per column (0: chosen per launch; read per call)
+     "jd_par_sub_bytes"  0  > 0: bytes of a subsequence of tf_jpegdec's parallel scan path, 16 to 1024 (0: the measured
+                          best, 64; read per decode).  "jd_par_group_subs" 0: > 0: subsequences per work-group of that
+                          path's synchronisation, 64, 128 or 256 (0: the measured best, 64; read per decode).
+                          "jd_par_staged" 0: 1 = the synchronisation reads a work-group's share of the scan from LDS
+                          where the subsequence is a power of two and the share fits 48 KB.  Test knobs
    Unknown names and out-of-range values return TF_ERR_ARG.  The environment is never read. */
 int tf_set_option(const char *name, long value);
 int tf_get_option(const char *name, long *value);
@@ -823,6 +828,21 @@ int tf_jpegdec_decode_dev(tf_jpegdec *dec, const uint8_t *file, size_t n, void *
 /* The same into host memory (through a buffer of the handle); out_host is written only when *reject == 0. */
 int tf_jpegdec_decode(tf_jpegdec *dec, const uint8_t *file, size_t n, uint8_t *out_host, int order, uint32_t *reject);
 const char *tf_jpegdec_reject_name(uint32_t reject);
+/* How a file WITHOUT a restart interval is entropy-decoded (files with DRI go one wave per interval in either mode):
+   0 (the default): as one interval, by one wave.  1: the scan is cut into subsequences of bytes, one lane each; every
+   lane decodes from a guessed state and hands its exit state to its neighbour until nothing changes (a Huffman decoder
+   started at a wrong bit finds the right code boundaries by itself after a while), then the blocks' numbers and DC
+   predictions are summed up and every lane decodes once more into place.  Same pixels, same verdicts.  The path's
+   buffers (sized by the handle's limits) are allocated by the first decode that takes it. */
+int tf_jpegdec_set_scan_mode(tf_jpegdec *dec, int mode);
+/* Of the last decode that took the parallel path: subsequences, work-groups, launches of the synchronisation kernel
+   (at most work-groups + 1), the largest number of rounds any work-group made in a launch (at most its lanes). */
+int tf_jpegdec_par_stats(tf_jpegdec *dec, uint32_t out[4]);
+/* For tests: per subsequence of that decode, 8 words into rows[capacity][8] -- the entry state's bit position (low word,
+   high word; a bit index into the scan, stuffed bytes included), block within the MCU and coefficient index k (0: a DC
+   code comes next), the number of the first block that begins in the subsequence and the three components' DC
+   predictions there (modulo 2^32).  *n_subs: the subsequences; TF_ERR_ARG when capacity is less. */
+int tf_jpegdec_par_entries(tf_jpegdec *dec, uint32_t *rows, size_t capacity, uint32_t *n_subs);
 
 /* ---- banded PNG frames decoded on the device (transflow_amd/csrc/pngdec.hip) --------------
  * The inverse of tf_png for the files it writes with tf_png_set_index, and for any file of that shape: 8-bit RGB, colour

@@ -268,6 +268,9 @@ PROTOTYPES = {
     "tf_jpegdec_decode_dev": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
     "tf_jpegdec_decode": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
     "tf_jpegdec_reject_name": (C.c_char_p, [C.c_uint32]),
+    "tf_jpegdec_set_scan_mode": (_I, [_P, _I]),
+    "tf_jpegdec_par_stats": (_I, [_P, C.POINTER(C.c_uint32)]),
+    "tf_jpegdec_par_entries": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_uint32)]),
     "tf_pngdec_probe": (_I, [_P, C.c_size_t, C.POINTER(TfPngdecInfo)]),
     "tf_pngdec_create": (_I, [_PP, _I, _I, C.c_size_t]),
     "tf_pngdec_destroy": (None, [_P]),

@@ -25,7 +25,21 @@
 // A file is untrusted.  Nothing it holds steers an address: intervals are clamped to the scan, the window to the
 // interval, coefficient indices go through a table of 64 entries, and a plane store is placed by the MCU's number alone.
 // Every kernel behind the marker scan returns at once when the status words already hold a rejection.
+//
+// A scan without restart markers is one interval, hence one wave, for k_jd_entropy.  tf_jpegdec_set_scan_mode(dec, 1)
+// sends such a file down a second entropy path instead (jpegdec_par_common.h has its rules and the lane function):
+//   k_jd_par_init   the scan minus the EOI is cut into subsequences of S bytes; each gets a guessed entry state.
+//   k_jd_par_sync   one lane per subsequence, G per work-group: every lane decodes leniently from its entry, storing
+//                   nothing, and hands its exit state to its neighbour, until no entry of the group changes (at most G
+//                   rounds).  The group's exit goes to the next group's first entry; the host launches again while any
+//                   of those changed (at most groups + 1 launches; a group whose first entry did not change does nothing).
+//   k_slot_scan     four exclusive sums over the subsequences: the blocks that begin in each, the DC differences per component.
+//   k_jd_par_write  one lane per subsequence decodes strictly from its now exact entry and stores undequantised int16
+//                   coefficients at block * 64 + ZIGZAG[k]; the first fault (the lowest subsequence) is the verdict.
+//   k_jd_par_idct   eight lanes per block: dequantise, column pass, row pass, the 8-byte stores of k_jd_entropy.
+// A store is placed by a block number checked against the picture's block count, never by what the file says.
 #include "jpegdec_common.h"
+#include "jpegdec_par_common.h"
 #include "stream_common.h"
 
 #include <cstring>
@@ -198,6 +212,217 @@ __global__ __launch_bounds__(WAVE) void k_jd_entropy(const Frame f, const DevTab
     }
 }
 
+// ---- the parallel path for a scan without restart markers -------------------------------------------------------------
+constexpr int PAR_BLOCK = 256;         // threads of the init and write kernels
+constexpr int PAR_MAX_GROUP = 256;     // G: subsequences (lanes) per work-group of the synchronisation
+constexpr uint32_t PAR_DEFAULT_SUB = 64, PAR_DEFAULT_GROUP = 64; // measured: profiles/NOTES.md
+constexpr int PAR_ENTRY_WORDS = 8;     // tf_jpegdec_par_entries: uint32 per subsequence
+
+__device__ __forceinline__ void par_load_tables(DevTables &s_t, const DevTables *__restrict__ tables, int tid, int n_threads)
+{
+    const uint32_t *g = reinterpret_cast<const uint32_t *>(tables);
+    uint32_t *s = reinterpret_cast<uint32_t *>(&s_t);
+    for (uint32_t i = tid; i < sizeof(DevTables) / 4; i += n_threads)
+        s[i] = g[i];
+}
+
+// first[0][] and first[1][]: the groups' first entries, read from one and written to the other launch by launch
+__global__ __launch_bounds__(PAR_BLOCK) void k_jd_par_init(const uint8_t *__restrict__ scan, const ParGeom g, uint32_t group, uint64_t *__restrict__ entries,
+                                                           uint64_t *__restrict__ first_a, uint64_t *__restrict__ first_b,
+                                                           const uint32_t *__restrict__ status)
+{
+    if (status[0] != ST_NONE)
+        return;
+    const uint32_t i = blockIdx.x * PAR_BLOCK + threadIdx.x;
+    if (i >= g.n_subs)
+        return;
+    const uint64_t e = i == 0 ? par_pack(0, 0, 0) : par_guess(scan, g.size, g.sub_bytes, i);
+    entries[i] = e;
+    if (i % group == 0)
+        first_a[i / group] = first_b[i / group] = e;
+}
+
+// A work-group's share of the scan in LDS (option jd_par_staged; S a power of two): subsequence j of the group begins
+// STAGE_PAD bytes behind where it would, so that lanes S bytes apart fall on different banks (at S = 128 they would all
+// fall on one), and STAGE_TAIL bytes of the next group's share follow for the last lane's window.  What lies outside
+// comes from memory.
+constexpr uint32_t STAGE_PAD = 4, STAGE_TAIL = 16, STAGE_MAX_BYTES = 48 * 1024;
+struct ParStaged {
+    const uint8_t *scan, *lds;
+    uint64_t first;   // the scan's byte lds[0] is
+    uint32_t span;    // bytes of the scan that are in LDS
+    uint32_t shift;   // log2 S
+    __device__ __forceinline__ uint32_t at(uint64_t i) const
+    {
+        const uint64_t off = i - first; // (a lane reads from its entry on, at or behind its group's first byte)
+        if (off < span)
+            return lds[(uint32_t)off + (((uint32_t)off >> shift) * STAGE_PAD)];
+        return scan[i];
+    }
+};
+
+// info[0]: some group's first entry changed in this launch; info[1]: the largest round count of any group
+template <bool STAGED>
+__global__ __launch_bounds__(PAR_MAX_GROUP) void k_jd_par_sync(const uint8_t *__restrict__ scan, const ParGeom g, const DevTables *__restrict__ tables,
+                                                               const uint32_t *__restrict__ status, uint64_t *__restrict__ entries,
+                                                               uint32_t *__restrict__ n_begin, uint32_t *__restrict__ dc0, uint32_t *__restrict__ dc1,
+                                                               uint32_t *__restrict__ dc2, const uint64_t *__restrict__ first_in,
+                                                               uint64_t *__restrict__ first_out, uint64_t *__restrict__ seen, uint32_t *__restrict__ info,
+                                                               int launch_no)
+{
+    __shared__ DevTables s_t;
+    __shared__ uint64_t s_exit[PAR_MAX_GROUP];
+    extern __shared__ uint32_t s_stage[]; // STAGED: group * (S + STAGE_PAD) + STAGE_TAIL bytes
+    if (status[0] != ST_NONE)
+        return;
+    const uint32_t tid = threadIdx.x, group = blockDim.x, grp = blockIdx.x, n_groups = gridDim.x;
+    const uint64_t e0 = first_in[grp];
+    if (launch_no > 0 && seen[grp] == e0) { // what this group left the last time stands (uniform over the group)
+        if (tid == 0 && grp + 1 < n_groups)
+            first_out[grp + 1] = first_in[grp + 1];
+        return;
+    }
+    par_load_tables(s_t, tables, (int)tid, (int)group);
+    ParStaged staged;
+    if (STAGED) {
+        staged.scan = scan, staged.lds = reinterpret_cast<const uint8_t *>(s_stage);
+        staged.first = (uint64_t)grp * group * g.sub_bytes; // a multiple of 4; below size: the group has a lane
+        staged.shift = (uint32_t)__ffs((int)g.sub_bytes) - 1;
+        const uint64_t left = g.size - staged.first;
+        staged.span = (uint32_t)(left < (uint64_t)group * g.sub_bytes + STAGE_TAIL ? left : (uint64_t)group * g.sub_bytes + STAGE_TAIL);
+        const uint32_t *words = reinterpret_cast<const uint32_t *>(scan + staged.first);
+        // whole dwords: the last may reach into the EOI behind the data (the scan's buffer holds it), at() never reads it
+        for (uint32_t d = tid; d < (staged.span + 3) / 4; d += group)
+            s_stage[d + ((4 * d) >> staged.shift)] = words[d]; // (STAGE_PAD is one dword)
+    }
+    const uint32_t i = grp * group + tid;
+    const bool active = i < g.n_subs;
+    uint64_t entry = tid == 0 ? e0 : (active ? entries[i] : 0);
+    bool changed = active;
+    ParLane out;
+    out.exit = 0, out.n_begin = 0, out.dc_sum[0] = out.dc_sum[1] = out.dc_sum[2] = 0, out.fault = 0;
+    uint32_t rounds = 0;
+    __syncthreads();
+    for (uint32_t round = 0; round < group; round++) { // entry r of the group is exact after round r
+        if (changed) {
+            if (STAGED)
+                par_lane<false>(staged, g, s_t.dc, s_t.ac, i, entry, 0u, nullptr, nullptr, out);
+            else
+                par_lane<false>(ParBytes{scan}, g, s_t.dc, s_t.ac, i, entry, 0u, nullptr, nullptr, out);
+        }
+        s_exit[tid] = out.exit;
+        __syncthreads();
+        const uint64_t handed = tid == 0 ? entry : s_exit[tid - 1];
+        changed = active && handed != entry;
+        entry = handed;
+        rounds++;
+        if (!__syncthreads_or((int)changed)) // (a barrier: s_exit is read before the next round writes it)
+            break;
+    }
+    if (active) {
+        entries[i] = entry;
+        n_begin[i] = out.n_begin, dc0[i] = out.dc_sum[0], dc1[i] = out.dc_sum[1], dc2[i] = out.dc_sum[2];
+    }
+    if (tid == group - 1 && grp + 1 < n_groups) { // (active: only the last group has lanes behind the grid)
+        first_out[grp + 1] = out.exit;
+        if (out.exit != first_in[grp + 1])
+            info[0] = 1;
+    }
+    if (tid == 0) {
+        seen[grp] = e0;
+        atomicMax(&info[1], rounds);
+    }
+}
+
+__global__ __launch_bounds__(PAR_BLOCK) void k_jd_par_write(const uint8_t *__restrict__ scan, const ParGeom g, const DevTables *__restrict__ tables,
+                                                            uint32_t *__restrict__ status, const uint64_t *__restrict__ entries,
+                                                            const uint32_t *__restrict__ first_block, const uint32_t *__restrict__ pred0,
+                                                            const uint32_t *__restrict__ pred1, const uint32_t *__restrict__ pred2,
+                                                            const unsigned long long *__restrict__ total_begun, int16_t *__restrict__ coef)
+{
+    __shared__ DevTables s_t;
+    if (status[0] != ST_NONE)
+        return;
+    par_load_tables(s_t, tables, (int)threadIdx.x, PAR_BLOCK);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * PAR_BLOCK + threadIdx.x;
+    if (i == 0 && total_begun[0] < g.total_blocks) // behind every lane's own fault
+        atomicMin(&status[1], (g.n_subs << PAR_REASON_BITS) | (uint32_t)R_EXHAUSTED);
+    if (i >= g.n_subs)
+        return;
+    const uint32_t pred[3] = {pred0[i], pred1[i], pred2[i]};
+    ParLane out;
+    par_lane<true>(ParBytes{scan}, g, s_t.dc, s_t.ac, i, entries[i], first_block[i], pred, coef, out);
+    if (out.fault != R_OK)
+        atomicMin(&status[1], (i << PAR_REASON_BITS) | out.fault);
+}
+
+// tf_jpegdec_par_entries' rows
+__global__ __launch_bounds__(PAR_BLOCK) void k_jd_par_entries(uint32_t n_subs, const uint64_t *__restrict__ entries, const uint32_t *__restrict__ first_block,
+                                                              const uint32_t *__restrict__ pred0, const uint32_t *__restrict__ pred1,
+                                                              const uint32_t *__restrict__ pred2, uint32_t *__restrict__ rows)
+{
+    const uint32_t i = blockIdx.x * PAR_BLOCK + threadIdx.x;
+    if (i >= n_subs)
+        return;
+    const uint64_t e = entries[i];
+    uint32_t *r = rows + (size_t)i * PAR_ENTRY_WORDS;
+    r[0] = (uint32_t)par_pos(e), r[1] = (uint32_t)(par_pos(e) >> 32), r[2] = par_blk(e), r[3] = par_k(e);
+    r[4] = first_block[i], r[5] = pred0[i], r[6] = pred1[i], r[7] = pred2[i];
+}
+
+constexpr int IDCT_BLOCK = 256, IDCT_BLOCKS = IDCT_BLOCK / 8; // 8 lanes a block
+constexpr int IDCT_STRIDE = 72; // dwords between two blocks in LDS: the column pass's lanes (block, column) fall on 64 different banks
+__global__ __launch_bounds__(IDCT_BLOCK) void k_jd_par_idct(const Frame f, const DevTables *__restrict__ tables, const int16_t *__restrict__ coef,
+                                                            uint32_t total_blocks, const uint32_t *__restrict__ status, const FastDiv div_mcus_x,
+                                                            const FastDiv div_blocks)
+{
+    __shared__ uint16_t s_q[3][64]; // by natural position
+    __shared__ int32_t s_coef[IDCT_BLOCKS][IDCT_STRIDE];
+    __shared__ int32_t s_ws[IDCT_BLOCKS][IDCT_STRIDE];
+    if (status[0] != ST_NONE || status[1] != ST_NONE)
+        return;
+    const int tid = threadIdx.x;
+    if (tid < 192)
+        s_q[tid >> 6][ZIGZAG[tid & 63]] = tables->quant[tid >> 6][tid & 63];
+    __syncthreads();
+    const int local = tid >> 3, sub = tid & 7;
+    const uint32_t j = blockIdx.x * IDCT_BLOCKS + local;
+    const bool valid = j < total_blocks;
+    const int luma_blocks = f.components == 1 ? 1 : f.h_samp * f.v_samp;
+    const int m = (int)fast_div(valid ? j : 0u, div_blocks), blk = (int)(valid ? j : 0u) - m * f.blocks;
+    const int c = blk < luma_blocks ? 0 : blk - luma_blocks + 1;
+    if (valid) {
+        const uint4 raw = *reinterpret_cast<const uint4 *>(coef + (size_t)j * 64 + sub * 8); // row `sub`: 16 bytes, aligned
+        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int x = 0; x < 8; x++) {
+            const int32_t v = (int16_t)(w[x >> 1] >> (16 * (x & 1)));
+            s_coef[local][sub * 8 + x] = v * (int32_t)s_q[c][sub * 8 + x];
+        }
+    }
+    __syncthreads();
+    if (valid)
+        idct_column(s_coef[local], sub, s_ws[local]);
+    __syncthreads();
+    if (valid) {
+        uint8_t px[8];
+        idct_row(s_ws[local], sub, px);
+        const int my = (int)fast_div((uint32_t)m, div_mcus_x), mx = m - my * f.mcus_x;
+        uint8_t *dst;
+        if (blk < luma_blocks) {
+            const int by = blk / f.h_samp, bx = blk - by * f.h_samp;
+            dst = f.planes[0] + ((size_t)(my * f.v_samp + by) * 8 + sub) * f.y_stride + (size_t)(mx * f.h_samp + bx) * 8;
+        } else {
+            dst = f.planes[blk - luma_blocks + 1] + ((size_t)my * 8 + sub) * f.c_stride + (size_t)mx * 8;
+        }
+        uint2 v;
+        v.x = px[0] | (px[1] << 8) | (px[2] << 16) | ((uint32_t)px[3] << 24);
+        v.y = px[4] | (px[5] << 8) | (px[6] << 16) | ((uint32_t)px[7] << 24);
+        *reinterpret_cast<uint2 *>(dst) = v; // j < total_blocks, so m < n_mcus: inside the plane of whole MCUs, 8-byte aligned
+    }
+}
+
 // ---- upsampling and colour -------------------------------------------------------------------------------------------------
 // jdsample.c h2v1_fancy_upsample at output column x of a row whose `dw` samples begin at p
 __device__ __forceinline__ int up_h2v1(const uint8_t *p, int dw, int x)
@@ -292,7 +517,129 @@ struct tf_jpegdec {
     PinnedBuf status_host; // page-locked uint32_t: the two status words
     Header header;
     Raw raw;
+    // the parallel path for scans without restart markers: allocated by the first decode that takes it
+    int scan_mode = 0;
+    size_t max_subs = 0, max_groups = 0, max_blocks = 0;
+    DevBuf par_entries, par_counts, par_offsets, par_first, par_totals, par_info, par_coef, par_rows;
+    PinnedBuf par_info_host; // page-locked uint32_t: the two info words
+    uint32_t par_stats[4] = {0, 0, 0, 0};
+    uint32_t par_last_subs = 0; // the subsequences of the last decode that took the path (0: none has)
 };
+
+static int par_ensure(tf_jpegdec *dec)
+{
+    if (dec->par_coef.p)
+        return TF_OK;
+    const size_t subs = dec->max_subs, groups = dec->max_groups;
+    TF_TRY(dec->par_entries.alloc(subs * sizeof(uint64_t)));
+    TF_TRY(dec->par_counts.alloc(4 * subs * sizeof(uint32_t)));
+    TF_TRY(dec->par_offsets.alloc(4 * subs * sizeof(uint32_t)));
+    TF_TRY(dec->par_first.alloc(3 * groups * sizeof(uint64_t)));
+    TF_TRY(dec->par_totals.alloc(4 * sizeof(unsigned long long)));
+    TF_TRY(dec->par_info.alloc(2 * sizeof(uint32_t)));
+    TF_TRY(dec->par_info_host.alloc(2 * sizeof(uint32_t)));
+    TF_TRY(dec->par_coef.alloc(dec->max_blocks * 64 * sizeof(int16_t)));
+    return TF_OK;
+}
+
+// the entropy stage of a scan without restart markers; the marker scan is queued, the colour kernel follows
+static int par_decode(tf_jpegdec *dec, const Frame &f, uint32_t *status)
+{
+    const long opt_sub = option(OPT_JD_PAR_SUB_BYTES), opt_group = option(OPT_JD_PAR_GROUP_SUBS), opt_staged = option(OPT_JD_PAR_STAGED);
+    TF_REQUIRE(opt_sub == 0 || (opt_sub >= (long)PAR_MIN_SUB && opt_sub <= (long)PAR_MAX_SUB), "jd_par_sub_bytes: %ld (0, or %u to %u)", opt_sub,
+               PAR_MIN_SUB, PAR_MAX_SUB);
+    TF_REQUIRE(opt_group == 0 || opt_group == 64 || opt_group == 128 || opt_group == 256, "jd_par_group_subs: %ld (0, 64, 128 or 256)", opt_group);
+    TF_TRY(par_ensure(dec));
+    ParGeom g;
+    g.size = f.scan_bytes - 2;
+    g.sub_bytes = opt_sub ? (uint32_t)opt_sub : PAR_DEFAULT_SUB;
+    g.n_subs = par_subs(g.size, g.sub_bytes);
+    g.blocks = (uint32_t)f.blocks, g.luma_blocks = f.components == 1 ? 1u : (uint32_t)(f.h_samp * f.v_samp);
+    g.total_blocks = (uint32_t)f.n_mcus * (uint32_t)f.blocks;
+    const uint32_t group = opt_group ? (uint32_t)opt_group : PAR_DEFAULT_GROUP;
+    const uint32_t n_groups = cdiv(g.n_subs, group);
+    TF_REQUIRE(g.n_subs <= dec->max_subs && n_groups <= dec->max_groups && g.total_blocks <= dec->max_blocks,
+               "tf_jpegdec_decode_dev: %u subsequences, %u blocks: beyond the handle", g.n_subs, g.total_blocks);
+    const size_t subs = dec->max_subs;
+    uint64_t *entries = dec->par_entries.as<uint64_t>();
+    uint32_t *counts = dec->par_counts.as<uint32_t>(), *offsets = dec->par_offsets.as<uint32_t>();
+    uint64_t *first[2] = {dec->par_first.as<uint64_t>(), dec->par_first.as<uint64_t>() + dec->max_groups};
+    uint64_t *seen = dec->par_first.as<uint64_t>() + 2 * dec->max_groups;
+    uint32_t *info = dec->par_info.as<uint32_t>();
+    unsigned long long *totals = dec->par_totals.as<unsigned long long>();
+    const DevTables *tables = dec->tables.as<DevTables>();
+    TF_HIP(hipMemsetAsync(dec->par_coef.p, 0, (size_t)g.total_blocks * 64 * sizeof(int16_t), stream()));
+    TF_HIP(hipMemsetAsync(info, 0, 2 * sizeof(uint32_t), stream()));
+    TF_TRY(launch("jd_par_init", k_jd_par_init, dim3(cdiv(g.n_subs, PAR_BLOCK)), dim3(PAR_BLOCK), 0, f.scan, g, group, entries, first[0], first[1],
+                  (const uint32_t *)status));
+    // the group's share in LDS: where S is a power of two and the share fits
+    const size_t stage_bytes = ((size_t)group * (g.sub_bytes + STAGE_PAD) + STAGE_TAIL + 3) / 4 * 4;
+    const bool staged = opt_staged == 1 && (g.sub_bytes & (g.sub_bytes - 1)) == 0 && stage_bytes <= STAGE_MAX_BYTES;
+    uint32_t launches = 0;
+    const uint32_t *info_host = dec->par_info_host.as<uint32_t>();
+    for (uint32_t l = 0; l <= n_groups; l++) { // entry r of the file is exact after launch r: at most n_groups + 1
+        if (l)
+            TF_HIP(hipMemsetAsync(info, 0, sizeof(uint32_t), stream()));
+        if (staged)
+            TF_TRY(launch("jd_par_sync", k_jd_par_sync<true>, dim3(n_groups), dim3(group), stage_bytes, f.scan, g, tables, (const uint32_t *)status,
+                          entries, counts, counts + subs, counts + 2 * subs, counts + 3 * subs, (const uint64_t *)first[l & 1], first[(l & 1) ^ 1],
+                          seen, info, (int)l));
+        else
+            TF_TRY(launch("jd_par_sync", k_jd_par_sync<false>, dim3(n_groups), dim3(group), 0, f.scan, g, tables, (const uint32_t *)status,
+                          entries, counts, counts + subs, counts + 2 * subs, counts + 3 * subs, (const uint64_t *)first[l & 1], first[(l & 1) ^ 1],
+                          seen, info, (int)l));
+        launches++;
+        TF_HIP(hipMemcpyAsync(dec->par_info_host.p, info, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream()));
+        TF_HIP(hipStreamSynchronize(stream()));
+        if (!info_host[0])
+            break;
+    }
+    for (int a = 0; a < 4; a++)
+        TF_TRY(launch("jd_par_scan", k_slot_scan, dim3(1), dim3(SCAN_BLOCK), 0, (const uint32_t *)(counts + a * subs), offsets + a * subs, (int)g.n_subs,
+                      0u, totals + a));
+    TF_TRY(launch("jd_par_write", k_jd_par_write, dim3(cdiv(g.n_subs, PAR_BLOCK)), dim3(PAR_BLOCK), 0, f.scan, g, tables, status,
+                  (const uint64_t *)entries, (const uint32_t *)offsets, (const uint32_t *)(offsets + subs), (const uint32_t *)(offsets + 2 * subs),
+                  (const uint32_t *)(offsets + 3 * subs), (const unsigned long long *)totals, dec->par_coef.as<int16_t>()));
+    TF_TRY(launch("jd_par_idct", k_jd_par_idct, dim3(cdiv(g.total_blocks, IDCT_BLOCKS)), dim3(IDCT_BLOCK), 0, f, tables,
+                  (const int16_t *)dec->par_coef.as<int16_t>(), g.total_blocks, (const uint32_t *)status, fast_div_setup((uint32_t)f.mcus_x),
+                  fast_div_setup((uint32_t)f.blocks)));
+    dec->par_stats[0] = g.n_subs, dec->par_stats[1] = n_groups, dec->par_stats[2] = launches, dec->par_stats[3] = info_host[1];
+    dec->par_last_subs = g.n_subs;
+    return TF_OK;
+}
+
+TF_API int tf_jpegdec_set_scan_mode(tf_jpegdec *dec, int mode)
+{
+    TF_REQUIRE(dec, "tf_jpegdec_set_scan_mode: null pointer");
+    TF_REQUIRE(mode == 0 || mode == 1, "tf_jpegdec_set_scan_mode: mode %d (0 one wave per restart interval, 1 scans without DRI in parallel)", mode);
+    dec->scan_mode = mode;
+    return TF_OK;
+}
+
+TF_API int tf_jpegdec_par_stats(tf_jpegdec *dec, uint32_t out[4])
+{
+    TF_REQUIRE(dec && out, "tf_jpegdec_par_stats: null pointer");
+    memcpy(out, dec->par_stats, sizeof(dec->par_stats));
+    return TF_OK;
+}
+
+TF_API int tf_jpegdec_par_entries(tf_jpegdec *dec, uint32_t *rows, size_t capacity, uint32_t *n_subs)
+{
+    TF_REQUIRE(dec && rows && n_subs, "tf_jpegdec_par_entries: null pointer");
+    const uint32_t n = dec->par_last_subs;
+    *n_subs = n;
+    TF_REQUIRE(n > 0, "tf_jpegdec_par_entries: no decode of this handle has taken the parallel path");
+    TF_REQUIRE(capacity >= n, "tf_jpegdec_par_entries: room for %zu subsequences, the last decode had %u", capacity, n);
+    const size_t bytes = (size_t)n * PAR_ENTRY_WORDS * sizeof(uint32_t), subs = dec->max_subs;
+    if (dec->par_rows.bytes < bytes)
+        TF_TRY(dec->par_rows.alloc(bytes));
+    const uint32_t *offsets = dec->par_offsets.as<uint32_t>();
+    TF_TRY(launch("jd_par_entries", k_jd_par_entries, dim3(cdiv(n, PAR_BLOCK)), dim3(PAR_BLOCK), 0, n, (const uint64_t *)dec->par_entries.as<uint64_t>(),
+                  offsets, offsets + subs, offsets + 2 * subs, offsets + 3 * subs, dec->par_rows.as<uint32_t>()));
+    TF_HIP(hipMemcpyAsync(rows, dec->par_rows.p, bytes, hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    return TF_OK;
+}
 
 TF_API const char *tf_jpegdec_reject_name(uint32_t reject) { return reject_name(reject); }
 
@@ -329,6 +676,11 @@ TF_API int tf_jpegdec_create(tf_jpegdec **out, int max_width, int max_height, si
     const size_t pw = ((size_t)max_width + 15) / 16 * 16, ph = ((size_t)max_height + 15) / 16 * 16;
     dec->max_intervals = (pw / 8) * (ph / 8);
     dec->plane_room = pw * ph;
+    // the parallel path's buffers (allocated when it is first taken): the smallest subsequence and group bound their
+    // counts, three components at 1 x 1 the blocks
+    dec->max_subs = (max_file_bytes + PAR_MIN_SUB - 1) / PAR_MIN_SUB;
+    dec->max_groups = (dec->max_subs + 63) / 64;
+    dec->max_blocks = 3 * dec->max_intervals;
     int rc = dec->tables.alloc(sizeof(DevTables));
     if (rc == TF_OK)
         rc = dec->scan.alloc(max_file_bytes + 4);
@@ -407,8 +759,11 @@ TF_API int tf_jpegdec_decode_dev(tf_jpegdec *dec, const uint8_t *file, size_t n,
                   dec->total.as<unsigned long long>()));
     TF_TRY(launch("jd_markers", k_jd_markers, dim3(cdiv(n_chunks, COUNT_BLOCK)), dim3(COUNT_BLOCK), 0, f.scan, f.scan_bytes, n_chunks,
                   dec->offsets.as<uint32_t>(), dec->total.as<unsigned long long>(), expected, dec->markers.as<uint32_t>(), status));
-    TF_TRY(launch("jd_entropy", k_jd_entropy, dim3((unsigned)hd.intervals), dim3(WAVE), 0, f, dec->tables.as<DevTables>(),
-                  dec->markers.as<uint32_t>(), status, fast_div_setup((uint32_t)hd.mcus_x)));
+    if (dec->scan_mode == 1 && hd.restart_mcus == 0)
+        TF_TRY(par_decode(dec, f, status));
+    else
+        TF_TRY(launch("jd_entropy", k_jd_entropy, dim3((unsigned)hd.intervals), dim3(WAVE), 0, f, dec->tables.as<DevTables>(),
+                      dec->markers.as<uint32_t>(), status, fast_div_setup((uint32_t)hd.mcus_x)));
     const size_t n_px = (size_t)hd.width * hd.height;
     TF_TRY(launch("jd_colour", k_jd_colour, dim3(cdiv(n_px, (size_t)COLOUR_BLOCK * PX_PER_LANE)), dim3(COLOUR_BLOCK), 0, f, (uint8_t *)out_dev, order,
                   (int)((uintptr_t)out_dev % 4 == 0), status, fast_div_setup((uint32_t)hd.width)));

@@ -45,6 +45,9 @@ static OptDef g_opts[OPT_COUNT] = {
     {"fb_chain", -1, -1, 1},                   // how a segmented march gets OpenCV's column sums: -1 the cheaper way per launch; 0 a pre-pass; 1 handed down inside the launch
     {"fb_segs", 0, 0, 64},                     // > 0: row segments per column of the marching kernels (0: chosen per launch)
     {"remap_quad", 1, 0, 1},                   // 1: with remap_px = 4 and a frame width that is a multiple of 4, the remap step's four pixels per thread are adjacent (16-byte accesses, no LDS); 0: a block apart
+    {"jd_par_sub_bytes", 0, 0, 1024},          // > 0: bytes of a subsequence of the JPEG decoder's parallel scan path, 16 to 1024 (0: the measured best; read per decode)
+    {"jd_par_group_subs", 0, 0, 256},          // > 0: subsequences per work-group of that path's synchronisation, 64, 128 or 256 (0: the measured best; read per decode)
+    {"jd_par_staged", 0, 0, 1},                // 1: that synchronisation reads a work-group's share of the scan from LDS where it fits (0: through the cache, the measured best; read per decode)
 };
 long option(Opt which) { return g_opts[which].value; }
 

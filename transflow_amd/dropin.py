@@ -27,7 +27,7 @@ import os
 import re
 
 _saved = {}
-_pixmap_options = {"stills": False, "mjpeg": False, "png": False}   # what the installed pixmap factory serves
+_pixmap_options = {"stills": False, "mjpeg": False, "png": False, "mjpeg_parallel": False}   # what the installed pixmap factory serves
 _saved_export = []      # (the reference's pipeline module, its NumpyOutput, deviceflow.DEVICE_ROUND) while device_flow_export is on
 
 
@@ -53,7 +53,7 @@ def _is_png_sequence(path) -> bool:
 
 
 def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None, motion_vectors=False,
-                    device_flow_replay=False, mjpeg_inputs=False, png_inputs=False):
+                    device_flow_replay=False, mjpeg_inputs=False, png_inputs=False, mjpeg_parallel=False):
     from .flow import HipFlowSource
 
     def from_args(cls, flow_path, use_mvs=False, mask_path=None, kernel_path=None, cv_config=None,
@@ -77,7 +77,7 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
                             lock_expr=lock_expr, lock_mode=lock_mode)
         if mjpeg_inputs and not use_mvs and _is_mjpeg(flow_path):   # a raw MJPEG stream: its frames are decoded on the device
             from .jpegdec import MjpegFrameProvider
-            flow_path = MjpegFrameProvider(flow_path, size=size)
+            flow_path = MjpegFrameProvider(flow_path, size=size, parallel_scan=mjpeg_parallel)
         elif png_inputs and not use_mvs and _is_png_sequence(flow_path):   # a PNG frame sequence: likewise
             from .pngdec import PngSequenceFrameProvider
             flow_path = PngSequenceFrameProvider(flow_path, size=size)
@@ -126,7 +126,7 @@ def _png_output_from_args(original):
     return classmethod(from_args)
 
 
-def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=False):
+def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=False, mjpeg_parallel=False):
     from .pixmap import HipPixmapSource
 
     def from_args(cls, path, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat=1, flow_path=None):
@@ -136,7 +136,8 @@ def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=Fals
         if not (still or image or video):                                  # a video: the reference's CvPixmapSource
             return original(path, size, seek=seek, seed=seed, seek_time=seek_time, alteration_path=alteration_path,
                             repeat=repeat, flow_path=flow_path)
-        return HipPixmapSource.from_args(path, size, seek, seed, seek_time, alteration_path, repeat, flow_path)
+        return HipPixmapSource.from_args(path, size, seek, seed, seek_time, alteration_path, repeat, flow_path,
+                                         mjpeg_parallel_scan=mjpeg_parallel)
 
     return classmethod(from_args)
 
@@ -144,7 +145,7 @@ def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=Fals
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
-            device_flow_replay: bool = False, mjpeg_inputs: bool = False, png_inputs: bool = False) -> None:
+            device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -181,6 +182,9 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     mjpeg_inputs: an existing file with extension .mjpeg / .mjpg (a raw MJPEG stream) is decoded on the device
     (transflow_amd/jpegdec.py), as a flow source's video (a MjpegFrameProvider under the HipFlowSource) and as a pixmap
     source (HipMjpegPixmapSource); by default such paths stay the reference's, like every other video.
+    mjpeg_inputs="parallel": the same, and frames without a restart interval -- what ffmpeg, OpenCV and cameras write --
+    are decoded on the device too (MjpegFrameProvider(parallel_scan=True)) instead of by Pillow; plain True keeps
+    routing them as before.
     png_inputs: a path with a `%...d` field that ends in .png and whose first frame (0 or 1) exists -- a PNG frame
     sequence -- is read by transflow_amd/pngdec.py, as a flow source's video (a PngSequenceFrameProvider under the
     HipFlowSource) and as a pixmap source (HipPngSequencePixmapSource): frames with a band index are decoded on the
@@ -194,7 +198,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
         RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet,
                                                      motion_vectors, bool(device_flow_replay), bool(mjpeg_inputs),
-                                                     bool(png_inputs))
+                                                     bool(png_inputs), mjpeg_inputs == "parallel")
     if compositor and "compositor" not in _saved:
         from transflow.compositor.compositor import Compositor as RefCompositor
 
@@ -228,21 +232,22 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from transflow.pixmap.source import PixmapSource as RefPixmapSource
         if "pixmaps" not in _saved:
             _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])
-            _pixmap_options.update(stills=False, mjpeg=False, png=False)
+            _pixmap_options.update(stills=False, mjpeg=False, png=False, mjpeg_parallel=False)
         wanted = dict(stills=_pixmap_options["stills"] or bool(pixmaps), mjpeg=_pixmap_options["mjpeg"] or bool(mjpeg_inputs),
-                      png=_pixmap_options["png"] or bool(png_inputs))
+                      png=_pixmap_options["png"] or bool(png_inputs),
+                      mjpeg_parallel=_pixmap_options["mjpeg_parallel"] or mjpeg_inputs == "parallel")
         if wanted != _pixmap_options:
             _pixmap_options.update(wanted)
             RefPixmapSource.from_args = _saved["pixmaps"][1]              # the reference's own, to be wrapped once
             RefPixmapSource.from_args = _pixmap_from_args(RefPixmapSource.from_args, wanted["stills"], wanted["mjpeg"],
-                                                          wanted["png"])
+                                                          wanted["png"], wanted["mjpeg_parallel"])
 
 
 def uninstall() -> None:
     for key in list(_saved):
         cls, original = _saved.pop(key)
         cls.from_args = original
-    _pixmap_options.update(stills=False, mjpeg=False, png=False)
+    _pixmap_options.update(stills=False, mjpeg=False, png=False, mjpeg_parallel=False)
     while _saved_export:
         from . import deviceflow
         module, original, switch = _saved_export.pop()

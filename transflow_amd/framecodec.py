@@ -257,8 +257,11 @@ class CompressedFrameProvider:
             if self._decoder is not None:            # a larger frame: the old handle's buffers go now, not with the collector
                 room = (max(room[0], self._decoder.max_width), max(room[1], self._decoder.max_height))
                 self._drop_decoder()
-            self._decoder = self.DECODER(room[0], room[1], self.device)
+            self._decoder = self._new_decoder(room[0], room[1])
         return self._decoder
+
+    def _new_decoder(self, max_width: int, max_height: int) -> FrameDecoder:
+        return self.DECODER(max_width, max_height, self.device)
 
     def seek_start(self):
         self.pos = 0

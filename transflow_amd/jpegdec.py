@@ -63,9 +63,32 @@ def probe(data) -> JpegInfo:
 
 
 class JpegDecoder(FrameDecoder):
-    """tf_jpegdec: frames of up to max_width x max_height."""
+    """tf_jpegdec: frames of up to max_width x max_height.
+
+    parallel_scan: a file without a restart interval -- one interval, hence one wave and seconds a frame otherwise -- is
+    cut into subsequences of bytes that are decoded side by side (tf_jpegdec_set_scan_mode 1; DESIGN.md section 19,
+    "scans without restart markers"): the same pixels and the same verdicts.  Files with a restart interval go the way
+    they always went.  Measured on one MI355X: a 4K quality-90 4:2:0 frame 2.95 ms (the one-wave
+    path 1394 ms, Pillow 41.0 ms), 1080p 2.18 ms (346 ms, Pillow 5.8 ms); a 1080p frame of noise at quality 100 35.5 ms,
+    SLOWER than Pillow's 18.4 ms -- such a file stays out of step for tens of KB.  Off by default."""
 
     CREATE, DECODE_DEV, DESTROY = "tf_jpegdec_create", "tf_jpegdec_decode_dev", "tf_jpegdec_destroy"
+
+    def __init__(self, max_width: int, max_height: int, device: int | None = None, max_file_bytes: int | None = None,
+                 parallel_scan: bool = False):
+        self.parallel_scan = bool(parallel_scan)
+        FrameDecoder.__init__(self, max_width, max_height, device, max_file_bytes)
+
+    def _create(self) -> None:
+        FrameDecoder._create(self)
+        if self.parallel_scan:
+            self._check(self._lib.tf_jpegdec_set_scan_mode(self._h, 1))
+
+    def par_stats(self) -> dict:
+        """tf_jpegdec_par_stats of the last decode that took the parallel path."""
+        out = (C.c_uint32 * 4)()
+        self._check(self._lib.tf_jpegdec_par_stats(self._h, out))
+        return dict(zip(("subsequences", "groups", "launches", "rounds"), (int(v) for v in out)))
 
     def _verdict(self, rc: int, reject: int) -> None:
         self._check(rc)
@@ -114,15 +137,20 @@ class MjpegFrameProvider(CompressedFrameProvider):
 
     source: a raw MJPEG stream file (.mjpeg / .mjpg), a `%0Nd.jpg` pattern, or a sequence of `bytes` / `JpegFrame`.
     With `require_restart`, a frame without a restart interval is decoded on the host (one wave would decode the whole
-    frame otherwise); `fallbacks` counts the frames that went that way, rejected ones included.  `device_decode=False`
-    decodes every frame with Pillow.  Containers (AVI ...) are not read."""
+    frame otherwise); `fallbacks` counts the frames that went that way, rejected ones included.  With `parallel_scan`
+    such a frame is decoded on the device whatever `require_restart` says, by `JpegDecoder(parallel_scan=True)` (its
+    docstring has the times: faster than Pillow at ordinary qualities, slower on noise at quality 100); everything else
+    routes as without it.  `device_decode=False` decodes every frame with Pillow.  Containers (AVI ...)
+    are not read."""
 
     DECODER, EMPTY = JpegDecoder, "the MJPEG source holds no frame"
     _stream_path = _data = None
+    parallel_scan = False                            # (a provider pickled before the option existed)
 
     def __init__(self, source, framerate: float = 25.0, size=None, device_decode: bool = True, require_restart: bool = True,
-                 device: int | None = None):
+                 device: int | None = None, parallel_scan: bool = False):
         self.require_restart = bool(require_restart)
+        self.parallel_scan = bool(parallel_scan)
         CompressedFrameProvider.__init__(self, source, framerate, size, device_decode, device)
 
     def _open_path(self, path: str) -> int:
@@ -166,9 +194,14 @@ class MjpegFrameProvider(CompressedFrameProvider):
             info = probe(raw)
         except JpegRejected:
             info = None
-        if info is None or (self.require_restart and info.restart_mcus == 0):
+        if info is None or (self.require_restart and not self.parallel_scan and info.restart_mcus == 0):
             return self._host_frame(raw, order)
         return self._decoder_for(info).decode_or_host(raw, order, info)
+
+    def _new_decoder(self, max_width: int, max_height: int) -> FrameDecoder:
+        if not self.parallel_scan:
+            return CompressedFrameProvider._new_decoder(self, max_width, max_height)
+        return self.DECODER(max_width, max_height, self.device, parallel_scan=True)
 
     def release(self):
         self._drop_decoder()

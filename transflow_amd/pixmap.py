@@ -289,9 +289,9 @@ class HipPixmapSource:
 
     @classmethod
     def from_args(cls, path: str, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat: int = 1,
-                  flow_path=None):
+                  flow_path=None, mjpeg_parallel_scan: bool = False):
         """source.py:71-120; of the video paths (CvPixmapSource there) a raw MJPEG stream file and a `%0Nd.png` frame
-        sequence are served."""
+        sequence are served.  mjpeg_parallel_scan: HipMjpegPixmapSource's `parallel_scan`."""
         ext = os.path.splitext(path)[1]
         still_match = re.match(cls.STILL_RE, path.lower().strip())
         if still_match is not None:
@@ -319,7 +319,7 @@ class HipPixmapSource:
         if os.path.isfile(path) and ext.lower() in cls.IMAGE_EXTS:
             return HipImagePixmapSource(path, alteration_path)
         if os.path.isfile(path) and ext.lower() in cls.MJPEG_EXTS:
-            return HipMjpegPixmapSource(path, seek, seek_time, alteration_path, repeat)
+            return HipMjpegPixmapSource(path, seek, seek_time, alteration_path, repeat, parallel_scan=mjpeg_parallel_scan)
         from .pngdec import is_png_sequence
         if is_png_sequence(path):
             return HipPngSequencePixmapSource(path, seek, seek_time, alteration_path, repeat)
@@ -478,9 +478,10 @@ class HipMjpegPixmapSource(HipPixmapSource):
     stills' overlay does.  (The overlay is loaded once the size is known; the reference loads it before, cv.py:33.)"""
 
     def __init__(self, path, seek: int | None = None, seek_time: float | None = None, alteration_path: str | None = None,
-                 repeat: int = 1, framerate: float = 25.0):
+                 repeat: int = 1, framerate: float = 25.0, parallel_scan: bool = False):
         HipPixmapSource.__init__(self, alteration_path)
         self.path = path
+        self.parallel_scan = bool(parallel_scan)    # MjpegFrameProvider's: frames without a restart interval on the device
         self.capture = None                          # the frame provider, under the reference's name for it
         self.seek = seek
         self.seek_time = seek_time
@@ -498,7 +499,7 @@ class HipMjpegPixmapSource(HipPixmapSource):
     def _open(self):
         """The frame provider over `path` (a subclass has another)."""
         from .jpegdec import MjpegFrameProvider
-        return MjpegFrameProvider(self.path, framerate=self._framerate)
+        return MjpegFrameProvider(self.path, framerate=self._framerate, parallel_scan=self.parallel_scan)
 
     def __enter__(self):
         self.capture = self._open()
