@@ -718,6 +718,14 @@ int tf_png_band_rows(tf_png *enc); /* the rows of a band of this handle */
    byte.  No GPU call; tf_png_copy_last has nothing to copy until the next encode.  No counterpart in the reference:
    cv2.imwrite (transflow/output/frames.py:31) writes one zlib stream and has no such option. */
 int tf_png_set_index(tf_png *enc, int on);
+/* The literal/length code of the handle's later encodes.  mode 0 (the default): the library's constant, the bytes the
+   files always had.  mode 1: the frame's own -- the tokens of all its bands are counted, the code is built from that
+   histogram on the device (the two smallest merged on (weight, order), at most 15 bits, canonical; an unused symbol has
+   no code), every coded band carries it in a header of the same 1222 bits, and a band whose coded form would not be
+   smaller than its stored form is stored: blocks of at most 65535 bytes behind 00, LEN, NLEN, nothing behind them.
+   Everything else about the file is as before and any PNG decoder, tf_pngdec included, reads it.  No GPU call.  No
+   counterpart in the reference: cv2.imwrite (transflow/output/frames.py:31) leaves the code to zlib. */
+int tf_png_set_code(tf_png *enc, int mode);
 /* rgb_dev: uint8 [H][W][3] in device memory.  Queues its kernels on the calling thread's stream and waits; the file is
    then copied to `out` (host) and *n_bytes is its size.  A file larger than `capacity` returns TF_ERR_ARG with *n_bytes
    the size needed; `out` is then not written at all, and in no case is anything written at or beyond out + capacity. */
@@ -728,6 +736,12 @@ int tf_png_encode(tf_png *enc, const uint8_t *rgb_host, uint8_t *out, size_t cap
    handle's staging slots, so only the packing runs again, up to the new capacity.  Same return values; TF_ERR_STATE if
    nothing has been encoded. */
 int tf_png_copy_last(tf_png *enc, uint8_t *out, size_t capacity, size_t *n_bytes);
+/* What the last encode made of the frame, if it ran in mode 1 of tf_png_set_code (TF_ERR_STATE otherwise): the lengths
+   of its code's 286 symbols and how often the weights were halved to bring it within 15 bits; the bytes of every band's
+   deflate data and whether the band is stored.  *n_bands is the handle's band count; more than `capacity` is TF_ERR_ARG
+   and nothing is written.  No GPU call. */
+int tf_png_last_code(tf_png *enc, uint8_t *lengths /* [286] */, uint32_t *repairs);
+int tf_png_last_bands(tf_png *enc, uint32_t *sizes, uint8_t *stored, size_t capacity, size_t *n_bands);
 /* No GPU call in these two.  The rows band_rows = 0 stands for at this size: max(1, ceil(8192 / (3 W + 1))), at most H
    (0 for a size that is none).  The lengths of the literal/length code's 286 symbols. */
 int tf_png_default_band_rows(int height, int width);

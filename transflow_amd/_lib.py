@@ -241,6 +241,9 @@ PROTOTYPES = {
     "tf_png_encode": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_png_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_png_set_index": (_I, [_P, _I]),
+    "tf_png_set_code": (_I, [_P, _I]),
+    "tf_png_last_code": (_I, [_P, _P, C.POINTER(C.c_uint32)]),
+    "tf_png_last_bands": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_png_default_band_rows": (_I, [_I, _I]),
     "tf_png_code_lengths": (_I, [_P]),
     "tf_flowzip_create": (_I, [_PP, C.c_size_t, _I]),

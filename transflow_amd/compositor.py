@@ -310,7 +310,7 @@ class HipCompositor:
     """Same constructor, methods and attributes as transflow.compositor.Compositor."""
 
     def __init__(self, height: int, width: int, layers, background_color: str = "#ffffff", lazy_frames: bool = False,
-                 jpeg_frames: int | None = None, png_frames: bool = False):
+                 jpeg_frames: int | None = None, png_frames: bool = False, png_code: str = "fixed"):
         """lazy_frames: render() returns a DeviceFrame (transflow_amd/deviceframe.py) -- the uint8 (H, W, 3) array to
         everything numpy, its download started but not waited for, so that frame t comes down (pipeline.py:518,
         output/ffmpeg.py:32-54) beside frame t + 1's uploads and kernels (pipeline.py:565).  Default: a plain ndarray.
@@ -320,7 +320,13 @@ class HipCompositor:
         png_frames: render() returns a PngFrame (transflow_amd/png.py): the same for the lossless frame-sequence output
         (output/frames.py).  Not together with lazy_frames or jpeg_frames.  png_frames="indexed": the files also carry
         the band index that lets transflow_amd/pngdec.py decode them on the device (PngEncoder(index=True)); True keeps
-        writing the bytes it wrote before."""
+        writing the bytes it wrote before.  png_code="frame": the PNG files are coded with the frame's own literal/length
+        code and a band that would not shrink is stored (PngEncoder(code="frame")): smaller files of the same pixels;
+        "fixed" keeps writing the bytes it wrote before.  Only with png_frames."""
+        if png_code not in ("fixed", "frame"):
+            raise ValueError(f"png_code is \"fixed\" or \"frame\", not {png_code!r}")
+        if png_code != "fixed" and not png_frames:
+            raise ValueError("png_code is for png_frames: there is no PNG to code")
         if png_frames and (lazy_frames or jpeg_frames is not None):
             raise ValueError("png_frames excludes lazy_frames and jpeg_frames: a frame leaves in one form")
         if jpeg_frames is not None:
@@ -337,6 +343,7 @@ class HipCompositor:
         self.jpeg_frames = None if jpeg_frames is None else int(jpeg_frames)
         self.png_frames = bool(png_frames)
         self.png_index = isinstance(png_frames, str) and png_frames == "indexed"
+        self.png_code = png_code
         self._jpeg = None           # the encoder, made at the first render
         self._png = None
         self._comp = None
@@ -380,7 +387,7 @@ class HipCompositor:
         if self.png_frames:
             if self._png is None:
                 from .png import PngEncoder
-                self._png = PngEncoder(self.height, self.width, index=self.png_index)
+                self._png = PngEncoder(self.height, self.width, index=self.png_index, code=self.png_code)
             return self._png.frame(comp)
         if self._frame_pool is None:
             from .device import ArrayPool
@@ -394,7 +401,8 @@ class HipCompositor:
 
     @classmethod
     def from_args(cls, height: int, width: int, layer_configs, background_color: str = "#ffffff", rng: str = "numpy",
-                  lazy_frames: bool = False, jpeg_frames: int | None = None, png_frames: bool = False):
+                  lazy_frames: bool = False, jpeg_frames: int | None = None, png_frames: bool = False,
+                  png_code: str = "fixed"):
         layers = []
         for config in layer_configs:
             classname = getattr(config, "classname", "moveref")
@@ -402,7 +410,7 @@ class HipCompositor:
                 raise ValueError(f"Unknown layer classname {classname}")                # layer.py:56
             layers.append(LAYER_CLASSES[classname](config, height, width, [], rng=rng))
         return cls(height, width, layers, background_color=background_color, lazy_frames=lazy_frames,
-                   jpeg_frames=jpeg_frames, png_frames=png_frames)
+                   jpeg_frames=jpeg_frames, png_frames=png_frames, png_code=png_code)
 
     def set_sources(self, pixmap_interfaces: dict):
         for i, layer in enumerate(self.layers):
@@ -417,6 +425,7 @@ class HipCompositor:
         self.jpeg_frames = state.get("jpeg_frames")
         self.png_frames = bool(state.get("png_frames", False))
         self.png_index = bool(state.get("png_index", False))
+        self.png_code = state.get("png_code", "fixed")
         self._jpeg = None
         self._png = None
         self._comp = None

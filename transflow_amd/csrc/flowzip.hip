@@ -10,10 +10,9 @@
 //                the trip before give it its place in a stretch, as in k_png_deflate.  The tokens are counted: the band's
 //                286 counts go to its row and, by integer atomics, to the member's histogram.  Then the band's CRC-32:
 //                the lanes take contiguous slices, the slices' CRCs are combined by x^(8 * bytes behind).
-//   k_fz_table   one work-group.  The used symbols are ranked by (weight, symbol); one thread merges the two smallest
-//                from the two queues -- sorted leaves, internal nodes in the order they were made, which is the order of
-//                the key (weight, 1000 + k) -- and the symbols walk to the root for their depths; weights are halved
-//                and the code rebuilt while a length exceeds 15.  Canonical codes, the token entries, the header bits.
+//   k_fz_table   one work-group.  The code of the histogram (deflate_code.h: the used symbols ranked by (weight, symbol),
+//                the two smallest merged on the key (weight, order), weights halved and the code rebuilt while a length
+//                exceeds 15, canonical codes), then the token entries and the header bits.
 //   k_fz_sizes   one wave per band: its coded bits from its counts and the code, coded or stored, its bytes.
 //   k_fz_scan    exclusive sum of the bands' bytes (one work-group, chunks of 1024 bands), the member's CRC-32 from the
 //                bands', and the final block 01 00 00 FF FF behind the last band.
@@ -88,17 +87,6 @@ __device__ __forceinline__ Tokens tokenise(int byte, int prev, uint32_t i, uint3
     }
     carry = __shfl(eq ? (run >= MAX_MATCH ? run - MAX_MATCH : run) : 0, WAVE - 1, WAVE);
     return t;
-}
-
-__device__ __forceinline__ int length_symbol(int n) // k of 257 + k
-{
-    int k = N_LENGTH_SYMBOLS - 1;
-    if (n < MAX_MATCH) {
-        k = 0;
-        while (k + 1 < N_LENGTH_SYMBOLS - 1 && LENGTH_BASE[k + 1] <= n)
-            k++;
-    }
-    return k;
 }
 
 constexpr int TRIPS = 4; // a block of trips: its bytes are loaded while the block before is coded
@@ -177,106 +165,20 @@ __global__ __launch_bounds__(WAVE) void k_fz_count(const Stream s, const Crc32Co
 }
 
 // ---- table -------------------------------------------------------------------------------------------------------------
-constexpr int TABLE_BLOCK = 512;
-
-__device__ __forceinline__ uint32_t reverse_bits(uint32_t code, int n)
-{
-    return n ? __brev(code) >> (32 - n) : 0;
-}
+constexpr int TABLE_BLOCK = HUFFMAN_BLOCK;
 
 __global__ __launch_bounds__(TABLE_BLOCK) void k_fz_table(const uint32_t *__restrict__ totals, int distance, Tables *__restrict__ out)
 {
-    __shared__ uint32_t s_w[N_SYMBOLS];          // the symbols' weights (0: unused)
-    __shared__ int s_leaf[N_SYMBOLS];            // the used symbols by (weight, symbol)
-    __shared__ int s_rank[N_SYMBOLS];            // a used symbol's place in s_leaf
-    __shared__ uint32_t s_node_w[2 * N_SYMBOLS]; // leaves in sorted order, then the internal nodes in the order made
-    __shared__ int s_parent[2 * N_SYMBOLS];
-    __shared__ int s_len[N_SYMBOLS];
-    __shared__ uint32_t s_code[N_SYMBOLS];
-    __shared__ uint32_t s_next[MAX_CODE_BITS + 2];
+    __shared__ HuffmanLds s; // (deflate_code.h)
     __shared__ uint32_t s_header[HEADER_WORDS];
-    __shared__ int s_used, s_longest;
     const int tid = threadIdx.x;
     if (tid < N_SYMBOLS)
-        s_w[tid] = totals[tid];
+        s.w[tid] = totals[tid];
     if (tid < HEADER_WORDS)
         s_header[tid] = 0;
-    uint32_t repairs = 0;
-    for (;;) {
-        if (tid == 0)
-            s_used = 0, s_longest = 0;
-        __syncthreads();
-        // ---- rank the used symbols by (weight, symbol)
-        if (tid < N_SYMBOLS && s_w[tid]) {
-            const uint32_t w = s_w[tid];
-            int rank = 0;
-            for (int o = 0; o < N_SYMBOLS; o++) {
-                const uint32_t v = s_w[o];
-                rank += (v && (v < w || (v == w && o < tid))) ? 1 : 0;
-            }
-            s_rank[tid] = rank, s_leaf[rank] = tid, s_node_w[rank] = w;
-            atomicAdd(&s_used, 1);
-        }
-        __syncthreads();
-        const int used = s_used;
-        // ---- merge the two smallest on (weight, order): a leaf's order is its symbol, the k-th internal node's 1000 + k,
-        // so of equal weights the leaf goes first and of two internal nodes the older
-        if (tid == 0) {
-            int leaf = 0, inner = used, made = used; // the next of either queue, the next node to make
-            for (int k = 0; k + 1 < used; k++) {
-                int pick[2];
-                for (int p = 0; p < 2; p++) {
-                    const bool take_leaf = leaf < used && (inner >= made || s_node_w[leaf] <= s_node_w[inner]);
-                    pick[p] = take_leaf ? leaf++ : inner++;
-                }
-                s_node_w[made] = s_node_w[pick[0]] + s_node_w[pick[1]];
-                s_parent[pick[0]] = s_parent[pick[1]] = made;
-                made++;
-            }
-        }
-        __syncthreads();
-        if (tid < N_SYMBOLS) {
-            int depth = 0;
-            if (s_w[tid]) {
-                const int root = 2 * used - 2;
-                for (int i = s_rank[tid]; i < root && depth < 2 * N_SYMBOLS; i = s_parent[i])
-                    depth++;
-                if (used == 1)
-                    depth = 1; // (never: the first byte and end-of-block are always there)
-                atomicMax(&s_longest, depth);
-            }
-            s_len[tid] = depth;
-        }
-        __syncthreads();
-        if (s_longest <= MAX_CODE_BITS)
-            break;
-        if (tid < N_SYMBOLS && s_w[tid])
-            s_w[tid] = max(1u, s_w[tid] >> 1);
-        repairs++;
-        __syncthreads();
-    }
-    // ---- canonical codes, RFC 1951 3.2.2
-    if (tid == 0) {
-        uint32_t count[MAX_CODE_BITS + 2] = {};
-        for (int sym = 0; sym < N_SYMBOLS; sym++)
-            count[s_len[sym]]++;
-        count[0] = 0;
-        uint32_t code = 0;
-        s_next[0] = 0;
-        for (int bits = 1; bits <= MAX_CODE_BITS; bits++) {
-            code = (code + count[bits - 1]) << 1;
-            s_next[bits] = code;
-        }
-    }
-    __syncthreads();
-    if (tid < N_SYMBOLS) {
-        const int len = s_len[tid];
-        uint32_t before = 0;
-        for (int o = 0; o < tid; o++)
-            before += s_len[o] == len ? 1 : 0;
-        s_code[tid] = len ? s_next[len] + before : 0;
-    }
-    __syncthreads();
+    const uint32_t repairs = huffman_build(s, tid);
+    const int *s_len = s.len;
+    const uint32_t *s_code = s.code;
     // ---- the distance symbol that contains `distance`
     int hdist = 0;
     while (hdist + 1 < N_DIST_SYMBOLS && DIST_BASE[hdist + 1] <= distance)

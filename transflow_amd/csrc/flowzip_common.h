@@ -4,6 +4,7 @@
 #include "common.h"
 #include "crc32_common.h"
 #include "deflate_tables.h"
+#include "deflate_code.h"
 
 namespace tf {
 namespace flowzip {
@@ -11,7 +12,7 @@ namespace flowzip {
 using namespace deflate;
 
 // distances as far as 64: the first twelve distance symbols
-constexpr int MAX_DISTANCE = 64, N_DIST_SYMBOLS = 12, MAX_CODE_BITS = 15;
+constexpr int MAX_DISTANCE = 64, N_DIST_SYMBOLS = 12;
 static_assert(DIST_BASE[N_DIST_SYMBOLS - 1] + (1 << DIST_EXTRA[N_DIST_SYMBOLS - 1]) - 1 == MAX_DISTANCE,
               "the last distance symbol in use must end at MAX_DISTANCE");
 
@@ -43,9 +44,6 @@ constexpr int LANE_MAX_BITS = 64;
 constexpr int LANE_WORST_BITS = 3 * MAX_CODE_BITS > MAX_CODE_BITS + 5 + 1 + 4 + MAX_CODE_BITS ? 3 * MAX_CODE_BITS
                                                                                               : 2 * MAX_CODE_BITS + 5 + 1 + 4;
 constexpr int BIT_WORDS = (MAX_HEADER_BITS + 64 * LANE_MAX_BITS + 3 + 7 + 32) / 32 + 3;
-
-constexpr uint32_t STORED_MAX = 65535;
-__host__ __device__ inline uint64_t stored_bytes(uint64_t n) { return n + 5 * ((n + STORED_MAX - 1) / STORED_MAX); }
 
 // the stream of N bytes in bands of B: at most N + 5 per stored block + 5
 inline uint64_t stream_bound(uint64_t N, uint64_t B)

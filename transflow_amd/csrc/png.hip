@@ -6,6 +6,8 @@
 // is a constant of the library: a fixed literal/length code, a distance alphabet of the single code 0 -- and an empty
 // stored block that brings the stream to a byte boundary, so a band's bytes depend on nothing but its own rows and the
 // bands concatenate into one valid stream.  Matches are runs: distance 1, never across the band's first byte.
+// With tf_png_set_code(enc, 1) the literal/length code is the frame's own, built from the tokens of all its bands, and a
+// band whose coded form would not be smaller is stored instead (tests/png_frame_code_ref.py states that mode).
 //
 //   k_png_filter   one work-group per row: the five candidates' sums, the choice, the filtered row to HBM, and the
 //                  row's two Adler sums (the plain sum and the sum weighted by the bytes behind, 64-bit, reduced once).
@@ -16,6 +18,13 @@
 //                  the band is a lane too and its own symbol is end-of-block.  A wave prefix sum of the bit counts
 //                  places the tokens in an LDS bit buffer that starts out holding the table header; after every trip
 //                  its whole bytes go to the band's staging slot and the bits left over to its front.
+//   k_png_count    (the frame's own code, tf_png_set_code) one wave per band: the same tokeniser, the tokens counted in
+//                  LDS; the band's 286 counts go to its row.
+//   k_png_total    (the same) the frame's histogram: the column sums of those rows.
+//   k_png_table    (the same) one work-group: the code of the histogram (deflate_code.h), the entries and the header
+//                  k_png_deflate reads, the bits each symbol costs.  k_png_deflate then adds up its band's counts x
+//                  costs first, and where the coded form would not be smaller than the stored one it copies the band
+//                  behind stored-block headers instead.
 //   k_slot_scan    exclusive sum of the bands' chunk sizes, data + 12 (one work-group; stream_common.h).
 //   k_png_pack     one wave per band writes length, "IDAT", the data and the chunk's CRC-32 at the band's offset: the
 //                  lanes take contiguous slices through the byte table and the slices' CRCs are combined by
@@ -131,7 +140,9 @@ struct DeflateArgs {
     const uint8_t *filtered; // H rows of row_bytes
     uint32_t row_bytes;
     int H, band_rows;
-    const Tables *tables;
+    const Tables *tables;    // the library's constant code, or what k_png_table made of the frame's histogram
+    const uint32_t *counts;  // null, or per band its 286 token counts: a band that would not shrink is stored
+    const FrameCode *code;   // with counts: the bits each symbol costs
     uint8_t *staging;        // n_bands slots of slot_bytes
     uint32_t slot_bytes;
     uint32_t *lengths;       // per band: the bytes it wrote
@@ -140,6 +151,177 @@ struct DeflateArgs {
 
 constexpr int TRIPS = 4;
 
+// What the lane of band byte i emits in a trip, in stream order: a match of `match` bytes, or `pending` (0 - 2) literals
+// of its left neighbour's byte; then `own` (a literal, END_OF_BLOCK at i == N, -1: nothing).
+struct Tokens {
+    int match, pending, own;
+};
+
+// left: the byte before (lane 0: the last trip's last).  carry: the run the last trip ended in, counted from its last
+// match of 258.
+__device__ __forceinline__ Tokens tokenise(int byte, int left, uint32_t i, uint32_t N, int lane, int &carry)
+{
+    Tokens t;
+    t.match = 0, t.pending = 0, t.own = -1;
+    const bool eq = i < N && i > 0 && byte == left;
+    const unsigned long long differ = ~__ballot(eq) & ((1ull << lane) - 1); // the lanes below that end a run
+    const int last_differ = differ ? 63 - __clzll((long long)differ) : -1;
+    int run = 0;
+    if (eq) {
+        run = differ ? lane - last_differ : carry + lane + 1; // < 258 + 64: it reaches 258 once at the most
+        if (run == MAX_MATCH)
+            t.match = MAX_MATCH;
+    } else if (i <= N) {
+        int pending = differ ? lane - 1 - last_differ : carry + lane; // the run that ended at the byte before
+        if (pending >= MAX_MATCH)
+            pending -= MAX_MATCH; // a lane below has emitted that match
+        if (pending >= MIN_MATCH)
+            t.match = pending;
+        else
+            t.pending = pending;
+        t.own = i < N ? byte : END_OF_BLOCK;
+    }
+    carry = __shfl(eq ? (run >= MAX_MATCH ? run - MAX_MATCH : run) : 0, WAVE - 1, WAVE);
+    return t;
+}
+
+// ---- the frame's own code: count, table -------------------------------------------------------------------------------
+__global__ __launch_bounds__(WAVE) void k_png_count(const uint8_t *__restrict__ filtered, uint32_t row_bytes, int H, int band_rows,
+                                                    uint32_t *__restrict__ counts)
+{
+    __shared__ uint32_t s_cnt[N_SYMBOLS];
+    const int lane = threadIdx.x;
+    for (int w = lane; w < N_SYMBOLS; w += WAVE)
+        s_cnt[w] = 0;
+    const int first_row = blockIdx.x * band_rows;
+    const int rows = min(band_rows, H - first_row);
+    const uint32_t N = (uint32_t)rows * row_bytes;
+    const uint8_t *src = filtered + (size_t)first_row * row_bytes;
+    int carry = 0, prev_last = 0;
+    int cur[TRIPS], next[TRIPS];
+#pragma unroll
+    for (int k = 0; k < TRIPS; k++) {
+        const uint32_t j = (uint32_t)(k * WAVE + lane);
+        cur[k] = j < N ? src[j] : 0;
+    }
+    __syncthreads();
+    for (uint32_t block = 0; block <= N; block += TRIPS * WAVE) {
+#pragma unroll
+        for (int k = 0; k < TRIPS; k++) {
+            const uint32_t j = block + (uint32_t)((TRIPS + k) * WAVE + lane);
+            next[k] = j < N ? src[j] : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < TRIPS; k++) {
+            const uint32_t base = block + (uint32_t)(k * WAVE);
+            if (base > N)
+                break;
+            const int byte = cur[k];
+            int left = __shfl_up(byte, 1, WAVE);
+            if (lane == 0)
+                left = prev_last;
+            const Tokens t = tokenise(byte, left, base + lane, N, lane, carry);
+            prev_last = __shfl(byte, WAVE - 1, WAVE);
+            if (t.match)
+                atomicAdd(&s_cnt[257 + length_symbol(t.match)], 1u);
+            if (t.pending)
+                atomicAdd(&s_cnt[left], (uint32_t)t.pending);
+            if (t.own >= 0)
+                atomicAdd(&s_cnt[t.own], 1u);
+        }
+#pragma unroll
+        for (int k = 0; k < TRIPS; k++)
+            cur[k] = next[k];
+    }
+    __syncthreads();
+    for (int w = lane; w < N_SYMBOLS; w += WAVE) {
+        const uint32_t c = s_cnt[w];
+        counts[(size_t)blockIdx.x * N_SYMBOLS + w] = c;
+    }
+}
+
+// The frame's histogram: the column sums of the bands' rows.  64 columns a work-group, a wave per 16th of the rows.
+constexpr int TOTAL_BLOCK = 1024;
+__global__ __launch_bounds__(TOTAL_BLOCK) void k_png_total(const uint32_t *__restrict__ counts, int n_bands, uint32_t *__restrict__ totals)
+{
+    __shared__ uint32_t s_sum[TOTAL_BLOCK / WAVE][WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const int col = blockIdx.x * WAVE + lane;
+    uint32_t sum = 0; // (a frame has less than 2^32 bytes, and a byte brings one token at the most)
+    if (col < N_SYMBOLS) {
+#pragma unroll 8
+        for (int band = wave; band < n_bands; band += TOTAL_BLOCK / WAVE)
+            sum += counts[(size_t)band * N_SYMBOLS + col];
+    }
+    s_sum[wave][lane] = sum;
+    __syncthreads();
+    if (wave == 0 && col < N_SYMBOLS) {
+        sum = 0;
+        for (int w = 0; w < TOTAL_BLOCK / WAVE; w++)
+            sum += s_sum[w][lane];
+        totals[col] = sum;
+    }
+}
+
+constexpr int HEADER_FIXED_BITS = HEADER_BITS - 4 * (N_SYMBOLS + 1);
+
+__global__ __launch_bounds__(HUFFMAN_BLOCK) void k_png_table(const uint32_t *__restrict__ totals, Tables *__restrict__ out,
+                                                             FrameCode *__restrict__ code)
+{
+    __shared__ HuffmanLds s; // (deflate_code.h)
+    __shared__ uint32_t s_header[HEADER_WORDS];
+    const int tid = threadIdx.x;
+    if (tid < N_SYMBOLS)
+        s.w[tid] = totals[tid];
+    if (tid < HEADER_WORDS)
+        s_header[tid] = 0;
+    const uint32_t repairs = huffman_build(s, tid);
+    // ---- the entries, in the layout of make_tables
+    if (tid <= END_OF_BLOCK)
+        out->lit[tid] = ((uint32_t)s.len[tid] << 24) | deflate::reverse_bits(s.code[tid], s.len[tid]);
+    if (tid <= MAX_MATCH) {
+        uint32_t entry = 0;
+        if (tid >= MIN_MATCH) {
+            const int k = length_symbol(tid), sym = 257 + k, len = s.len[sym];
+            const uint32_t bits = (uint32_t)len + LENGTH_EXTRA[k] + 1; // the code, the extra bits, the distance code 0
+            if (len)
+                entry = (bits << 24) | deflate::reverse_bits(s.code[sym], len) | ((uint32_t)(tid - LENGTH_BASE[k]) << len);
+        }
+        out->match[tid] = entry;
+    }
+    if (tid < N_SYMBOLS) {
+        code->cost[tid] = (uint32_t)s.len[tid] + (tid > END_OF_BLOCK ? LENGTH_EXTRA[tid - 257] + 1 : 0);
+        code->lengths[tid] = (uint8_t)s.len[tid];
+    }
+    // ---- the header: the fixed part by one thread, the 4-bit codes of the lengths (the code of a length is the length)
+    // one thread each; the last is the distance code's
+    if (tid == 0) {
+        int n = 0;
+        auto put = [&](uint32_t value, int bits) {
+            for (int i = 0; i < bits; i++, n++)
+                if ((value >> i) & 1)
+                    atomicOr(&s_header[n >> 5], 1u << (n & 31));
+        };
+        put(0, 1), put(2, 2), put(N_SYMBOLS - 257, 5), put(0, 5), put(19 - 4, 4);
+        for (int k = 0; k < 19; k++)
+            put(CLEN_ORDER[k] >= 16 ? 0 : 4, 3);
+        code->repairs = repairs;
+    }
+    if (tid <= N_SYMBOLS) {
+        const int len = tid < N_SYMBOLS ? s.len[tid] : 1;
+        const uint32_t v = deflate::reverse_bits((uint32_t)len, 4), at = (uint32_t)(HEADER_FIXED_BITS + 4 * tid);
+        if (v) {
+            atomicOr(&s_header[at >> 5], v << (at & 31));
+            if ((at & 31) > 28)
+                atomicOr(&s_header[(at >> 5) + 1], v >> (32 - (at & 31)));
+        }
+    }
+    __syncthreads();
+    if (tid < HEADER_WORDS)
+        out->header[tid] = s_header[tid];
+}
+
+// ---- deflate ---------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void put_token(unsigned long long &bits, int &len, uint32_t entry)
 {
     bits |= (unsigned long long)(entry & 0xFFFFFFu) << len;
@@ -152,6 +334,39 @@ __global__ __launch_bounds__(WAVE) void k_png_deflate(const DeflateArgs a)
     __shared__ uint32_t s_lit[END_OF_BLOCK + 1];
     __shared__ uint32_t s_match[MAX_MATCH + 1];
     const int lane = threadIdx.x;
+    const int first_row = blockIdx.x * a.band_rows; // (n_bands * band_rows < H + band_rows <= 2^17)
+    const int rows = min(a.band_rows, a.H - first_row);
+    const uint32_t N = (uint32_t)rows * a.row_bytes; // (at most 2^28: tf_png_create)
+    const uint8_t *src = a.filtered + (size_t)first_row * a.row_bytes;
+    uint8_t *slot = a.staging + (size_t)blockIdx.x * a.slot_bytes;
+    if (a.counts) {
+        // ---- the frame's own code: the band's coded bytes from its counts; stored where that is not smaller
+        unsigned long long token_bits = 0;
+        for (int sym = lane; sym < N_SYMBOLS; sym += WAVE)
+            token_bits += (unsigned long long)a.counts[(size_t)blockIdx.x * N_SYMBOLS + sym] * a.code->cost[sym];
+        const unsigned long long coded = (HEADER_BITS + wave_sum64(token_bits) + 3 + 7) / 8 + 4;
+        const unsigned long long stored = stored_bytes(N);
+        if (!(coded < stored)) {
+            // blocks of at most 65535 bytes, each behind 00, its length and the length's complement
+            for (uint32_t j = lane; j < stored; j += WAVE) {
+                const uint32_t blk = j / (STORED_MAX + 5), r = j % (STORED_MAX + 5);
+                const uint32_t len = min(STORED_MAX, N - blk * STORED_MAX);
+                int v;
+                if (r >= 5)
+                    v = src[blk * STORED_MAX + (r - 5)];
+                else
+                    v = r == 0 ? 0 : (int)(((r < 3 ? len : ~len) >> (8 * ((r - 1) & 1))) & 0xFF);
+                if (j < a.slot_bytes)
+                    slot[j] = (uint8_t)v;
+            }
+            if (lane == 0) {
+                a.lengths[blockIdx.x] = (uint32_t)min(stored, (unsigned long long)a.slot_bytes);
+                if (stored > a.slot_bytes)
+                    *a.overflow = 1;
+            }
+            return;
+        }
+    }
     const Tables &t = *a.tables;
     for (int w = lane; w < BIT_WORDS; w += WAVE)
         s_bits[w] = w < HEADER_WORDS ? t.header[w] : 0;
@@ -159,11 +374,6 @@ __global__ __launch_bounds__(WAVE) void k_png_deflate(const DeflateArgs a)
         s_lit[w] = t.lit[w];
     for (int w = lane; w <= MAX_MATCH; w += WAVE)
         s_match[w] = t.match[w];
-    const int first_row = blockIdx.x * a.band_rows; // (n_bands * band_rows < H + band_rows <= 2^17)
-    const int rows = min(a.band_rows, a.H - first_row);
-    const uint32_t N = (uint32_t)rows * a.row_bytes; // (at most 2^28: tf_png_create)
-    const uint8_t *src = a.filtered + (size_t)first_row * a.row_bytes;
-    uint8_t *slot = a.staging + (size_t)blockIdx.x * a.slot_bytes;
     uint32_t bitpos = HEADER_BITS; // bits in s_bits
     uint32_t outpos = 0;           // bytes in the slot
     int carry = 0;                 // the run the last trip ended in, counted from its last match of 258
@@ -186,34 +396,20 @@ __global__ __launch_bounds__(WAVE) void k_png_deflate(const DeflateArgs a)
         const uint32_t base = block + (uint32_t)(k * WAVE);
         if (base > N)
             break;
-        const uint32_t i = base + lane;
         const int byte = cur[k];
         int left = __shfl_up(byte, 1, WAVE);
         if (lane == 0)
             left = prev_last;
-        const bool eq = i < N && i > 0 && byte == left;
-        const unsigned long long differ = ~__ballot(eq) & ((1ull << lane) - 1); // the lanes below that end a run
-        const int last_differ = differ ? 63 - __clzll((long long)differ) : -1;
-        unsigned long long bits = 0;
-        int len = 0, run = 0;
-        if (eq) {
-            run = differ ? lane - last_differ : carry + lane + 1; // < 258 + 64: it reaches 258 once at the most
-            if (run == MAX_MATCH)
-                put_token(bits, len, s_match[MAX_MATCH]);
-        } else if (i <= N) {
-            int pending = differ ? lane - 1 - last_differ : carry + lane; // the run that ended at the byte before
-            if (pending >= MAX_MATCH)
-                pending -= MAX_MATCH; // a lane below has emitted that match
-            if (pending >= MIN_MATCH) {
-                put_token(bits, len, s_match[pending]);
-            } else {
-                for (int k = 0; k < pending; k++)
-                    put_token(bits, len, s_lit[left]);
-            }
-            put_token(bits, len, s_lit[i < N ? byte : END_OF_BLOCK]);
-        }
-        carry = __shfl(eq ? (run >= MAX_MATCH ? run - MAX_MATCH : run) : 0, WAVE - 1, WAVE);
+        const Tokens tok = tokenise(byte, left, base + lane, N, lane, carry);
         prev_last = __shfl(byte, WAVE - 1, WAVE);
+        unsigned long long bits = 0;
+        int len = 0;
+        if (tok.match)
+            put_token(bits, len, s_match[tok.match]);
+        for (int k = 0; k < tok.pending; k++)
+            put_token(bits, len, s_lit[left]);
+        if (tok.own >= 0)
+            put_token(bits, len, s_lit[tok.own]);
         len = min(len, LANE_MAX_BITS); // (never: the host checked the table)
         const int incl = wave_inclusive_sum(len, lane);
         if (len) {
@@ -477,6 +673,12 @@ struct tf_png {
     Tables tables;
     std::vector<uint8_t> head, tail; // what the host writes in front of the bands' chunks and behind them
     DevBuf dev_tables, filtered, rowsums, staging, lengths, offsets, info, packed, upload;
+    // the frame's own code (tf_png_set_code): allocated by the first encode that uses it
+    int code = 0;
+    DevBuf counts, totals, frame_tables, frame_code;
+    PinnedBuf frame_code_host; // page-locked FrameCode: the last frame's
+    PinnedBuf lengths_host;    // page-locked uint32_t: the last frame's bands' bytes
+    bool last_own_code = false; // the last encode that ran used the frame's own code: the two buffers above hold it
     PinnedBuf info_host;    // page-locked unsigned long long: [0] the chunks' bytes, [1] the overflow flag
     PinnedBuf rowsums_host; // page-locked uint32_t: the rows' Adler sums
     size_t last_chunks = 0;                  // the chunks' bytes of the last encode that ran; 0: none to copy again
@@ -504,6 +706,25 @@ TF_API int tf_png_set_index(tf_png *enc, int on)
     TF_REQUIRE(enc, "tf_png_set_index: null pointer");
     make_head(enc, on != 0);
     enc->last_chunks = 0; // the head of the last encode is gone: nothing to copy again
+    return TF_OK;
+}
+
+TF_API int tf_png_set_code(tf_png *enc, int mode)
+{
+    TF_REQUIRE(enc, "tf_png_set_code: null pointer");
+    TF_REQUIRE(mode == 0 || mode == 1, "tf_png_set_code: mode %d (0: the library's code, 1: the frame's own)", mode);
+    if (mode == 1) {
+        // whatever code a histogram gives: a lane's tokens of a trip -- three literals, or a match and a literal -- fit
+        // its 64-bit accumulator, a match its entry's 24 bits, and a band's stored form its slot
+        constexpr int MATCH_BITS = MAX_CODE_BITS + 5 + 1;
+        static_assert(3 * MAX_CODE_BITS <= LANE_MAX_BITS && MATCH_BITS + MAX_CODE_BITS <= LANE_MAX_BITS, "a lane's tokens outgrow its accumulator");
+        static_assert(MATCH_BITS <= 24, "a match outgrows its entry");
+        const uint64_t band = (uint64_t)enc->band_rows * enc->row_bytes;
+        if (stored_bytes(band) > enc->slot)
+            return set_error(TF_ERR_STATE, "tf_png_set_code: a stored band of %llu bytes would not fit its slot of %u",
+                             (unsigned long long)stored_bytes(band), enc->slot);
+    }
+    enc->code = mode;
     return TF_OK;
 }
 
@@ -591,6 +812,19 @@ TF_API int tf_png_band_rows(tf_png *enc)
     return enc ? enc->band_rows : 0;
 }
 
+// what the frame's own code takes beside the handle's other buffers
+static int own_code_buffers(tf_png *enc)
+{
+    if (enc->lengths_host.p)
+        return TF_OK;
+    TF_TRY(enc->counts.alloc((size_t)enc->n_bands * N_SYMBOLS * sizeof(uint32_t)));
+    TF_TRY(enc->totals.alloc(N_SYMBOLS * sizeof(uint32_t)));
+    TF_TRY(enc->frame_tables.alloc(sizeof(Tables)));
+    TF_TRY(enc->frame_code.alloc(sizeof(FrameCode)));
+    TF_TRY(enc->frame_code_host.alloc(sizeof(FrameCode)));
+    return enc->lengths_host.alloc(enc->lengths.bytes);
+}
+
 // the slots to their chunks in the packed stream, as far as `dev_capacity` reaches
 static int pack(tf_png *enc, size_t dev_capacity)
 {
@@ -628,7 +862,19 @@ TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, siz
                   enc->filtered.as<uint8_t>(), enc->rowsums.as<uint32_t>()));
     DeflateArgs a;
     a.filtered = enc->filtered.as<uint8_t>(), a.row_bytes = enc->row_bytes, a.H = enc->H, a.band_rows = enc->band_rows;
-    a.tables = enc->dev_tables.as<Tables>(), a.staging = enc->staging.as<uint8_t>(), a.slot_bytes = enc->slot;
+    a.tables = enc->dev_tables.as<Tables>(), a.counts = nullptr, a.code = nullptr;
+    a.staging = enc->staging.as<uint8_t>(), a.slot_bytes = enc->slot;
+    enc->last_own_code = false;
+    if (enc->code) {
+        TF_TRY(own_code_buffers(enc));
+        TF_TRY(launch("png_count", k_png_count, dim3(enc->n_bands), dim3(WAVE), 0, a.filtered, a.row_bytes, a.H, a.band_rows,
+                      enc->counts.as<uint32_t>()));
+        TF_TRY(launch("png_total", k_png_total, dim3(cdiv(N_SYMBOLS, WAVE)), dim3(TOTAL_BLOCK), 0, enc->counts.as<uint32_t>(), enc->n_bands,
+                      enc->totals.as<uint32_t>()));
+        TF_TRY(launch("png_table", k_png_table, dim3(1), dim3(HUFFMAN_BLOCK), 0, enc->totals.as<uint32_t>(), enc->frame_tables.as<Tables>(),
+                      enc->frame_code.as<FrameCode>()));
+        a.tables = enc->frame_tables.as<Tables>(), a.counts = enc->counts.as<uint32_t>(), a.code = enc->frame_code.as<FrameCode>();
+    }
     a.lengths = enc->lengths.as<uint32_t>();
     a.overflow = reinterpret_cast<uint32_t *>(enc->info.as<unsigned long long>() + 1);
     TF_TRY(launch("png_deflate", k_png_deflate, dim3(enc->n_bands), dim3(WAVE), 0, a));
@@ -638,6 +884,10 @@ TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, siz
     enc->last_chunks = 0;
     TF_HIP(hipMemcpyAsync(enc->info_host.p, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipMemcpyAsync(enc->rowsums_host.p, enc->rowsums.p, enc->rowsums.bytes, hipMemcpyDeviceToHost, stream()));
+    if (enc->code) {
+        TF_HIP(hipMemcpyAsync(enc->frame_code_host.p, enc->frame_code.p, sizeof(FrameCode), hipMemcpyDeviceToHost, stream()));
+        TF_HIP(hipMemcpyAsync(enc->lengths_host.p, enc->lengths.p, enc->lengths.bytes, hipMemcpyDeviceToHost, stream()));
+    }
     TF_HIP(hipStreamSynchronize(stream()));
     if (enc->info_host.as<unsigned long long>()[1])
         return set_error(TF_ERR_STATE, "tf_png_encode_dev: a band outgrew its staging slot of %u bytes", enc->slot);
@@ -653,7 +903,36 @@ TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, siz
     put_chunk(enc->tail, enc->tables, "IDAT", last);
     put_chunk(enc->tail, enc->tables, "IEND", {});
     enc->last_chunks = (size_t)enc->info_host.as<unsigned long long>()[0];
+    enc->last_own_code = enc->code != 0;
     return copy_out(enc, "tf_png_encode_dev", out, capacity, n_bytes);
+}
+
+TF_API int tf_png_last_code(tf_png *enc, uint8_t *lengths, uint32_t *repairs)
+{
+    TF_REQUIRE(enc && lengths && repairs, "tf_png_last_code: null pointer");
+    if (!enc->last_own_code)
+        return set_error(TF_ERR_STATE, "tf_png_last_code: no frame has been encoded with its own code");
+    const FrameCode *code = enc->frame_code_host.as<FrameCode>();
+    memcpy(lengths, code->lengths, N_SYMBOLS);
+    *repairs = code->repairs;
+    return TF_OK;
+}
+
+TF_API int tf_png_last_bands(tf_png *enc, uint32_t *sizes, uint8_t *stored, size_t capacity, size_t *n_bands)
+{
+    TF_REQUIRE(enc && n_bands && ((sizes && stored) || capacity == 0), "tf_png_last_bands: null pointer");
+    *n_bands = 0;
+    if (!enc->last_own_code)
+        return set_error(TF_ERR_STATE, "tf_png_last_bands: no frame has been encoded with its own code");
+    *n_bands = (size_t)enc->n_bands;
+    TF_REQUIRE(*n_bands <= capacity, "tf_png_last_bands: %zu bands, room for %zu", *n_bands, capacity);
+    for (int i = 0; i < enc->n_bands; i++) {
+        // a band is coded only where that is smaller than its stored form: the size says which it is
+        const int rows = enc->band_rows < enc->H - i * enc->band_rows ? enc->band_rows : enc->H - i * enc->band_rows;
+        sizes[i] = enc->lengths_host.as<uint32_t>()[i];
+        stored[i] = sizes[i] == stored_bytes((uint64_t)rows * enc->row_bytes);
+    }
+    return TF_OK;
 }
 
 TF_API int tf_png_copy_last(tf_png *enc, uint8_t *out, size_t capacity, size_t *n_bytes)

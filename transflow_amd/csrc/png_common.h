@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "crc32_common.h"
+#include "deflate_code.h"
 #include "deflate_tables.h"
 
 namespace tf {
@@ -24,6 +25,13 @@ struct Tables {
     uint32_t header[HEADER_WORDS];  // the HEADER_BITS above, stream bit 32 w + k in bit k of word w
 };
 
+// ---- what k_png_table writes beside a Tables' entries and header when the code is the frame's own (tf_png_set_code)
+struct FrameCode {
+    uint32_t cost[N_SYMBOLS]; // the bits one occurrence of the symbol takes, a match's extra bits and distance bit included
+    uint32_t repairs;         // how often the weights were halved to bring the code within 15 bits
+    uint8_t lengths[N_SYMBOLS + 2];
+};
+
 // ---- the bound.  A band's data is the header, its bytes' tokens, end-of-block, the three bits of the empty stored
 // block, at most 7 bits of padding and that block's four bytes.  A byte is coded as a literal, or as one of the n >= 3
 // bytes of a match that costs its length code, at most 5 extra bits and the distance bit: the costliest coding of a
@@ -33,6 +41,8 @@ inline size_t slot_bytes(size_t band_bytes, int byte_bits, int eob_bits)
     const size_t bits = HEADER_BITS + band_bytes * (size_t)byte_bits + (size_t)eob_bits + 3 + 7 + 32;
     return (bits / 8 + 3) & ~(size_t)3; // slots stay dword-aligned
 }
+// With the frame's own code a band is coded only where that is smaller than stored_bytes(band_bytes), and that is below
+// the bound above for any code whose longest literal has 8 bits or more (tf_png_set_code checks it for the handle's band).
 
 // The LDS bit buffer of a wave holds the header or the 7 bits carried into a trip, what 64 lanes can physically OR into
 // it per trip -- a lane's tokens are at most 64 bits, checked on the host when the table is made -- and the band's end.

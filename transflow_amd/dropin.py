@@ -89,13 +89,14 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
     return classmethod(from_args)
 
 
-def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_frames=False):
+def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_frames=False, png_code="fixed"):
     from .compositor import LAYER_CLASSES, HipCompositor
 
     def from_args(cls, height, width, layer_configs, background_color="#ffffff"):
         if all(getattr(c, "classname", None) in LAYER_CLASSES for c in layer_configs):
             return HipCompositor.from_args(height, width, layer_configs, background_color=background_color,
-                                           lazy_frames=lazy_frames, jpeg_frames=jpeg_frames, png_frames=png_frames)
+                                           lazy_frames=lazy_frames, jpeg_frames=jpeg_frames, png_frames=png_frames,
+                                           png_code=png_code)
         return original(height, width, layer_configs, background_color=background_color)
 
     return classmethod(from_args)
@@ -145,7 +146,7 @@ def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=Fals
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
-            device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False) -> None:
+            device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed") -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -169,6 +170,9 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     option when it is fed a PngFrame.  Not together with jpeg_frames or lazy_frames.  By default nothing of this is
     touched.  png_frames="indexed": the same, and the files carry the band index (PngEncoder(index=True), DESIGN.md
     section 20) that lets `png_inputs` decode them on the device; plain True keeps writing the bytes it wrote before.
+    png_code="frame": with png_frames (True or "indexed"), the files are coded with the frame's own literal/length code
+    and a band that would not shrink is stored (PngEncoder(code="frame")): smaller files of the
+    same pixels, which any decoder and `png_inputs` read; "fixed" (the default) keeps writing the bytes it wrote before.
     device_flow_export: the flow export (`--export-flow`, `--export-rounded-flow`) writes its `.flow.zip` through
     archive.DeviceFlowArchiveWriter, put where pipeline.py:369 finds NumpyOutput: a DeviceFlow is deflated on the device
     (transflow_amd/flowzip.py) and only the member comes down; and `numpy.round(flow).astype(int)` (pipeline.py:506) of a
@@ -193,6 +197,10 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         raise ValueError("jpeg_frames and lazy_frames exclude each other")
     if png_frames and (jpeg_frames is not None or lazy_frames):
         raise ValueError("png_frames excludes jpeg_frames and lazy_frames")
+    if png_code not in ("fixed", "frame"):
+        raise ValueError(f"png_code is \"fixed\" or \"frame\", not {png_code!r}")
+    if png_code != "fixed" and not png_frames:
+        raise ValueError("png_code is for png_frames: without them no PNG is written")
     if flow and "flow" not in _saved:
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
@@ -206,7 +214,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         bind_reference_data_layer()    # extra/control.py:155 asks isinstance(layer, DataLayer) of checkpointed layers
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
         RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames,
-                                                        "indexed" if png_frames == "indexed" else bool(png_frames))
+                                                        "indexed" if png_frames == "indexed" else bool(png_frames), png_code)
     if jpeg_frames is not None and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])

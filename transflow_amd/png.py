@@ -54,9 +54,15 @@ class PngEncoder(FrameEncoder):
 
     ENCODE_DEV, ENCODE, COPY_LAST, DESTROY = "tf_png_encode_dev", "tf_png_encode", "tf_png_copy_last", "tf_png_destroy"
 
-    def __init__(self, height: int, width: int, band_rows: int | None = None, index: bool = False):
+    CODES = {"fixed": 0, "frame": 1}
+
+    def __init__(self, height: int, width: int, band_rows: int | None = None, index: bool = False, code: str = "fixed"):
         """index: the files carry the band index (the ancillary chunk tfBX) that lets
-        transflow_amd/pngdec.py decode them on the device; without it they are the bytes they always were."""
+        transflow_amd/pngdec.py decode them on the device; without it they are the bytes they always were.
+        code: "fixed", the library's constant literal/length code; "frame", the code of the frame's own tokens, and a
+        band that would not shrink stored: smaller files, the same pixels."""
+        if code not in self.CODES:
+            raise ValueError(f"code {code!r}: one of {sorted(self.CODES)}")
         super().__init__(height, width)
         self._check(self._lib.tf_png_create(C.byref(self._h), self.height, self.width,
                                             0 if band_rows is None else int(band_rows)))
@@ -64,6 +70,28 @@ class PngEncoder(FrameEncoder):
         self.index = bool(index)
         if self.index:
             self._check(self._lib.tf_png_set_index(self._h, 1))
+        self.code = "fixed"
+        self.set_code(code)
+
+    def set_code(self, code: str) -> None:
+        """The code of the later encodes (no GPU call)."""
+        if code not in self.CODES:
+            raise ValueError(f"code {code!r}: one of {sorted(self.CODES)}")
+        self._check(self._lib.tf_png_set_code(self._h, self.CODES[code]))
+        self.code = code
+
+    def last_code(self):
+        """(the 286 code lengths, how often the weights were halved) of the last frame encoded with code="frame"."""
+        lengths, repairs = (C.c_uint8 * 286)(), C.c_uint32()
+        self._check(self._lib.tf_png_last_code(self._h, lengths, C.byref(repairs)))
+        return list(lengths), int(repairs.value)
+
+    def last_bands(self):
+        """(the bytes of each band's deflate data, whether each band is stored) of the same frame."""
+        n_bands = -(-self.height // self.band_rows)
+        sizes, stored, n = (C.c_uint32 * n_bands)(), (C.c_uint8 * n_bands)(), C.c_size_t()
+        self._check(self._lib.tf_png_last_bands(self._h, sizes, stored, n_bands, C.byref(n)))
+        return list(sizes[:n.value]), [bool(v) for v in stored[:n.value]]
 
     def _first_capacity(self) -> int:   # rendered frames are a part of this
         return self.height * self.width * 3 // 2 + 4096
