@@ -2,8 +2,11 @@
 import glob
 import json
 import os
+import shutil
+import subprocess
 
 import numpy as np
+import pytest
 
 from oracle import remap_ref
 
@@ -328,3 +331,36 @@ def polar_flow(x) -> np.ndarray:
     """The flow (x, 0) as a C-contiguous float32 (1, N, 2) array."""
     x = np.asarray(x, np.float32).ravel()
     return np.ascontiguousarray(np.stack([x, np.zeros_like(x)], axis=-1)[None])
+
+
+def build_host_check(tmp_path, source_name):
+    """tools/<source_name> (a stand-alone program: exit status 2 and a usage line when run without arguments) built by
+    the first host compiler there is: with the sanitizers where their runtime links and the program runs, without them
+    otherwise.  (program, sanitized).  A machine without any host compiler skips; a compiler that cannot build the plain
+    program, or whose program does not start, fails the test with what it said."""
+    source = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", source_name)
+    compilers = [c for c in ("g++", "clang++", "c++") if shutil.which(c) is not None]
+    if not compilers:
+        pytest.skip("no host compiler here")
+
+    def build(compiler, flags, tag):
+        out = str(tmp_path / ("check_" + compiler.replace("+", "x") + tag))
+        built = subprocess.run([compiler, "-O1", "-g", "-std=c++17", *flags, source, "-o", out], capture_output=True, text=True)
+        if built.returncode != 0:
+            return None, built.stderr
+        ran = subprocess.run([out], capture_output=True, text=True)
+        if ran.returncode == 2 and "usage" in ran.stderr:
+            return out, ""
+        return None, ran.stderr
+
+    for compiler in compilers:
+        program, _ = build(compiler, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "_san")
+        if program:
+            return program, True
+    said = []
+    for compiler in compilers:
+        program, stderr = build(compiler, [], "")
+        if program:
+            return program, False
+        said.append(f"{compiler}: {stderr[-2000:]}")
+    pytest.fail(f"no host compiler builds tools/{source_name}:\n" + "\n".join(said))

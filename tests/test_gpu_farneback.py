@@ -1071,3 +1071,122 @@ def test_bgr_frame_into_a_slot_matches_the_host_conversion_and_validates(FB):
     with pytest.raises(ValueError):
         fb.set_frame_bgr(0, view.astype(np.float32))   # not uint8
     fb.close()
+
+
+# ---- the driver's call plan, seen through the library's own event profiler --------------------------------------
+# 160 x 128 frames, levels=2: level sizes 160x128, 80x64, 40x32 (K = 2), winsize 15, 3 iterations
+
+EXP_LABELS = ("fb_level_image", "fb_level_rowpass", "fb_level_colpass", "fb_polyexp", "fb_polyexp_generic", "fb_level_polyexp")
+PLAN_KW = dict(levels=2, winsize=15, iterations=3)
+
+
+def _launches(run):
+    """run() under the profiler: label -> launches, for the labels of the Farnebäck path"""
+    from transflow_amd import _lib
+    _lib.profile(True, "fb_")
+    try:
+        run()
+        return {name: n for name, (n, _) in _lib.profile_report().items()}
+    finally:
+        _lib.profile(False)
+
+
+def _expansions(report):
+    return sum(n for name, n in report.items() if name in EXP_LABELS)
+
+
+def test_a_kept_handle_expands_only_what_was_written(FB):
+    """tf_fb_keep_expansions: a call whose slots were all expanded launches no expansion at all, a call after one frame
+    was written one run of one image, after two frames that are not neighbours two such runs -- and the flows are a fresh
+    handle's, bit for bit."""
+    h, w = 128, 160
+    frames = [synth_pair(h, w, seed=120, shift=(0.7 * i, 0.4 * i))[1] for i in range(7)]
+    slots = list(frames[:4])
+
+    def fresh():
+        fb = FB(w, h, frame_slots=4, max_pairs=2, **PLAN_KW)
+        for i, f in enumerate(slots):
+            fb.set_frame(i, f)
+        fb.calc_slots([0, 2], [1, 3])
+        out = [fb.get_flow(0), fb.get_flow(1)]
+        fb.close()
+        return out
+
+    fb = FB(w, h, frame_slots=4, max_pairs=2, **PLAN_KW)
+    fb.keep_expansions(True)
+    for i, f in enumerate(slots):
+        fb.set_frame(i, f)
+    call = lambda: fb.calc_slots([0, 2], [1, 3])
+    assert _expansions(_launches(call)) > 0
+    first = [fb.get_flow(0), fb.get_flow(1)]
+    again = _launches(call)
+    assert not set(again) & set(EXP_LABELS), again
+    for got, exp in zip([fb.get_flow(0), fb.get_flow(1)], first):
+        np.testing.assert_array_equal(got, exp)
+    slots[1] = frames[4]
+    fb.set_frame(1, slots[1])
+    one = _expansions(_launches(call))                     # one run of one image
+    assert one > 0
+    for got, exp in zip([fb.get_flow(0), fb.get_flow(1)], fresh()):
+        np.testing.assert_array_equal(got, exp)
+    slots[0], slots[2] = frames[5], frames[6]
+    fb.set_frame(0, slots[0])
+    fb.set_frame(2, slots[2])
+    assert _expansions(_launches(call)) == 2 * one         # two runs of one image each
+    for got, exp in zip([fb.get_flow(0), fb.get_flow(1)], fresh()):
+        np.testing.assert_array_equal(got, exp)
+    fb.close()
+
+
+@pytest.mark.parametrize("fused", [1, 0])
+def test_the_level_loop_issues_what_the_algorithm_says(FB, lib_option, fused):
+    """(K + 1) x iterations launches per call: of the one-kernel iteration with option "fb_fused" = 1 (and no
+    update-matrices), of update-matrices with 0 (and no one-kernel iteration); the flow within tolerance of the oracle."""
+    h, w = 128, 160
+    a, b = synth_pair(h, w, seed=121, shift=(1.5, 1.0))
+    lib_option("fb_fused", fused)                          # read when the handle is created
+    fb = FB(w, h, **PLAN_KW)
+    assert len(fb.level_sizes()) == 3
+    fb.set_frame(0, a)
+    fb.set_frame(1, b)
+    report = _launches(lambda: fb.calc_slots([0], [1]))
+    got = fb.get_flow(0)
+    fb.close()
+    one, two = report.get("fb_flow_iter", 0), report.get("fb_update_matrices", 0)
+    assert (one, two) == ((9, 0) if fused else (0, 9)), report
+    ref = O.calc(a, b, **PLAN_KW)
+    assert np.abs(got - ref).max() <= flow_tol(ref)
+
+
+def test_stage_entry_points_after_a_batch_call_are_those_of_a_fresh_handle(FB):
+    """A stage entry point takes images 0 and 1 from the head of the buffers, whatever the last batch call's pair -> image
+    map (pair 0 = a frame against itself here) and last run (a kept handle's run of slot 3 alone) were."""
+    h, w = 128, 160
+    frames = [synth_pair(h, w, seed=122, shift=(0.8 * i, 0.5 * i))[1] for i in range(4)]
+    rng = np.random.default_rng(9)
+    r0 = rng.normal(0, 3, (h, w, 5)).astype(np.float32)
+    r1 = rng.normal(0, 3, (h, w, 5)).astype(np.float32)
+    flow = rng.normal(0, 2, (h, w, 2)).astype(np.float32)
+
+    def stages(fb):
+        out = [fb.stage_update_matrices(r0, r1, flow)]
+        out += [fb.stage_level_polyexp(frames[2], k) for k in range(len(fb.level_sizes()))]
+        return out
+
+    fresh = FB(w, h, frame_slots=4, max_pairs=2, **PLAN_KW)
+    exp = stages(fresh)
+    fresh.close()
+    shared = FB(w, h, frame_slots=4, max_pairs=2, **PLAN_KW)
+    kept = FB(w, h, frame_slots=4, max_pairs=2, **PLAN_KW)
+    kept.keep_expansions(True)
+    for fb in (shared, kept):
+        for i, f in enumerate(frames):
+            fb.set_frame(i, f)
+    shared.calc_slots([1, 0], [1, 2])                      # images: slot 1, 0, 2; map (0,0) (1,2)
+    kept.calc_slots([0, 2], [1, 3])
+    kept.set_frame(3, frames[0])
+    kept.calc_slots([0, 2], [1, 3])                        # one run: slot 3 alone
+    for fb in (shared, kept):
+        for got, want in zip(stages(fb), exp):
+            np.testing.assert_array_equal(got, want)
+        fb.close()

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import build_host_check
 from tests import jpegdec_ref as JR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,35 +173,8 @@ def test_reject_reasons_of_the_fixtures():
 
 
 def _build_host_check(tmp_path):
-    """tools/jpegdec_host_check.cpp built by the first host compiler there is: with the sanitizers where their runtime
-    links and the program runs, without them otherwise.  (program, sanitized).  A machine without any host compiler
-    skips; a compiler that cannot build the plain program fails the test with what it said."""
-    source = os.path.join(ROOT, "tools", "jpegdec_host_check.cpp")
-    compilers = [c for c in ("g++", "clang++", "c++") if shutil.which(c) is not None]
-    if not compilers:
-        pytest.skip("no host compiler here")
-
-    def build(compiler, flags, tag):
-        out = str(tmp_path / ("check_" + compiler.replace("+", "x") + tag))
-        built = subprocess.run([compiler, "-O1", "-g", "-std=c++17", *flags, source, "-o", out], capture_output=True, text=True)
-        if built.returncode != 0:
-            return None, built.stderr
-        ran = subprocess.run([out], capture_output=True, text=True)
-        if ran.returncode == 2 and "usage" in ran.stderr:
-            return out, ""
-        return None, ran.stderr
-
-    for compiler in compilers:
-        program, _ = build(compiler, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "_san")
-        if program:
-            return program, True
-    said = []
-    for compiler in compilers:
-        program, stderr = build(compiler, [], "")
-        if program:
-            return program, False
-        said.append(f"{compiler}: {stderr[-2000:]}")
-    pytest.fail("no host compiler builds tools/jpegdec_host_check.cpp:\n" + "\n".join(said))
+    """tools/jpegdec_host_check.cpp, with the sanitizers where they run here: (program, sanitized)."""
+    return build_host_check(tmp_path, "jpegdec_host_check.cpp")
 
 
 def test_host_check_program(tmp_path):

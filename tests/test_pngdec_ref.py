@@ -12,6 +12,7 @@ import numpy as np
 import PIL.Image
 import pytest
 
+from tests.helpers import build_host_check
 from tests import png_ref as P
 from tests import pngdec_cases as K
 from tests import pngdec_ref as D
@@ -114,36 +115,8 @@ def test_reject_names_are_the_librarys():
 
 
 def _build_host_check(tmp_path):
-    """tools/pngdec_host_check.cpp built by the first host compiler there is: with the sanitizers where their runtime
-    links and the program runs, without them otherwise.  (program, sanitized).  A machine without any host compiler
-    skips; a compiler that cannot build the plain program, or whose program does not start, fails the test with what
-    it said."""
-    source = os.path.join(ROOT, "tools", "pngdec_host_check.cpp")
-    compilers = [c for c in ("g++", "clang++", "c++") if shutil.which(c) is not None]
-    if not compilers:
-        pytest.skip("no host compiler here")
-
-    def build(compiler, flags, tag):
-        out = str(tmp_path / ("check_" + compiler.replace("+", "x") + tag))
-        built = subprocess.run([compiler, "-O1", "-g", "-std=c++17", *flags, source, "-o", out], capture_output=True, text=True)
-        if built.returncode != 0:
-            return None, built.stderr
-        ran = subprocess.run([out], capture_output=True, text=True)
-        if ran.returncode == 2 and "usage" in ran.stderr:
-            return out, ""
-        return None, ran.stderr
-
-    for compiler in compilers:
-        program, _ = build(compiler, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "_san")
-        if program:
-            return program, True
-    said = []
-    for compiler in compilers:
-        program, stderr = build(compiler, [], "")
-        if program:
-            return program, False
-        said.append(f"{compiler}: {stderr[-2000:]}")
-    pytest.fail("no host compiler builds tools/pngdec_host_check.cpp:\n" + "\n".join(said))
+    """tools/pngdec_host_check.cpp, with the sanitizers where they run here: (program, sanitized)."""
+    return build_host_check(tmp_path, "pngdec_host_check.cpp")
 
 
 def _run_host_check(tmp_path, lines):

@@ -102,14 +102,10 @@ struct tf_batch {
     DevBuf scratch; // the reduction's few doubles
     // tf_batch_gather_begin / _end: a gather beside the next pass
     hipStream_t gather_stream = nullptr;
-    hipEvent_t gather_from = nullptr, gather_done = nullptr;
+    Event gather_from, gather_done;
     bool gather_pending = false;
     ~tf_batch()
     {
-        if (gather_from)
-            (void)hipEventDestroy(gather_from);
-        if (gather_done)
-            (void)hipEventDestroy(gather_done);
         if (gather_stream)
             (void)hipStreamDestroy(gather_stream);
     }
@@ -285,8 +281,8 @@ TF_API int tf_batch_gather_begin(tf_batch *b, const void *send_dev, size_t send_
     TF_TRY(ensure_init());
     if (!b->gather_stream) {
         TF_HIP(hipStreamCreateWithFlags(&b->gather_stream, hipStreamNonBlocking));
-        TF_HIP(hipEventCreateWithFlags(&b->gather_from, hipEventDisableTiming));
-        TF_HIP(hipEventCreateWithFlags(&b->gather_done, hipEventDisableTiming));
+        TF_TRY(b->gather_from.create());
+        TF_TRY(b->gather_done.create());
     }
     TF_HIP(hipEventRecord(b->gather_from, main_stream()));
     TF_HIP(hipStreamWaitEvent(b->gather_stream, b->gather_from, 0));

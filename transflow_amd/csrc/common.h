@@ -111,7 +111,7 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-// Simple owning page-locked host buffer (hipHostMallocDefault).
+// Simple owning page-locked host buffer (default flags).
 struct PinnedBuf {
     void *p = nullptr;
     PinnedBuf() = default;
@@ -121,6 +121,18 @@ struct PinnedBuf {
     int alloc(size_t n);
     void release();
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// Simple owning event without timing (hipEventDisableTiming).  Converts to the hipEvent_t it holds: null until create().
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { release(); }
+    int create();
+    void release();
+    operator hipEvent_t() const { return e; }
 };
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }

@@ -219,11 +219,7 @@ static int fb_create(tf_fb **out, int width, int height, const tf_fb_params *par
     TF_TRY(fb_validate_params(params, width, height));
     TF_REQUIRE(frame_slots >= 2 && max_pairs >= 1, "tf_fb_create: need >= 2 frame slots and >= 1 pair");
     TF_TRY(ensure_init());
-    tf_fb *fb = new tf_fb;
-    auto fail = [&](int rc) {
-        delete fb;
-        return rc;
-    };
+    std::unique_ptr<tf_fb> fb(new tf_fb); // released on every early return below
     fb->W = width;
     fb->H = height;
     fb->prm = *params;
@@ -241,10 +237,9 @@ static int fb_create(tf_fb **out, int width, int height, const tf_fb_params *par
         }
         fb->K = k;
     }
-    int rc;
     for (int k = 0; k <= fb->K; k++) {
-        Level *L = new Level;
-        fb->lv.push_back(L);
+        fb->lv.emplace_back(new Level);
+        Level *L = fb->lv.back().get();
         double scale = 1;
         for (int i = 0; i < k; i++)
             scale *= params->pyr_scale;
@@ -254,25 +249,20 @@ static int fb_create(tf_fb **out, int width, int height, const tf_fb_params *par
         L->W = cv_round(width * scale);
         L->H = cv_round(height * scale);
         if (L->W < 1 || L->H < 1)
-            return fail(set_error(TF_ERR_ARG, "tf_fb_create: level %d is empty", k));
+            return set_error(TF_ERR_ARG, "tf_fb_create: level %d is empty", k);
         std::vector<float> kern = gaussian_kernel(L->ksz, L->sigma);
         L->kern_host = kern;
-        if ((rc = L->kern.alloc(kern.size() * 4)))
-            return fail(rc);
-        if (hipMemcpy(L->kern.p, kern.data(), kern.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            return fail(set_error(TF_ERR_HIP, "hipMemcpy failed"));
-        if ((rc = L->img_lerp.upload_tabs(width, height, L->W, L->H)))
-            return fail(rc);
+        TF_TRY(L->kern.alloc(kern.size() * 4));
+        TF_HIP(hipMemcpy(L->kern.p, kern.data(), kern.size() * 4, hipMemcpyHostToDevice));
+        TF_TRY(L->img_lerp.upload_tabs(width, height, L->W, L->H));
         L->tile = choose_tile(width, height, L->W, L->H, L->ksz, k);
         {
             std::vector<int> colsrc;
             L->quarter = plan_quarter_level(width, height, *L);
             L->split = !L->quarter && plan_split_level(width, height, *L, colsrc);
             if (L->split) {
-                if ((rc = L->colsrc.alloc(colsrc.size() * 4)))
-                    return fail(rc);
-                if (hipMemcpy(L->colsrc.p, colsrc.data(), colsrc.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-                    return fail(set_error(TF_ERR_HIP, "hipMemcpy failed"));
+                TF_TRY(L->colsrc.alloc(colsrc.size() * 4));
+                TF_HIP(hipMemcpy(L->colsrc.p, colsrc.data(), colsrc.size() * 4, hipMemcpyHostToDevice));
             }
         }
         if (tune("TF_DEBUG_TILES", 0))
@@ -282,33 +272,32 @@ static int fb_create(tf_fb **out, int width, int height, const tf_fb_params *par
             size_t smem = (size_t)L->tile.LH * L->tile.pitch + (size_t)L->tile.LH * L->tile.rstride * sizeof(float) +
                           (size_t)L->ksz * sizeof(float);
             if (smem > 64 * 1024)
-                return fail(set_error(TF_ERR_UNSUPPORTED, "tf_fb_create: level %d needs %zu bytes of LDS per tile "
-                                                          "(blur kernel %d taps)", k, smem, L->ksz));
+                return set_error(TF_ERR_UNSUPPORTED, "tf_fb_create: level %d needs %zu bytes of LDS per tile "
+                                                          "(blur kernel %d taps)", k, smem, L->ksz);
         }
     }
     for (int k = 0; k < fb->K; k++) {
         Level &L = *fb->lv[k], &C = *fb->lv[k + 1];
-        if ((rc = L.flow_lerp.upload_tabs(C.W, C.H, L.W, L.H)))
-            return fail(rc);
+        TF_TRY(L.flow_lerp.upload_tabs(C.W, C.H, L.W, L.H));
     }
-    if ((rc = fb_setup_flags(fb)))
-        return fail(rc);
+    TF_TRY(fb_setup_flags(fb.get()));
     const size_t N0 = (size_t)width * height, P = (size_t)max_pairs;
     fb->nsets = (fb_overlap_enabled() && fb->K > 0) ? 2 : 1; // a single scale: every launch fills the chip anyway
     if (share)
         fb->frames.borrow(share->frames.p, N0 * frame_slots);
+    int rc;
     if ((!share && (rc = fb->frames.alloc(N0 * frame_slots))) || (rc = fb->img.alloc(P * 2 * N0 * 4)) ||
         (rc = fb->R.alloc(P * 10 * N0 * 4)) ||
         (rc = fb->lflow[0].alloc(P * N0 * 8)) || (rc = fb->lflow[1].alloc(P * N0 * 8)) ||
         (rc = fb->lflow[2].alloc(P * N0 * 8)) ||
         (fb->nsets > 1 && ((rc = fb->lflow[3].alloc(P * N0 * 8)) || (rc = fb->lflow[4].alloc(P * N0 * 8)))) ||
         (rc = fb->pairs.alloc(3 * P * 8)) || (rc = fb->winner.alloc(N0 * 4)) || (rc = fb->scratch.alloc(N0 * 20)))
-        return fail(rc);
+        return rc;
     for (int k = 1; k <= fb->K; k++) {
         Level &L = *fb->lv[k];
         const size_t nk = (size_t)L.W * L.H;
-        if ((rc = L.img.alloc(P * 2 * nk * 4)) || (rc = L.R.alloc(P * 10 * nk * 4)))
-            return fail(rc);
+        TF_TRY(L.img.alloc(P * 2 * nk * 4));
+        TF_TRY(L.R.alloc(P * 10 * nk * 4));
     }
     {
         // one row-pass launch for all split levels: rows staged with the longest kernel's margin, pitch = 1
@@ -343,24 +332,24 @@ static int fb_create(tf_fb **out, int width, int height, const tf_fb_params *par
                 fb->rp_first = -1;
             } else {
                 fb->rp_RB = std::min(RB, 64);
-                if ((rc = fb->rowf.alloc(floats * 4)))
-                    return fail(rc);
+                TF_TRY(fb->rowf.alloc(floats * 4));
             }
         }
     }
-    if (hipEventCreateWithFlags(&fb->chain_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&fb->pairs_copied, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&fb->entry[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&fb->entry[1], hipEventDisableTiming) != hipSuccess ||
-        side_stream(share ? 2 : 1, &fb->chain_stream) != TF_OK ||
-        hipHostMalloc((void **)&fb->pairs_host, 3 * P * sizeof(int2), hipHostMallocDefault) != hipSuccess)
-        return fail(set_error(TF_ERR_HIP, "creating the handle's events and staging buffer failed"));
+    TF_TRY(fb->chain_done.create());
+    TF_TRY(fb->pairs_copied.create());
+    TF_TRY(fb->entry[0].create());
+    TF_TRY(fb->entry[1].create());
+    TF_TRY(side_stream(share ? 2 : 1, &fb->chain_stream));
+    TF_TRY(fb->pairs_host.alloc(3 * P * sizeof(int2)));
+    fb->image_of.resize((size_t)frame_slots);
+    fb->runs.resize(((size_t)frame_slots + 1) / 2); // the most runs a plan makes: every other slot
     if (share) {
         fb->lane_of = share;
         fb->exact = share->exact;
         share->lanes++;
     }
-    *out = fb;
+    *out = fb.release();
     return TF_OK;
 }
 
@@ -422,16 +411,32 @@ TF_API int tf_fb_level_size(tf_fb *fb, int level, int *w, int *h)
     return TF_OK;
 }
 
+// What tf_fb_set_frame / _bgr / _bgr_dev do with a (checked) slot before they write it: *dst is where the frame goes, a
+// kept expansion of the slot is no longer valid, and *up is the stream the write goes to.
 // tf_fb_async_io: a frame goes up on the upload stream, which first waits for the last call that read the slot's old
 // frame (a streaming caller's slot was read two calls ago: no wait in practice).  Without async io: nothing to do, the
 // upload is ordered on the caller's stream.
-static int fb_upload_scope_begin(tf_fb *fb, int slot)
+static int fb_slot_write_begin(tf_fb *fb, int slot, uint8_t **dst, hipStream_t *up)
 {
+    *dst = fb->frames.as<uint8_t>() + (size_t)slot * fb->W * fb->H;
+    if (fb->keep)
+        fb->expanded[slot] = 0;
+    *up = fb->async_io ? fb->up_stream : stream();
     if (!fb->async_io)
         return TF_OK;
     const long last = fb->slot_read_call[(size_t)slot];
     if (last >= 0 && fb->call_done[last & 1])
         TF_HIP(hipStreamWaitEvent(fb->up_stream, fb->call_done[last & 1], 0)); // (that call's event, or a later call's of the same parity)
+    return TF_OK;
+}
+
+// ends the pending download of result set s, if there is one
+static int fb_download_end(tf_fb *fb, int s)
+{
+    if (fb->download_pending[s]) {
+        TF_HIP(hipEventSynchronize(fb->download_done[s]));
+        fb->download_pending[s] = false;
+    }
     return TF_OK;
 }
 
@@ -446,18 +451,15 @@ TF_API int tf_fb_async_io(tf_fb *fb, int on)
         TF_TRY(side_stream(3, &fb->up_stream));
         TF_TRY(side_stream(4, &fb->down_stream));
         for (int i = 0; i < 2; i++) {
-            TF_HIP(hipEventCreateWithFlags(&fb->call_done[i], hipEventDisableTiming));
-            TF_HIP(hipEventCreateWithFlags(&fb->result_ready[i], hipEventDisableTiming));
-            TF_HIP(hipEventCreateWithFlags(&fb->download_done[i], hipEventDisableTiming));
+            TF_TRY(fb->call_done[i].create());
+            TF_TRY(fb->result_ready[i].create());
+            TF_TRY(fb->download_done[i].create());
         }
         fb->slot_read_call.assign((size_t)fb->slots, -1);
     }
     if (!on)
         for (int i = 0; i < 2; i++)
-            if (fb->download_pending[i]) {
-                TF_HIP(hipEventSynchronize(fb->download_done[i]));
-                fb->download_pending[i] = false;
-            }
+            TF_TRY(fb_download_end(fb, i));
     fb->async_io = on != 0;
     return TF_OK;
 }
@@ -468,11 +470,10 @@ TF_API int tf_fb_set_frame(tf_fb *fb, int slot, const uint8_t *grey, ptrdiff_t s
     TF_REQUIRE(slot >= 0 && slot < fb->slots, "tf_fb_set_frame: slot %d out of range (%d slots)", slot, fb->slots);
     TF_REQUIRE(stride >= fb->W, "tf_fb_set_frame: stride %td smaller than width %d", stride, fb->W);
     TF_TRY(ensure_init());
-    uint8_t *dst = fb->frames.as<uint8_t>() + (size_t)slot * fb->W * fb->H;
-    if (fb->keep)
-        fb->expanded[slot] = 0;
-    TF_TRY(fb_upload_scope_begin(fb, slot));
-    StreamScope up(fb->async_io ? fb->up_stream : stream());
+    uint8_t *dst;
+    hipStream_t up_to;
+    TF_TRY(fb_slot_write_begin(fb, slot, &dst, &up_to));
+    StreamScope up(up_to);
     TF_HIP(hipMemcpy2DAsync(dst, fb->W, grey, (size_t)stride, fb->W, fb->H, hipMemcpyHostToDevice, stream()));
     TF_HIP(hipStreamSynchronize(stream())); // the host frame is borrowed for this call only
     return TF_OK;
@@ -492,11 +493,10 @@ TF_API int tf_fb_set_frame_bgr(tf_fb *fb, int slot, const uint8_t *bgr, int src_
     const size_t row = (size_t)3 * src_width, need = row * src_height;
     if (fb->bgr_stage.bytes < need)
         TF_TRY(fb->bgr_stage.alloc(need));
-    uint8_t *dst = fb->frames.as<uint8_t>() + (size_t)slot * fb->W * fb->H;
-    if (fb->keep)
-        fb->expanded[slot] = 0;
-    TF_TRY(fb_upload_scope_begin(fb, slot));
-    StreamScope up(fb->async_io ? fb->up_stream : stream());
+    uint8_t *dst;
+    hipStream_t up_to;
+    TF_TRY(fb_slot_write_begin(fb, slot, &dst, &up_to));
+    StreamScope up(up_to);
     TF_HIP(hipMemcpy2DAsync(fb->bgr_stage.p, row, bgr, (size_t)stride, row, src_height, hipMemcpyHostToDevice, stream()));
     TF_TRY(tf_frame_grey_dev(fb->bgr_stage.p, src_width, src_height, dst, fb->W, fb->H));
     TF_HIP(hipStreamSynchronize(stream())); // the host frame is borrowed for this call only
@@ -511,11 +511,10 @@ TF_API int tf_fb_set_frame_bgr_dev(tf_fb *fb, int slot, const void *bgr_dev, int
     TF_REQUIRE(src_width >= 1 && src_height >= 1 && (long long)src_width * src_height < (1ll << 31),
                "tf_fb_set_frame_bgr_dev: bad source size %dx%d", src_width, src_height);
     TF_TRY(ensure_init());
-    uint8_t *dst = fb->frames.as<uint8_t>() + (size_t)slot * fb->W * fb->H;
-    if (fb->keep)
-        fb->expanded[slot] = 0;
-    TF_TRY(fb_upload_scope_begin(fb, slot));
-    StreamScope up(fb->async_io ? fb->up_stream : stream());
+    uint8_t *dst;
+    hipStream_t up_to;
+    TF_TRY(fb_slot_write_begin(fb, slot, &dst, &up_to));
+    StreamScope up(up_to);
     TF_TRY(tf_frame_grey_dev(bgr_dev, src_width, src_height, dst, fb->W, fb->H));
     TF_HIP(hipStreamSynchronize(stream())); // returns with the frame in place, as tf_fb_set_frame does
     return TF_OK;
@@ -544,7 +543,9 @@ TF_API int tf_fb_keep_expansions(tf_fb *fb, int on)
     return TF_OK;
 }
 
-TF_API int tf_fb_calc_slots(tf_fb *fb, int n_pairs, const int *prev_slots, const int *next_slots)
+// ---- tf_fb_calc_slots: check, plan, begin, expand, the levels coarse to fine, end -------------------------------
+
+static int fb_call_check(tf_fb *fb, int n_pairs, const int *prev_slots, const int *next_slots)
 {
     TF_REQUIRE(fb && prev_slots && next_slots, "tf_fb_calc_slots: null pointer");
     TF_REQUIRE(n_pairs >= 1 && n_pairs <= fb->max_pairs, "tf_fb_calc_slots: n_pairs %d not in [1,%d]", n_pairs,
@@ -556,67 +557,30 @@ TF_API int tf_fb_calc_slots(tf_fb *fb, int n_pairs, const int *prev_slots, const
     TF_TRY(fb_check_fault(fb, "tf_fb_calc_slots (an earlier call)"));
     if (!fb_exact(fb) && fb->exact_vsum.p && fb->prm.winsize / 2 != 0)
         fb->exact_vsum.release(); // the exact mode's column sums (40 bytes per pixel and pair): not kept once it is off
+    return TF_OK;
+}
+
+// The call's image plan (fb_plan.h has the rules) into the pinned staging buffer, laid out as it is uploaded: the image
+// list ([4P] ints: the runs, each padded to an even length), then the pair -> image map ([P] int2).
+static int fb_call_plan(tf_fb *fb, int n_pairs, const int *prev_slots, const int *next_slots, ImagePlan &plan)
+{
+    static_assert(sizeof(ImagePair) == sizeof(int2), "the map is uploaded as int2");
     if (fb->pairs_pending) { // the previous call's copy out of the staging buffer (long done in practice)
         TF_HIP(hipEventSynchronize(fb->pairs_copied));
         fb->pairs_pending = false;
     }
-    // A1+A2 depend on the frame alone, and consecutive pairs of a video share one: every slot the batch
-    // names is expanded once (16 consecutive pairs: 17 expansions, not 32) and each pair carries the
-    // indices of its two.  TF_FB_NO_SHARE=1: one expansion per pair and side, as separate calls would do.
-    // With tf_fb_keep_expansions an image IS its slot and survives the call: only slots written since
-    // their last expansion are listed, in runs of consecutive slots (a run = one set of launches).
-    const bool no_share = option(OPT_FB_NO_SHARE) != 0; // read per call
     const int P = fb->max_pairs;
-    int *image_slot = reinterpret_cast<int *>(fb->pairs_host); // [4P]: the runs, each padded to an even length
-    int2 *rmap_host = fb->pairs_host + 2 * P;
-    struct Run {
-        int image0, list0, n; // first image index written, offset into image_slot (even), images
-    };
-    std::vector<Run> runs;
-    if (fb->keep) {
-        std::vector<int> need;
-        fb->image_of.assign((size_t)fb->slots, -1);
-        for (int i = 0; i < n_pairs; i++) {
-            for (int s : {prev_slots[i], next_slots[i]})
-                if (fb->image_of[s] < 0 && (!fb->expanded[s] || fb->external[s])) {
-                    fb->image_of[s] = 1;
-                    need.push_back(s);
-                }
-            rmap_host[i] = make_int2(prev_slots[i], next_slots[i]);
-        }
-        std::sort(need.begin(), need.end());
-        int off = 0;
-        for (size_t q = 0; q < need.size();) {
-            size_t e = q + 1;
-            while (e < need.size() && need[e] == need[e - 1] + 1)
-                e++;
-            runs.push_back({need[q], off, (int)(e - q)});
-            for (size_t j = q; j < e; j++)
-                image_slot[off++] = need[j];
-            if (off & 1)
-                image_slot[off++] = need[q];
-            q = e;
-        }
-    } else {
-        int n_images = 0;
-        fb->image_of.assign((size_t)fb->slots, -1);
-        auto image = [&](int slot) {
-            if (no_share || fb->image_of[slot] < 0) {
-                fb->image_of[slot] = n_images;
-                image_slot[n_images++] = slot;
-            }
-            return fb->image_of[slot];
-        };
-        for (int i = 0; i < n_pairs; i++) {
-            const int a = image(prev_slots[i]);
-            rmap_host[i] = make_int2(a, image(next_slots[i]));
-        }
-        if (n_images & 1)
-            image_slot[n_images] = image_slot[0]; // the unused half of the last int2
-        runs.push_back({0, 0, n_images});
-    }
-    const int m = fb->prm.winsize / 2;
-    const bool fusable = m == 3 || m == 5 || m == 7; // the pair-sum window of the fused kernel
+    const bool no_share = option(OPT_FB_NO_SHARE) != 0; // read per call
+    plan = ImagePlan{fb->image_of.data(), fb->pairs_host.as<int>(), 4 * P, fb->pairs_host.as<ImagePair>() + 2 * P,
+                     fb->runs.data(), (int)fb->runs.size(), 0, 0};
+    if (!plan_images(plan, fb->slots, n_pairs, prev_slots, next_slots, fb->keep, no_share, fb->expanded.data(), fb->external.data()))
+        return set_error(TF_ERR_STATE, "tf_fb_calc_slots: the image plan of %d pairs does not fit the handle's staging buffer", n_pairs);
+    return TF_OK;
+}
+
+// Stream choice, the entry events and the upload of the plan.  *cs: the stream the call's work goes to.
+static int fb_call_begin(tf_fb *fb, const ImagePlan &plan, hipStream_t *cs_out)
+{
     // A call's work goes to a stream of its own.  The library stream -- where the caller's work on the
     // result goes (post_process, the remap of each pair) -- waits for its end, and the NEXT call does
     // not wait for that work: the result lands in one of two buffers by call parity, and this call
@@ -639,139 +603,157 @@ TF_API int tf_fb_calc_slots(tf_fb *fb, int n_pairs, const int *prev_slots, const
     if (fb->async_io) {
         if (fb->download_pending[set]) // this call's result takes the place of the one still on its way down
             TF_HIP(hipStreamWaitEvent(cs, fb->download_done[set], 0));
-        for (const Run &run : runs) // the slots whose frame bytes this call reads
-            for (int j = 0; j < run.n; j++)
-                fb->slot_read_call[(size_t)image_slot[run.list0 + j]] = fb->n_calls;
+        for (int r = 0; r < plan.n_runs; r++) // the slots whose frame bytes this call reads
+            for (int j = 0; j < plan.runs[r].n; j++)
+                fb->slot_read_call[(size_t)plan.list[plan.runs[r].list0 + j]] = fb->n_calls;
     }
-    TF_HIP(hipMemcpyAsync(fb->pairs.p, fb->pairs_host, (size_t)3 * P * sizeof(int2), hipMemcpyHostToDevice, cs));
+    TF_HIP(hipMemcpyAsync(fb->pairs.p, fb->pairs_host.p, (size_t)3 * fb->max_pairs * sizeof(int2), hipMemcpyHostToDevice, cs));
     TF_HIP(hipEventRecord(fb->pairs_copied, cs));
     fb->pairs_pending = true;
-    struct MapScope { // the launchers below read these from the handle; stage entry points run without them
-        tf_fb *fb;
-        ~MapScope()
-        {
-            fb->rmap_dev = nullptr;
-            fb->prep_image0 = fb->prep_list0 = 0;
-        }
-    } map_scope{fb};
-    fb->rmap_dev = fb->pairs.as<int2>() + 2 * P;
-    StreamScope chain_scope(cs);
-    // A1+A2 of every level (they depend on the frames only), coarse level first: the shared row pass
-    // of the long-kernel levels is launched with the coarsest of them
-    for (const Run &run : runs) {
-        fb->prep_image0 = run.image0;
-        fb->prep_list0 = run.list0 / 2;
-        for (int k = fb->K; k >= 0; k--) {
-            Level &L = *fb->lv[k];
-            if (fb_can_fuse_level(fb, k)) {
-                TF_TRY(fb_level0_polyexp(fb, k, run.n)); // A1+A2 in one kernel: the level image stays on chip
-            } else if (fb_can_fuse_half_level(fb, k)) {
-                TF_TRY(fb_level1_polyexp(fb, k, run.n));
-            } else {
-                TF_TRY(fb_level_image(fb, k, run.n));
-                TF_TRY(fb_polyexp(fb, L.W, L.H, run.n, k));
-            }
-        }
+    *cs_out = cs;
+    return TF_OK;
+}
+
+// A1+A2 of every level (they depend on the frames only), coarse level first: the shared row pass
+// of the long-kernel levels is launched with the coarsest of them
+static int fb_expand_runs(tf_fb *fb, const ImagePlan &plan)
+{
+    for (int r = 0; r < plan.n_runs; r++) {
+        const ImageRun &run = plan.runs[r];
+        for (int k = fb->K; k >= 0; k--)
+            TF_TRY(fb_expand_level(fb, k, run));
     }
-    fb->prep_image0 = fb->prep_list0 = 0;
     if (fb->keep) // valid from here on (until tf_fb_set_frame writes the slot)
-        for (const Run &run : runs)
-            for (int j = 0; j < run.n; j++)
-                fb->expanded[run.image0 + j] = 1;
-    int coarse = -1; // lflow buffer holding the coarser level's result
-    for (int k = fb->K; k >= 0; k--) {
-        Level &L = *fb->lv[k];
-        FlowInit fi;
-        memset(&fi, 0, sizeof(fi));
-        if (k < fb->K) {
-            Level &C = *fb->lv[k + 1];
-            fi.mode = 1;
-            fi.src = fb->lflow[coarse].as<float2>();
-            fi.Wc = C.W;
-            fi.Hc = C.H;
-            fi.xofs = L.flow_lerp.xofs.as<int>();
-            fi.yofs = L.flow_lerp.yofs.as<int>();
-            fi.xfrac = L.flow_lerp.xfrac.as<float>();
-            fi.yfrac = L.flow_lerp.yfrac.as<float>();
-            fi.mul = (float)(1. / fb->prm.pyr_scale);
-        }
-        // two buffers other than `coarse` for this level's iterations
-        int a = (coarse + 1) % 3, b = (coarse + 2) % 3;
-        if (coarse < 0) {
-            a = 0;
-            b = 1;
-        }
-        const int out_buf = overlap ? 3 + set : -1; // where the full-resolution result of this call lives
-        const long fuse_min_px = option(OPT_FB_FUSE_MIN_PX);
-        // (the fused kernel multiplies the edge weights unconditionally: identical from 10 x 10 up, border_scale)
-        // fb_exact_sums: column sums straight from R (k_flow_carry_pc<.., STORE>, one march per column) where many columns
-        // stand side by side, through M in memory otherwise (4K: 7.0 against 9.3 ms per level-0 iteration with 32 pairs,
-        // 2.9 against 2.5 with 8, 1.8 against 0.5 with one)
-        const bool exact_one_kernel = !fb_exact(fb) || fb->fused > 0 || (long)cdiv(L.W, 112) * n_pairs >= 560;
-        const bool fused_here = fusable && !fb->gaussian() && exact_one_kernel && L.W >= 10 && L.H >= 10 && (size_t)L.W * L.H < (1u << 28) && L.W < (1 << 24) && L.H < (1 << 24) &&
-                                (fb->fused > 0 || (fb->fused < 0 && (long)L.W * L.H * n_pairs >= fuse_min_px));
-        if (k == 0 && overlap && !fused_here)
-            a = out_buf;
-        int result;
-        // one kernel per iteration where the level fills the chip (>= 4M pixels over the batch), two otherwise
-        if (fused_here) {
-            // the iterations ping-pong between two buffers, ordered so that the LAST one writes p: the
-            // call's result buffer at full resolution, otherwise any buffer the coarser level is not in
-            const int I = fb->prm.iterations;
-            const int p = (k == 0 && overlap) ? out_buf : a, q = (k == 0 && overlap) ? a : b;
-            auto buf_of = [&](int i) { return ((I - i) & 1) ? q : p; }; // what iteration i (1..I) writes
-            const float2 *src = nullptr; // zero flow at the coarsest scale ...
-            if (k == fb->K && fb->use_initial()) { // ... or the caller's, shrunk to it (a buffer neither p nor q)
-                int c = 0;
-                while (c == p || c == q)
-                    c++;
-                TF_TRY(fb_initial_flow(fb, n_pairs, fb->lflow[c].as<float2>()));
-                src = fb->lflow[c].as<float2>();
-            }
-            for (int i = 1; i <= I; i++) {
-                int rc = TF_OK;
-                // the first iteration below the coarsest scale upsamples the coarser level's flow itself
-                if (!fb_flow_iter(fb, L.W, L.H, n_pairs, src, fb->lflow[buf_of(i)].as<float2>(), k, rc,
-                                  (i == 1 && k < fb->K) ? &fi : nullptr))
-                    return set_error(TF_ERR_STATE, "tf_fb_calc_slots: no one-kernel iteration for level %d", k);
-                TF_TRY(rc);
-                src = fb->lflow[buf_of(i)].as<float2>();
-            }
-            result = p;
-        } else {
-            FlowInit fl;
-            memset(&fl, 0, sizeof(fl));
-            fl.mode = 2;
-            fl.src = fb->lflow[a].as<float2>();
-            if (k == fb->K && fb->use_initial()) { // the caller's flow, shrunk to the coarsest scale, instead of zero
-                TF_TRY(fb_initial_flow(fb, n_pairs, fb->lflow[a].as<float2>()));
-                TF_TRY(fb_update_matrices(fb, L.W, L.H, n_pairs, fl, k));
-            } else {
-                TF_TRY(fb_update_matrices(fb, L.W, L.H, n_pairs, fi, k));
-            }
-            for (int i = 0; i < fb->prm.iterations; i++) {
-                if (fb->gaussian())
-                    TF_TRY(fb_gauss_solve(fb, L.W, L.H, n_pairs, fb->lflow[a].as<float2>(), k));
-                else
-                    TF_TRY(fb_blur_solve(fb, L.W, L.H, n_pairs, fb->lflow[a].as<float2>(), k));
-                if (i < fb->prm.iterations - 1) // M is a pure function of (R0, R1, flow): rebuild it in place
-                    TF_TRY(fb_update_matrices(fb, L.W, L.H, n_pairs, fl, k));
-            }
-            result = a;
-        }
-        coarse = result;
-        fb->final_buf = result;
+        for (int r = 0; r < plan.n_runs; r++)
+            for (int j = 0; j < plan.runs[r].n; j++)
+                fb->expanded[plan.runs[r].image0 + j] = 1;
+    return TF_OK;
+}
+
+// The flow a level starts from: zero at the coarsest scale, below it the coarser level's result (lflow[coarse]),
+// upsampled (A5).  `rmap`: the call's pair -> image map on the device.
+static FlowInit fb_level_start(tf_fb *fb, int k, int coarse, const int2 *rmap)
+{
+    FlowInit fi;
+    memset(&fi, 0, sizeof(fi));
+    if (k < fb->K)
+        fi = fb_upsampled(fb, k, fb->lflow[coarse].as<float2>());
+    fi.rmap = rmap;
+    return fi;
+}
+
+// The buffer rule.  lflow[0..2] rotate: `coarse` (-1 at the coarsest scale) holds the coarser level's result, and this
+// level may use the two others.  `result` is where the level's flow ends up, `other` a second buffer for iterations
+// that ping-pong.  The full-resolution result of an overlapped call lands in lflow[3 + set], where it lives until the
+// call after next (tf_fb_flow_ptr), and one rotating buffer serves as `other`.
+struct LevelBufs {
+    int result, other;
+};
+static LevelBufs fb_level_buffers(int coarse, bool lands_in_set, int set)
+{
+    const int a = coarse < 0 ? 0 : (coarse + 1) % 3, b = coarse < 0 ? 1 : (coarse + 2) % 3;
+    return lands_in_set ? LevelBufs{3 + set, a} : LevelBufs{a, b};
+}
+
+// one kernel per iteration where the level fills the chip (>= 4M pixels over the batch), two otherwise
+static bool fb_one_kernel_level(tf_fb *fb, const Level &L, int n_pairs)
+{
+    const long fuse_min_px = option(OPT_FB_FUSE_MIN_PX);
+    // fb_exact_sums: column sums straight from R (k_flow_carry_pc<.., STORE>, one march per column) where many columns
+    // stand side by side, through M in memory otherwise (4K: 7.0 against 9.3 ms per level-0 iteration with 32 pairs,
+    // 2.9 against 2.5 with 8, 1.8 against 0.5 with one)
+    const bool exact_one_kernel = !fb_exact(fb) || fb->fused > 0 || (long)cdiv(L.W, 112) * n_pairs >= 560;
+    return fb_flow_iter_serves(fb, L.W, L.H) && exact_one_kernel &&
+           (fb->fused > 0 || (fb->fused < 0 && (long)L.W * L.H * n_pairs >= fuse_min_px));
+}
+
+static int fb_level_one_kernel(tf_fb *fb, int k, int n_pairs, const FlowInit &start, const LevelBufs &use)
+{
+    const Level &L = *fb->lv[k];
+    // the iterations ping-pong between two buffers, ordered so that the LAST one writes p: the
+    // call's result buffer at full resolution, otherwise any buffer the coarser level is not in
+    const int I = fb->prm.iterations, p = use.result, q = use.other;
+    auto buf_of = [&](int i) { return ((I - i) & 1) ? q : p; }; // what iteration i (1..I) writes
+    FlowInit fi = start; // zero flow at the coarsest scale ...
+    if (k == fb->K && fb->use_initial()) { // ... or the caller's, shrunk to it (a buffer neither p nor q)
+        int c = 0;
+        while (c == p || c == q)
+            c++;
+        TF_TRY(fb_initial_flow(fb, n_pairs, fb->lflow[c].as<float2>()));
+        fi.mode = 2;
+        fi.src = fb->lflow[c].as<float2>();
     }
-    if (overlap) {
+    for (int i = 1; i <= I; i++) {
+        // the first iteration below the coarsest scale upsamples the coarser level's flow itself
+        TF_TRY(fb_flow_iter(fb, L.W, L.H, n_pairs, fb->lflow[buf_of(i)].as<float2>(), k, fi));
+        fi.mode = 2; // the next one reads what this one wrote
+        fi.src = fb->lflow[buf_of(i)].as<float2>();
+    }
+    return TF_OK;
+}
+
+// every iteration in lflow[a]
+static int fb_level_two_kernel(tf_fb *fb, int k, int n_pairs, const FlowInit &start, int a)
+{
+    const Level &L = *fb->lv[k];
+    FlowInit fl;
+    memset(&fl, 0, sizeof(fl));
+    fl.mode = 2;
+    fl.src = fb->lflow[a].as<float2>();
+    fl.rmap = start.rmap;
+    if (k == fb->K && fb->use_initial()) { // the caller's flow, shrunk to the coarsest scale, instead of zero
+        TF_TRY(fb_initial_flow(fb, n_pairs, fb->lflow[a].as<float2>()));
+        TF_TRY(fb_update_matrices(fb, L.W, L.H, n_pairs, fl, k));
+    } else {
+        TF_TRY(fb_update_matrices(fb, L.W, L.H, n_pairs, start, k));
+    }
+    for (int i = 0; i < fb->prm.iterations; i++) {
+        if (fb->gaussian())
+            TF_TRY(fb_gauss_solve(fb, L.W, L.H, n_pairs, fb->lflow[a].as<float2>(), k));
+        else
+            TF_TRY(fb_blur_solve(fb, L.W, L.H, n_pairs, fb->lflow[a].as<float2>(), k));
+        if (i < fb->prm.iterations - 1) // M is a pure function of (R0, R1, flow): rebuild it in place
+            TF_TRY(fb_update_matrices(fb, L.W, L.H, n_pairs, fl, k));
+    }
+    return TF_OK;
+}
+
+static int fb_call_end(tf_fb *fb, hipStream_t cs, int n_pairs)
+{
+    if (fb->nsets > 1) {
         TF_HIP(hipEventRecord(fb->chain_done, cs));
         TF_HIP(hipStreamWaitEvent(main_stream(), fb->chain_done, 0));
     }
     if (fb->async_io)
         TF_HIP(hipEventRecord(fb->call_done[fb->n_calls & 1], cs));
     fb->n_calls++;
-    fb->cur = (set + 1) % fb->nsets;
+    fb->cur = (fb->cur + 1) % fb->nsets;
     fb->last_pairs = n_pairs;
     return TF_OK;
+}
+
+TF_API int tf_fb_calc_slots(tf_fb *fb, int n_pairs, const int *prev_slots, const int *next_slots)
+{
+    TF_TRY(fb_call_check(fb, n_pairs, prev_slots, next_slots));
+    ImagePlan plan;
+    TF_TRY(fb_call_plan(fb, n_pairs, prev_slots, next_slots, plan));
+    hipStream_t cs;
+    TF_TRY(fb_call_begin(fb, plan, &cs));
+    StreamScope chain_scope(cs);
+    TF_TRY(fb_expand_runs(fb, plan));
+    const bool overlap = fb->nsets > 1;
+    const int2 *rmap = fb->pairs.as<int2>() + 2 * fb->max_pairs; // the plan's map, uploaded
+    int coarse = -1; // lflow buffer holding the coarser level's result
+    for (int k = fb->K; k >= 0; k--) {
+        const FlowInit start = fb_level_start(fb, k, coarse, rmap);
+        const LevelBufs use = fb_level_buffers(coarse, k == 0 && overlap, fb->cur);
+        if (fb_one_kernel_level(fb, *fb->lv[k], n_pairs))
+            TF_TRY(fb_level_one_kernel(fb, k, n_pairs, start, use));
+        else
+            TF_TRY(fb_level_two_kernel(fb, k, n_pairs, start, use.result));
+        coarse = fb->final_buf = use.result;
+    }
+    return fb_call_end(fb, cs, n_pairs);
 }
 
 TF_API int tf_fb_flow_ptr(tf_fb *fb, int pair, void **dev)
@@ -804,14 +786,11 @@ TF_API int tf_fb_get_flow_begin(tf_fb *fb, int pair, float *flow_out, int *token
     TF_REQUIRE(pair >= 0 && pair < fb->last_pairs, "tf_fb_get_flow_begin: pair %d was not computed by the last call", pair);
     TF_TRY(ensure_init());
     const int set = (fb->cur + fb->nsets - 1) % fb->nsets; // the last call's result set
-    if (fb->download_pending[set]) {
-        // A handle with ONE result set in rotation (a single scale, or option fb_no_overlap): the download a streaming
-        // caller still holds is of this very set.  The call in between already waited for it on the device before it
-        // wrote the set again (tf_fb_calc_slots), so it is over or about to be: end it here; its tf_fb_get_flow_end then
-        // finds nothing left to wait for but this download.
-        TF_HIP(hipEventSynchronize(fb->download_done[set]));
-        fb->download_pending[set] = false;
-    }
+    // A handle with ONE result set in rotation (a single scale, or option fb_no_overlap): the download a streaming
+    // caller still holds is of this very set.  The call in between already waited for it on the device before it
+    // wrote the set again (tf_fb_calc_slots), so it is over or about to be: end it here; its tf_fb_get_flow_end then
+    // finds nothing left to wait for but this download.
+    TF_TRY(fb_download_end(fb, set));
     void *src;
     TF_TRY(tf_fb_flow_ptr(fb, pair, &src));
     TF_HIP(hipEventRecord(fb->result_ready[set], stream()));
@@ -827,10 +806,7 @@ TF_API int tf_fb_get_flow_end(tf_fb *fb, int token)
 {
     TF_REQUIRE(fb, "tf_fb_get_flow_end: null handle");
     TF_REQUIRE(token == 0 || token == 1, "tf_fb_get_flow_end: token %d", token);
-    if (fb->download_pending[token]) {
-        TF_HIP(hipEventSynchronize(fb->download_done[token]));
-        fb->download_pending[token] = false;
-    }
+    TF_TRY(fb_download_end(fb, token));
     return fb_check_fault(fb, "tf_fb_get_flow_end");
 }
 

@@ -1,6 +1,8 @@
 // Shared by the translation units of the Farneback path (fb_*.hip, farneback.hip): the device helpers several kernels
 // use, the layout of R, the per-level and per-handle host state, and the stage launchers one unit offers the others.
-//   fb_pyramid.hip      A1 + A2: level images, polynomial expansion (and their fused forms)
+//   fb_plan.h           the image plan of a call: which slots are expanded, in which runs, the pair -> image map (host only)
+//   fb_level_image.hip  A1: level images (k_level_image, the long-kernel row / column passes, the quarter level)
+//   fb_pyramid.hip      A2 and A1 + A2 fused: polynomial expansion, k_level0_polyexp_t, k_level1_polyexp_t
 //   fb_matrices.hip     A3 / A4 as two kernels: update-matrices, the marching blur + solve, Gaussian window, INTER_AREA init
 //   fb_iterate.hip      A3 + A4 (+ A5) as ONE kernel: k_flow_iter_pc, its pre-pass, the march planner
 //   fb_exact.hip        A4 in OpenCV's own summation order (tf_fb_set_exact / option fb_exact_sums), winsize 1
@@ -15,12 +17,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 
 #include "common.h"
-
-#include <mutex>
+#include "fb_plan.h"
 
 struct tf_fb;
 
@@ -225,7 +227,7 @@ struct FlowInit {
     const float *xfrac, *yfrac;
     float mul;
     // which two expansions (images of R, [image][5][Nk]) pair p compares: frames shared by the pairs of a
-    // batch are expanded once.  Null: images 2p and 2p+1 (stage entry points).
+    // batch are expanded once (the call's map on the device).  Null: images 2p and 2p+1 (stage entry points).
     const int2 *rmap;
 };
 
@@ -295,20 +297,20 @@ struct tf_fb {
     int K = 0; // scales K..0
     int slots = 0, max_pairs = 0;
     PolyConst pc;
-    std::vector<Level *> lv;
+    std::vector<std::unique_ptr<Level>> lv;
     DevBuf frames, img, R, M, lflow[5], pairs, winner, scratch; // lflow[3..4]: the result of even / odd calls
     DevBuf rowf; // row-pass planes of the split levels, [level][image][H][NC]
     int rp_RB = 0, rp_pitch = 0, rp_r4 = 0, rp_rmax = 0, rp_first = -1; // one k_level_rowpass launch serves them all
     int nsets = 1, cur = 0;                    // result buffers in rotation / the one this call writes
     hipStream_t chain_stream = nullptr;        // everything a call launches; the library stream only waits for its end, so
                                                // what the caller queues after a call (its remap) runs beside the NEXT call
-    hipEvent_t entry[2] = {nullptr, nullptr};  // position of the library stream when call (parity) was issued
+    Event entry[2];                            // position of the library stream when call (parity) was issued
     bool entry_pending[2] = {false, false};
-    hipEvent_t chain_done = nullptr;           // end of the latest call's work on chain_stream
-    int2 *pairs_host = nullptr;                // pinned staging: the call's image list (slots, up to 4P ints), then its pair -> image map (P int2)
-    const int2 *rmap_dev = nullptr;            // that map on the device while a batch is being issued; null: images 2p, 2p+1
-    std::vector<int> image_of;                 // slot -> index in the image list of the call being issued
-    hipEvent_t pairs_copied = nullptr;
+    Event chain_done;                          // end of the latest call's work on chain_stream
+    PinnedBuf pairs_host;                      // pinned staging: the call's image list (slots, up to 4P ints), then its pair -> image map (P int2)
+    std::vector<int> image_of;                 // the plan's scratch (fb_plan.h), [slots]
+    std::vector<ImageRun> runs;                // the runs of the call being issued; room for the most a plan can make
+    Event pairs_copied;
     bool pairs_pending = false;
     int last_pairs = 0;
     int final_buf = 0; // which lflow buffer holds the level-0 result
@@ -323,14 +325,14 @@ struct tf_fb {
     DevBuf col_carry;            // the chain's value in front of every segment of the launch being issued
     DevBuf chain_words;          // words 0-7: the ticket counters of a launch; from word 16 on: the hand-off flags
     unsigned chain_epoch = 0;
-    unsigned *chain_fault = nullptr; // pinned, device-visible: a wait for a carry gave up (k_flow_iter_pc)
+    PinnedBuf chain_fault;       // one word, device-visible: a wait for a carry gave up (k_flow_iter_pc)
     // tf_fb_async_io: uploads of frames and downloads of results on copy streams of their own, so that a streaming
     // caller's next frame goes up and its previous flow comes down while the current pair is being computed
     bool async_io = false;
     hipStream_t up_stream = nullptr, down_stream = nullptr;
-    hipEvent_t call_done[2] = {nullptr, nullptr};      // end of a call's kernels, by the call's number mod 2
-    hipEvent_t result_ready[2] = {nullptr, nullptr};   // the library stream's position when a download of result set s was asked for
-    hipEvent_t download_done[2] = {nullptr, nullptr};  // ... and its end
+    Event call_done[2];                                // end of a call's kernels, by the call's number mod 2
+    Event result_ready[2];                             // the library stream's position when a download of result set s was asked for
+    Event download_done[2];                            // ... and its end
     bool download_pending[2] = {false, false};
     std::vector<long> slot_read_call;                  // the last call that read each slot's frame bytes (expanded it)
     long n_calls = 0;
@@ -345,40 +347,36 @@ struct tf_fb {
     // otherwise.  Option "fb_fused" = 0 / 1 forces never / always (read at tf_fb_create).
     int fused = (int)option(OPT_FB_FUSED);
     float *Rk(int k) { return (k <= 0 ? R : lv[k]->R).as<float>(); }
-    // where the expansion launches being issued write and which part of the image list they read
-    // (tf_fb_calc_slots; zero outside it)
-    int prep_image0 = 0, prep_list0 = 0;
-    float *Rk_out(int k) { return Rk(k) + (size_t)prep_image0 * 5 * (k <= 0 ? (size_t)W * H : (size_t)lv[k]->W * lv[k]->H); }
-    const int2 *image_list() { return pairs.as<int2>() + prep_list0; }
+    // where the expansion launches of a run write, and the part of the uploaded image list they read
+    float *Rk(int k, const ImageRun &run) { return Rk(k) + (size_t)run.image0 * 5 * (k <= 0 ? (size_t)W * H : (size_t)lv[k]->W * lv[k]->H); }
+    const int2 *image_list(const ImageRun &run) { return pairs.as<int2>() + run.list0 / 2; }
     // tf_fb_keep_expansions: R is indexed by frame slot and an expansion stays valid until its slot is written
     bool keep = false;
     std::vector<char> expanded, external;
     float *imgk(int k) { return (k <= 0 ? img : lv[k]->img).as<float>(); }
-    ~tf_fb()
-    {
-        for (auto *l : lv)
-            delete l;
-        if (chain_done)
-            (void)hipEventDestroy(chain_done);
-        if (pairs_copied)
-            (void)hipEventDestroy(pairs_copied);
-        if (pairs_host)
-            (void)hipHostFree(pairs_host);
-        if (chain_fault)
-            (void)hipHostFree(chain_fault);
-        for (int i = 0; i < 2; i++)
-            for (hipEvent_t e : {call_done[i], result_ready[i], download_done[i]})
-                if (e)
-                    (void)hipEventDestroy(e);
-        for (auto e : entry)
-            if (e)
-                (void)hipEventDestroy(e);
-        // chain_stream is the library's side stream (runtime.hip), not ours to destroy
-    }
+    // (chain_stream is the library's side stream (runtime.hip), not ours to destroy)
 };
 
 namespace tf {
 namespace fb {
+
+// A5: the flow level k (< K) starts from is the coarser level's, upsampled by the first kernel that reads it
+inline FlowInit fb_upsampled(tf_fb *fb, int k, const float2 *coarse_flow)
+{
+    const Level &L = *fb->lv[k], &C = *fb->lv[k + 1];
+    FlowInit fi;
+    memset(&fi, 0, sizeof(fi));
+    fi.mode = 1;
+    fi.src = coarse_flow;
+    fi.Wc = C.W;
+    fi.Hc = C.H;
+    fi.xofs = L.flow_lerp.xofs.as<int>();
+    fi.yofs = L.flow_lerp.yofs.as<int>();
+    fi.xfrac = L.flow_lerp.xfrac.as<float>();
+    fi.yfrac = L.flow_lerp.yfrac.as<float>();
+    fi.mul = (float)(1. / fb->prm.pyr_scale);
+    return fi;
+}
 
 // The exact mode is a property of the HANDLE (tf_fb_set_exact); a handle that was never told follows the process-wide
 // option, read at each call.
@@ -394,15 +392,13 @@ struct March {
 const char *lvl_name(const char *base, int k);
 
 // ---- fb_pyramid.hip ----
-int fb_level_image(tf_fb *fb, int k, int n_images, bool standalone = false);
+// the expansion launchers take the run they serve (stage entry points: {0, 0, n}, images 0 .. n - 1 from the head of the list)
+int fb_level_image(tf_fb *fb, int k, const ImageRun &run, bool standalone = false);
 bool plan_split_level(int W, int H, Level &L, std::vector<int> &colsrc);
 bool plan_quarter_level(int W, int H, const Level &L);
 ImgTile choose_tile(int W, int H, int Wk, int Hk, int ksz, int level);
-int fb_polyexp(tf_fb *fb, int w, int h, int n_images, int k = -1);
-bool fb_can_fuse_level(tf_fb *fb, int k);
-bool fb_can_fuse_half_level(tf_fb *fb, int k);
-int fb_level1_polyexp(tf_fb *fb, int k, int n_images);
-int fb_level0_polyexp(tf_fb *fb, int k, int n_images);
+int fb_polyexp(tf_fb *fb, int w, int h, const ImageRun &run, int k = -1);
+int fb_expand_level(tf_fb *fb, int k, const ImageRun &run, bool standalone = false); // fused where a level allows it
 // ---- fb_matrices.hip ----
 int fb_m_room(tf_fb *fb, int w, int h, int n_pairs);
 int fb_update_matrices(tf_fb *fb, int w, int h, int n_pairs, const FlowInit &fi, int k = -1);
@@ -419,10 +415,11 @@ int fb_exact_from_matrices(tf_fb *fb, int w, int h, int n_pairs, float2 *flow_ou
 int fb_exact_hsolve(tf_fb *fb, int w, int h, int n_pairs, float2 *flow_out, int k);     // rows + solve over fb->exact_vsum
 int fb_w1_solve(tf_fb *fb, int w, int h, int n_pairs, float2 *flow_out);                // winsize 1
 // ---- fb_iterate.hip ----
-// true if the one-kernel iteration exists for this window; launches it.  `up`: the first iteration of a level below the
-// coarsest takes its flow from the coarser level (A5 fused)
-bool fb_flow_iter(tf_fb *fb, int w, int h, int n_pairs, const float2 *flow_in, float2 *flow_out, int k, int &rc,
-                  const FlowInit *up = nullptr);
+// does the one-kernel iteration serve this handle's window and a level of this size?
+bool fb_flow_iter_serves(const tf_fb *fb, int w, int h);
+// one iteration from the flow fi names: zero, the coarser level's (the first iteration of a level below the coarsest:
+// A5 fused) or an array at this level
+int fb_flow_iter(tf_fb *fb, int w, int h, int n_pairs, float2 *flow_out, int k, const FlowInit &fi);
 
 } // namespace fb
 } // namespace tf

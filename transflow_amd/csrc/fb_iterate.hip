@@ -782,20 +782,21 @@ static March choose_march(long columns, int h, int warm, long slots, int slots_p
     return m;
 }
 
-// `up`: the first iteration of a level below the coarsest takes its flow from the coarser level (A5 fused)
+// fi.mode 1: the first iteration of a level below the coarsest takes its flow from the coarser level (A5 fused)
 template <int M>
-static int launch_flow_iter(tf_fb *fb, int w, int h, int n_pairs, const float2 *flow_in, float2 *flow_out, int k,
-                            const FlowInit *up)
+static int launch_flow_iter(tf_fb *fb, int w, int h, int n_pairs, float2 *flow_out, int k, const FlowInit &fi)
 {
+    const bool up = fi.mode == 1;
+    const float2 *flow_in = fi.mode == 2 ? fi.src : nullptr; // null: zero flow, or the coarser level's through f
     const double scale = 1. / ((double)fb->prm.winsize * fb->prm.winsize);
     const float *R = fb->Rk(k);
     constexpr int OUTC = 128 - 2 * ((M + 1) & ~1), WIN = 2 * M + 1;
     const unsigned strips = cdiv(w, OUTC);
-    FlowInit f;
+    FlowInit f; // what the kernels take: the upsampling tables if they upsample, and the pair -> image map
     memset(&f, 0, sizeof(f));
     if (up)
-        f = *up;
-    f.rmap = fb->rmap_dev;
+        f = fi;
+    f.rmap = fi.rmap;
     if (fb_exact(fb)) {
         // fb_exact_sums on a large launch: the column sums of EVERY row straight from R0, R1 and the flow (the pre-pass
         // kernel with one segment, storing as it goes: M is never in memory), then the row walker.  4K x 32, level 0: 4.3 +
@@ -838,12 +839,12 @@ static int launch_flow_iter(tf_fb *fb, int w, int h, int n_pairs, const float2 *
         cc.epoch = fb->chain_epoch;
         cc.ticket = fb->chain_words.as<unsigned>();
         TF_HIP(hipMemsetAsync(cc.ticket, 0, 8 * sizeof(unsigned), stream()));
-        cc.fault = fb->chain_fault;
+        cc.fault = fb->chain_fault.as<unsigned>();
         grid = dim3((unsigned)items);
     } else if (mc.segs > 1) {
         TF_TRY(fb_carry_room(fb, (size_t)mc.segs * n_pairs * 5 * w, 0));
         cc.carry = fb->col_carry.as<double>();
-        cc.fault = fb->chain_fault;
+        cc.fault = fb->chain_fault.as<unsigned>();
         const dim3 pgrid(cdiv(w, 128), mc.segs, n_pairs);
         if (up)
             TF_TRY(launch(lvl_name("fb_flow_carry", k), k_flow_carry_pc<M, 2>, pgrid, dim3(128), 0, R, flow_in, w, h, mc.seg, f, f.yofs, f.yfrac, cc.carry));
@@ -866,16 +867,23 @@ static int launch_flow_iter(tf_fb *fb, int w, int h, int n_pairs, const float2 *
     return rc;
 }
 
-bool fb_flow_iter(tf_fb *fb, int w, int h, int n_pairs, const float2 *flow_in, float2 *flow_out, int k, int &rc,
-                         const FlowInit *up)
+bool fb_flow_iter_serves(const tf_fb *fb, int w, int h)
 {
-    if (w < 10 || h < 10) // border_scale: below 10 x 10 the two-kernel form carries OpenCV's edge test
-        return false;
-    switch (fb->prm.winsize / 2) { // odd half-widths: the pair-sum window
-    case 3: rc = launch_flow_iter<3>(fb, w, h, n_pairs, flow_in, flow_out, k, up); return true;
-    case 5: rc = launch_flow_iter<5>(fb, w, h, n_pairs, flow_in, flow_out, k, up); return true;
-    case 7: rc = launch_flow_iter<7>(fb, w, h, n_pairs, flow_in, flow_out, k, up); return true;
-    default: return false;
+    const int m = fb->prm.winsize / 2;
+    // (the fused kernel multiplies the edge weights unconditionally: identical from 10 x 10 up; below, the two-kernel
+    // form carries OpenCV's edge test: border_scale)
+    return (m == 3 || m == 5 || m == 7) && !fb->gaussian() && w >= 10 && h >= 10 && // odd half-widths: the pair-sum window
+           (size_t)w * h < (1u << 28) && w < (1 << 24) && h < (1 << 24);
+}
+
+int fb_flow_iter(tf_fb *fb, int w, int h, int n_pairs, float2 *flow_out, int k, const FlowInit &fi)
+{
+    if (!fb_flow_iter_serves(fb, w, h))
+        return set_error(TF_ERR_STATE, "tf_fb_calc_slots: no one-kernel iteration for level %d", k);
+    switch (fb->prm.winsize / 2) {
+    case 3: return launch_flow_iter<3>(fb, w, h, n_pairs, flow_out, k, fi);
+    case 5: return launch_flow_iter<5>(fb, w, h, n_pairs, flow_out, k, fi);
+    default: return launch_flow_iter<7>(fb, w, h, n_pairs, flow_out, k, fi);
     }
 }
 

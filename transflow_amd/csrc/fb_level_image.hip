@@ -805,12 +805,12 @@ namespace tf {
 namespace fb {
 
 // `standalone`: a single level is wanted (stage entry points): run the shared row pass regardless of the order
-int fb_level_image(tf_fb *fb, int k, int n_images, bool standalone)
+int fb_level_image(tf_fb *fb, int k, const ImageRun &run, bool standalone)
 {
     Level &L = *fb->lv[k];
     if (L.quarter)
-        return launch(lvl_name("fb_level_image", k), k_level_quarter_image, dim3(cdiv(L.W, QI_TW), cdiv(L.H, QI_TH), n_images),
-                      dim3(256), 0, (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(), fb->imgk(k), fb->W, fb->H,
+        return launch(lvl_name("fb_level_image", k), k_level_quarter_image, dim3(cdiv(L.W, QI_TW), cdiv(L.H, QI_TH), run.n),
+                      dim3(256), 0, (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(run), fb->imgk(k), fb->W, fb->H,
                       (const float *)L.kern.as<float>(), (const float *)L.img_lerp.xfrac.as<float>(),
                       (const float *)L.img_lerp.yfrac.as<float>());
     if (L.split) {
@@ -832,22 +832,22 @@ int fb_level_image(tf_fb *fb, int k, int n_images, bool standalone)
                 taps += (size_t)S.ksz;
             }
             const size_t smem_rp = (size_t)fb->rp_RB * fb->rp_pitch + taps * sizeof(float);
-            TF_TRY(launch(lvl_name("fb_level_rowpass", -1), k_level_rowpass, dim3(cdiv(fb->H, fb->rp_RB), n_images),
+            TF_TRY(launch(lvl_name("fb_level_rowpass", -1), k_level_rowpass, dim3(cdiv(fb->H, fb->rp_RB), run.n),
                           dim3(RP_THREADS), smem_rp, (const uint8_t *)fb->frames.as<uint8_t>(),
-                          fb->image_list(), fb->W, fb->H, a, fb->rp_RB, fb->rp_pitch, fb->rp_r4,
+                          fb->image_list(run), fb->W, fb->H, a, fb->rp_RB, fb->rp_pitch, fb->rp_r4,
                           fb->rp_rmax));
         }
-        return launch(lvl_name("fb_level_colpass", k), k_level_colpass, dim3(cdiv(L.W, 64), cdiv(L.H, 4), n_images), dim3(256),
+        return launch(lvl_name("fb_level_colpass", k), k_level_colpass, dim3(cdiv(L.W, 64), cdiv(L.H, 4), run.n), dim3(256),
                       (size_t)L.ksz * sizeof(float), (const float *)(fb->rowf.as<float>() + L.rowf_off), fb->imgk(k), fb->W, fb->H,
                       L.W, L.H, L.NC, (const float *)L.kern.as<float>(), L.ksz, (const int *)L.img_lerp.xofs.as<int>(),
                       (const float *)L.img_lerp.xfrac.as<float>(), (const int *)L.img_lerp.yofs.as<int>(),
                       (const float *)L.img_lerp.yfrac.as<float>());
     }
     const ImgTile &t = L.tile;
-    dim3 grid(cdiv(L.W, t.TWo), cdiv(L.H, t.THo), n_images);
+    dim3 grid(cdiv(L.W, t.TWo), cdiv(L.H, t.THo), run.n);
     size_t smem = (size_t)t.LH * t.pitch + (size_t)t.LH * t.rstride * sizeof(float) + (size_t)L.ksz * sizeof(float);
     return launch(lvl_name("fb_level_image", k), k_level_image, grid, dim3(256), smem,
-                  (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(), fb->imgk(k),
+                  (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(run), fb->imgk(k),
                   fb->W, fb->H, L.W, L.H, (const float *)L.kern.as<float>(), L.ksz, t);
 }
 

@@ -647,10 +647,8 @@ int fb_update_matrices(tf_fb *fb, int w, int h, int n_pairs, const FlowInit &fi,
 {
     TF_TRY(fb_m_room(fb, w, h, n_pairs));
     dim3 grid(cdiv(w, UM_TW), cdiv(h, UM_TH), n_pairs);
-    FlowInit f = fi;
-    f.rmap = fb->rmap_dev;
     return launch(lvl_name("fb_update_matrices", k), k_update_matrices, grid, dim3(256), 0, (const float *)fb->Rk(k),
-                  fb->M.as<float>(), w, h, f);
+                  fb->M.as<float>(), w, h, fi);
 }
 
 // room for the carries of a launch (and, for hand-offs inside it, its flags); the fault word
@@ -664,9 +662,9 @@ int fb_carry_room(tf_fb *fb, size_t carry_doubles, size_t flags)
         TF_HIP(hipMemsetAsync(fb->chain_words.p, 0, words * 4, stream()));
         fb->chain_epoch = 0;
     }
-    if (!fb->chain_fault) {
-        TF_HIP(hipHostMalloc((void **)&fb->chain_fault, 64, hipHostMallocDefault));
-        *fb->chain_fault = 0;
+    if (!fb->chain_fault.p) {
+        TF_TRY(fb->chain_fault.alloc(64));
+        *fb->chain_fault.as<unsigned>() = 0;
     }
     return TF_OK;
 }
@@ -674,8 +672,8 @@ int fb_carry_room(tf_fb *fb, size_t carry_doubles, size_t flags)
 // a wait inside an earlier launch gave up: its flow is wrong
 int fb_check_fault(tf_fb *fb, const char *where)
 {
-    if (fb->chain_fault && *(volatile unsigned *)fb->chain_fault) {
-        *fb->chain_fault = 0;
+    if (fb->chain_fault.p && *fb->chain_fault.as<volatile unsigned>()) {
+        *fb->chain_fault.as<unsigned>() = 0;
         return set_error(TF_ERR_HIP, "%s: a segment of k_flow_iter_pc waited more than 5 s for the column sums of the segment "
                                      "above it; the flow of that call is invalid", where);
     }

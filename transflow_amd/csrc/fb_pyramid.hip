@@ -506,24 +506,24 @@ k_level1_polyexp_t(const uint8_t *__restrict__ frames, const int2 *__restrict__ 
 namespace tf {
 namespace fb {
 
-int fb_polyexp(tf_fb *fb, int w, int h, int n_images, int k)
+int fb_polyexp(tf_fb *fb, int w, int h, const ImageRun &run, int k)
 {
     const int n = fb->pc.n;
-    dim3 grid(cdiv(w, PX_TW), cdiv(h, PX_TH), n_images);
+    dim3 grid(cdiv(w, PX_TW), cdiv(h, PX_TH), run.n);
     if (n == 5)
         return launch(lvl_name("fb_polyexp", k), k_polyexp_t<5>, grid, dim3(256), 0, (const float *)fb->imgk(k),
-                      fb->Rk_out(k), w, h, fb->pc);
+                      fb->Rk(k, run), w, h, fb->pc);
     if (n == 7)
         return launch(lvl_name("fb_polyexp", k), k_polyexp_t<7>, grid, dim3(256), 0, (const float *)fb->imgk(k),
-                      fb->Rk_out(k), w, h, fb->pc);
+                      fb->Rk(k, run), w, h, fb->pc);
     size_t smem = ((size_t)(PX_TH + 2 * n) * (PX_TW + 2 * n) + 3 * (size_t)PX_TH * (PX_TW + 2 * n)) * sizeof(float);
     return launch(lvl_name("fb_polyexp_generic", k), k_polyexp, grid, dim3(256), smem,
-                  (const float *)fb->imgk(k), fb->Rk_out(k), w, h, fb->pc);
+                  (const float *)fb->imgk(k), fb->Rk(k, run), w, h, fb->pc);
 }
 
 // A1+A2 fusion applies to a level that is a copy-sized resize of the frame with the 3-tap blur
 // (level 0 of every pyramid) and a poly_n the blocked expansion is instantiated for.
-bool fb_can_fuse_level(tf_fb *fb, int k)
+static bool fb_can_fuse_level(tf_fb *fb, int k)
 {
     static const bool off = tune("TF_FB_NO_A1A2", 0) != 0;
     const Level &L = *fb->lv[k];
@@ -531,39 +531,50 @@ bool fb_can_fuse_level(tf_fb *fb, int k)
 }
 
 // ... and to a level that is exactly half the frame (k_level1_polyexp_t)
-bool fb_can_fuse_half_level(tf_fb *fb, int k)
+static bool fb_can_fuse_half_level(tf_fb *fb, int k)
 {
     static const bool off = tune("TF_FB_NO_A1A2", 0) != 0;
     const Level &L = *fb->lv[k];
     return !off && 2 * L.W == fb->W && 2 * L.H == fb->H && L.ksz == 3 && (fb->pc.n == 5 || fb->pc.n == 7);
 }
 
-int fb_level1_polyexp(tf_fb *fb, int k, int n_images)
+static int fb_level1_polyexp(tf_fb *fb, int k, const ImageRun &run)
 {
     Level &L = *fb->lv[k];
-    dim3 grid(cdiv(L.W, 64), cdiv(L.H, TF_EXP_TH1), n_images);
+    dim3 grid(cdiv(L.W, 64), cdiv(L.H, TF_EXP_TH1), run.n);
     const float kc = L.kern_host[1], k1 = L.kern_host[2];
     if (fb->pc.n == 5)
         return launch(lvl_name("fb_level_polyexp", k), k_level1_polyexp_t<5>, grid, dim3(256), 0,
-                      (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(), fb->Rk_out(k), fb->W,
+                      (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(run), fb->Rk(k, run), fb->W,
                       fb->H, kc, k1, fb->pc);
     return launch(lvl_name("fb_level_polyexp", k), k_level1_polyexp_t<7>, grid, dim3(256), 0,
-                  (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(), fb->Rk_out(k), fb->W, fb->H,
+                  (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(run), fb->Rk(k, run), fb->W, fb->H,
                   kc, k1, fb->pc);
 }
 
-int fb_level0_polyexp(tf_fb *fb, int k, int n_images)
+static int fb_level0_polyexp(tf_fb *fb, int k, const ImageRun &run)
 {
     Level &L = *fb->lv[k];
-    dim3 grid(cdiv(L.W, 64), cdiv(L.H, TF_EXP_TH0), n_images);
+    dim3 grid(cdiv(L.W, 64), cdiv(L.H, TF_EXP_TH0), run.n);
     const float kc = L.kern_host[1], k1 = L.kern_host[2];
     if (fb->pc.n == 5)
         return launch(lvl_name("fb_level_polyexp", k), k_level0_polyexp_t<5>, grid, dim3(256), 0,
-                      (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(), fb->Rk_out(k),
+                      (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(run), fb->Rk(k, run),
                       L.W, L.H, kc, k1, fb->pc);
     return launch(lvl_name("fb_level_polyexp", k), k_level0_polyexp_t<7>, grid, dim3(256), 0,
-                  (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(), fb->Rk_out(k), L.W,
+                  (const uint8_t *)fb->frames.as<uint8_t>(), fb->image_list(run), fb->Rk(k, run), L.W,
                   L.H, kc, k1, fb->pc);
+}
+
+// A1+A2 of one level for the images of a run.  `standalone`: see fb_level_image
+int fb_expand_level(tf_fb *fb, int k, const ImageRun &run, bool standalone)
+{
+    if (fb_can_fuse_level(fb, k))
+        return fb_level0_polyexp(fb, k, run); // A1+A2 in one kernel: the level image stays on chip
+    if (fb_can_fuse_half_level(fb, k))
+        return fb_level1_polyexp(fb, k, run);
+    TF_TRY(fb_level_image(fb, k, run, standalone));
+    return fb_polyexp(fb, fb->lv[k]->W, fb->lv[k]->H, run, k);
 }
 
 } // namespace fb

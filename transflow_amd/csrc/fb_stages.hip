@@ -52,7 +52,7 @@ TF_API int tf_fb_stage_level_image(tf_fb *fb, const uint8_t *grey, ptrdiff_t str
     TF_TRY(tf_fb_set_frame(fb, 0, grey, stride));
     int2 pr = make_int2(0, 0);
     TF_HIP(hipMemcpy(fb->pairs.p, &pr, 8, hipMemcpyHostToDevice));
-    TF_TRY(fb_level_image(fb, level, 2, true));
+    TF_TRY(fb_level_image(fb, level, ImageRun{0, 0, 2}, true));
     Level &L = *fb->lv[level];
     TF_HIP(hipMemcpyAsync(out, fb->imgk(level), (size_t)L.W * L.H * 4, hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
@@ -106,14 +106,7 @@ TF_API int tf_fb_stage_level_polyexp(tf_fb *fb, const uint8_t *grey, ptrdiff_t s
     int2 pr = make_int2(0, 0);
     TF_HIP(hipMemcpy(fb->pairs.p, &pr, 8, hipMemcpyHostToDevice));
     Level &L = *fb->lv[level];
-    if (fb_can_fuse_level(fb, level)) {
-        TF_TRY(fb_level0_polyexp(fb, level, 2));
-    } else if (fb_can_fuse_half_level(fb, level)) {
-        TF_TRY(fb_level1_polyexp(fb, level, 2));
-    } else {
-        TF_TRY(fb_level_image(fb, level, 2, true));
-        TF_TRY(fb_polyexp(fb, L.W, L.H, 2, level));
-    }
+    TF_TRY(fb_expand_level(fb, level, ImageRun{0, 0, 2}, true)); // images 0 and 1 from the head of the list
     return download_rpairs(r_out, fb->Rk(level), (size_t)L.W * L.H, fb->scratch);
 }
 
@@ -124,7 +117,7 @@ TF_API int tf_fb_stage_polyexp(tf_fb *fb, const float *img, int w, int h, float 
     TF_TRY(ensure_init());
     size_t n = (size_t)w * h;
     TF_HIP(hipMemcpyAsync(fb->img.p, img, n * 4, hipMemcpyHostToDevice, stream()));
-    TF_TRY(fb_polyexp(fb, w, h, 1));
+    TF_TRY(fb_polyexp(fb, w, h, ImageRun{0, 0, 1}));
     return download_rpairs(r_out, fb->Rk(0), n, fb->scratch);
 }
 
@@ -163,18 +156,7 @@ TF_API int tf_fb_stage_upsampled_matrices(tf_fb *fb, int level, const float *r0,
     TF_HIP(hipStreamSynchronize(stream()));
     TF_TRY(upload_rpairs(fb->Rk(0) + 5 * n, r1, n, fb->scratch));
     TF_HIP(hipMemcpyAsync(fb->lflow[1].p, coarse_flow, nc * 8, hipMemcpyHostToDevice, stream()));
-    FlowInit fi;
-    memset(&fi, 0, sizeof(fi));
-    fi.mode = 1;
-    fi.src = fb->lflow[1].as<float2>();
-    fi.Wc = C.W;
-    fi.Hc = C.H;
-    fi.xofs = L.flow_lerp.xofs.as<int>();
-    fi.yofs = L.flow_lerp.yofs.as<int>();
-    fi.xfrac = L.flow_lerp.xfrac.as<float>();
-    fi.yfrac = L.flow_lerp.yfrac.as<float>();
-    fi.mul = (float)(1. / fb->prm.pyr_scale);
-    TF_TRY(fb_update_matrices(fb, L.W, L.H, 1, fi));
+    TF_TRY(fb_update_matrices(fb, L.W, L.H, 1, fb_upsampled(fb, level, fb->lflow[1].as<float2>())));
     return download_planar5(m_out, fb->M.as<float>(), n, fb->scratch);
 }
 

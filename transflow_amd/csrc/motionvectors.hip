@@ -84,10 +84,9 @@ static int reserve(tf_mv *mv, size_t n)
         TF_HIP(hipEventSynchronize(mv->uploaded));
     if (n > mv->stage_cap) {
         const size_t cap = n + n / 2 + 1024;
-        if (mv->stage)
-            (void)hipHostFree(mv->stage);
-        mv->stage = nullptr, mv->stage_cap = 0;
-        TF_HIP(hipHostMalloc(&mv->stage, cap * sizeof(Item), hipHostMallocDefault));
+        mv->stage.release();
+        mv->stage_cap = 0;
+        TF_TRY(mv->stage.alloc(cap * sizeof(Item)));
         mv->stage_cap = cap;
     }
     return TF_OK;
@@ -104,7 +103,7 @@ static int rasterize(tf_mv *mv, const tf_mv_vector *v, int n, float2 *flow_dev)
 {
     TF_TRY(ensure_init());
     TF_TRY(reserve(mv, (size_t)n));
-    Item *items = (Item *)mv->stage;
+    Item *items = mv->stage.as<Item>();
     int m = 0;
     for (int k = 0; k < n; k++) {          // every vector is checked before anything is launched
         Rect r;
@@ -151,8 +150,8 @@ TF_API int tf_mv_create(tf_mv **out, int width, int height)
     TF_REQUIRE(mv, "tf_mv_create: out of memory");
     mv->W = width, mv->H = height;
     int rc = mv->winner.alloc((size_t)width * height * sizeof(uint32_t));
-    if (rc == TF_OK && hipEventCreateWithFlags(&mv->uploaded, hipEventDisableTiming) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_mv_create: hipEventCreate failed");
+    if (rc == TF_OK)
+        rc = mv->uploaded.create();
     if (rc == TF_OK)
         rc = clear_map(mv);                // the one clear: mv_resolve leaves the map clean behind it
     if (rc != TF_OK) {
@@ -168,10 +167,6 @@ TF_API void tf_mv_destroy(tf_mv *mv)
     if (!mv)
         return;
     (void)hipStreamSynchronize(stream()); // kernels of the handle's last call may still read its buffers
-    if (mv->uploaded)
-        (void)hipEventDestroy(mv->uploaded);
-    if (mv->stage)
-        (void)hipHostFree(mv->stage);
     delete mv;
 }
 

@@ -39,8 +39,8 @@ struct tf_mv {
     tf::DevBuf winner;        // [H][W] uint32: 1 + the index (among the painting rectangles) of the last writer, 0 = none
     tf::DevBuf table;         // [dev_cap] {Rect, value}: the painting rectangles of the frame, grows on demand
     tf::DevBuf flow;          // [H][W][2] float: tf_mv_rasterize's result on its way down (allocated on first use)
-    void *stage = nullptr;    // page-locked host image of the table for the upload
+    tf::PinnedBuf stage;      // page-locked host image of the table for the upload
     size_t stage_cap = 0, dev_cap = 0;       // in rectangles
-    hipEvent_t uploaded = nullptr;           // the last upload has left the stage
+    tf::Event uploaded;                      // the last upload has left the stage
     bool dirty = false;       // a call failed between its two launches: the winner map is cleared before the next one
 };

@@ -494,8 +494,8 @@ TF_API int tf_comp_download_begin(tf_comp *comp, uint8_t *rgb_out)
     if (!comp->N)
         return TF_OK;
     if (!comp->image_ready) {
-        TF_HIP(hipEventCreateWithFlags(&comp->image_ready, hipEventDisableTiming));
-        TF_HIP(hipEventCreateWithFlags(&comp->download_done, hipEventDisableTiming));
+        TF_TRY(comp->image_ready.create());
+        TF_TRY(comp->download_done.create());
     }
     hipStream_t down;
     TF_TRY(tf::side_stream(4, &down));
@@ -785,8 +785,8 @@ static int stage_pixmap(tf_remap *L, const uint8_t *pixmap, int channels, bool b
     if (L->scratch_pix.bytes < bytes)
         TF_TRY(L->scratch_pix.alloc(bytes));
     if (!L->pix_up) {
-        TF_HIP(hipEventCreateWithFlags(&L->pix_up, hipEventDisableTiming));
-        TF_HIP(hipEventCreateWithFlags(&L->pix_used, hipEventDisableTiming));
+        TF_TRY(L->pix_up.create());
+        TF_TRY(L->pix_used.create());
     }
     hipStream_t up = stream();
     if (beside)

@@ -58,16 +58,12 @@ struct tf_comp {
     uchar4 bg;
     DevBuf image;
     // tf_comp_download_begin / _end: the image on its way down on the library's download stream
-    hipEvent_t image_ready = nullptr, download_done = nullptr;
+    tf::Event image_ready, download_done;
     bool download_pending = false;
     ~tf_comp()
     {
-        if (download_pending)
+        if (download_pending) // before the events go
             (void)hipEventSynchronize(download_done);
-        if (image_ready)
-            (void)hipEventDestroy(image_ready);
-        if (download_done)
-            (void)hipEventDestroy(download_done);
     }
 };
 
@@ -99,15 +95,9 @@ struct tf_remap {
     bool state_fits = true;    // false after a set_state with values outside int16
     bool state_fits32 = true;  // false after a set_state with a row / column outside [0, 8191], an alpha other than 0 / 1 or a source index outside [0, 31]
     // tf_remap_gather_beside: the pixmap goes up on the library's upload stream, beside the update kernel queued before it
-    hipEvent_t pix_up = nullptr, pix_used = nullptr; // the upload's end; the end of the last kernel that read scratch_pix
+    tf::Event pix_up, pix_used; // the upload's end; the end of the last kernel that read scratch_pix
     bool pix_used_pending = false;
     int4 *cur_data() { return data[cur].as<int4>(); }
-    ~tf_remap()
-    {
-        for (hipEvent_t e : {pix_up, pix_used})
-            if (e)
-                (void)hipEventDestroy(e);
-    }
 };
 
 namespace tf {

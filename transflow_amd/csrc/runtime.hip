@@ -161,6 +161,20 @@ void PinnedBuf::release()
     p = nullptr;
 }
 
+int Event::create()
+{
+    release();
+    TF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return TF_OK;
+}
+
+void Event::release()
+{
+    if (e)
+        (void)hipEventDestroy(e);
+    e = nullptr;
+}
+
 // ---- profiler ---------------------------------------------------------------------
 struct ProfRec {
     const char *name;
