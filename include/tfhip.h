@@ -684,7 +684,7 @@ int tf_comp_image_ptr(tf_comp *comp, void **dev);
 typedef struct tf_jpeg tf_jpeg;
 int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int restart_mcus);
 void tf_jpeg_destroy(tf_jpeg *enc);
-int tf_jpeg_header(tf_jpeg *enc, const uint8_t **bytes, size_t *n); /* valid as long as the handle */
+int tf_jpeg_header(tf_jpeg *enc, const uint8_t **bytes, size_t *n); /* valid as long as the handle (mode 1: see below) */
 /* rgb_dev: uint8 [H][W][3] in device memory (tf_comp_image_ptr's, a pixmap's ...).  Queues its kernels on the calling
    thread's stream and waits; header and stream are then copied to `out` (host) and *n_bytes is the file's size.  A file
    larger than `capacity` returns TF_ERR_ARG with *n_bytes the size needed; `out` is then not written at all, and in no
@@ -699,6 +699,27 @@ int tf_jpeg_copy_last(tf_jpeg *enc, uint8_t *out, size_t capacity, size_t *n_byt
 /* The interval restart_mcus = 0 stands for.  No GPU call: a process that only encodes on the host with the same
    settings (transflow_amd/output.py) asks here. */
 int tf_jpeg_default_restart_mcus(void);
+/* The Huffman tables of the files.  mode 0 (the default): the Annex K tables, the bytes the files always had.  mode 1:
+   the frame's own tables, libjpeg's optimize_coding -- Pillow's save(..., optimize=True), byte for byte: the same pixels
+   in a smaller file.  The symbols are counted in a pass of their own, the four tables are made on the device by
+   jpeg_gen_optimal_table's rule, and the four DHT segments carry them, so the header's length differs from frame to
+   frame.  Makes no GPU call; the mode's buffers are allocated by the first call that needs them.  TF_ERR_ARG for any
+   other mode, and for mode 1 on a size of more than 1 000 000 000 coefficients (6 * 64 per MCU).  Changing the mode
+   forgets the last file (tf_jpeg_copy_last).
+   In mode 1: tf_jpeg_header returns the header of the last encode, valid until the next one, and TF_ERR_STATE before
+   any; the encode calls and tf_jpeg_copy_last count with that header's length.  A frame whose tables would need a code
+   of more than 32 bits (libjpeg refuses it as JERR_HUFF_CLEN_OVERFLOW) returns TF_ERR_STATE, the message names the
+   table, and nothing is written to `out`. */
+int tf_jpeg_set_optimize(tf_jpeg *enc, int mode);
+/* What the last mode 1 encode built, in the order of the DHT segments (DC luma, AC luma, DC chroma, AC chroma):
+   bits[4][16], vals[4][256] (the first sum(bits[t]) of vals[t] are meant, the rest is 0) and, if `counts` is not null,
+   the histograms counts[4][257] (entry 256, the reserved symbol, is 1), copied from the device.  TF_ERR_STATE
+   if the last call was no such encode. */
+int tf_jpeg_last_tables(tf_jpeg *enc, uint8_t *bits, uint8_t *vals, uint32_t *counts);
+/* The table stage alone, for tests: the four tables of the histograms counts[4][257] (entry 256 is ignored and taken
+   as 1).  *fault: bit t set if table t would need a code of more than 32 bits, and the call returns TF_ERR_STATE.
+   TF_ERR_ARG for a histogram whose 256 counts are all zero or sum to more than 1 000 000 000.  Forgets the last file. */
+int tf_jpeg_tables_from_counts(tf_jpeg *enc, const uint32_t *counts, uint8_t *bits, uint8_t *vals, uint32_t *fault);
 
 /* ---- PNG of a frame in device memory (transflow/output/frames.py: `-o out/%05d.png`) -----------------------------------
  * 8-bit RGB (colour type 2, no interlace): lossless.  Every row is filtered with the type -- None, Sub, Up, Average,

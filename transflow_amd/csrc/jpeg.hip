@@ -20,14 +20,26 @@
 //   k_jpeg_pack    one wave per interval copies its slot to its place in the packed stream and puts RSTn behind it, EOI
 //                  behind the last; no byte at or past `capacity` is written.
 //
+// Mode 1 (tf_jpeg_set_optimize), the frame's own Huffman tables -- libjpeg's optimize_coding, Pillow's optimize=True,
+// byte for byte (tests/jpeg_optimize_ref.py, tests/golden/jpegopt_*.npz).  k_jpeg_encode is a template over its pass:
+//   k_jpeg_encode<GATHER>     the same front; in place of placing bits the lanes count their symbols (jchuff.c
+//                             encode_mcu_gather) into an LDS histogram of the wave, added to the frame's at the end.
+//   k_jpeg_tables             one work-group, a wave per table: jpeg_gen_optimal_table's rule (jpeg_huff.h) -> the DHT
+//                             form for the header, the entries for a second Tables, a fault word.
+//   k_jpeg_encode<EMIT_WIDE>  the emit pass with those tables; a lane's symbols may take 75 bits and go in two pieces.
+// The scan of lengths and the pack are the same; the header is made on the host from the DHT form, per frame.
+//
 // Dummy blocks (jccoefct.c compress_data): the luma blocks of an MCU beyond ceil(W / 8) x ceil(H / 8) are not made
 // from pixels; their AC coefficients are zero and their DC is that of the block coded before them.
 // Chroma rows (jcprepct.c pre_process_data): the input is padded to an even row count only, and the DOWNSAMPLED plane
 // is then padded with its last row -- a chroma row below the image averages rows H - 2 and H - 1 of an image of even
 // height, not H - 1 twice.
 #include "jpeg_common.h"
+#include "jpeg_huff.h"
 #include "stream_common.h"
 
+#include <cstddef>
+#include <cstdlib>
 #include <cstring>
 
 namespace tf {
@@ -100,17 +112,46 @@ struct EncodeArgs {
     uint32_t slot_bytes;
     uint32_t *lengths;    // per interval: the bytes it wrote
     uint32_t *overflow;   // set if an interval had more bytes than its slot (the bound of jpeg_common.h says: never)
+    uint32_t *counts;     // GATHER: the frame's histograms, OwnTables::partial
 };
 
-__global__ __launch_bounds__(WAVE) void k_jpeg_encode(const EncodeArgs a, const FastDiv div_mcus_x)
+// `len` bits (1 to 64), right-aligned in `bits`, ORed into the bit buffer at bit `p`; nothing outside WORDS words
+template <int WORDS> __device__ __forceinline__ void place_bits(uint32_t *s_bits, uint32_t p, unsigned long long bits, int len)
 {
+    const unsigned long long w = bits << (64 - len);
+    const uint32_t word = p >> 5, sh = p & 31;
+    const uint32_t w0 = (uint32_t)(w >> 32 >> sh), w1 = (uint32_t)(w >> sh);
+    const uint32_t w2 = sh ? (uint32_t)(w << (32 - sh)) : 0u;
+    if (word + 2 < WORDS) {
+        if (w0)
+            atomicOr(&s_bits[word], w0);
+        if (w1)
+            atomicOr(&s_bits[word + 1], w1);
+        if (w2)
+            atomicOr(&s_bits[word + 2], w2);
+    }
+}
+
+// One kernel, three passes: EMIT codes with tables whose lanes the host has checked to fit 64 bits (Annex K's);
+// GATHER runs the same front and counts the symbols EMIT would write, into an LDS histogram of the wave whose non-zero
+// counters are added to the frame's when the interval is done (jchuff.c encode_mcu_gather); EMIT_WIDE codes with
+// tables made on the device (k_jpeg_tables), where a lane's symbols may take 75 bits.
+enum Pass { EMIT = 0, GATHER = 1, EMIT_WIDE = 2 };
+
+template <int PASS> __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const EncodeArgs a, const FastDiv div_mcus_x)
+{
+    constexpr int WORDS = PASS == EMIT_WIDE ? BIT_WORDS_WIDE : (PASS == GATHER ? 1 : BIT_WORDS);
+    constexpr int HIST = PASS == GATHER ? 4 * 256 : 1;
     __shared__ int s_blk[6][64];          // samples - 128, then coefficients: Y00 Y01 Y10 Y11 Cb Cr
-    __shared__ uint32_t s_bits[BIT_WORDS]; // the MCU's bits, first bit of the stream in bit 31 of word 0
+    __shared__ uint32_t s_bits[WORDS];    // the MCU's bits, first bit of the stream in bit 31 of word 0
+    __shared__ uint32_t s_hist[HIST];     // GATHER: [DC luma, AC luma, DC chroma, AC chroma][symbol]
     const int lane = threadIdx.x;
     const Tables &t = *a.tables;
     const int q_luma = t.q8[0][lane], q_chroma = t.q8[1][lane], zz = t.zz[lane];
-    for (int w = lane; w < BIT_WORDS; w += WAVE)
+    for (int w = lane; w < WORDS; w += WAVE)
         s_bits[w] = 0;
+    for (int w = lane; w < HIST; w += WAVE)
+        s_hist[w] = 0;
     const int first = blockIdx.x * a.restart_mcus; // (n_intervals * restart_mcus < n_mcus + restart_mcus <= 2^25)
     const int last = min(first + a.restart_mcus, a.n_mcus);
     uint8_t *slot = a.staging + (size_t)blockIdx.x * a.slot_bytes;
@@ -164,50 +205,71 @@ __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const EncodeArgs a, const 
             prev_dc = dc;
             const unsigned long long nonzero = __ballot(v != 0) & ~1ull; // the AC lanes
             int sym_v = v;
-            uint32_t entry = 0; // what the lane's value is coded with
+            int symbol = -1; // what the lane's value is coded with: 0 .. 255 in the AC table, 256 + category in the DC table
             int n_zrl = 0;
             if (lane == 0) {
                 sym_v = max(-2047, min(2047, dc - last_dc[comp]));
-                entry = t.dc[tb][32 - __clz(abs(sym_v))];
+                symbol = 256 + 32 - __clz(abs(sym_v));
             } else if (v != 0) {
                 const unsigned long long below = nonzero & ((1ull << lane) - 1);
                 const int prev = below ? 63 - __clzll((long long)below) : 0;
                 const int run = lane - 1 - prev;
                 n_zrl = run >> 4;
-                entry = t.ac[tb][((run & 15) << 4) | (32 - __clz(abs(v)))];
+                symbol = ((run & 15) << 4) | (32 - __clz(abs(v)));
             } else if (lane == 63) {
-                entry = t.ac[tb][0x00]; // EOB: the block ends in zeros
+                symbol = 0x00; // EOB: the block ends in zeros
             }
             last_dc[comp] = dc;
+            if constexpr (PASS == GATHER) {
+                uint32_t *dc_hist = &s_hist[(2 * tb) * 256], *ac_hist = &s_hist[(2 * tb + 1) * 256];
+                if (symbol >= 256)
+                    atomicAdd(&dc_hist[symbol - 256], 1u);
+                else if (symbol >= 0)
+                    atomicAdd(&ac_hist[symbol], 1u);
+                if (n_zrl)
+                    atomicAdd(&ac_hist[0xF0], (uint32_t)n_zrl);
+                continue;
+            }
+            const uint32_t entry = symbol < 0 ? 0u : (symbol >= 256 ? t.dc[tb][symbol - 256] : t.ac[tb][symbol]);
             const int nbits = sym_v == 0 ? 0 : 32 - __clz(abs(sym_v));
             const uint32_t value = (uint32_t)(sym_v < 0 ? sym_v - 1 : sym_v) & ((1u << nbits) - 1);
             unsigned long long bits = 0;
             int len = 0;
-            if (n_zrl) {
-                const uint32_t zrl = t.ac[tb][0xF0];
-                for (int i = 0; i < n_zrl; i++)
-                    bits = (bits << (zrl >> 16)) | (zrl & 0xFFFF), len += zrl >> 16;
-            }
-            bits = (bits << (entry >> 16)) | (entry & 0xFFFF), len += entry >> 16;
-            bits = (bits << nbits) | value, len += nbits;
-            len = min(len, LANE_MAX_BITS); // (never: the host checked the tables)
-            const int incl = wave_inclusive_sum(len, lane);
-            if (len) {
-                const uint32_t p = bitpos + (uint32_t)(incl - len);
-                const unsigned long long w = bits << (64 - len);
-                const uint32_t word = p >> 5, sh = p & 31;
-                const uint32_t w0 = (uint32_t)(w >> 32 >> sh), w1 = (uint32_t)(w >> sh);
-                const uint32_t w2 = sh ? (uint32_t)(w << (32 - sh)) : 0u;
-                if (word + 2 < BIT_WORDS) {
-                    if (w0)
-                        atomicOr(&s_bits[word], w0);
-                    if (w1)
-                        atomicOr(&s_bits[word + 1], w1);
-                    if (w2)
-                        atomicOr(&s_bits[word + 2], w2);
+            if constexpr (PASS == EMIT) {
+                if (n_zrl) {
+                    const uint32_t zrl = t.ac[tb][0xF0];
+                    for (int i = 0; i < n_zrl; i++)
+                        bits = (bits << (zrl >> 16)) | (zrl & 0xFFFF), len += zrl >> 16;
                 }
+                bits = (bits << (entry >> 16)) | (entry & 0xFFFF), len += entry >> 16;
+                bits = (bits << nbits) | value, len += nbits;
+                len = min(len, LANE_MAX_BITS); // (never: the host checked the tables)
+                const int incl = wave_inclusive_sum(len, lane);
+                if (len)
+                    place_bits<WORDS>(s_bits, bitpos + (uint32_t)(incl - len), bits, len);
+                bitpos += (uint32_t)__shfl(incl, WAVE - 1, WAVE);
+            } else { // two pieces: the ZRLs, then the code with its value
+                if (n_zrl) {
+                    const uint32_t zrl = t.ac[tb][0xF0];
+                    const int zl = min((int)(zrl >> 16), 16); // (never more: k_jpeg_tables limits to 16)
+                    for (int i = 0; i < min(n_zrl, 3); i++)
+                        bits = (bits << zl) | (zrl & 0xFFFF), len += zl;
+                }
+                const int el = min((int)(entry >> 16), 16);
+                const unsigned long long tail = ((unsigned long long)(entry & 0xFFFF) << nbits) | value;
+                const int tail_len = el + nbits; // at most 27
+                const int incl = wave_inclusive_sum(len + tail_len, lane);
+                const uint32_t p = bitpos + (uint32_t)(incl - len - tail_len);
+                if (len)
+                    place_bits<WORDS>(s_bits, p, bits, len);
+                if (tail_len)
+                    place_bits<WORDS>(s_bits, p + (uint32_t)len, tail, tail_len);
+                bitpos += (uint32_t)__shfl(incl, WAVE - 1, WAVE);
             }
-            bitpos += (uint32_t)__shfl(incl, WAVE - 1, WAVE);
+        }
+        if constexpr (PASS == GATHER) {
+            __syncthreads(); // s_blk is the next MCU's
+            continue;        // nothing to flush
         }
         // ---- the MCU's whole bytes to the slot; the interval's last MCU pads with ones first (flush_bits)
         if (m == last - 1 && (bitpos & 7)) {
@@ -237,16 +299,182 @@ __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const EncodeArgs a, const 
         const uint32_t carry = rem ? ((s_bits[n_bytes >> 2] >> (24 - 8 * (n_bytes & 3))) & 0xFF) << 24 : 0;
         const uint32_t used = (bitpos >> 5) + 3;
         __syncthreads();
-        for (uint32_t w = lane; w < used && w < BIT_WORDS; w += WAVE)
+        for (uint32_t w = lane; w < used && w < WORDS; w += WAVE)
             s_bits[w] = w == 0 ? carry : 0;
         bitpos = rem;
         __syncthreads();
+    }
+    if constexpr (PASS == GATHER) {
+        __syncthreads();
+        uint32_t *counts = a.counts + (size_t)(blockIdx.x % GATHER_COPIES) * (4 * 257);
+        for (int i = lane; i < HIST; i += WAVE)
+            if (const uint32_t n = s_hist[i])
+                atomicAdd(&counts[(i >> 8) * 257 + (i & 255)], n);
+        return;
     }
     if (lane == 0) {
         a.lengths[blockIdx.x] = min(outpos, a.slot_bytes);
         if (outpos > a.slot_bytes)
             *a.overflow = 1;
     }
+}
+
+// The four tables of the frame from its histograms: wave t makes table t (jpeg_huff.h has the rule).  With WAVE_PICK
+// the lanes hold the 257 frequencies in registers, five each, and one wave reduction per merge finds the two smallest
+// keys (frequency, -index): libjpeg's c1, and c2, "the same choice over the rest".  The trees are not chained: every
+// lane keeps, for each of its symbols, the index its tree goes by (c1 survives a merge, c2's tree takes c1's) and its
+// code size, one more for every merge its tree is part of -- what libjpeg's walk along the `others` chains adds up.
+// The wave then finishes as huff_finish does.  Without WAVE_PICK lane 0 runs gen_optimal_table as the host does: the
+// form the other is measured against and tested equal to.
+// Writes the DHT form to `own`, the entries to the frame's Tables, and own->fault.
+constexpr int TABLES_BLOCK = 4 * WAVE;
+
+struct TwoKeys {
+    unsigned long long k1, k2; // the smallest and the second smallest
+};
+
+__device__ __forceinline__ void two_keys_add(TwoKeys &t, unsigned long long k)
+{
+    const unsigned long long lo = k < t.k1 ? k : t.k1, hi = k < t.k1 ? t.k1 : k;
+    t.k1 = lo, t.k2 = hi < t.k2 ? hi : t.k2;
+}
+
+// the keys of lane (l ^ 1), (l ^ 2), then of the mirrored lane of 8 and of 16: data-parallel moves within a row of 16
+// lanes, which cost an ALU instruction where a shuffle goes through the LDS crossbar
+template <int CTRL> __device__ __forceinline__ unsigned long long row_move(unsigned long long v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
+    return ((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
+template <int CTRL> __device__ __forceinline__ void two_keys_row_step(TwoKeys &t)
+{
+    const unsigned long long a = row_move<CTRL>(t.k1), b = row_move<CTRL>(t.k2);
+    two_keys_add(t, a); // (the two lanes hold different keys, or NONE)
+    two_keys_add(t, b);
+}
+
+__device__ __forceinline__ TwoKeys wave_two_smallest(TwoKeys t)
+{
+    two_keys_row_step<0xB1>(t);  // quad_perm [1, 0, 3, 2]
+    two_keys_row_step<0x4E>(t);  // quad_perm [2, 3, 0, 1]
+    two_keys_row_step<0x141>(t); // row_half_mirror: the other quad of the eight
+    two_keys_row_step<0x140>(t); // row_mirror: the other eight of the row
+#pragma unroll
+    for (int o = 16; o < WAVE; o <<= 1) {
+        const unsigned long long a = __shfl_xor(t.k1, o, WAVE), b = __shfl_xor(t.k2, o, WAVE);
+        two_keys_add(t, a);
+        two_keys_add(t, b);
+    }
+    return t;
+}
+
+template <bool WAVE_PICK> __global__ __launch_bounds__(TABLES_BLOCK) void k_jpeg_tables(OwnTables *own, Tables *tables)
+{
+    __shared__ HuffWork s_work[4];
+    __shared__ uint8_t s_bits16[4][16], s_vals[4][256];
+    __shared__ int s_count[4][HUFF_MAX_CLEN + 2]; // WAVE_PICK: the symbols of every code size
+    const int t = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    HuffWork &w = s_work[t];
+    uint32_t *counts = own->counts[t];
+    int fault = HUFF_OK, n_vals = 0;
+    for (int i = lane; i < 256; i += WAVE) {
+        s_vals[t][i] = 0;
+        uint32_t n = 0;
+        for (int c = 0; c < GATHER_COPIES; c++)
+            n += own->partial[c][t][i];
+        counts[i] = n;
+    }
+    __syncthreads();
+    if (!WAVE_PICK) {
+        for (int i = lane; i < 256; i += WAVE)
+            w.freq[i] = counts[i];
+        __syncthreads();
+        if (lane == 0)
+            fault = gen_optimal_table(w, s_bits16[t], s_vals[t], &n_vals);
+    } else {
+        constexpr unsigned long long NONE = ~0ull;
+        // symbols lane, lane + 64 ...; the reserved symbol 256 is lane 0's fifth
+        uint32_t f[5];
+        int tree[5], size[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const int i = lane + WAVE * k;
+            f[k] = i < 256 ? counts[i] : (i == 256 ? 1u : 0u);
+            tree[k] = i, size[k] = 0;
+        }
+        for (;;) {
+            TwoKeys two{NONE, NONE};
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                const int i = lane + WAVE * k;
+                if (f[k] && f[k] <= HUFF_SENTINEL && i < HUFF_SYMS)
+                    two_keys_add(two, ((unsigned long long)f[k] << 32) | (uint32_t)(256 - i)); // smallest frequency, largest index
+            }
+            two = wave_two_smallest(two);
+            if (two.k2 == NONE)
+                break;
+            const int c1 = 256 - (int)(uint32_t)two.k1, c2 = 256 - (int)(uint32_t)two.k2;
+            const uint32_t sum = (uint32_t)(two.k1 >> 32) + (uint32_t)(two.k2 >> 32);
+#pragma unroll
+            for (int k = 0; k < 5; k++) {
+                const int i = lane + WAVE * k;
+                f[k] = i == c1 ? sum : (i == c2 ? 0u : f[k]);
+                const bool in1 = tree[k] == c1, in2 = tree[k] == c2;
+                size[k] += (in1 || in2) && size[k] < 0xFFFF;
+                tree[k] = in2 ? c1 : tree[k];
+            }
+        }
+        // huff_finish, by the wave: the counts per size with LDS atomics, a symbol's place among the values by counting
+        // the symbols before it in (code size, symbol) order; lane 0 limits the sizes
+        bool over = false, used = false;
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const int i = lane + WAVE * k;
+            if (i < HUFF_SYMS)
+                w.codesize[i] = (uint16_t)size[k];
+            over |= i < HUFF_SYMS && size[k] > HUFF_MAX_CLEN;
+            used |= i < 256 && size[k] > 0;
+        }
+        if (lane < HUFF_MAX_CLEN + 2)
+            s_count[t][lane] = 0;
+        __syncthreads();
+        fault = __ballot(over) ? HUFF_CLEN_OVERFLOW : (__ballot(used) ? HUFF_OK : HUFF_EMPTY);
+        if (fault == HUFF_OK) {
+#pragma unroll
+            for (int k = 0; k < 5; k++)
+                if (lane + WAVE * k < HUFF_SYMS && size[k])
+                    atomicAdd(&s_count[t][size[k]], 1);
+            int before[4] = {0, 0, 0, 0};
+            for (int j = 0; j < 256; j++) {
+                const int sj = w.codesize[j];
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    before[k] += sj && (sj < size[k] || (sj == size[k] && j < lane + WAVE * k));
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (size[k])
+                    s_vals[t][before[k] & 255] = (uint8_t)(lane + WAVE * k);
+        }
+        __syncthreads();
+        if (lane == 0 && fault == HUFF_OK)
+            huff_limit(s_count[t], s_bits16[t]);
+    }
+    if (lane == 0) {
+        if (fault != HUFF_OK) {
+            atomicOr(&own->fault, 1u << (fault == HUFF_CLEN_OVERFLOW ? t : 4 + t));
+            for (int i = 0; i < 16; i++)
+                s_bits16[t][i] = 0; // no code: the emit pass then writes nothing with this table
+        }
+        huff_entries(s_bits16[t], s_vals[t], t & 1 ? tables->ac[t >> 1] : tables->dc[t >> 1], t & 1 ? 256 : 16);
+    }
+    __syncthreads();
+    for (int i = lane; i < 256; i += WAVE)
+        own->vals[t][i] = s_vals[t][i];
+    if (lane < 16)
+        own->bits[t][lane] = s_bits16[t][lane];
 }
 
 // interval i: its bytes to out + offsets[i] (the markers before it are counted in), then FF D0+(i mod 8), or FF D9
@@ -280,21 +508,6 @@ static void quant_table(const uint8_t *base, int quality, uint8_t *out /*natural
     }
 }
 
-// jchuff.c jpeg_make_c_derived_tbl
-static void huff_entries(const uint8_t *bits, const uint8_t *vals, uint32_t *entries, int n_entries)
-{
-    for (int s = 0; s < n_entries; s++)
-        entries[s] = 0;
-    uint32_t code = 0;
-    int k = 0;
-    for (int len = 1; len <= 16; len++) {
-        for (int c = 0; c < bits[len - 1]; c++, k++, code++)
-            if (vals[k] < n_entries)
-                entries[vals[k]] = ((uint32_t)len << 16) | code;
-        code <<= 1;
-    }
-}
-
 static void put_segment(std::vector<uint8_t> &out, int marker, const std::vector<uint8_t> &payload)
 {
     const size_t n = payload.size() + 2;
@@ -313,7 +526,13 @@ static void put_dht(std::vector<uint8_t> &out, int tc_th, const uint8_t *bits, c
 }
 
 // jcmarker.c: write_file_header, write_frame_header, write_scan_header
-static std::vector<uint8_t> make_header(int H, int W, const uint8_t q[2][64], int restart_mcus)
+struct Dht {
+    const uint8_t *bits, *vals;
+};
+static const Dht ANNEX_K[4] = {{DC_LUMA_BITS, DC_LUMA_VALS}, {AC_LUMA_BITS, AC_LUMA_VALS}, {DC_CHROMA_BITS, DC_CHROMA_VALS},
+                               {AC_CHROMA_BITS, AC_CHROMA_VALS}};
+
+static std::vector<uint8_t> make_header(int H, int W, const uint8_t q[2][64], int restart_mcus, const Dht *dht = ANNEX_K)
 {
     std::vector<uint8_t> out{0xFF, 0xD8};
     put_segment(out, 0xE0, {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
@@ -324,10 +543,10 @@ static std::vector<uint8_t> make_header(int H, int W, const uint8_t q[2][64], in
         put_segment(out, 0xDB, p);
     }
     put_segment(out, 0xC0, {8, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1});
-    put_dht(out, 0x00, DC_LUMA_BITS, DC_LUMA_VALS);
-    put_dht(out, 0x10, AC_LUMA_BITS, AC_LUMA_VALS);
-    put_dht(out, 0x01, DC_CHROMA_BITS, DC_CHROMA_VALS);
-    put_dht(out, 0x11, AC_CHROMA_BITS, AC_CHROMA_VALS);
+    put_dht(out, 0x00, dht[0].bits, dht[0].vals);
+    put_dht(out, 0x10, dht[1].bits, dht[1].vals);
+    put_dht(out, 0x01, dht[2].bits, dht[2].vals);
+    put_dht(out, 0x11, dht[3].bits, dht[3].vals);
     put_segment(out, 0xDD, {(uint8_t)(restart_mcus >> 8), (uint8_t)restart_mcus});
     put_segment(out, 0xDA, {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
     return out;
@@ -352,7 +571,71 @@ struct tf_jpeg {
     DevBuf tables, staging, lengths, offsets, info, packed, upload;
     PinnedBuf info_host; // page-locked unsigned long long: [0] the scan's bytes, [1] the overflow flag
     size_t last_scan = 0;                    // the scan's bytes of the last encode that ran; 0: none to copy again
+    // mode 1, the frame's own tables (tf_jpeg_set_optimize); the buffers are allocated by the first call that needs them
+    int optimize = 0;
+    uint8_t q[2][64];                        // the quantisation tables, natural order: a header is made per frame
+    DevBuf own, own_tables;                  // OwnTables; the Tables the emit pass reads (tables' copy, own entries)
+    PinnedBuf own_host;                      // OwnTables' fault, bits and vals, as the last encode left them
+    std::vector<uint8_t> own_header;         // the header of the last mode 1 encode; empty: none
+    bool one_lane_tables = false;            // TF_JPEG_TABLES_ONE_LANE=1: k_jpeg_tables without its wave reductions, to measure
+    const std::vector<uint8_t> &file_header() const { return optimize ? own_header : header; }
 };
+
+static const char *const TABLE_NAMES[4] = {"DC luma", "AC luma", "DC chroma", "AC chroma"};
+constexpr size_t OWN_RESULT = offsetof(OwnTables, fault); // what comes down after an encode: fault, bits, vals
+
+// OwnTables' result in host memory
+struct OwnResult {
+    uint32_t fault, pad;
+    uint8_t bits[4][16], vals[4][256];
+};
+static_assert(sizeof(OwnResult) == offsetof(OwnTables, partial) - OWN_RESULT, "OwnResult is OwnTables from fault to vals");
+
+static int ensure_own(tf_jpeg *enc)
+{
+    if (enc->own.p)
+        return TF_OK;
+    TF_TRY(enc->own.alloc(sizeof(OwnTables)));
+    TF_TRY(enc->own_tables.alloc(sizeof(Tables)));
+    TF_TRY(enc->own_host.alloc(sizeof(OwnResult)));
+    TF_HIP(hipMemcpyAsync(enc->own_tables.p, enc->tables.p, sizeof(Tables), hipMemcpyDeviceToDevice, stream()));
+    const char *one_lane = getenv("TF_JPEG_TABLES_ONE_LANE");
+    enc->one_lane_tables = one_lane && one_lane[0] == '1';
+    return TF_OK;
+}
+
+static int make_tables(tf_jpeg *enc)
+{
+    return launch("jpeg_tables", enc->one_lane_tables ? k_jpeg_tables<false> : k_jpeg_tables<true>, dim3(1), dim3(TABLES_BLOCK), 0,
+                  enc->own.as<OwnTables>(), enc->own_tables.as<Tables>());
+}
+
+static int own_fault(const char *who, uint32_t fault)
+{
+    for (int t = 0; t < 4; t++)
+        if (fault & (1u << t))
+            return set_error(TF_ERR_STATE, "%s: the %s table would need a code of more than %d bits (libjpeg's JERR_HUFF_CLEN_OVERFLOW)",
+                             who, TABLE_NAMES[t], HUFF_MAX_CLEN);
+    for (int t = 0; t < 4; t++)
+        if (fault & (16u << t))
+            return set_error(TF_ERR_STATE, "%s: the %s table has no symbol", who, TABLE_NAMES[t]);
+    return TF_OK;
+}
+
+TF_API int tf_jpeg_set_optimize(tf_jpeg *enc, int mode)
+{
+    TF_REQUIRE(enc, "tf_jpeg_set_optimize: null pointer");
+    TF_REQUIRE(mode == 0 || mode == 1, "tf_jpeg_set_optimize: mode %d (0: the Annex K tables, 1: the frame's own)", mode);
+    // a frequency stays at or below libjpeg's selection sentinel, and within uint32_t (jpeg_huff.h)
+    TF_REQUIRE(mode == 0 || (long long)6 * 64 * enc->n_mcus <= (long long)HUFF_SENTINEL,
+               "tf_jpeg_set_optimize: %dx%d has more than %u coefficients", enc->W, enc->H, HUFF_SENTINEL);
+    if (mode != enc->optimize) {
+        enc->optimize = mode;
+        enc->last_scan = 0; // the file of the other mode is not this mode's to copy again
+        enc->own_header.clear();
+    }
+    return TF_OK;
+}
 
 TF_API void tf_jpeg_destroy(tf_jpeg *enc) { delete enc; }
 
@@ -384,6 +667,7 @@ TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int
         t.zz[k] = ZIGZAG[k];
         t.q8[0][k] = (uint16_t)(8 * q[0][ZIGZAG[k]]), t.q8[1][k] = (uint16_t)(8 * q[1][ZIGZAG[k]]);
     }
+    memcpy(enc->q, q, sizeof(q));
     huff_entries(DC_LUMA_BITS, DC_LUMA_VALS, t.dc[0], 16);
     huff_entries(DC_CHROMA_BITS, DC_CHROMA_VALS, t.dc[1], 16);
     huff_entries(AC_LUMA_BITS, AC_LUMA_VALS, t.ac[0], 256);
@@ -424,8 +708,11 @@ TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int
 TF_API int tf_jpeg_header(tf_jpeg *enc, const uint8_t **bytes, size_t *n)
 {
     TF_REQUIRE(enc && bytes && n, "tf_jpeg_header: null pointer");
-    *bytes = enc->header.data();
-    *n = enc->header.size();
+    *bytes = nullptr, *n = 0;
+    if (enc->optimize && enc->own_header.empty())
+        return set_error(TF_ERR_STATE, "tf_jpeg_header: the header is the frame's, and nothing has been encoded");
+    *bytes = enc->file_header().data();
+    *n = enc->file_header().size();
     return TF_OK;
 }
 
@@ -440,10 +727,10 @@ static int pack(tf_jpeg *enc, size_t dev_capacity)
 // header and packed stream to the caller, if they fit; *n_bytes either way
 static int copy_out(tf_jpeg *enc, const char *who, uint8_t *out, size_t capacity, size_t *n_bytes)
 {
-    const size_t hdr = enc->header.size(), scan = enc->last_scan;
+    const size_t hdr = enc->file_header().size(), scan = enc->last_scan;
     *n_bytes = hdr + scan;
     TF_REQUIRE(hdr + scan <= capacity, "%s: the file has %zu bytes, the buffer %zu", who, hdr + scan, capacity);
-    memcpy(out, enc->header.data(), hdr);
+    memcpy(out, enc->file_header().data(), hdr);
     TF_HIP(hipMemcpyAsync(out + hdr, enc->packed.p, scan, hipMemcpyDeviceToHost, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
     return TF_OK;
@@ -454,9 +741,15 @@ TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, s
     TF_REQUIRE(enc && rgb_dev && n_bytes && (out || capacity == 0), "tf_jpeg_encode_dev: null pointer");
     *n_bytes = 0;
     const size_t hdr = enc->header.size();
-    // what the pack kernel may write: the caller's room behind the header, and never more than the packed buffer
+    // what the pack kernel may write: the caller's room behind the header, and never more than the packed buffer (the
+    // frame's own header is not known before the kernels have run: all of the packed buffer then)
     const size_t room = capacity > hdr ? capacity - hdr : 0;
-    const size_t dev_capacity = room < enc->packed.bytes ? room : enc->packed.bytes;
+    const size_t dev_capacity = !enc->optimize && room < enc->packed.bytes ? room : enc->packed.bytes;
+    if (enc->optimize) {
+        TF_TRY(ensure_own(enc));
+        enc->own_header.clear();
+        TF_HIP(hipMemsetAsync(enc->own.p, 0, sizeof(OwnTables), stream())); // the histograms and the fault word
+    }
     TF_HIP(hipMemsetAsync(enc->info.p, 0, enc->info.bytes, stream()));
     EncodeArgs a;
     a.rgb = (const uint8_t *)rgb_dev, a.W = enc->W, a.H = enc->H;
@@ -465,13 +758,33 @@ TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, s
     a.tables = enc->tables.as<Tables>(), a.staging = enc->staging.as<uint8_t>(), a.slot_bytes = enc->slot;
     a.lengths = enc->lengths.as<uint32_t>();
     a.overflow = reinterpret_cast<uint32_t *>(enc->info.as<unsigned long long>() + 1);
-    TF_TRY(launch("jpeg_encode", k_jpeg_encode, dim3(enc->n_intervals), dim3(WAVE), 0, a, fast_div_setup((uint32_t)enc->mcus_x)));
+    a.counts = nullptr;
+    const FastDiv div = fast_div_setup((uint32_t)enc->mcus_x);
+    if (enc->optimize) { // count, make the tables, code with them
+        OwnTables *own = enc->own.as<OwnTables>();
+        a.counts = &own->partial[0][0][0];
+        TF_TRY(launch("jpeg_gather", k_jpeg_encode<GATHER>, dim3(enc->n_intervals), dim3(WAVE), 0, a, div));
+        TF_TRY(make_tables(enc));
+        a.tables = enc->own_tables.as<Tables>();
+        TF_TRY(launch("jpeg_emit", k_jpeg_encode<EMIT_WIDE>, dim3(enc->n_intervals), dim3(WAVE), 0, a, div));
+    } else {
+        TF_TRY(launch("jpeg_encode", k_jpeg_encode<EMIT>, dim3(enc->n_intervals), dim3(WAVE), 0, a, div));
+    }
     TF_TRY(launch("jpeg_scan", k_slot_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
                   enc->n_intervals, 2u, enc->info.as<unsigned long long>())); // a marker behind each interval
     TF_TRY(pack(enc, dev_capacity));
     enc->last_scan = 0;
     TF_HIP(hipMemcpyAsync(enc->info_host.p, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
+    if (enc->optimize) // comes down with `info`: the one wait below is for both
+        TF_HIP(hipMemcpyAsync(enc->own_host.p, (const uint8_t *)enc->own.p + OWN_RESULT, sizeof(OwnResult), hipMemcpyDeviceToHost,
+                              stream()));
     TF_HIP(hipStreamSynchronize(stream()));
+    if (enc->optimize) {
+        const OwnResult &r = *enc->own_host.as<OwnResult>();
+        TF_TRY(own_fault("tf_jpeg_encode_dev", r.fault));
+        const Dht dht[4] = {{r.bits[0], r.vals[0]}, {r.bits[1], r.vals[1]}, {r.bits[2], r.vals[2]}, {r.bits[3], r.vals[3]}};
+        enc->own_header = make_header(enc->H, enc->W, enc->q, enc->restart_mcus, dht);
+    }
     if (enc->info_host.as<unsigned long long>()[1])
         return set_error(TF_ERR_STATE, "tf_jpeg_encode_dev: an interval outgrew its staging slot of %u bytes", enc->slot);
     enc->last_scan = (size_t)enc->info_host.as<unsigned long long>()[0];
@@ -484,10 +797,54 @@ TF_API int tf_jpeg_copy_last(tf_jpeg *enc, uint8_t *out, size_t capacity, size_t
     *n_bytes = 0;
     if (!enc->last_scan)
         return set_error(TF_ERR_STATE, "tf_jpeg_copy_last: nothing has been encoded");
-    const size_t hdr = enc->header.size();
+    const size_t hdr = enc->file_header().size();
     const size_t room = capacity > hdr ? capacity - hdr : 0;
     TF_TRY(pack(enc, room < enc->packed.bytes ? room : enc->packed.bytes));
     return copy_out(enc, "tf_jpeg_copy_last", out, capacity, n_bytes);
+}
+
+TF_API int tf_jpeg_last_tables(tf_jpeg *enc, uint8_t *bits, uint8_t *vals, uint32_t *counts)
+{
+    TF_REQUIRE(enc && bits && vals, "tf_jpeg_last_tables: null pointer");
+    if (!enc->optimize || enc->own_header.empty())
+        return set_error(TF_ERR_STATE, "tf_jpeg_last_tables: no encode with the frame's own tables has run");
+    const OwnResult &r = *enc->own_host.as<OwnResult>();
+    memcpy(bits, r.bits, sizeof(r.bits));
+    memcpy(vals, r.vals, sizeof(r.vals));
+    if (counts) {
+        TF_HIP(hipMemcpyAsync(counts, enc->own.p, sizeof(uint32_t) * 4 * 257, hipMemcpyDeviceToHost, stream()));
+        TF_HIP(hipStreamSynchronize(stream()));
+        for (int t = 0; t < 4; t++)
+            counts[t * 257 + 256] = 1; // the reserved symbol: the gather pass does not count it
+    }
+    return TF_OK;
+}
+
+TF_API int tf_jpeg_tables_from_counts(tf_jpeg *enc, const uint32_t *counts, uint8_t *bits, uint8_t *vals, uint32_t *fault)
+{
+    TF_REQUIRE(enc && counts && bits && vals && fault, "tf_jpeg_tables_from_counts: null pointer");
+    *fault = 0;
+    for (int t = 0; t < 4; t++) {
+        unsigned long long sum = 0;
+        for (int i = 0; i < 256; i++)
+            sum += counts[t * 257 + i];
+        TF_REQUIRE(sum > 0, "tf_jpeg_tables_from_counts: the %s histogram has no symbol", TABLE_NAMES[t]);
+        TF_REQUIRE(sum <= HUFF_SENTINEL, "tf_jpeg_tables_from_counts: the %s histogram sums to more than %u", TABLE_NAMES[t],
+                   HUFF_SENTINEL);
+    }
+    TF_TRY(ensure_own(enc));
+    enc->own_header.clear(), enc->last_scan = 0; // the tables of the last encode are gone
+    OwnTables *own = enc->own.as<OwnTables>();
+    TF_HIP(hipMemsetAsync(enc->own.p, 0, sizeof(OwnTables), stream()));
+    TF_HIP(hipMemcpyAsync(own->partial[0], counts, sizeof(own->counts), hipMemcpyHostToDevice, stream())); // the other copies are zero
+    TF_TRY(make_tables(enc));
+    TF_HIP(hipMemcpyAsync(enc->own_host.p, (const uint8_t *)enc->own.p + OWN_RESULT, sizeof(OwnResult), hipMemcpyDeviceToHost, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    const OwnResult &r = *enc->own_host.as<OwnResult>();
+    *fault = r.fault;
+    memcpy(bits, r.bits, sizeof(r.bits));
+    memcpy(vals, r.vals, sizeof(r.vals));
+    return own_fault("tf_jpeg_tables_from_counts", r.fault);
 }
 
 TF_API int tf_jpeg_default_restart_mcus(void) { return DEFAULT_RESTART_MCUS; }

@@ -91,6 +91,7 @@ struct Tables {
 // would not have refused).  A ZRL stands for 16 zero coefficients and an EOB for at least one, and both cost less than
 // one coded coefficient, so a block costs at most 16 + 11 + 63 (16 + 10) = 1665 bits and an MCU of six blocks 9990.
 // The interval is padded to a byte once, and every byte can be an 0xFF that takes an 0x00 after it.
+// The bound assumes a 16-bit code for every symbol, so it holds for the frame's own tables (mode 1) as it stands.
 constexpr int BLOCK_MAX_BITS = 16 + 11 + 63 * (16 + 10);
 constexpr int MCU_MAX_BITS = 6 * BLOCK_MAX_BITS;
 inline size_t slot_bytes(int restart_mcus)
@@ -104,6 +105,25 @@ inline size_t slot_bytes(int restart_mcus)
 // -- not for the bound above: no data can make the kernel write outside it.
 constexpr int LANE_MAX_BITS = 64;
 constexpr int BIT_WORDS = (8 + 6 * 64 * LANE_MAX_BITS) / 32 + 3;
+// With the frame's own tables nothing is checked on the host: ZRL may have a 16-bit code like any other symbol, and a
+// lane's three ZRLs, its code and an 11-bit value come to 75 bits.  That kernel places a lane's bits as two pieces, the
+// ZRLs (at most 48 bits) and the code with its value (at most 27), and its buffer is sized for 75.
+constexpr int LANE_MAX_BITS_WIDE = 3 * 16 + 16 + 11;
+constexpr int BIT_WORDS_WIDE = (8 + 6 * 64 * LANE_MAX_BITS_WIDE) / 32 + 3;
+
+// ---- mode 1, the frame's own tables: what the gather pass counts and what k_jpeg_tables makes of it.  The four tables
+// are in the order of the file's DHT segments: DC luma, AC luma, DC chroma, AC chroma.
+constexpr int GATHER_COPIES = 8;
+struct OwnTables {
+    uint32_t counts[4][257]; // the histograms, summed by k_jpeg_tables; entry 256, the reserved symbol, is not counted
+    uint32_t fault;          // bit t: table t has a code size above 32; bit 4 + t: table t has no symbol
+    uint32_t pad;
+    uint8_t bits[4][16];     // as DHT carries them
+    uint8_t vals[4][256];    // the first sum(bits) of each are meant
+    // what the gather pass adds to: interval i counts into copy i % GATHER_COPIES, so that fewer waves meet at one
+    // counter (at 4K, 4050 waves add some 150 counters each)
+    uint32_t partial[GATHER_COPIES][4][257];
+};
 
 } // namespace jpeg
 } // namespace tf

@@ -89,20 +89,21 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
     return classmethod(from_args)
 
 
-def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_frames=False, png_code="fixed"):
+def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_frames=False, png_code="fixed",
+                          jpeg_optimize=False):
     from .compositor import LAYER_CLASSES, HipCompositor
 
     def from_args(cls, height, width, layer_configs, background_color="#ffffff"):
         if all(getattr(c, "classname", None) in LAYER_CLASSES for c in layer_configs):
             return HipCompositor.from_args(height, width, layer_configs, background_color=background_color,
                                            lazy_frames=lazy_frames, jpeg_frames=jpeg_frames, png_frames=png_frames,
-                                           png_code=png_code)
+                                           png_code=png_code, jpeg_optimize=jpeg_optimize)
         return original(height, width, layer_configs, background_color=background_color)
 
     return classmethod(from_args)
 
 
-def _output_from_args(original, quality):
+def _output_from_args(original, quality, optimize=False):
     from .output import HipMjpegOutput, RawFramesOnly, mjpeg_address
 
     def from_args(cls, path, width, height, framerate=None, vcodec="h264", execute=False, replace=False, initial_counter=0):
@@ -110,7 +111,8 @@ def _output_from_args(original, quality):
         if address is None:         # the reference's own output; it takes pixels, and says so if it is given a file
             return RawFramesOnly(original(path, width, height, framerate=framerate, vcodec=vcodec, execute=execute,
                                           replace=replace, initial_counter=initial_counter))
-        return HipMjpegOutput(address[0], address[1], width, height, 30 if framerate is None else framerate, quality)
+        return HipMjpegOutput(address[0], address[1], width, height, 30 if framerate is None else framerate, quality,
+                              optimize=optimize)
 
     return classmethod(from_args)
 
@@ -146,7 +148,8 @@ def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=Fals
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
-            device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed") -> None:
+            device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed",
+            jpeg_optimize: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -164,6 +167,9 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     VideoOutput.from_args (pipeline.py's output process) builds a HipMjpegOutput (transflow_amd/output.py) for `mjpeg...`
     paths; any other output is the reference's own and raises a TypeError that names this option when it is fed a
     JpegFrame.  Not together with lazy_frames.  By default (None) nothing of this is touched.
+    jpeg_optimize: with jpeg_frames, the files carry the frame's own Huffman tables (JpegEncoder(optimize=True),
+    DESIGN.md section 15; libjpeg's optimize_coding): smaller files of the same pixels, and a raw frame that reaches the
+    MJPEG output is encoded on the host with the same setting; False (the default) keeps writing the bytes it wrote before.
     png_frames: the compositors built for the pipeline return PngFrames from render() (transflow_amd/png.py: the
     lossless file, made on the device), and VideoOutput.from_args builds a HipFramesOutput (transflow_amd/output.py) for
     `%d` templates that end in `.png`; any other output is the reference's own and raises a TypeError that names this
@@ -201,6 +207,8 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         raise ValueError(f"png_code is \"fixed\" or \"frame\", not {png_code!r}")
     if png_code != "fixed" and not png_frames:
         raise ValueError("png_code is for png_frames: without them no PNG is written")
+    if jpeg_optimize and jpeg_frames is None:
+        raise ValueError("jpeg_optimize is for jpeg_frames: without them no JPEG is written")
     if flow and "flow" not in _saved:
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
@@ -214,11 +222,12 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         bind_reference_data_layer()    # extra/control.py:155 asks isinstance(layer, DataLayer) of checkpointed layers
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
         RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames,
-                                                        "indexed" if png_frames == "indexed" else bool(png_frames), png_code)
+                                                        "indexed" if png_frames == "indexed" else bool(png_frames), png_code,
+                                                        bool(jpeg_optimize))
     if jpeg_frames is not None and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
-        RefVideoOutput.from_args = _output_from_args(RefVideoOutput.from_args, int(jpeg_frames))
+        RefVideoOutput.from_args = _output_from_args(RefVideoOutput.from_args, int(jpeg_frames), bool(jpeg_optimize))
     if png_frames and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])

@@ -5,6 +5,9 @@ The reference's MJPEG output serves `cv2.imencode(".jpg", frame, [IMWRITE_JPEG_Q
 is -- 8-bit YCbCr 4:2:0, the standard tables, a restart interval: the bytes of Pillow's
 `save(quality=q, subsampling=2, restart_marker_blocks=r)` -- and only the file comes down, a few percent of the
 (H, W, 3) array.  `JpegFrame` is what then travels: the bytes and four numbers.
+
+`optimize=True` is libjpeg's `optimize_coding`, Pillow's `save(..., optimize=True)`: the same pixels coded with the
+frame's own Huffman tables (tf_jpeg_set_optimize), a file some 5 % smaller for about twice the entropy kernel.
 """
 from __future__ import annotations
 
@@ -16,52 +19,91 @@ import numpy as np
 from .framecodec import EncodedFrame, FrameEncoder
 
 
-def pillow_encode(image: np.ndarray, quality: int, restart_mcus: int) -> bytes:
+def pillow_encode(image: np.ndarray, quality: int, restart_mcus: int, optimize: bool = False) -> bytes:
     """The same file made on the host by libjpeg (Pillow >= 10.2 for `restart_marker_blocks`): what a process without
-    a GPU does with a raw frame (transflow_amd/output.py)."""
+    a GPU does with a raw frame (transflow_amd/output.py).
+    With `optimize` libjpeg writes nothing before the whole image is counted, and Pillow's encoder then needs its
+    buffer to hold the file at once ("broken data stream" for a 1 x 65500 image otherwise): PIL.ImageFile.MAXBLOCK is
+    raised for the call to the most the file can take -- the header and jpeg_common.h's bound on the scan, 2498 bytes
+    per MCU stuffed, a marker per interval -- and put back behind it."""
     import PIL
     import PIL.Image
+    import PIL.ImageFile
     if tuple(int(v) for v in PIL.__version__.split(".")[:2]) < (10, 2):
         # an older save() ignores the option without a word: the file would announce an interval and hold no marker
         raise RuntimeError(f"Pillow {PIL.__version__} has no restart_marker_blocks; 10.2 or later is needed")
     buf = io.BytesIO()
-    PIL.Image.fromarray(np.ascontiguousarray(image, dtype=np.uint8)).save(
-        buf, format="JPEG", quality=int(quality), subsampling=2, restart_marker_blocks=int(restart_mcus))
+    picture = PIL.Image.fromarray(np.ascontiguousarray(image, dtype=np.uint8))
+    if not optimize:
+        picture.save(buf, format="JPEG", quality=int(quality), subsampling=2, restart_marker_blocks=int(restart_mcus))
+        return buf.getvalue()
+    n_mcus = ((picture.height + 15) // 16) * ((picture.width + 15) // 16)
+    before = PIL.ImageFile.MAXBLOCK
+    PIL.ImageFile.MAXBLOCK = max(before, 2048 + n_mcus * (2498 + 2))
+    try:
+        picture.save(buf, format="JPEG", quality=int(quality), subsampling=2, restart_marker_blocks=int(restart_mcus),
+                     optimize=True)
+    finally:
+        PIL.ImageFile.MAXBLOCK = before
     return buf.getvalue()
 
 
 class JpegFrame(EncodedFrame):
-    """A frame as a JPEG file: `data`, the `shape` (H, W, 3) of the image it decodes to, `quality`, `restart_mcus`."""
+    """A frame as a JPEG file: `data`, the `shape` (H, W, 3) of the image it decodes to, `quality`, `restart_mcus`,
+    and `optimize`: whether the file carries the frame's own Huffman tables."""
 
-    __slots__ = ("quality", "restart_mcus")
+    __slots__ = ("quality", "restart_mcus", "optimize")
 
-    def __init__(self, data: bytes, shape, quality: int, restart_mcus: int):
+    def __init__(self, data: bytes, shape, quality: int, restart_mcus: int, optimize: bool = False):
         super().__init__(data, shape)
         self.quality = int(quality)
         self.restart_mcus = int(restart_mcus)
+        self.optimize = bool(optimize)
 
 
 class JpegEncoder(FrameEncoder):
-    """tf_jpeg: one size, one quality, one restart interval; its device buffers are allocated once."""
+    """tf_jpeg: one size, one quality, one restart interval; its device buffers are allocated once.  `optimize`: the
+    files carry the frame's own Huffman tables; `header` is then the last file's, and there is none before the first."""
 
     ENCODE_DEV, ENCODE, COPY_LAST, DESTROY = "tf_jpeg_encode_dev", "tf_jpeg_encode", "tf_jpeg_copy_last", "tf_jpeg_destroy"
 
-    def __init__(self, height: int, width: int, quality: int = 50, restart_mcus: int | None = None):
+    def __init__(self, height: int, width: int, quality: int = 50, restart_mcus: int | None = None, optimize: bool = False):
         super().__init__(height, width)
         self.quality = int(quality)
+        self.optimize = bool(optimize)
         self._check(self._lib.tf_jpeg_create(C.byref(self._h), self.height, self.width, self.quality,
                                              0 if restart_mcus is None else int(restart_mcus)))
-        self.header = self._header()
-        # the interval the library chose is in the header's DRI segment, the 4 bytes before SOS's 14
-        self.restart_mcus = int.from_bytes(self.header[-16:-14], "big") if restart_mcus is None else int(restart_mcus)
+        self.restart_mcus = int(self._lib.tf_jpeg_default_restart_mcus()) if restart_mcus is None else int(restart_mcus)
+        self._fixed_header = self._header()      # the Annex K tables': made once
+        if self.optimize:
+            try:
+                self._check(self._lib.tf_jpeg_set_optimize(self._h, 1))
+            except Exception:
+                self.close()
+                raise
 
     def _header(self) -> bytes:
         p, n = C.c_void_p(), C.c_size_t()
         self._check(self._lib.tf_jpeg_header(self._h, C.byref(p), C.byref(n)))
         return C.string_at(p.value, n.value)
 
-    def _first_capacity(self) -> int:   # most frames are a small part of this
-        return len(self.header) + self.height * self.width * 3 // 4 + 4096
+    @property
+    def header(self) -> bytes:
+        """The bytes before the scan: the same for every file, or with `optimize` the last file's (an error before it)."""
+        return self._header() if self.optimize else self._fixed_header
+
+    def _first_capacity(self) -> int:   # most frames are a small part of this (no own header is longer than Annex K's + 400)
+        return len(self._fixed_header) + 400 + self.height * self.width * 3 // 4 + 4096
+
+    def last_tables(self, counts: bool = False):
+        """What the last `optimize` encode built, in the DHT segments' order (DC luma, AC luma, DC chroma, AC chroma):
+        a list of four (bits, vals), and with `counts` the uint32 (4, 257) histograms behind them."""
+        bits, vals = np.zeros((4, 16), np.uint8), np.zeros((4, 256), np.uint8)
+        hist = np.zeros((4, 257), np.uint32) if counts else None
+        self._check(self._lib.tf_jpeg_last_tables(self._h, C.c_void_p(bits.ctypes.data), C.c_void_p(vals.ctypes.data),
+                                                  C.c_void_p(hist.ctypes.data) if counts else None))
+        tables = [(bits[t].tolist(), vals[t, :int(bits[t].sum())].tolist()) for t in range(4)]
+        return (tables, hist) if counts else tables
 
     def frame(self, image) -> JpegFrame:
-        return JpegFrame(self.encode(image), (self.height, self.width, 3), self.quality, self.restart_mcus)
+        return JpegFrame(self.encode(image), (self.height, self.width, 3), self.quality, self.restart_mcus, self.optimize)

@@ -46,7 +46,9 @@ class HipMjpegStream:
     """MjpegStream's surface (mjpeg.py:26-73) for the reference's _StreamHandler and MjpegServer.add_stream:
     `name`, `fps`, `set_frame`, `get_frame`, `get_frame_processed`, `get_bandwidth`."""
 
-    def __init__(self, name: str, size, quality: int = 50, fps: float = 30, restart_mcus: int | None = None):
+    def __init__(self, name: str, size, quality: int = 50, fps: float = 30, restart_mcus: int | None = None,
+                 optimize: bool = False):
+        self.optimize = bool(optimize)                     # a raw frame is encoded with its own Huffman tables
         self.name = name.lower().casefold().replace(" ", "_")
         self.size = size                                   # (width, height)
         self.quality = max(1, min(int(quality), 100))
@@ -67,7 +69,7 @@ class HipMjpegStream:
         else:
             if self.restart_mcus is None:
                 self.restart_mcus = default_restart_mcus()
-            data = pillow_encode(np.asarray(frame), self.quality, self.restart_mcus)
+            data = pillow_encode(np.asarray(frame), self.quality, self.restart_mcus, self.optimize)
         self._sizes = (self._sizes + [len(data)])[-30:]
         return _Encoded(data)
 
@@ -84,12 +86,13 @@ class HipMjpegStream:
 class HipMjpegOutput:
     """Same constructor, context-manager protocol and `feed` as transflow's MjpegOutput."""
 
-    def __init__(self, host: str, port: int, width: int, height: int, framerate: float, quality: int = 50):
+    def __init__(self, host: str, port: int, width: int, height: int, framerate: float, quality: int = 50,
+                 optimize: bool = False):
         self.width, self.height = int(width), int(height)
         self.host, self.port = host, port
         self.framerate = framerate
         self.quality = quality
-        self.stream = HipMjpegStream("transflow", (self.width, self.height), quality=quality, fps=framerate)
+        self.stream = HipMjpegStream("transflow", (self.width, self.height), quality=quality, fps=framerate, optimize=optimize)
         self.server = None
 
     @property
