@@ -54,6 +54,11 @@ int tf_device_count(int *count);
      "remap_quad"     1   1 = with remap_px = 4, a frame width that is a multiple of 4 and 16-byte aligned buffers, a thread's
                           four pixels are adjacent ones of a row (16-byte loads and stores, the RGB frame stored from
                           registers); 0 = they are a block apart.  Same state and frames either way
+     "remap_lean"     1   1 = where the step would take the adjacent-pixel kernel on the one-word state and the layer has no
+                          source, destination or alpha mask, no reset_source, pixels_can_move_to_empty_spot and
+                          _to_filled_spot on and no uniform field is supplied, it takes a kernel compiled for that
+                          configuration (no run-time tests of it, 32-bit indices, one load per RGB pixel); 0 = the
+                          general kernel.  Same state and frames
      "remap_no_pack"  0   0 = tf_remap_step_dev keeps the layer state as ONE 32-bit word per pixel between steps where row,
                           column, alpha and source index fit 13 + 13 + 1 + 5 bits (frames up to 8192 x 8192, 32
                           sources), as int16 x 4 otherwise; 2 = as int16 x 4 at most; 1 = as int32 x 4 (never packed)

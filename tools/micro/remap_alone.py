@@ -2,7 +2,7 @@
 """What does one launch of the remap step take with nothing beside it?  The bench's pass of remap steps (one tf_remap_steps_dev
 call over the pass's flows) on an otherwise idle GPU, per launch, and the bytes per second that is on the step's 26 B/px
 by the counters -- next to the rate of the library's 16-byte-per-lane copy kernel (bench.copy_ceiling).  With a library
-that has the option, once per value of remap_quad.  usage (GPU box): python3 tools/micro/remap_alone.py [workload] [batch] [reps]"""
+that has the options, once per value of remap_lean and remap_quad.  usage (GPU box): python3 tools/micro/remap_alone.py [workload] [batch] [reps]"""
 import os
 import sys
 import time
@@ -19,14 +19,23 @@ wl = bench.WORKLOADS[name]
 job = bench.Job(wl, batch, bench.make_plan(batch + 1, batch, 0, 1), batch + 1, seed=2000, device=0, lanes=1)
 job.calc_pass(0)
 job.sync()
-try:
-    _lib.get_option("remap_quad")
-    forms = [("remap_quad=1", 1), ("remap_quad=0", 0)]
-except ValueError:
-    forms = [("(no remap_quad option)", None)]
-for label, value in forms:
-    if value is not None:
-        _lib.set_option("remap_quad", value)
+def has(option):
+    try:
+        _lib.get_option(option)
+        return True
+    except ValueError:
+        return False
+
+
+# a form is the options it sets; with a library that has neither option, the kernel it has
+forms = [("(no remap_quad option)", {})]
+if has("remap_quad"):
+    forms = [("remap_quad=1", {"remap_quad": 1}), ("remap_quad=0", {"remap_quad": 0})]
+if has("remap_lean"):
+    forms = [("remap_lean=1", {"remap_lean": 1})] + [(f"remap_lean=0 {label}", dict(opts, remap_lean=0)) for label, opts in forms]
+for label, opts in forms:
+    for option, value in opts.items():
+        _lib.set_option(option, value)
     for _ in range(2):
         job.remap_pass(job.layer)
     job.sync()

@@ -645,6 +645,189 @@ k_remap_step_quad(const float2 *__restrict__ flow, const S *__restrict__ old, S 
     }
 }
 
+// ---- the lean step: k_remap_step_quad for the layer most layers are, with that configuration known at compile time.
+//
+// Taken (step_dev_impl) for a one-source moveref layer whose state is the one word, with no source, destination or alpha
+// mask, no reset_source, no supplied uniform field, and pixels_can_move_to_empty_spot and _to_filled_spot both on.  Same
+// statements per pixel, in the same order, as k_remap_step_quad; what the configuration settles is not tested at run
+// time, every index is 32 bits wide, and what is left of the body is straight-line code with selects.
+
+struct LeanParams {
+    FastDiv div;
+    float factor;    // reset_random_factor
+    uint64_t seed, frame;
+    unsigned bg;     // r | g << 8 | b << 16
+    const int *rgba_dead; // as StepParams'
+};
+
+// base + a 32-bit byte offset: one 64-bit base in scalar registers and one 32-bit offset per lane, no 64-bit address
+// arithmetic per access.  Every offset of the lean kernel fits (step_dev_impl states the bound).
+template <typename T>
+__device__ __forceinline__ T ld32(const void *base, uint32_t byte_off)
+{
+    return *reinterpret_cast<const T *>(static_cast<const char *>(base) + byte_off);
+}
+template <typename T>
+__device__ __forceinline__ void st32(void *base, uint32_t byte_off, T v)
+{
+    *reinterpret_cast<T *>(static_cast<char *>(base) + byte_off) = v;
+}
+__device__ __forceinline__ uint32_t ld32_unaligned(const void *base, uint32_t byte_off)
+{
+    uint32_t v;
+    __builtin_memcpy(&v, static_cast<const char *>(base) + byte_off, 4);
+    return v;
+}
+
+// source.py:361-362 for a vector that is rounded to integers next: clip_nan, with NaN -> 0 said here rather than left to
+// the conversion (v_cvt_i32_f32 turns NaN into 0, which is what flow_offset makes of clip_nan's NaN in the other kernels).
+__device__ __forceinline__ float clip_nan_zero(float v, float lo, float hi) { return v != v ? 0.f : fminf(fmaxf(v, lo), hi); }
+
+// C: pixmap channels; CLIP: clip_flow; RESET: 0 off, 1 random with the factor as the threshold (no reset mask), 2 random
+// through the reset mask; TCM: transparent_pixels_can_move.
+//
+// The move (movement.py:20-48) with no masks and to_empty = to_filled = 1:  md = true,  ms = TCM || src_filled,  and
+// where it moves d = so with alpha := 1 if (!TCM || src_filled) -- in both of which cases alpha(so) is 1 already (alpha
+// is one bit of the word).  So a move copies `so` unchanged.  Where nothing moves (offset 0, or a source outside the
+// frame) the kernel gathers the pixel's own state, so == me.  Hence   d = TCM ? so : (alpha(so) ? so : me)   everywhere.
+//
+// The out-of-frame test with CLIP != 0.  Pixel (i, j), 0 <= i < H, 0 <= j < W, H, W <= 8192.  clip_nan_zero(x, -j, W-1-j):
+// NaN -> 0; otherwise fmaxf(x, -j) >= -j (for x = -inf too: -j) and fminf(., W-1-j) <= W-1-j (for +inf too), so the
+// result is a finite float in [-j, W-1-j], an interval with integer ends of magnitude < 2^24 that contains 0.  rintf
+// maps [a, b] with integer a, b into [a, b], and the conversion of a finite integer-valued float below 2^31 is exact:
+// fx in [-j, W-1-j], fy in [-i, H-1-i] likewise (CLIP == 2 forms x, y from integers and clips them the same way).  Then
+// s = t + fy W + fx = (i + fy) W + (j + fx) with 0 <= i + fy < H, 0 <= j + fx < W: 0 <= s < N for EVERY input, in 32
+// bits.  So with CLIP != 0 `inside`, the 64-bit s and the atomicOr are not compiled; with CLIP == 0 they are
+// k_remap_step_quad's.
+template <int C, int CLIP, int RESET, bool TCM>
+__global__ void __launch_bounds__(BLOCK)
+k_remap_step_lean(const void *__restrict__ flow, const unsigned *__restrict__ old, unsigned *__restrict__ neu,
+                  const float *__restrict__ reset_mask, unsigned *__restrict__ rgba, const uint8_t *__restrict__ pixmap,
+                  uint8_t *__restrict__ image, int N, int H, int W, LeanParams lp, int *err)
+{
+    using Q = QuadWord;
+    // (the XCD-aware renumbering of k_remap_step_px)
+    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7, qn = nb >> 3, rn = nb & 7;
+    const unsigned bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+    const int t = (int)(bid * BLOCK + threadIdx.x) * 4;
+    const bool live = t < N;
+    const int tc = live ? t : N - 4; // a dead lane of the last block reads a valid quad and stores nothing
+    const uint32_t utc = (uint32_t)tc;
+    // --- phase 1: what the pixels themselves address
+    float fx[4], fy[4];
+    int wv[4];
+    if (CLIP == 2) {
+        const int4 w4 = ld32<int4>(flow, utc * 4);
+        wv[0] = w4.x, wv[1] = w4.y, wv[2] = w4.z, wv[3] = w4.w;
+    } else {
+        const float4 a = ld32<float4>(flow, utc * 8), b = ld32<float4>(flow, utc * 8 + 16);
+        fx[0] = a.x, fy[0] = a.y, fx[1] = a.z, fy[1] = a.w;
+        fx[2] = b.x, fy[2] = b.y, fx[3] = b.z, fy[3] = b.w;
+    }
+    const uint4 me4 = ld32<uint4>(old, utc * 4);
+    const unsigned me[4] = {me4.x, me4.y, me4.z, me4.w};
+    float rm[4] = {1.f, 1.f, 1.f, 1.f};
+    if (RESET == 2) {
+        const float4 a = ld32<float4>(reset_mask, utc * 4);
+        rm[0] = a.x, rm[1] = a.y, rm[2] = a.z, rm[3] = a.w;
+    }
+    // --- phase 2: the source pixels of the move
+    const int i = (int)fast_div(utc, lp.div), j0 = tc - i * W;
+    const float ylo = (float)(-i), yhi = (float)(H - 1 - i);
+    int sidx[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        const int j = j0 + p;
+        float2 g;
+        if (CLIP == 2) {
+            const int src = wv[p] >= 0 ? wv[p] : tc + p;
+            const int si = (int)fast_div((uint32_t)src, lp.div);
+            g = make_float2((float)(src - si * W - j), (float)(si - i)); // source.py:359-360
+        } else {
+            g = make_float2(fx[p], fy[p]);
+        }
+        if (CLIP != 0) {
+            g.x = clip_nan_zero(g.x, (float)(-j), (float)(W - 1 - j));
+            g.y = clip_nan_zero(g.y, ylo, yhi);
+            sidx[p] = tc + p + (int)rintf(g.y) * W + (int)rintf(g.x); // inside the frame: see above
+        } else {
+            const long long off = flow_offset(g, W);
+            const long long s = tc + p + off;
+            const bool inside = s >= 0 && s < N;
+            if (off != 0 && !inside && live)
+                atomicOr(err, 1);
+            sidx[p] = inside ? (int)s : tc + p;
+        }
+    }
+    // --- phase 3: what the sources address
+    unsigned so[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++)
+        so[p] = ld32<unsigned>(old, (uint32_t)sidx[p] * 4);
+    // --- phase 4: the new states (move, then the random reset of reference.py:58-67), the gather addresses
+    // (Deciding the reset from the draw's top 16 bits against a 16-bit table kept with the layer, with this comparison
+    // on a tie only, was measured and left out: inside the run-to-run spread of the step.  profiles/NOTES.md,
+    // tools/variants/remap_lean_t16_table.patch.txt.)
+    bool reset[4] = {false, false, false, false};
+    if (RESET != 0) {
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            const float thr = lp.factor * rm[p]; // factor * 1.f == factor where no mask is set
+            reset[p] = philox_uniform(utc + p, lp.frame, lp.seed) < (double)thr;
+        }
+    }
+    unsigned d[4];
+    uint32_t gidx[4];
+    bool sel[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        d[p] = TCM ? so[p] : (Q::alpha(so[p]) != 0 ? so[p] : me[p]);
+        if (RESET != 0)
+            d[p] = reset[p] ? Q::reset_to(d[p], i, j0 + p) : d[p];
+        sel[p] = Q::selected(d[p]);
+        const int gi = min(Q::row(d[p]), H - 1), gj = min(Q::col(d[p]), W - 1); // (row and column of the word are >= 0)
+        gidx[p] = sel[p] ? (uint32_t)(gi * W + gj) : 0u;
+    }
+    if (live)
+        st32(neu, (uint32_t)t * 4, make_uint4(d[0], d[1], d[2], d[3]));
+    // --- phase 5: gather of source 0 (reference.py:94-105); pixels not selected keep their previous colour
+    const bool store_rgba = !(lp.rgba_dead && *lp.rgba_dead);
+    uint32_t px[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        if (C == 4) {
+            px[p] = ld32<uint32_t>(pixmap, gidx[p] * 4);
+        } else {
+            // the pixel's three bytes as one 4-byte load that never reaches past the pixmap's last byte, 3N - 1: the
+            // last pixel's load starts a byte early and is shifted back
+            const uint32_t b = gidx[p] * 3, a = min(b, (uint32_t)N * 3 - 4);
+            px[p] = ((ld32_unaligned(pixmap, a) >> (8 * (b - a))) & 0xffffffu) | (1u << 24);
+        }
+    }
+    // (wave-uniform: the previous colours are 4 bytes per pixel that a frame whose pixels are all selected never needs)
+    if (__any(!(sel[0] && sel[1] && sel[2] && sel[3]))) {
+        const uint4 prev = ld32<uint4>(rgba, utc * 4);
+        const uint32_t pv[4] = {prev.x, prev.y, prev.z, prev.w};
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+            px[p] = sel[p] ? px[p] : (C == 3 ? pv[p] & 0xffffffu : pv[p]);
+    }
+    // --- Layer.render without an alpha mask (layer.py:32-34), Compositor.render over the background (compositor.py:35-39)
+    uint32_t rgb[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++)
+        rgb[p] = (px[p] >> 24) != 0 ? px[p] & 0xffffffu : lp.bg;
+    if (live) {
+        if (store_rgba)
+            st32(rgba, (uint32_t)t * 4, make_uint4(px[0], px[1], px[2], px[3]));
+        rgb12 v;
+        v.a = rgb[0] | (rgb[1] << 24);
+        v.b = (rgb[1] >> 8) | (rgb[2] << 16);
+        v.c = (rgb[2] >> 16) | (rgb[3] << 8);
+        st32(image, (uint32_t)t * 3, v);
+    }
+}
+
 __global__ void k_remap_clip_flow(float2 *flow, int W, int H)
 {
     int t = blockIdx.x * BLOCK + threadIdx.x;
@@ -735,6 +918,43 @@ static int state_packed(tf_remap *L, int kind)
     return TF_OK;
 }
 
+// f(std::integral_constant<int, v>) for the one v of Vs that `value` equals
+template <int... Vs, typename F>
+static int with_constant(int value, F &&f)
+{
+    int rc = set_error(TF_ERR_ARG, "remap step: no kernel for the value %d", value);
+    (void)((value == Vs ? (rc = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+    return rc;
+}
+
+// The lean step's launch (k_remap_step_lean's note; the caller has checked that the layer and the call qualify).
+static int step_lean(tf_remap *L, tf_comp *comp, const void *flow_dev, int clip_flow, uint64_t seed, const void *pixmap_dev,
+                     int channels, const int *rgba_dead, const packed32 *old, packed32 *neu)
+{
+    const bool random = L->cfg.reset_mode == 1;
+    LeanParams lp;
+    lp.div = fast_div_setup((uint32_t)L->W);
+    lp.factor = (float)L->cfg.reset_random_factor;
+    lp.seed = seed;
+    lp.frame = L->frame;
+    lp.bg = (unsigned)comp->bg.x | ((unsigned)comp->bg.y << 8) | ((unsigned)comp->bg.z << 16);
+    lp.rgba_dead = rgba_dead;
+    const dim3 grid(cdiv((size_t)L->N, (size_t)4 * BLOCK)), block(BLOCK);
+    return with_constant<3, 4>(channels, [&](auto c) {
+        return with_constant<0, 1, 2>(clip_flow, [&](auto clip) {
+            return with_constant<0, 1, 2>(random ? (L->reset_mask.p ? 2 : 1) : 0, [&](auto reset) {
+                return with_constant<0, 1>(L->fl.transparent_can_move ? 1 : 0, [&](auto tcm) {
+                    return launch(c() == 4 ? "remap_step_lean_rgba" : "remap_step_lean_rgb",
+                                  k_remap_step_lean<c(), clip(), reset(), tcm() != 0>, grid, block, 0, flow_dev,
+                                  reinterpret_cast<const unsigned *>(old), reinterpret_cast<unsigned *>(neu),
+                                  (const float *)L->reset_mask.as<float>(), L->rgba.as<unsigned>(), (const uint8_t *)pixmap_dev,
+                                  comp->image.as<uint8_t>(), L->N, L->H, L->W, lp, L->err.as<int>());
+                });
+            });
+        });
+    });
+}
+
 static bool step_fusable(const tf_remap *L) { return !L->fl.leave_empty && (L->cfg.reset_mode == 0 || L->cfg.reset_mode == 1); }
 
 static int step_dev_impl(tf_remap *L, tf_comp *comp, const void *flow_dev, int clip_flow, const void *uniform_dev, uint64_t seed,
@@ -810,7 +1030,20 @@ static int step_dev_impl(tf_remap *L, tf_comp *comp, const void *flow_dev, int c
     };
     if (const int kind = state_can_pack(L)) {
         TF_TRY(state_packed(L, kind));
-        if (kind == 2)
+        // The lean kernel (option remap_lean): the quad kernel's conditions, the state as one word, and a layer
+        // configuration under which the step is straight-line code -- no source, destination or alpha mask, no
+        // reset_source (so no introduction mask is read), no supplied uniform field, to_empty and to_filled on (the move
+        // then copies the source's state wherever one is gathered: k_remap_step_lean's note; transparent_can_move is a
+        // template flag).  Moveref and one source are required of every call above.  Its indices are 32 bits wide: the
+        // one-word state means H, W <= 8192, so N <= 2^26, and the largest byte offset it forms is the flow's 8 N <=
+        // 2^29 (pixmap 4 N, state, rgba and reset mask 4 N, RGB frame 3 N).
+        const bool lean = kind == 2 && option(OPT_REMAP_LEAN) == 1 && quad && aligned(L->pdata[0].p, 16) &&
+                          aligned(L->pdata[1].p, 16) && !L->mask_src.p && !L->mask_dst.p && !L->mask_alpha.p &&
+                          !L->cfg.reset_source && !uniform_dev && L->fl.to_empty && L->fl.to_filled && L->N <= (1 << 26);
+        if (lean)
+            TF_TRY(step_lean(L, comp, flow_dev, clip_flow, seed, pixmap_dev, channels, rgba_dead,
+                             (const packed32 *)L->pdata[L->pcur].as<packed32>(), L->pdata[L->pcur ^ 1].as<packed32>()));
+        else if (kind == 2)
             TF_TRY(run((const packed32 *)L->pdata[L->pcur].as<packed32>(), L->pdata[L->pcur ^ 1].as<packed32>()));
         else
             TF_TRY(run((const short4s *)L->pdata[L->pcur].as<short4s>(), L->pdata[L->pcur ^ 1].as<short4s>()));
