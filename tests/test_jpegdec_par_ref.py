@@ -12,6 +12,7 @@ import pytest
 from tests.helpers import build_host_check
 from tests import jpegdec_par_ref as PR
 from tests import jpegdec_ref as JR
+from tests import jpegdec_sweep as SW
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -22,6 +23,9 @@ MALFORMED = np.load(os.path.join(GOLDEN, "jpegdec_par_malformed.npz"))
 VALID_NAMES = [str(n) for n in VALID["names"]]
 MALFORMED_NAMES = [str(n) for n in MALFORMED["names"]]
 HOSTILE_NAMES = [str(n) for n in MALFORMED["hostile_names"]]
+# the hand-built files of tests/jpegdec_sweep.py without DRI that the header walker takes: more of the accepted kind
+SWEEP = {name: built.data for name, built in SW.all_cases() if JR.probe(built.data).get("restart_mcus") == 0}
+SWEEP_NAMES = list(SWEEP)
 
 _TRUTH = {}
 
@@ -29,7 +33,7 @@ _TRUTH = {}
 def _truth(name):
     """The serial decoder's word on a file, computed once: (verdict, dequantised coefficients or None)."""
     if name not in _TRUTH:
-        data = (VALID if name in VALID_NAMES else MALFORMED)[name + ".file"].tobytes()
+        data = SWEEP[name] if name in SWEEP else (VALID if name in VALID_NAMES else MALFORMED)[name + ".file"].tobytes()
         try:
             _, coefs = JR.decode_coefficients(data)
             _TRUTH[name] = (data, "ok", coefs)
@@ -94,12 +98,13 @@ def _build_host_check(tmp_path):
 
 def test_host_check_program(tmp_path):
     """The shared lane function on the CPU, lane after lane, the scan, the entries and the coefficients heap blocks of
-    the size the decoder is entitled to, over the valid, the malformed and the hostile files at every subsequence
-    size: no sanitizer report; every verdict and coefficient CRC-32 is the serial decoder's, every round count the
+    the size the decoder is entitled to, over the valid, the malformed and the hostile files and the hand-built ones of
+    tests/jpegdec_sweep.py without DRI, at every subsequence size: no sanitizer report; every verdict and coefficient CRC-32 is the serial decoder's, every round count the
     restatement's."""
     program, sanitized = _build_host_check(tmp_path)
-    names = VALID_NAMES + MALFORMED_NAMES + HOSTILE_NAMES
-    files = {n: (VALID if n in VALID_NAMES else MALFORMED)[n + ".file"].tobytes() for n in names}
+    names = VALID_NAMES + MALFORMED_NAMES + HOSTILE_NAMES + SWEEP_NAMES
+    assert len(SWEEP_NAMES) >= 30 and len(names) >= 32 + 30
+    files = {n: _truth(n)[0] if n in SWEEP else (VALID if n in VALID_NAMES else MALFORMED)[n + ".file"].tobytes() for n in names}
     corpus = tmp_path / "corpus.txt"
     corpus.write_text("\n".join(f"{name} {data.hex() or '-'}" for name, data in files.items()) + "\n")
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
@@ -112,7 +117,7 @@ def test_host_check_program(tmp_path):
             name, verdict, crc, rounds = line.split()
             got[name] = (int(verdict), int(crc), int(rounds))
         assert sorted(got) == sorted(names)
-        for name in VALID_NAMES + MALFORMED_NAMES:
+        for name in VALID_NAMES + MALFORMED_NAMES + SWEEP_NAMES:
             _, verdict, coefs = _truth(name)
             want = (JR.R[verdict], JR.coefficients_crc(coefs) if coefs is not None else 0)
             assert got[name][:2] == want, (name, sub, got[name], want)

@@ -179,13 +179,15 @@ def _build_host_check(tmp_path):
 
 def test_host_check_program(tmp_path):
     """The shared core of jpegdec_common.h on the CPU, every buffer a heap block of the size the decoder is entitled
-    to, over the valid and the malformed fixtures and the hostile files: no sanitizer report, and every verdict and
-    coefficient CRC-32 the restatement's.  The hostile files are taken (their coefficients are as large as the rules
+    to, over the valid and the malformed fixtures, the hostile files and the hand-built files of tests/jpegdec_sweep.py:
+    no sanitizer report, and every verdict and coefficient CRC-32 the restatement's.  The hostile files are taken (their coefficients are as large as the rules
     allow: the IDCT's arithmetic must stay defined)."""
     from tests import jpegdec_cases as JC
     valid, malformed = _golden_cases()
+    from tests import jpegdec_sweep as SW
     hostile = JC.hostile_cases()
-    cases = valid + malformed + hostile
+    sweep = [(name, built.data) for name, built in SW.all_cases()]
+    cases = valid + malformed + hostile + sweep
     program, sanitized = _build_host_check(tmp_path)
     corpus = tmp_path / "corpus.txt"
     corpus.write_text("\n".join(f"{name} {data.hex() or '-'}" for name, data in cases) + "\n")
@@ -204,10 +206,11 @@ def test_host_check_program(tmp_path):
             want[name] = (0, JR.coefficients_crc(coefs))
         except JR.Rejected as e:
             want[name] = (JR.R[e.reason], 0)
-    assert len(got) == len(want) >= 110
+    assert len(sweep) >= 38 and len(got) == len(want) >= 110 + 38
     wrong = {k: (got.get(k), v) for k, v in want.items() if got.get(k) != v}
     assert not wrong, sorted(wrong.items())[:10]
     assert all(want[name][0] == 0 for name, _ in valid + hostile) and all(want[name][0] != 0 for name, _ in malformed)
+    assert [name for name, _ in sweep if want[name][0] != 0] == ["f_dht_cut_short"]
     print("sanitized" if sanitized else "not sanitized: the sanitizer runtime does not link here")
 
 
