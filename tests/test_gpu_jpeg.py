@@ -191,6 +191,35 @@ def test_a_file_larger_than_the_encoders_buffer_is_packed_again_not_encoded_agai
         enc.close()
 
 
+@pytest.mark.parametrize("optimize, launches", [
+    (False, {"jpeg_encode": 1, "jpeg_scan": 1, "jpeg_pack": 1}),
+    (True, {"jpeg_gather": 1, "jpeg_tables": 1, "jpeg_emit": 1, "jpeg_scan": 1, "jpeg_pack": 1}),
+], ids=["annex_k", "own_tables"])
+def test_an_encode_and_a_copy_last_launch_what_they_always_did(optimize, launches):
+    """Every label and count of one encode into a buffer that is large enough, and of one tf_jpeg_copy_last: a single
+    pack.  17 x 33 at the default restart length."""
+    from transflow_amd import _lib
+    from transflow_amd.jpeg import JpegEncoder
+    image = jpeg_ref.stored_image(17, 33, seed=3)
+    enc = JpegEncoder(17, 33, optimize=optimize)
+    try:
+        out, again, n = np.zeros(1 << 16, np.uint8), np.zeros(1 << 16, np.uint8), C.c_size_t()
+        _lib.profile(True, "jpeg_")
+        try:
+            size = enc.encode_into(image, out)
+            encode = {label: count for label, (count, _) in _lib.profile_report().items()}
+            _lib.profile(True, "jpeg_")                                   # (resets the counts)
+            _lib.check(enc._lib.tf_jpeg_copy_last(enc._h, C.c_void_p(again.ctypes.data), again.nbytes, C.byref(n)))
+            copy = {label: count for label, (count, _) in _lib.profile_report().items()}
+        finally:
+            _lib.profile(False)
+        assert encode == launches
+        assert copy == {"jpeg_pack": 1}
+        assert n.value == size and again[:size].tobytes() == out[:size].tobytes()
+    finally:
+        enc.close()
+
+
 def _intervals(scan: bytes):
     """The scan (EOI stripped) split at its RST markers: (the intervals' bytes, the markers' low bytes).  An 0xFF of the
     entropy-coded data has an 0x00 behind it, so FF D0 .. FF D7 is a marker wherever it stands."""

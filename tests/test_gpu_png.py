@@ -159,6 +159,42 @@ def test_a_file_larger_than_the_encoders_buffer_is_packed_again_not_encoded_agai
         enc.close()
 
 
+@pytest.mark.parametrize("code, launches", [
+    ("fixed", {"png_filter": 1, "png_deflate": 1, "png_scan": 1, "png_pack": 1}),
+    ("frame", {"png_filter": 1, "png_count": 1, "png_total": 1, "png_table": 1, "png_deflate": 1, "png_scan": 1, "png_pack": 1}),
+])
+def test_an_encode_and_a_copy_last_launch_what_they_always_did(code, launches):
+    """Every label and count of one encode into a buffer that is large enough, and of one tf_png_copy_last: a single
+    pack.  Then tf_png_set_index: the head of that file is gone, and there is nothing to copy again."""
+    from transflow_amd import _lib
+    from transflow_amd.png import PngEncoder
+    image = np.random.default_rng(7).integers(0, 256, (16, 16, 3), dtype=np.uint8)
+    enc = PngEncoder(16, 16, 5, code=code)
+    try:
+        out, again, n = np.zeros(1 << 12, np.uint8), np.full(1 << 12, 0xA5, np.uint8), C.c_size_t()
+        _lib.profile(True, "png_")
+        try:
+            size = enc.encode_into(image, out)
+            encode = {label: count for label, (count, _) in _lib.profile_report().items()}
+            _lib.profile(True, "png_")                                    # (resets the counts)
+            _lib.check(enc._lib.tf_png_copy_last(enc._h, C.c_void_p(again.ctypes.data), again.nbytes, C.byref(n)))
+            copy = {label: count for label, (count, _) in _lib.profile_report().items()}
+        finally:
+            _lib.profile(False)
+        assert encode == launches
+        assert copy == {"png_pack": 1}
+        assert n.value == size and again[:size].tobytes() == out[:size].tobytes()
+        np.testing.assert_array_equal(_decode(out[:size].tobytes()), image)
+        again[:] = 0xA5
+        _lib.check(enc._lib.tf_png_set_index(enc._h, 1))
+        rc = enc._lib.tf_png_copy_last(enc._h, C.c_void_p(again.ctypes.data), again.nbytes, C.byref(n))
+        assert rc == _lib.TF_ERR_STATE and n.value == 0 and (again == 0xA5).all()
+        indexed = enc.encode_into(image, again)                           # the next encode has the new head
+        assert indexed > size and b"tfBX" in again[:indexed].tobytes()
+    finally:
+        enc.close()
+
+
 def test_abi_reports_the_needed_size():
     """tf_png_encode_dev itself: TF_ERR_ARG and *n_bytes for a short buffer, device pointer in."""
     from transflow_amd import _lib

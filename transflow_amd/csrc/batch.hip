@@ -106,6 +106,8 @@ struct tf_batch {
     bool gather_pending = false;
     ~tf_batch()
     {
+        if (comm && g_rccl.CommDestroy)
+            (void)g_rccl.CommDestroy(comm);
         if (gather_stream)
             (void)hipStreamDestroy(gather_stream);
     }
@@ -128,23 +130,19 @@ TF_API int tf_batch_init(tf_batch **out, int rank, int world, const uint8_t *id)
     TF_REQUIRE(world >= 1 && rank >= 0 && rank < world, "tf_batch_init: rank %d of %d", rank, world);
     TF_TRY(ensure_init()); // the communicator binds to the device tf_init chose
     TF_TRY(rccl_load());
-    tf_batch *b = new tf_batch;
+    auto b = make_handle<tf_batch>(); // deleted, not tf_batch_destroy: no caller has had the handle, so no stream holds work of it
+    TF_REQUIRE(b, "tf_batch_init: out of memory");
     b->rank = rank;
     b->world = world;
     ncclUniqueId u;
     memcpy(u.internal, id, TF_BATCH_ID_BYTES);
     ncclResult_t r = g_rccl.CommInitRank(&b->comm, world, u, rank);
     if (r != ncclSuccess) {
-        delete b;
+        b->comm = nullptr; // no communicator to destroy
         return set_error(TF_ERR_HIP, "ncclCommInitRank(rank %d of %d) failed: %s", rank, world, g_rccl.GetErrorString(r));
     }
-    int rc = b->scratch.alloc(64 * sizeof(double));
-    if (rc != TF_OK) {
-        (void)g_rccl.CommDestroy(b->comm);
-        delete b;
-        return rc;
-    }
-    *out = b;
+    TF_TRY(b->scratch.alloc(64 * sizeof(double)));
+    *out = b.release();
     return TF_OK;
 }
 
@@ -155,9 +153,7 @@ TF_API void tf_batch_destroy(tf_batch *b)
     (void)hipStreamSynchronize(main_stream());
     if (b->gather_stream)
         (void)hipStreamSynchronize(b->gather_stream);
-    if (b->comm && g_rccl.CommDestroy)
-        (void)g_rccl.CommDestroy(b->comm);
-    delete b;
+    delete b; // the communicator first, then the gather stream
 }
 
 TF_API int tf_batch_info(tf_batch *b, int *rank, int *world, int *rccl_version)

@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -69,6 +71,12 @@ struct StreamScope {
             return tf::set_error(TF_ERR_ARG, __VA_ARGS__); \
     } while (0)
 
+// The handle a create function builds: null when memory is out, destroyed by every return before `*out = h.release()`.
+// Where a handle's tf_*_destroy does more than delete, that function is the deleter.
+template <typename T> using Handle = std::unique_ptr<T, void (*)(T *)>;
+template <typename T> inline std::unique_ptr<T> make_handle() { return std::unique_ptr<T>(new (std::nothrow) T); }
+template <typename T> inline Handle<T> make_handle(void (*destroy)(T *)) { return Handle<T>(new (std::nothrow) T, destroy); }
+
 // Per-kernel profiler: brackets a launch with events when enabled.  Any thread may launch (a flow source prefetching
 // in a worker thread beside the compositor's thread): a scope owns its two events until it ends and the shared record
 // lists are only touched under the profiler's lock.
@@ -106,6 +114,7 @@ struct DevBuf {
     DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { release(); }
     int alloc(size_t n);
+    int upload(const void *host, size_t n); // alloc(n) where the buffer is smaller, then the host array queued on stream()
     void borrow(void *ptr, size_t n);
     void release();
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }

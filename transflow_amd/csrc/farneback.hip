@@ -219,7 +219,8 @@ static int fb_create(tf_fb **out, int width, int height, const tf_fb_params *par
     TF_TRY(fb_validate_params(params, width, height));
     TF_REQUIRE(frame_slots >= 2 && max_pairs >= 1, "tf_fb_create: need >= 2 frame slots and >= 1 pair");
     TF_TRY(ensure_init());
-    std::unique_ptr<tf_fb> fb(new tf_fb); // released on every early return below
+    auto fb = make_handle<tf_fb>();
+    TF_REQUIRE(fb, "tf_fb_create: out of memory");
     fb->W = width;
     fb->H = height;
     fb->prm = *params;
@@ -285,14 +286,15 @@ static int fb_create(tf_fb **out, int width, int height, const tf_fb_params *par
     fb->nsets = (fb_overlap_enabled() && fb->K > 0) ? 2 : 1; // a single scale: every launch fills the chip anyway
     if (share)
         fb->frames.borrow(share->frames.p, N0 * frame_slots);
-    int rc;
-    if ((!share && (rc = fb->frames.alloc(N0 * frame_slots))) || (rc = fb->img.alloc(P * 2 * N0 * 4)) ||
-        (rc = fb->R.alloc(P * 10 * N0 * 4)) ||
-        (rc = fb->lflow[0].alloc(P * N0 * 8)) || (rc = fb->lflow[1].alloc(P * N0 * 8)) ||
-        (rc = fb->lflow[2].alloc(P * N0 * 8)) ||
-        (fb->nsets > 1 && ((rc = fb->lflow[3].alloc(P * N0 * 8)) || (rc = fb->lflow[4].alloc(P * N0 * 8)))) ||
-        (rc = fb->pairs.alloc(3 * P * 8)) || (rc = fb->winner.alloc(N0 * 4)) || (rc = fb->scratch.alloc(N0 * 20)))
-        return rc;
+    else
+        TF_TRY(fb->frames.alloc(N0 * frame_slots));
+    TF_TRY(fb->img.alloc(P * 2 * N0 * 4));
+    TF_TRY(fb->R.alloc(P * 10 * N0 * 4));
+    for (int i = 0; i < (fb->nsets > 1 ? 5 : 3); i++)
+        TF_TRY(fb->lflow[i].alloc(P * N0 * 8));
+    TF_TRY(fb->pairs.alloc(3 * P * 8));
+    TF_TRY(fb->winner.alloc(N0 * 4));
+    TF_TRY(fb->scratch.alloc(N0 * 20));
     for (int k = 1; k <= fb->K; k++) {
         Level &L = *fb->lv[k];
         const size_t nk = (size_t)L.W * L.H;

@@ -224,37 +224,23 @@ TF_API int tf_flowunzip_create(tf_flowunzip **out, size_t max_stream_bytes, size
                max_stream_bytes);
     TF_REQUIRE(max_bands >= 1 && max_bands <= ((size_t)1 << 25), "tf_flowunzip_create: %zu bands (1 to 2^25)", max_bands);
     TF_TRY(ensure_init());
-    tf_flowunzip *h = new (std::nothrow) tf_flowunzip;
+    auto h = make_handle<tf_flowunzip>();
     TF_REQUIRE(h, "tf_flowunzip_create: out of memory");
     h->max_stream = max_stream_bytes, h->max_bands = max_bands;
     Crc32Consts consts;
     make_crc32_consts(consts);
-    int rc = h->consts.alloc(sizeof(Crc32Consts));
-    if (rc == TF_OK)
-        rc = h->stream.alloc(max_stream_bytes);
-    if (rc == TF_OK)
-        rc = h->offsets.alloc((max_bands + 1) * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = h->status.alloc(max_bands * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = h->band_crc.alloc(max_bands * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = h->head.alloc(MAX_SPLIT);
-    if (rc == TF_OK)
-        rc = h->info.alloc(4 * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = h->offsets_host.alloc((max_bands + 1) * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = h->info_host.alloc(4 * sizeof(uint32_t));
-    if (rc == TF_OK && hipMemcpyAsync(h->consts.p, &consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: table upload failed");
-    if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_flowunzip_create: hipStreamSynchronize failed");
-    if (rc != TF_OK) {
-        tf_flowunzip_destroy(h);
-        return rc;
-    }
-    *out = h;
+    TF_TRY(h->consts.alloc(sizeof(Crc32Consts)));
+    TF_TRY(h->stream.alloc(max_stream_bytes));
+    TF_TRY(h->offsets.alloc((max_bands + 1) * sizeof(uint32_t)));
+    TF_TRY(h->status.alloc(max_bands * sizeof(uint32_t)));
+    TF_TRY(h->band_crc.alloc(max_bands * sizeof(uint32_t)));
+    TF_TRY(h->head.alloc(MAX_SPLIT));
+    TF_TRY(h->info.alloc(4 * sizeof(uint32_t)));
+    TF_TRY(h->offsets_host.alloc((max_bands + 1) * sizeof(uint32_t)));
+    TF_TRY(h->info_host.alloc(4 * sizeof(uint32_t)));
+    TF_HIP(hipMemcpyAsync(h->consts.p, &consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipStreamSynchronize(stream())); // `consts` is on this stack
+    *out = h.release();
     return TF_OK;
 }
 

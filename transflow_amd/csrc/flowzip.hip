@@ -490,7 +490,7 @@ TF_API int tf_flowzip_create(tf_flowzip **out, size_t max_stream_bytes, int band
     if (MAX_HEADER_BITS + WAVE * LANE_WORST_BITS + 3 + 7 + 32 > 32 * (BIT_WORDS - 3))
         return set_error(TF_ERR_STATE, "tf_flowzip_create: a trip's tokens would not fit the bit buffer");
     TF_TRY(ensure_init());
-    tf_flowzip *enc = new (std::nothrow) tf_flowzip;
+    auto enc = make_handle<tf_flowzip>();
     TF_REQUIRE(enc, "tf_flowzip_create: out of memory");
     enc->max_stream = (uint32_t)max_stream_bytes;
     enc->band_bytes = band_bytes ? (uint32_t)band_bytes : (uint32_t)DEFAULT_BAND_BYTES;
@@ -498,38 +498,21 @@ TF_API int tf_flowzip_create(tf_flowzip **out, size_t max_stream_bytes, int band
     const size_t n = (size_t)enc->max_bands;
     Crc32Consts consts;
     make_crc32_consts(consts);
-    int rc = enc->consts.alloc(sizeof(Crc32Consts));
-    if (rc == TF_OK)
-        rc = enc->tables.alloc(sizeof(Tables));
-    if (rc == TF_OK)
-        rc = enc->prefix.alloc(MAX_PREFIX_BYTES);
-    if (rc == TF_OK)
-        rc = enc->counts.alloc(n * N_SYMBOLS * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->totals.alloc(N_SYMBOLS * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->band_crc.alloc(n * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->sizes.alloc(n * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->offsets.alloc(n * sizeof(unsigned long long));
-    if (rc == TF_OK)
-        rc = enc->info.alloc(4 * sizeof(unsigned long long));
-    if (rc == TF_OK) // the bound: every band stored
-        rc = enc->packed.alloc((size_t)stream_bound(max_stream_bytes, enc->band_bytes));
-    if (rc == TF_OK)
-        rc = enc->info_host.alloc(4 * sizeof(unsigned long long));
-    if (rc == TF_OK)
-        rc = enc->tables_host.alloc(sizeof(Tables));
-    if (rc == TF_OK && hipMemcpyAsync(enc->consts.p, &consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_flowzip_create: table upload failed");
-    if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_flowzip_create: hipStreamSynchronize failed");
-    if (rc != TF_OK) {
-        tf_flowzip_destroy(enc);
-        return rc;
-    }
-    *out = enc;
+    TF_TRY(enc->consts.alloc(sizeof(Crc32Consts)));
+    TF_TRY(enc->tables.alloc(sizeof(Tables)));
+    TF_TRY(enc->prefix.alloc(MAX_PREFIX_BYTES));
+    TF_TRY(enc->counts.alloc(n * N_SYMBOLS * sizeof(uint32_t)));
+    TF_TRY(enc->totals.alloc(N_SYMBOLS * sizeof(uint32_t)));
+    TF_TRY(enc->band_crc.alloc(n * sizeof(uint32_t)));
+    TF_TRY(enc->sizes.alloc(n * sizeof(uint32_t)));
+    TF_TRY(enc->offsets.alloc(n * sizeof(unsigned long long)));
+    TF_TRY(enc->info.alloc(4 * sizeof(unsigned long long)));
+    TF_TRY(enc->packed.alloc((size_t)stream_bound(max_stream_bytes, enc->band_bytes))); // the bound: every band stored
+    TF_TRY(enc->info_host.alloc(4 * sizeof(unsigned long long)));
+    TF_TRY(enc->tables_host.alloc(sizeof(Tables)));
+    TF_HIP(hipMemcpyAsync(enc->consts.p, &consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipStreamSynchronize(stream())); // `consts` is on this stack
+    *out = enc.release();
     return TF_OK;
 }
 
@@ -598,9 +581,9 @@ TF_API int tf_flowzip_encode(tf_flowzip *enc, const uint8_t *prefix_host, size_t
     TF_REQUIRE(data_bytes <= enc->max_stream, "tf_flowzip_encode: %zu bytes of data, the handle is for streams of %u", data_bytes,
                enc->max_stream);
     if (!enc->upload.p)
-        TF_TRY(enc->upload.alloc(enc->max_stream));
+        TF_TRY(enc->upload.alloc(enc->max_stream)); // once, for the longest stream: nothing below grows it
     if (data_bytes)
-        TF_HIP(hipMemcpyAsync(enc->upload.p, data_host, data_bytes, hipMemcpyHostToDevice, stream()));
+        TF_TRY(enc->upload.upload(data_host, data_bytes));
     return tf_flowzip_encode_dev(enc, prefix_host, prefix_len, enc->upload.p, data_bytes, distance, out, capacity, n_bytes, crc32);
 }
 

@@ -209,28 +209,18 @@ TF_API int tf_hs_create(tf_hs **out, int width, int height, int frame_slots, int
     TF_REQUIRE(frame_slots >= 2, "tf_hs_create: frame_slots %d < 2", frame_slots);
     TF_REQUIRE(max_pairs >= 1 && max_pairs <= MAX_PAIRS, "tf_hs_create: max_pairs %d not in [1, %d]", max_pairs, MAX_PAIRS);
     TF_TRY(ensure_init());
-    tf_hs *hs = new tf_hs;
+    auto hs = make_handle<tf_hs>();
+    TF_REQUIRE(hs, "tf_hs_create: out of memory");
     hs->W = width, hs->H = height, hs->slots = frame_slots, hs->max_pairs = max_pairs;
     const size_t npx = (size_t)width * height;
-    int rc = hs->frames.alloc((size_t)frame_slots * npx);
-    if (rc == TF_OK)
-        rc = hs->deriv.alloc((size_t)max_pairs * npx * sizeof(float4));
-    if (rc == TF_OK)
-        rc = hs->uv.alloc((size_t)max_pairs * 4 * hs->plane_bytes());
-    if (rc == TF_OK)
-        rc = hs->init_flow.alloc((size_t)max_pairs * npx * 2 * sizeof(float));
-    if (rc == TF_OK)
-        rc = hs->flow.alloc((size_t)max_pairs * npx * 2 * sizeof(float));
-    if (rc == TF_OK)
-        rc = hs->partials.alloc((size_t)max_pairs * partial_doubles(width, height) * sizeof(double));
-    if (rc == TF_OK)
-        rc = hs->blocks.alloc((size_t)max_pairs * n_bound_blocks(width, height) * 4 * sizeof(double));
-    if (rc == TF_OK)
-        rc = hs->norm.init(width, height);
-    if (rc != TF_OK) {
-        delete hs;
-        return rc;
-    }
+    TF_TRY(hs->frames.alloc((size_t)frame_slots * npx));
+    TF_TRY(hs->deriv.alloc((size_t)max_pairs * npx * sizeof(float4)));
+    TF_TRY(hs->uv.alloc((size_t)max_pairs * 4 * hs->plane_bytes()));
+    TF_TRY(hs->init_flow.alloc((size_t)max_pairs * npx * 2 * sizeof(float)));
+    TF_TRY(hs->flow.alloc((size_t)max_pairs * npx * 2 * sizeof(float)));
+    TF_TRY(hs->partials.alloc((size_t)max_pairs * partial_doubles(width, height) * sizeof(double)));
+    TF_TRY(hs->blocks.alloc((size_t)max_pairs * n_bound_blocks(width, height) * 4 * sizeof(double)));
+    TF_TRY(hs->norm.init(width, height));
     hs->host_blocks.resize((size_t)max_pairs * n_bound_blocks(width, height) * 4);
     hs->has_init.assign(max_pairs, 0);
     hs->state.assign(max_pairs, tf_hs::DONE);
@@ -238,7 +228,7 @@ TF_API int tf_hs_create(tf_hs **out, int width, int height, int frame_slots, int
     hs->cur.assign(max_pairs, 0);
     hs->f64.assign(max_pairs, 1);
     hs->stats.assign(max_pairs, {0, 0, 0, 0, 0});
-    *out = hs;
+    *out = hs.release();
     return TF_OK;
 }
 

@@ -566,11 +566,9 @@ static constexpr int DEFAULT_RESTART_MCUS = 8;
 struct tf_jpeg {
     int H = 0, W = 0, quality = 0, restart_mcus = 0;
     int mcus_x = 0, n_mcus = 0, n_intervals = 0;
-    uint32_t slot = 0;
     std::vector<uint8_t> header;
-    DevBuf tables, staging, lengths, offsets, info, packed, upload;
-    PinnedBuf info_host; // page-locked unsigned long long: [0] the scan's bytes, [1] the overflow flag
-    size_t last_scan = 0;                    // the scan's bytes of the last encode that ran; 0: none to copy again
+    DevBuf tables, upload;
+    SlotStream s; // a slot an interval; packed, the scan: the intervals with a marker behind each
     // mode 1, the frame's own tables (tf_jpeg_set_optimize); the buffers are allocated by the first call that needs them
     int optimize = 0;
     uint8_t q[2][64];                        // the quantisation tables, natural order: a header is made per frame
@@ -631,7 +629,7 @@ TF_API int tf_jpeg_set_optimize(tf_jpeg *enc, int mode)
                "tf_jpeg_set_optimize: %dx%d has more than %u coefficients", enc->W, enc->H, HUFF_SENTINEL);
     if (mode != enc->optimize) {
         enc->optimize = mode;
-        enc->last_scan = 0; // the file of the other mode is not this mode's to copy again
+        enc->s.last = 0; // the file of the other mode is not this mode's to copy again
         enc->own_header.clear();
     }
     return TF_OK;
@@ -649,15 +647,13 @@ TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int
     TF_REQUIRE(restart_mcus >= 0 && restart_mcus <= 65535, "tf_jpeg_create: restart interval %d (0 = default, 1 to 65535)",
                restart_mcus);
     TF_TRY(ensure_init());
-    tf_jpeg *enc = new (std::nothrow) tf_jpeg;
+    auto enc = make_handle<tf_jpeg>();
     TF_REQUIRE(enc, "tf_jpeg_create: out of memory");
     enc->H = height, enc->W = width, enc->quality = quality;
     enc->restart_mcus = restart_mcus ? restart_mcus : DEFAULT_RESTART_MCUS;
     enc->mcus_x = (width + 15) / 16;
     enc->n_mcus = enc->mcus_x * ((height + 15) / 16);
     enc->n_intervals = (enc->n_mcus + enc->restart_mcus - 1) / enc->restart_mcus;
-    // (an interval longer than the image codes n_mcus MCUs: its slot need not be larger than that)
-    enc->slot = (uint32_t)slot_bytes(enc->restart_mcus < enc->n_mcus ? enc->restart_mcus : enc->n_mcus);
 
     Tables t;
     uint8_t q[2][64];
@@ -674,34 +670,15 @@ TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int
     huff_entries(AC_CHROMA_BITS, AC_CHROMA_VALS, t.ac[1], 256);
     enc->header = make_header(height, width, q, enc->restart_mcus);
 
-    int rc = TF_OK;
     for (int c = 0; c < 2; c++) // a lane's symbols: three ZRLs, a code, 10 value bits (11 with a DC code)
         if (3 * (t.ac[c][0xF0] >> 16) + 16 + 10 > (uint32_t)LANE_MAX_BITS)
-            rc = set_error(TF_ERR_STATE, "tf_jpeg_create: a lane's symbols would not fit %d bits", LANE_MAX_BITS);
-    const size_t n = (size_t)enc->n_intervals;
-    if (rc == TF_OK)
-        rc = enc->tables.alloc(sizeof(Tables));
-    if (rc == TF_OK)
-        rc = enc->staging.alloc(n * enc->slot);
-    if (rc == TF_OK)
-        rc = enc->lengths.alloc(n * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->offsets.alloc(n * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->info.alloc(2 * sizeof(unsigned long long));
-    if (rc == TF_OK) // the worst case again: every slot full, a marker behind each
-        rc = enc->packed.alloc(n * enc->slot + 2 * n);
-    if (rc == TF_OK)
-        rc = enc->info_host.alloc(2 * sizeof(unsigned long long));
-    if (rc == TF_OK && hipMemcpyAsync(enc->tables.p, &t, sizeof(Tables), hipMemcpyHostToDevice, stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_jpeg_create: table upload failed");
-    if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess) // `t` is on this stack
-        rc = set_error(TF_ERR_HIP, "tf_jpeg_create: hipStreamSynchronize failed");
-    if (rc != TF_OK) {
-        tf_jpeg_destroy(enc);
-        return rc;
-    }
-    *out = enc;
+            return set_error(TF_ERR_STATE, "tf_jpeg_create: a lane's symbols would not fit %d bits", LANE_MAX_BITS);
+    TF_TRY(enc->tables.alloc(sizeof(Tables)));
+    // (an interval longer than the image codes n_mcus MCUs: its slot need not be larger than that)
+    TF_TRY(enc->s.alloc(enc->n_intervals, (uint32_t)slot_bytes(enc->restart_mcus < enc->n_mcus ? enc->restart_mcus : enc->n_mcus), 2));
+    TF_HIP(hipMemcpyAsync(enc->tables.p, &t, sizeof(Tables), hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipStreamSynchronize(stream())); // `t` is on this stack
+    *out = enc.release();
     return TF_OK;
 }
 
@@ -719,45 +696,29 @@ TF_API int tf_jpeg_header(tf_jpeg *enc, const uint8_t **bytes, size_t *n)
 // the slots to their places in the packed stream, as far as `dev_capacity` reaches
 static int pack(tf_jpeg *enc, size_t dev_capacity)
 {
-    return launch("jpeg_pack", k_jpeg_pack, dim3(cdiv(enc->n_intervals, PACK_BLOCK / WAVE)), dim3(PACK_BLOCK), 0,
-                  enc->staging.as<uint8_t>(), enc->slot, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(), enc->n_intervals,
-                  enc->packed.as<uint8_t>(), dev_capacity);
-}
-
-// header and packed stream to the caller, if they fit; *n_bytes either way
-static int copy_out(tf_jpeg *enc, const char *who, uint8_t *out, size_t capacity, size_t *n_bytes)
-{
-    const size_t hdr = enc->file_header().size(), scan = enc->last_scan;
-    *n_bytes = hdr + scan;
-    TF_REQUIRE(hdr + scan <= capacity, "%s: the file has %zu bytes, the buffer %zu", who, hdr + scan, capacity);
-    memcpy(out, enc->file_header().data(), hdr);
-    TF_HIP(hipMemcpyAsync(out + hdr, enc->packed.p, scan, hipMemcpyDeviceToHost, stream()));
-    TF_HIP(hipStreamSynchronize(stream()));
-    return TF_OK;
+    const SlotStream &s = enc->s;
+    return launch("jpeg_pack", k_jpeg_pack, dim3(cdiv(s.n, PACK_BLOCK / WAVE)), dim3(PACK_BLOCK), 0, s.staging.as<uint8_t>(), s.slot,
+                  s.lengths.as<uint32_t>(), s.offsets.as<uint32_t>(), s.n, s.packed.as<uint8_t>(), dev_capacity);
 }
 
 TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, size_t capacity, size_t *n_bytes)
 {
     TF_REQUIRE(enc && rgb_dev && n_bytes && (out || capacity == 0), "tf_jpeg_encode_dev: null pointer");
     *n_bytes = 0;
-    const size_t hdr = enc->header.size();
-    // what the pack kernel may write: the caller's room behind the header, and never more than the packed buffer (the
-    // frame's own header is not known before the kernels have run: all of the packed buffer then)
-    const size_t room = capacity > hdr ? capacity - hdr : 0;
-    const size_t dev_capacity = !enc->optimize && room < enc->packed.bytes ? room : enc->packed.bytes;
+    SlotStream &s = enc->s;
+    TF_TRY(s.begin());
     if (enc->optimize) {
         TF_TRY(ensure_own(enc));
         enc->own_header.clear();
         TF_HIP(hipMemsetAsync(enc->own.p, 0, sizeof(OwnTables), stream())); // the histograms and the fault word
     }
-    TF_HIP(hipMemsetAsync(enc->info.p, 0, enc->info.bytes, stream()));
     EncodeArgs a;
     a.rgb = (const uint8_t *)rgb_dev, a.W = enc->W, a.H = enc->H;
     a.mcus_x = enc->mcus_x, a.n_mcus = enc->n_mcus, a.restart_mcus = enc->restart_mcus;
     a.lum_bx = (enc->W + 7) / 8, a.lum_by = (enc->H + 7) / 8, a.chroma_rows = (enc->H + 1) / 2;
-    a.tables = enc->tables.as<Tables>(), a.staging = enc->staging.as<uint8_t>(), a.slot_bytes = enc->slot;
-    a.lengths = enc->lengths.as<uint32_t>();
-    a.overflow = reinterpret_cast<uint32_t *>(enc->info.as<unsigned long long>() + 1);
+    a.tables = enc->tables.as<Tables>(), a.staging = s.staging.as<uint8_t>(), a.slot_bytes = s.slot;
+    a.lengths = s.lengths.as<uint32_t>();
+    a.overflow = s.overflow();
     a.counts = nullptr;
     const FastDiv div = fast_div_setup((uint32_t)enc->mcus_x);
     if (enc->optimize) { // count, make the tables, code with them
@@ -770,12 +731,11 @@ TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, s
     } else {
         TF_TRY(launch("jpeg_encode", k_jpeg_encode<EMIT>, dim3(enc->n_intervals), dim3(WAVE), 0, a, div));
     }
-    TF_TRY(launch("jpeg_scan", k_slot_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
-                  enc->n_intervals, 2u, enc->info.as<unsigned long long>())); // a marker behind each interval
-    TF_TRY(pack(enc, dev_capacity));
-    enc->last_scan = 0;
-    TF_HIP(hipMemcpyAsync(enc->info_host.p, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
-    if (enc->optimize) // comes down with `info`: the one wait below is for both
+    TF_TRY(s.scan("jpeg_scan"));
+    // (the frame's own header is not known before the kernels have run)
+    TF_TRY(pack(enc, enc->optimize ? s.pack_room() : s.pack_room(capacity, enc->header.size())));
+    TF_TRY(s.fetch());
+    if (enc->optimize) // comes down with the stream's info: the one wait below is for both
         TF_HIP(hipMemcpyAsync(enc->own_host.p, (const uint8_t *)enc->own.p + OWN_RESULT, sizeof(OwnResult), hipMemcpyDeviceToHost,
                               stream()));
     TF_HIP(hipStreamSynchronize(stream()));
@@ -785,22 +745,17 @@ TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, s
         const Dht dht[4] = {{r.bits[0], r.vals[0]}, {r.bits[1], r.vals[1]}, {r.bits[2], r.vals[2]}, {r.bits[3], r.vals[3]}};
         enc->own_header = make_header(enc->H, enc->W, enc->q, enc->restart_mcus, dht);
     }
-    if (enc->info_host.as<unsigned long long>()[1])
-        return set_error(TF_ERR_STATE, "tf_jpeg_encode_dev: an interval outgrew its staging slot of %u bytes", enc->slot);
-    enc->last_scan = (size_t)enc->info_host.as<unsigned long long>()[0];
-    return copy_out(enc, "tf_jpeg_encode_dev", out, capacity, n_bytes);
+    TF_TRY(s.finish("tf_jpeg_encode_dev", "an interval"));
+    return s.copy_out("tf_jpeg_encode_dev", enc->file_header(), {}, out, capacity, n_bytes);
 }
 
 TF_API int tf_jpeg_copy_last(tf_jpeg *enc, uint8_t *out, size_t capacity, size_t *n_bytes)
 {
     TF_REQUIRE(enc && n_bytes && (out || capacity == 0), "tf_jpeg_copy_last: null pointer");
     *n_bytes = 0;
-    if (!enc->last_scan)
-        return set_error(TF_ERR_STATE, "tf_jpeg_copy_last: nothing has been encoded");
-    const size_t hdr = enc->file_header().size();
-    const size_t room = capacity > hdr ? capacity - hdr : 0;
-    TF_TRY(pack(enc, room < enc->packed.bytes ? room : enc->packed.bytes));
-    return copy_out(enc, "tf_jpeg_copy_last", out, capacity, n_bytes);
+    TF_TRY(enc->s.have_last("tf_jpeg_copy_last"));
+    TF_TRY(pack(enc, enc->s.pack_room(capacity, enc->file_header().size())));
+    return enc->s.copy_out("tf_jpeg_copy_last", enc->file_header(), {}, out, capacity, n_bytes);
 }
 
 TF_API int tf_jpeg_last_tables(tf_jpeg *enc, uint8_t *bits, uint8_t *vals, uint32_t *counts)
@@ -833,7 +788,7 @@ TF_API int tf_jpeg_tables_from_counts(tf_jpeg *enc, const uint32_t *counts, uint
                    HUFF_SENTINEL);
     }
     TF_TRY(ensure_own(enc));
-    enc->own_header.clear(), enc->last_scan = 0; // the tables of the last encode are gone
+    enc->own_header.clear(), enc->s.last = 0; // the tables of the last encode are gone
     OwnTables *own = enc->own.as<OwnTables>();
     TF_HIP(hipMemsetAsync(enc->own.p, 0, sizeof(OwnTables), stream()));
     TF_HIP(hipMemcpyAsync(own->partial[0], counts, sizeof(own->counts), hipMemcpyHostToDevice, stream())); // the other copies are zero
@@ -853,8 +808,6 @@ TF_API int tf_jpeg_encode(tf_jpeg *enc, const uint8_t *rgb_host, uint8_t *out, s
 {
     TF_REQUIRE(enc && rgb_host && n_bytes, "tf_jpeg_encode: null pointer");
     const size_t bytes = (size_t)enc->H * enc->W * 3;
-    if (!enc->upload.p)
-        TF_TRY(enc->upload.alloc(bytes));
-    TF_HIP(hipMemcpyAsync(enc->upload.p, rgb_host, bytes, hipMemcpyHostToDevice, stream()));
+    TF_TRY(enc->upload.upload(rgb_host, bytes));
     return tf_jpeg_encode_dev(enc, enc->upload.p, out, capacity, n_bytes);
 }

@@ -668,7 +668,7 @@ TF_API int tf_jpegdec_create(tf_jpegdec **out, int max_width, int max_height, si
                max_width, max_height);
     TF_REQUIRE(max_file_bytes >= 1 && max_file_bytes <= ((size_t)1 << 30), "tf_jpegdec_create: a file of %zu bytes (1 to 2^30)", max_file_bytes);
     TF_TRY(ensure_init());
-    tf_jpegdec *dec = new (std::nothrow) tf_jpegdec;
+    auto dec = make_handle<tf_jpegdec>();
     TF_REQUIRE(dec, "tf_jpegdec_create: out of memory");
     dec->max_w = max_width, dec->max_h = max_height, dec->max_file = max_file_bytes;
     dec->max_chunks = (max_file_bytes + CHUNK - 1) / CHUNK;
@@ -681,32 +681,18 @@ TF_API int tf_jpegdec_create(tf_jpegdec **out, int max_width, int max_height, si
     dec->max_subs = (max_file_bytes + PAR_MIN_SUB - 1) / PAR_MIN_SUB;
     dec->max_groups = (dec->max_subs + 63) / 64;
     dec->max_blocks = 3 * dec->max_intervals;
-    int rc = dec->tables.alloc(sizeof(DevTables));
-    if (rc == TF_OK)
-        rc = dec->scan.alloc(max_file_bytes + 4);
-    if (rc == TF_OK)
-        rc = dec->counts.alloc(dec->max_chunks * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->offsets.alloc(dec->max_chunks * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->total.alloc(sizeof(unsigned long long));
-    if (rc == TF_OK)
-        rc = dec->markers.alloc(dec->max_intervals * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->status.alloc(2 * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->planes.alloc(3 * dec->plane_room);
-    if (rc == TF_OK)
-        rc = dec->stage.alloc(max_file_bytes);
-    if (rc == TF_OK)
-        rc = dec->tables_host.alloc(sizeof(DevTables));
-    if (rc == TF_OK)
-        rc = dec->status_host.alloc(2 * sizeof(uint32_t));
-    if (rc != TF_OK) {
-        tf_jpegdec_destroy(dec);
-        return rc;
-    }
-    *out = dec;
+    TF_TRY(dec->tables.alloc(sizeof(DevTables)));
+    TF_TRY(dec->scan.alloc(max_file_bytes + 4));
+    TF_TRY(dec->counts.alloc(dec->max_chunks * sizeof(uint32_t)));
+    TF_TRY(dec->offsets.alloc(dec->max_chunks * sizeof(uint32_t)));
+    TF_TRY(dec->total.alloc(sizeof(unsigned long long)));
+    TF_TRY(dec->markers.alloc(dec->max_intervals * sizeof(uint32_t)));
+    TF_TRY(dec->status.alloc(2 * sizeof(uint32_t)));
+    TF_TRY(dec->planes.alloc(3 * dec->plane_room));
+    TF_TRY(dec->stage.alloc(max_file_bytes));
+    TF_TRY(dec->tables_host.alloc(sizeof(DevTables)));
+    TF_TRY(dec->status_host.alloc(2 * sizeof(uint32_t)));
+    *out = dec.release();
     return TF_OK;
 }
 

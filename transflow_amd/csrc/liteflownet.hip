@@ -739,7 +739,8 @@ TF_API int tf_lfn_create(tf_lfn **out, int width, int height, int frame_slots, i
     TF_REQUIRE(frame_slots >= 2, "tf_lfn_create: frame_slots %d < 2", frame_slots);
     TF_REQUIRE(max_pairs >= 1 && max_pairs <= MAX_PAIRS, "tf_lfn_create: max_pairs %d not in [1, %d]", max_pairs, MAX_PAIRS);
     TF_TRY(ensure_init());
-    std::unique_ptr<tf_lfn> L(new tf_lfn);
+    auto L = make_handle<tf_lfn>();
+    TF_REQUIRE(L, "tf_lfn_create: out of memory");
     L->W = width, L->H = height, L->n_slots = frame_slots, L->max_pairs = max_pairs;
     L->Wp = (width + 31) / 32 * 32, L->Hp = (height + 31) / 32 * 32;
     L->net = make_net();

@@ -375,21 +375,17 @@ TF_API int tf_lk_create(tf_lk **out, int width, int height, int frame_slots, int
     TF_REQUIRE(frame_slots >= 2, "tf_lk_create: frame_slots %d < 2", frame_slots);
     TF_REQUIRE(max_pairs >= 1 && max_pairs <= MAX_PAIRS, "tf_lk_create: max_pairs %d not in [1, %d]", max_pairs, MAX_PAIRS);
     TF_TRY(ensure_init());
-    tf_lk *lk = new tf_lk;
+    auto lk = make_handle<tf_lk>();
+    TF_REQUIRE(lk, "tf_lk_create: out of memory");
     lk->W = width, lk->H = height, lk->n_slots = frame_slots, lk->max_pairs = max_pairs;
-    lk->slots.reset(new tf_lk::Slot[frame_slots]);
+    lk->slots.reset(new (std::nothrow) tf_lk::Slot[frame_slots]);
+    TF_REQUIRE(lk->slots, "tf_lk_create: out of memory");
     const size_t npx = (size_t)width * height;
-    int rc = lk->frames.alloc((size_t)frame_slots * npx);
-    if (rc == TF_OK)
-        rc = lk->flow.alloc((size_t)max_pairs * npx * sizeof(float2));
-    if (rc == TF_OK)
-        rc = lk->stats.alloc((size_t)max_pairs * MAX_LEVELS * 2 * sizeof(unsigned long long));
-    if (rc != TF_OK) {
-        delete lk;
-        return rc;
-    }
+    TF_TRY(lk->frames.alloc((size_t)frame_slots * npx));
+    TF_TRY(lk->flow.alloc((size_t)max_pairs * npx * sizeof(float2)));
+    TF_TRY(lk->stats.alloc((size_t)max_pairs * MAX_LEVELS * 2 * sizeof(unsigned long long)));
     lk->host_stats.assign((size_t)max_pairs * MAX_LEVELS * 2, 0);
-    *out = lk;
+    *out = lk.release();
     return TF_OK;
 }
 

@@ -146,19 +146,13 @@ TF_API int tf_mv_create(tf_mv **out, int width, int height)
     TF_REQUIRE(width >= 1 && height >= 1 && (long long)width * height < (1ll << 31), "tf_mv_create: bad size %dx%d", width,
                height);
     TF_TRY(ensure_init());
-    tf_mv *mv = new (std::nothrow) tf_mv;
+    auto mv = make_handle(tf_mv_destroy); // synchronises first: a failure may come after the clear was queued
     TF_REQUIRE(mv, "tf_mv_create: out of memory");
     mv->W = width, mv->H = height;
-    int rc = mv->winner.alloc((size_t)width * height * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = mv->uploaded.create();
-    if (rc == TF_OK)
-        rc = clear_map(mv);                // the one clear: mv_resolve leaves the map clean behind it
-    if (rc != TF_OK) {
-        tf_mv_destroy(mv);
-        return rc;
-    }
-    *out = mv;
+    TF_TRY(mv->winner.alloc((size_t)width * height * sizeof(uint32_t)));
+    TF_TRY(mv->uploaded.create());
+    TF_TRY(clear_map(mv.get())); // the one clear: mv_resolve leaves the map clean behind it
+    *out = mv.release();
     return TF_OK;
 }
 

@@ -669,19 +669,18 @@ using namespace tf::png;
 
 struct tf_png {
     int H = 0, W = 0, band_rows = 0, n_bands = 0;
-    uint32_t row_bytes = 0, slot = 0;
+    uint32_t row_bytes = 0;
     Tables tables;
     std::vector<uint8_t> head, tail; // what the host writes in front of the bands' chunks and behind them
-    DevBuf dev_tables, filtered, rowsums, staging, lengths, offsets, info, packed, upload;
+    DevBuf dev_tables, filtered, rowsums, upload;
+    SlotStream s; // a slot a band; packed, the bands' IDAT chunks
     // the frame's own code (tf_png_set_code): allocated by the first encode that uses it
     int code = 0;
     DevBuf counts, totals, frame_tables, frame_code;
     PinnedBuf frame_code_host; // page-locked FrameCode: the last frame's
     PinnedBuf lengths_host;    // page-locked uint32_t: the last frame's bands' bytes
     bool last_own_code = false; // the last encode that ran used the frame's own code: the two buffers above hold it
-    PinnedBuf info_host;    // page-locked unsigned long long: [0] the chunks' bytes, [1] the overflow flag
     PinnedBuf rowsums_host; // page-locked uint32_t: the rows' Adler sums
-    size_t last_chunks = 0;                  // the chunks' bytes of the last encode that ran; 0: none to copy again
 };
 
 // What the host writes in front of the bands' chunks: the signature, IHDR, with `index` the band index tfBX (version 1,
@@ -705,7 +704,7 @@ TF_API int tf_png_set_index(tf_png *enc, int on)
 {
     TF_REQUIRE(enc, "tf_png_set_index: null pointer");
     make_head(enc, on != 0);
-    enc->last_chunks = 0; // the head of the last encode is gone: nothing to copy again
+    enc->s.last = 0; // the head of the last encode is gone: nothing to copy again
     return TF_OK;
 }
 
@@ -720,9 +719,9 @@ TF_API int tf_png_set_code(tf_png *enc, int mode)
         static_assert(3 * MAX_CODE_BITS <= LANE_MAX_BITS && MATCH_BITS + MAX_CODE_BITS <= LANE_MAX_BITS, "a lane's tokens outgrow its accumulator");
         static_assert(MATCH_BITS <= 24, "a match outgrows its entry");
         const uint64_t band = (uint64_t)enc->band_rows * enc->row_bytes;
-        if (stored_bytes(band) > enc->slot)
+        if (stored_bytes(band) > enc->s.slot)
             return set_error(TF_ERR_STATE, "tf_png_set_code: a stored band of %llu bytes would not fit its slot of %u",
-                             (unsigned long long)stored_bytes(band), enc->slot);
+                             (unsigned long long)stored_bytes(band), enc->s.slot);
     }
     enc->code = mode;
     return TF_OK;
@@ -756,54 +755,27 @@ TF_API int tf_png_create(tf_png **out, int height, int width, int band_rows)
     TF_REQUIRE(rows * row_bytes <= (size_t)1 << 28, "tf_png_create: a band of %d rows has %zu bytes (at most 2^28)", rows,
                rows * row_bytes);
     TF_TRY(ensure_init());
-    tf_png *enc = new (std::nothrow) tf_png;
+    auto enc = make_handle<tf_png>();
     TF_REQUIRE(enc, "tf_png_create: out of memory");
     enc->H = height, enc->W = width, enc->band_rows = rows, enc->row_bytes = (uint32_t)row_bytes;
     enc->n_bands = (height + rows - 1) / rows;
     int byte_bits = 0, eob_bits = 0;
-    int rc = make_tables(enc->tables, &byte_bits, &eob_bits);
-    const size_t n = (size_t)enc->n_bands;
-    size_t slot = 0;
-    if (rc == TF_OK) {
-        slot = slot_bytes(rows * row_bytes, byte_bits, eob_bits);
-        if (n * (slot + 12) >= (size_t)1 << 32) // offsets are 32-bit
-            rc = set_error(TF_ERR_ARG, "tf_png_create: %dx%d in bands of %d rows could take %zu bytes (less than 2^32)", width, height,
-                           rows, n * (slot + 12));
-    }
-    if (rc == TF_OK && crc32_bytes(enc->tables.crc, (const uint8_t *)"IDAT", 4) != IDAT_CRC)
-        rc = set_error(TF_ERR_STATE, "tf_png_create: the CRC table is wrong");
-    enc->slot = (uint32_t)slot;
-    if (rc == TF_OK)
-        make_head(enc, false);
-    if (rc == TF_OK)
-        rc = enc->dev_tables.alloc(sizeof(Tables));
-    if (rc == TF_OK)
-        rc = enc->filtered.alloc((size_t)height * row_bytes);
-    if (rc == TF_OK)
-        rc = enc->rowsums.alloc((size_t)height * 2 * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->staging.alloc(n * slot);
-    if (rc == TF_OK)
-        rc = enc->lengths.alloc(n * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->offsets.alloc(n * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = enc->info.alloc(2 * sizeof(unsigned long long));
-    if (rc == TF_OK) // the worst case again: every slot full, 12 bytes of chunk around each
-        rc = enc->packed.alloc(n * (slot + 12));
-    if (rc == TF_OK)
-        rc = enc->info_host.alloc(2 * sizeof(unsigned long long));
-    if (rc == TF_OK)
-        rc = enc->rowsums_host.alloc(enc->rowsums.bytes);
-    if (rc == TF_OK && hipMemcpyAsync(enc->dev_tables.p, &enc->tables, sizeof(Tables), hipMemcpyHostToDevice, stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_png_create: table upload failed");
-    if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_png_create: hipStreamSynchronize failed");
-    if (rc != TF_OK) {
-        tf_png_destroy(enc);
-        return rc;
-    }
-    *out = enc;
+    TF_TRY(make_tables(enc->tables, &byte_bits, &eob_bits));
+    const size_t n = (size_t)enc->n_bands, slot = slot_bytes(rows * row_bytes, byte_bits, eob_bits);
+    // offsets are 32-bit
+    TF_REQUIRE(n * (slot + 12) < (size_t)1 << 32, "tf_png_create: %dx%d in bands of %d rows could take %zu bytes (less than 2^32)", width,
+               height, rows, n * (slot + 12));
+    if (crc32_bytes(enc->tables.crc, (const uint8_t *)"IDAT", 4) != IDAT_CRC)
+        return set_error(TF_ERR_STATE, "tf_png_create: the CRC table is wrong");
+    make_head(enc.get(), false);
+    TF_TRY(enc->dev_tables.alloc(sizeof(Tables)));
+    TF_TRY(enc->filtered.alloc((size_t)height * row_bytes));
+    TF_TRY(enc->rowsums.alloc((size_t)height * 2 * sizeof(uint32_t)));
+    TF_TRY(enc->s.alloc(enc->n_bands, (uint32_t)slot, 12)); // a chunk: length, type, data, CRC
+    TF_TRY(enc->rowsums_host.alloc(enc->rowsums.bytes));
+    TF_HIP(hipMemcpyAsync(enc->dev_tables.p, &enc->tables, sizeof(Tables), hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    *out = enc.release();
     return TF_OK;
 }
 
@@ -822,48 +794,30 @@ static int own_code_buffers(tf_png *enc)
     TF_TRY(enc->frame_tables.alloc(sizeof(Tables)));
     TF_TRY(enc->frame_code.alloc(sizeof(FrameCode)));
     TF_TRY(enc->frame_code_host.alloc(sizeof(FrameCode)));
-    return enc->lengths_host.alloc(enc->lengths.bytes);
+    return enc->lengths_host.alloc(enc->s.lengths.bytes);
 }
 
-// the slots to their chunks in the packed stream, as far as `dev_capacity` reaches
-static int pack(tf_png *enc, size_t dev_capacity)
+// the slots to their chunks in the packed stream, as far as the caller's `capacity` reaches behind the head
+static int pack(tf_png *enc, size_t capacity)
 {
-    return launch("png_pack", k_png_pack, dim3(cdiv(enc->n_bands, PACK_BLOCK / WAVE)), dim3(PACK_BLOCK), 0, enc->staging.as<uint8_t>(),
-                  enc->slot, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(), enc->n_bands, enc->dev_tables.as<Tables>(),
-                  enc->packed.as<uint8_t>(), dev_capacity);
-}
-
-// what the pack kernel may write: the caller's room behind the head, and never more than the packed buffer
-static size_t dev_room(const tf_png *enc, size_t capacity)
-{
-    const size_t room = capacity > enc->head.size() ? capacity - enc->head.size() : 0;
-    return room < enc->packed.bytes ? room : enc->packed.bytes;
-}
-
-// head, the bands' chunks and tail to the caller, if they fit; *n_bytes either way
-static int copy_out(tf_png *enc, const char *who, uint8_t *out, size_t capacity, size_t *n_bytes)
-{
-    const size_t head = enc->head.size(), chunks = enc->last_chunks, tail = enc->tail.size();
-    *n_bytes = head + chunks + tail;
-    TF_REQUIRE(*n_bytes <= capacity, "%s: the file has %zu bytes, the buffer %zu", who, *n_bytes, capacity);
-    memcpy(out, enc->head.data(), head);
-    TF_HIP(hipMemcpyAsync(out + head, enc->packed.p, chunks, hipMemcpyDeviceToHost, stream()));
-    TF_HIP(hipStreamSynchronize(stream()));
-    memcpy(out + head + chunks, enc->tail.data(), tail);
-    return TF_OK;
+    const SlotStream &s = enc->s;
+    return launch("png_pack", k_png_pack, dim3(cdiv(s.n, PACK_BLOCK / WAVE)), dim3(PACK_BLOCK), 0, s.staging.as<uint8_t>(), s.slot,
+                  s.lengths.as<uint32_t>(), s.offsets.as<uint32_t>(), s.n, enc->dev_tables.as<Tables>(), s.packed.as<uint8_t>(),
+                  s.pack_room(capacity, enc->head.size()));
 }
 
 TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, size_t capacity, size_t *n_bytes)
 {
     TF_REQUIRE(enc && rgb_dev && n_bytes && (out || capacity == 0), "tf_png_encode_dev: null pointer");
     *n_bytes = 0;
-    TF_HIP(hipMemsetAsync(enc->info.p, 0, enc->info.bytes, stream()));
+    SlotStream &s = enc->s;
+    TF_TRY(s.begin());
     TF_TRY(launch("png_filter", k_png_filter, dim3(enc->H), dim3(FILTER_BLOCK), 0, (const uint8_t *)rgb_dev, enc->W,
                   enc->filtered.as<uint8_t>(), enc->rowsums.as<uint32_t>()));
     DeflateArgs a;
     a.filtered = enc->filtered.as<uint8_t>(), a.row_bytes = enc->row_bytes, a.H = enc->H, a.band_rows = enc->band_rows;
     a.tables = enc->dev_tables.as<Tables>(), a.counts = nullptr, a.code = nullptr;
-    a.staging = enc->staging.as<uint8_t>(), a.slot_bytes = enc->slot;
+    a.staging = s.staging.as<uint8_t>(), a.slot_bytes = s.slot;
     enc->last_own_code = false;
     if (enc->code) {
         TF_TRY(own_code_buffers(enc));
@@ -875,22 +829,19 @@ TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, siz
                       enc->frame_code.as<FrameCode>()));
         a.tables = enc->frame_tables.as<Tables>(), a.counts = enc->counts.as<uint32_t>(), a.code = enc->frame_code.as<FrameCode>();
     }
-    a.lengths = enc->lengths.as<uint32_t>();
-    a.overflow = reinterpret_cast<uint32_t *>(enc->info.as<unsigned long long>() + 1);
+    a.lengths = s.lengths.as<uint32_t>();
+    a.overflow = s.overflow();
     TF_TRY(launch("png_deflate", k_png_deflate, dim3(enc->n_bands), dim3(WAVE), 0, a));
-    TF_TRY(launch("png_scan", k_slot_scan, dim3(1), dim3(SCAN_BLOCK), 0, enc->lengths.as<uint32_t>(), enc->offsets.as<uint32_t>(),
-                  enc->n_bands, 12u, enc->info.as<unsigned long long>())); // a chunk: length, type, data, CRC
-    TF_TRY(pack(enc, dev_room(enc, capacity)));
-    enc->last_chunks = 0;
-    TF_HIP(hipMemcpyAsync(enc->info_host.p, enc->info.p, enc->info.bytes, hipMemcpyDeviceToHost, stream()));
+    TF_TRY(s.scan("png_scan"));
+    TF_TRY(pack(enc, capacity));
+    TF_TRY(s.fetch());
     TF_HIP(hipMemcpyAsync(enc->rowsums_host.p, enc->rowsums.p, enc->rowsums.bytes, hipMemcpyDeviceToHost, stream()));
     if (enc->code) {
         TF_HIP(hipMemcpyAsync(enc->frame_code_host.p, enc->frame_code.p, sizeof(FrameCode), hipMemcpyDeviceToHost, stream()));
-        TF_HIP(hipMemcpyAsync(enc->lengths_host.p, enc->lengths.p, enc->lengths.bytes, hipMemcpyDeviceToHost, stream()));
+        TF_HIP(hipMemcpyAsync(enc->lengths_host.p, s.lengths.p, s.lengths.bytes, hipMemcpyDeviceToHost, stream()));
     }
     TF_HIP(hipStreamSynchronize(stream()));
-    if (enc->info_host.as<unsigned long long>()[1])
-        return set_error(TF_ERR_STATE, "tf_png_encode_dev: a band outgrew its staging slot of %u bytes", enc->slot);
+    TF_TRY(s.finish("tf_png_encode_dev", "a band"));
     // Adler-32 of the whole stream from the rows' sums: a row of L bytes moves s2 by L s1 + its weighted sum
     uint64_t s1 = 1, s2 = 0;
     for (int r = 0; r < enc->H; r++) {
@@ -902,9 +853,8 @@ TF_API int tf_png_encode_dev(tf_png *enc, const void *rgb_dev, uint8_t *out, siz
     put_be32(last, (uint32_t)((s2 << 16) | s1));
     put_chunk(enc->tail, enc->tables, "IDAT", last);
     put_chunk(enc->tail, enc->tables, "IEND", {});
-    enc->last_chunks = (size_t)enc->info_host.as<unsigned long long>()[0];
     enc->last_own_code = enc->code != 0;
-    return copy_out(enc, "tf_png_encode_dev", out, capacity, n_bytes);
+    return s.copy_out("tf_png_encode_dev", enc->head, enc->tail, out, capacity, n_bytes);
 }
 
 TF_API int tf_png_last_code(tf_png *enc, uint8_t *lengths, uint32_t *repairs)
@@ -939,18 +889,15 @@ TF_API int tf_png_copy_last(tf_png *enc, uint8_t *out, size_t capacity, size_t *
 {
     TF_REQUIRE(enc && n_bytes && (out || capacity == 0), "tf_png_copy_last: null pointer");
     *n_bytes = 0;
-    if (!enc->last_chunks)
-        return set_error(TF_ERR_STATE, "tf_png_copy_last: nothing has been encoded");
-    TF_TRY(pack(enc, dev_room(enc, capacity)));
-    return copy_out(enc, "tf_png_copy_last", out, capacity, n_bytes);
+    TF_TRY(enc->s.have_last("tf_png_copy_last"));
+    TF_TRY(pack(enc, capacity));
+    return enc->s.copy_out("tf_png_copy_last", enc->head, enc->tail, out, capacity, n_bytes);
 }
 
 TF_API int tf_png_encode(tf_png *enc, const uint8_t *rgb_host, uint8_t *out, size_t capacity, size_t *n_bytes)
 {
     TF_REQUIRE(enc && rgb_host && n_bytes, "tf_png_encode: null pointer");
     const size_t bytes = (size_t)enc->H * enc->W * 3;
-    if (!enc->upload.p)
-        TF_TRY(enc->upload.alloc(bytes));
-    TF_HIP(hipMemcpyAsync(enc->upload.p, rgb_host, bytes, hipMemcpyHostToDevice, stream()));
+    TF_TRY(enc->upload.upload(rgb_host, bytes));
     return tf_png_encode_dev(enc, enc->upload.p, out, capacity, n_bytes);
 }

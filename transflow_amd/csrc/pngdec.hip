@@ -426,41 +426,26 @@ TF_API int tf_pngdec_create(tf_pngdec **out, int max_width, int max_height, size
                max_width, max_height);
     TF_REQUIRE(max_file_bytes >= 1 && max_file_bytes <= ((size_t)1 << 31), "tf_pngdec_create: a file of %zu bytes (1 to 2^31)", max_file_bytes);
     TF_TRY(ensure_init());
-    tf_pngdec *dec = new (std::nothrow) tf_pngdec;
+    auto dec = make_handle<tf_pngdec>();
     TF_REQUIRE(dec, "tf_pngdec_create: out of memory");
     dec->max_w = max_width, dec->max_h = max_height, dec->max_file = max_file_bytes;
     // the bands' bytes, each but the last rounded up to SLOT_ALIGN: at most H rows' bytes and SLOT_ALIGN a band
     dec->filt_bytes = (size_t)max_height * ((size_t)row_bytes((uint32_t)max_width) + SLOT_ALIGN) + FILT_PAD;
     make_crc32_consts(dec->consts);
     const size_t h = (size_t)max_height;
-    int rc = dec->dev_consts.alloc(sizeof(Crc32Consts));
-    if (rc == TF_OK)
-        rc = dec->file.alloc(max_file_bytes + 4);
-    if (rc == TF_OK)
-        rc = dec->bands.alloc(2 * h * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->filt.alloc(dec->filt_bytes);
-    if (rc == TF_OK)
-        rc = dec->rowsums.alloc(2 * h * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->status.alloc(ST_WORDS * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->stage.alloc(max_file_bytes);
-    if (rc == TF_OK)
-        rc = dec->bands_host.alloc(2 * h * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->rowsums_host.alloc(2 * h * sizeof(uint32_t));
-    if (rc == TF_OK)
-        rc = dec->status_host.alloc(ST_WORDS * sizeof(uint32_t));
-    if (rc == TF_OK && hipMemcpyAsync(dec->dev_consts.p, &dec->consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_pngdec_create: table upload failed");
-    if (rc == TF_OK && hipStreamSynchronize(stream()) != hipSuccess)
-        rc = set_error(TF_ERR_HIP, "tf_pngdec_create: hipStreamSynchronize failed");
-    if (rc != TF_OK) {
-        tf_pngdec_destroy(dec);
-        return rc;
-    }
-    *out = dec;
+    TF_TRY(dec->dev_consts.alloc(sizeof(Crc32Consts)));
+    TF_TRY(dec->file.alloc(max_file_bytes + 4));
+    TF_TRY(dec->bands.alloc(2 * h * sizeof(uint32_t)));
+    TF_TRY(dec->filt.alloc(dec->filt_bytes));
+    TF_TRY(dec->rowsums.alloc(2 * h * sizeof(uint32_t)));
+    TF_TRY(dec->status.alloc(ST_WORDS * sizeof(uint32_t)));
+    TF_TRY(dec->stage.alloc(max_file_bytes));
+    TF_TRY(dec->bands_host.alloc(2 * h * sizeof(uint32_t)));
+    TF_TRY(dec->rowsums_host.alloc(2 * h * sizeof(uint32_t)));
+    TF_TRY(dec->status_host.alloc(ST_WORDS * sizeof(uint32_t)));
+    TF_HIP(hipMemcpyAsync(dec->dev_consts.p, &dec->consts, sizeof(Crc32Consts), hipMemcpyHostToDevice, stream()));
+    TF_HIP(hipStreamSynchronize(stream()));
+    *out = dec.release();
     return TF_OK;
 }
 

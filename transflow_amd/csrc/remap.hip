@@ -421,35 +421,24 @@ __global__ void k_intro_render(int4 *__restrict__ data, const float *__restrict_
 
 } // namespace
 
-static int upload(DevBuf &buf, const void *host, size_t bytes)
-{
-    if (buf.bytes < bytes)
-        TF_TRY(buf.alloc(bytes));
-    TF_HIP(hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, stream()));
-    return TF_OK;
-}
-
 static int comp_create(tf_comp **out, int height, int width, const uint8_t background_rgb[3], void *image_dev)
 {
     TF_REQUIRE(height >= 0 && width >= 0 && (long long)height * width < (1ll << 31), "tf_comp_create: bad size %dx%d",
                width, height);
     TF_TRY(ensure_init());
-    tf_comp *c = new tf_comp;
+    auto c = make_handle<tf_comp>();
+    TF_REQUIRE(c, "tf_comp_create: out of memory");
     c->H = height;
     c->W = width;
     c->N = height * width;
     c->bg = make_uchar4(background_rgb[0], background_rgb[1], background_rgb[2], 0);
-    int rc = TF_OK;
     if (image_dev)
         c->image.borrow(image_dev, (size_t)c->N * 3);
     else
-        rc = c->image.alloc((size_t)c->N * 3);
-    if (rc != TF_OK) {
-        delete c;
-        return rc;
-    }
-    *out = c;
-    return tf_comp_begin(c);
+        TF_TRY(c->image.alloc((size_t)c->N * 3));
+    TF_TRY(tf_comp_begin(c.get()));
+    *out = c.release();
+    return TF_OK;
 }
 
 TF_API int tf_comp_create(tf_comp **out, int height, int width, const uint8_t background_rgb[3])
@@ -534,7 +523,8 @@ TF_API int tf_remap_create(tf_remap **out, int height, int width, const tf_layer
     TF_REQUIRE(cfg->layer_class >= TF_LAYER_MOVEREF && cfg->layer_class <= TF_LAYER_INTRODUCTION,
                "tf_remap_create: unknown layer class %d", cfg->layer_class);
     TF_TRY(ensure_init());
-    tf_remap *L = new tf_remap;
+    auto L = make_handle<tf_remap>();
+    TF_REQUIRE(L, "tf_remap_create: out of memory");
     L->H = height;
     L->W = width;
     L->N = height * width;
@@ -542,47 +532,37 @@ TF_API int tf_remap_create(tf_remap **out, int height, int width, const tf_layer
     L->fl = MoveFlags{cfg->transparent_pixels_can_move != 0, cfg->pixels_can_move_to_empty_spot != 0,
                       cfg->pixels_can_move_to_filled_spot != 0, cfg->moving_pixels_leave_empty_spot != 0};
     size_t n = (size_t)L->N;
-    int rc = TF_OK;
-    auto fail = [&](int code) {
-        delete L;
-        return code;
-    };
     const size_t px_bytes = (size_t)L->depth() * 4;
-    if ((rc = L->data[0].alloc(n * px_bytes)) || (rc = L->data[1].alloc(n * px_bytes)) || (rc = L->rgba.alloc(n * 4)) ||
-        (rc = L->err.alloc(4)))
-        return fail(rc);
-    if (cfg->layer_class == TF_LAYER_INTRODUCTION && (rc = L->intro_sel.alloc(n)))
-        return fail(rc);
-    if (mask_src && (rc = upload(L->mask_src, mask_src, n)))
-        return fail(rc);
-    if (mask_dst && (rc = upload(L->mask_dst, mask_dst, n)))
-        return fail(rc);
-    if (mask_alpha && (rc = upload(L->mask_alpha, mask_alpha, n * 4)))
-        return fail(rc);
-    if (reset_mask && (rc = upload(L->reset_mask, reset_mask, n * 4)))
-        return fail(rc);
-    hipError_t e;
-    if (n && (e = hipMemsetAsync(L->rgba.p, 0, n * 4, stream())) != hipSuccess)
-        return fail(set_error(TF_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e)));
-    if ((e = hipMemsetAsync(L->err.p, 0, 4, stream())) != hipSuccess)
-        return fail(set_error(TF_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e)));
+    TF_TRY(L->data[0].alloc(n * px_bytes));
+    TF_TRY(L->data[1].alloc(n * px_bytes));
+    TF_TRY(L->rgba.alloc(n * 4));
+    TF_TRY(L->err.alloc(4));
+    if (cfg->layer_class == TF_LAYER_INTRODUCTION)
+        TF_TRY(L->intro_sel.alloc(n));
+    if (mask_src)
+        TF_TRY(L->mask_src.upload(mask_src, n));
+    if (mask_dst)
+        TF_TRY(L->mask_dst.upload(mask_dst, n));
+    if (mask_alpha)
+        TF_TRY(L->mask_alpha.upload(mask_alpha, n * 4));
+    if (reset_mask)
+        TF_TRY(L->reset_mask.upload(reset_mask, n * 4));
+    if (n)
+        TF_HIP(hipMemsetAsync(L->rgba.p, 0, n * 4, stream()));
+    TF_HIP(hipMemsetAsync(L->err.p, 0, 4, stream()));
     switch (cfg->layer_class) {
     case TF_LAYER_STATIC:
-        rc = launch("layer_static_init", k_layer_static_init, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0, L->rgba.as<uchar4>(),
-                    L->N);
+        TF_TRY(launch("layer_static_init", k_layer_static_init, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0, L->rgba.as<uchar4>(), L->N));
         break;
     case TF_LAYER_INTRODUCTION: // data.py:17: an all-zero canvas
-        if (n && (e = hipMemsetAsync(L->data[0].p, 0, n * px_bytes, stream())) != hipSuccess)
-            return fail(set_error(TF_ERR_HIP, "hipMemsetAsync failed: %s", hipGetErrorString(e)));
+        if (n)
+            TF_HIP(hipMemsetAsync(L->data[0].p, 0, n * px_bytes, stream()));
         break;
     default:
-        rc = launch("remap_init", k_remap_init, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0, L->cur_data(), L->N, L->W);
+        TF_TRY(launch("remap_init", k_remap_init, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0, L->cur_data(), L->N, L->W));
     }
-    if (rc)
-        return fail(rc);
-    if ((e = hipStreamSynchronize(stream())) != hipSuccess) // host mask buffers are borrowed for this call only
-        return fail(set_error(TF_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e)));
-    *out = L;
+    TF_HIP(hipStreamSynchronize(stream())); // host mask buffers are borrowed for this call only
+    *out = L.release();
     return TF_OK;
 }
 
@@ -684,10 +664,10 @@ TF_API int tf_remap_update(tf_remap *L, const float *flow, const double *uniform
     if (L->N == 0 || L->cfg.layer_class == TF_LAYER_STATIC)
         return TF_OK;
     size_t n = (size_t)L->N;
-    TF_TRY(upload(L->scratch_flow, flow, n * 8));
+    TF_TRY(L->scratch_flow.upload(flow, n * 8));
     const double *u = nullptr;
     if (uniform && L->cfg.reset_mode == 1) {
-        TF_TRY(upload(L->scratch_u, uniform, n * 8));
+        TF_TRY(L->scratch_u.upload(uniform, n * 8));
         u = L->scratch_u.as<double>();
     }
     TF_HIP(hipMemsetAsync(L->err.p, 0, 4, stream()));
@@ -765,7 +745,7 @@ TF_API int tf_remap_gather(tf_remap *L, int source_index, const uint8_t *pixmap,
     TF_TRY(ensure_init());
     if (L->N == 0)
         return TF_OK;
-    TF_TRY(upload(L->scratch_pix, pixmap, (size_t)L->N * channels));
+    TF_TRY(L->scratch_pix.upload(pixmap, (size_t)L->N * channels));
     TF_TRY(tf_remap_gather_dev(L, source_index, L->scratch_pix.p, channels));
     TF_HIP(hipStreamSynchronize(stream())); // the host pixmap is borrowed for this call only
     return TF_OK;
@@ -881,7 +861,7 @@ TF_API int tf_remap_introduce(tf_remap *L, int source_index, const uint8_t *pixm
     TF_TRY(ensure_init());
     if (L->N == 0)
         return TF_OK;
-    TF_TRY(upload(L->scratch_pix, pixmap, (size_t)L->N * channels));
+    TF_TRY(L->scratch_pix.upload(pixmap, (size_t)L->N * channels));
     TF_TRY(tf_remap_introduce_dev(L, source_index, L->scratch_pix.p, channels, frame_number));
     TF_HIP(hipStreamSynchronize(stream())); // the host pixmap is borrowed for this call only
     return TF_OK;

@@ -131,6 +131,14 @@ int DevBuf::alloc(size_t n)
     return TF_OK;
 }
 
+int DevBuf::upload(const void *host, size_t n)
+{
+    if (bytes < n)
+        TF_TRY(alloc(n));
+    TF_HIP(hipMemcpyAsync(p, host, n, hipMemcpyHostToDevice, stream()));
+    return TF_OK;
+}
+
 void DevBuf::borrow(void *ptr, size_t n)
 {
     release();
@@ -309,13 +317,10 @@ TF_API int tf_event_create(tf_event **ev)
 {
     TF_REQUIRE(ev, "tf_event_create: null pointer");
     TF_TRY(ensure_init());
-    tf_event *e = new tf_event;
-    hipError_t rc = hipEventCreate(&e->ev);
-    if (rc != hipSuccess) {
-        delete e;
-        return set_error(TF_ERR_HIP, "hipEventCreate failed: %s", hipGetErrorString(rc));
-    }
-    *ev = e;
+    auto e = make_handle<tf_event>();
+    TF_REQUIRE(e, "tf_event_create: out of memory");
+    TF_HIP(hipEventCreate(&e->ev));
+    *ev = e.release();
     return TF_OK;
 }
 
