@@ -53,6 +53,10 @@ EPS2 = 0.01 * 0.01               # criteria.epsilon *= criteria.epsilon (double)
 # trace codes of one point at one level
 TR_DONE, TR_LOST_PREV, TR_LOST_EIG, TR_LOST_NEXT = 0, 1, 2, 3
 
+# why a point's steps at one level ended (calc_pyr_lk's probe): none were run (TR_LOST_PREV, TR_LOST_EIG), the step
+# was at most epsilon, two steps cancelled (the oscillation rule), all MAX_COUNT ran, the window left the frame
+STOP_NONE, STOP_EPS, STOP_OSC, STOP_COUNT, STOP_LOST = 0, 1, 2, 3, 4
+
 F32 = np.float32
 
 
@@ -88,6 +92,18 @@ def pyr_down(img: np.ndarray) -> np.ndarray:
     t = sum(k[j] * src[:, cols[:, j]] for j in range(5))                                     # [h][dw]
     s = sum(k[i] * t[rows[:, i], :] for i in range(5))
     return ((s + 128) >> 8).astype(np.uint8)
+
+
+def pyr_down_sum(img: np.ndarray) -> np.ndarray:
+    """pyr_down's 5x5 sums before the rounding: int64 [(h+1)/2][(w+1)/2]; pyr_down(img) == (sum + 128) >> 8."""
+    h, w = img.shape
+    dh, dw = (h + 1) // 2, (w + 1) // 2
+    k = (1, 4, 6, 4, 1)
+    src = img.astype(np.int64)
+    rows = border_interpolate(2 * np.arange(dh)[:, None] + np.arange(-2, 3)[None, :], h)
+    cols = border_interpolate(2 * np.arange(dw)[:, None] + np.arange(-2, 3)[None, :], w)
+    t = sum(k[j] * src[:, cols[:, j]] for j in range(5))
+    return sum(k[i] * t[rows[:, i], :] for i in range(5))
 
 
 def level_count(w: int, h: int, win: int, max_level: int) -> int:
@@ -206,7 +222,17 @@ def _bilinear(patch: np.ndarray, w, shift: int, win: int) -> np.ndarray:
 
 # ---- the tracker ----------------------------------------------------------------------------------------------------
 
-def _track_level(level, max_level, I, J, dx, dy, win, prev_pts, next_pts, trace, chunk=2048):
+def _probe_b(probe, diff, gx, gy):
+    """The largest |diff * d| and the largest |pair sum| that SUM_ORDER "simd128" converts to float, into probe."""
+    ww = diff.shape[2]
+    w8 = (ww // 8) * 8
+    for p in (diff * gx, diff * gy):
+        probe["max_product"] = max(probe["max_product"], int(np.abs(p).max(initial=0)))
+        q = p[:, :, :w8].reshape(p.shape[0], p.shape[1], w8 // 8, 2, 4)
+        probe["max_pair_sum"] = max(probe["max_pair_sum"], int(np.abs(q[:, :, :, 0] + q[:, :, :, 1]).max(initial=0)))
+
+
+def _track_level(level, max_level, I, J, dx, dy, win, prev_pts, next_pts, trace, chunk=2048, probe=None):
     """One parallel_for_ of LKTrackerInvoker over every point (in place on next_pts)."""
     h, w = I.shape
     pad = win
@@ -248,6 +274,9 @@ def _track_level(level, max_level, I, J, dx, dy, win, prev_pts, next_pts, trace,
             min_eig = (((A22 + A11).astype(F32) - root).astype(F32) / F32(2 * win * win)).astype(F32)
             good = ~((min_eig < MIN_EIG) | (D < FLT_EPSILON))
             code[idx[~good]] = TR_LOST_EIG
+            if probe is not None:
+                probe["min_eig"][s0 + idx, level] = min_eig
+                probe["det"][s0 + idx, level] = D
             sel = np.nonzero(good)[0]
             idx = idx[sel]
             ival, gx, gy = ival[sel], gx[sel], gy[sel]
@@ -264,6 +293,8 @@ def _track_level(level, max_level, I, J, dx, dy, win, prev_pts, next_pts, trace,
                 inb = (fn[:, 0] >= -win) & (fn[:, 0] < w) & (fn[:, 1] >= -win) & (fn[:, 1] < h)
                 code[idx[li[~inb]]] = TR_LOST_NEXT
                 live[li[~inb]] = False
+                if probe is not None:
+                    probe["stop"][s0 + idx[li[~inb]], level] = STOP_LOST
                 li = li[inb]
                 if not len(li):
                     break
@@ -274,6 +305,8 @@ def _track_level(level, max_level, I, J, dx, dy, win, prev_pts, next_pts, trace,
                 jval = _bilinear(_patch(Jp, pad, inx, iny, win), _weights(a, b), W_BITS - 5, win)
                 diff = jval - ival[li]
                 ib1, ib2 = _sum_b(diff, gx[li], gy[li])
+                if probe is not None:
+                    _probe_b(probe, diff, gx[li], gy[li])
                 b1, b2 = (ib1 * FLT_SCALE).astype(F32), (ib2 * FLT_SCALE).astype(F32)
                 ddx = (((A12[li] * b2).astype(F32) - (A22[li] * b1).astype(F32)).astype(F32) * D[li]).astype(F32)
                 ddy = (((A12[li] * b1).astype(F32) - (A11[li] * b2).astype(F32)).astype(F32) * D[li]).astype(F32)
@@ -293,6 +326,8 @@ def _track_level(level, max_level, I, J, dx, dy, win, prev_pts, next_pts, trace,
                         next_pts[g, 0] = (next_pts[g, 0] - (ddx[oi] * F32(0.5)).astype(F32)).astype(F32)
                         next_pts[g, 1] = (next_pts[g, 1] - (ddy[oi] * F32(0.5)).astype(F32)).astype(F32)
                     stop = stop | osc
+                if probe is not None:
+                    probe["stop"][gi, level] = np.where(dd <= EPS2, STOP_EPS, np.where(stop, STOP_OSC, STOP_COUNT))
                 live[li[stop]] = False
                 prev_delta[li, 0] = ddx
                 prev_delta[li, 1] = ddy
@@ -302,19 +337,25 @@ def _track_level(level, max_level, I, J, dx, dy, win, prev_pts, next_pts, trace,
             trace[sl, level, 3] = code
 
 
-def calc_pyr_lk(prev: np.ndarray, nxt: np.ndarray, pts: np.ndarray, win: int, max_level: int, with_trace=False):
+def calc_pyr_lk(prev: np.ndarray, nxt: np.ndarray, pts: np.ndarray, win: int, max_level: int, with_trace=False,
+                probe=None):
     """cv2.calcOpticalFlowPyrLK(prev, next, pts, None, winSize=(win, win), maxLevel=max_level)[0] with the default
     criteria and flags: nextPts [n][2] float32 (whatever the status).  with_trace: also [n][levels][4] float64
-    {nextPts.x, nextPts.y, steps run, code} after each level (index = level)."""
+    {nextPts.x, nextPts.y, steps run, code} after each level (index = level).  probe: a dict that receives "stop"
+    [n][levels] (a STOP_* per point and level), "min_eig" and "det" [n][levels] float32 (NaN where TR_LOST_PREV), and
+    "max_product" and "max_pair_sum", the largest integers |diff * d| and |diff_k * d_k + diff_k+4 * d_k+4| of b."""
     assert win > 2 and max_level >= 0
     pts = np.asarray(pts, F32).reshape(-1, 2)
     L = level_count(prev.shape[1], prev.shape[0], win, max_level)
     pp, pn = pyramid(prev, win, L), pyramid(nxt, win, L)
     next_pts = pts.copy()
     trace = np.zeros((len(pts), L + 1, 4)) if with_trace else None
+    if probe is not None:
+        probe.update(stop=np.full((len(pts), L + 1), STOP_NONE, np.int64), max_product=0, max_pair_sum=0,
+                     min_eig=np.full((len(pts), L + 1), np.nan, F32), det=np.full((len(pts), L + 1), np.nan, F32))
     for level in range(L, -1, -1):
         dx, dy = scharr(pp[level])
-        _track_level(level, L, pp[level], pn[level], dx, dy, win, pts, next_pts, trace)
+        _track_level(level, L, pp[level], pn[level], dx, dy, win, pts, next_pts, trace, probe=probe)
     return (next_pts, trace) if with_trace else next_pts
 
 
