@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import GOLDEN
+from tests.lfn_exact_cases import _rne_bf16, _values
 from transflow_amd import liteflownet as LF
 
 
@@ -30,28 +31,6 @@ lfn_ref = _Lazy("tests.lfn_ref")
 lfn_q_ref = _Lazy("tests.lfn_q_ref")
 
 FIXTURES = [p for p in sorted(glob.glob(os.path.join(GOLDEN, "lfn_*.npz"))) if "raises" not in np.load(p)]
-
-
-def _values():
-    """float32 values: normals of many magnitudes, exact ties between two bfloat16 values (even and odd below, both
-    signs), their float32 neighbours, and the top of the range (the largest float32 values round to infinity)."""
-    rng = np.random.default_rng(5)
-    v = [rng.standard_normal(3000).astype(np.float32) * np.float32(10.0) ** rng.integers(-20, 20, 3000).astype(np.float32)]
-    hi = rng.integers(0x0080, 0x7f7f, 500).astype(np.uint32)        # positive normal bfloat16 patterns
-    hi[:4] = (0x3f80, 0x3f81, 0x7f7e, 0x7f7f)
-    for low in (0x8000, 0x7fff, 0x8001, 0x0001, 0xffff, 0x0000):
-        bits = (hi << np.uint32(16)) | np.uint32(low)
-        v += [bits.view(np.float32), (bits | np.uint32(0x80000000)).view(np.float32)]
-    v.append(np.array([0.0, -0.0, 3.4028235e38, -3.4028235e38, 3.3895314e38, 3.38e38, 1e38, -1e38], np.float32))
-    return np.concatenate(v)
-
-
-def _rne_bf16(x: np.ndarray) -> np.ndarray:
-    """Round to nearest even on the bits: add 0x7fff plus the lowest kept bit, drop 16 bits (finite values; a carry out
-    of the largest exponent is the infinity)."""
-    u = x.view(np.uint32).astype(np.uint64)
-    r = ((u + np.uint64(0x7fff) + ((u >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16)) << np.uint64(16)
-    return r.astype(np.uint32).view(np.float32)
 
 
 def test_q_is_round_to_nearest_even_on_the_bits():
