@@ -213,7 +213,10 @@ int tf_fb_set_frame_bgr(tf_fb *fb, int slot, const uint8_t *bgr, int src_width, 
 int tf_fb_set_frame_bgr_dev(tf_fb *fb, int slot, const void *bgr_dev, int src_width, int src_height);
 /* Resident path with TF_OPTFLOW_USE_INITIAL_FLOW: the initial flow of `pair` for the next tf_fb_calc_slots
    (float32 [height][width][2]; kept until written again, zero at creation), from the host or -- through
-   its device address -- filled on the GPU (e.g. copied from a previous result). */
+   its device address -- filled on the GPU (e.g. copied from a previous result, or left there as the chain state by
+   tf_flow_post_process_chain_dev).  Ordering: tf_fb_calc_slots of such a handle waits, on the device, for everything
+   the calling thread's library stream was given before the call, so a buffer filled by work queued on that stream
+   needs no synchronise; work on any other stream the caller orders itself. */
 int tf_fb_set_initial_flow(tf_fb *fb, int pair, const float *flow);
 int tf_fb_initial_flow_ptr(tf_fb *fb, int pair, void **dev);
 /* Streaming use (cv.py:460-490 holds prev_gray and reads one new frame per call): with `on`, the
@@ -294,6 +297,16 @@ int tf_flow_post_process_dev(void *flow_dev, int wide, int width, int height, in
    needed by FORWARD; it holds the winner map of tf_fb_post_process_scatter afterwards. */
 int tf_flow_post_process_ex_dev(void *flow_dev, int wide, int width, int height, int direction, int n_ops,
                                 const tf_flow_op *ops, const void *mask_dev, void *winner_dev);
+/* The same on float32 flows, out of place, for a flow that sits in a method handle's own buffer (tf_hs_flow_ptr ...):
+   src_dev is read once and left as it is (the handle writes it again on its next call); dst_dev receives exactly the
+   bits tf_flow_post_process_ex_dev would leave in place.  chain_dev, where not NULL, receives what the reference's
+   `prev_flow` holds after post_process (source.py:317, 337-363), the next call's initial flow: with a mask the flow
+   after the filters and BEFORE the mask multiply (numpy.multiply makes a new array, which the direction handling and
+   the clip then work on), without one the same bits as dst_dev.  Three distinct buffers of 8 bytes per pixel, 8-byte
+   aligned.  BACKWARD and -1 are one launch, FORWARD a scatter and a resolve; no copy of the flow is made. */
+int tf_flow_post_process_chain_dev(const void *src_dev, void *dst_dev, void *chain_dev, int width, int height,
+                                   int direction, int n_ops, const tf_flow_op *ops, const void *mask_dev,
+                                   void *winner_dev);
 
 /* The `polar` flow filter, transflow/flow/filters.py:75-87, in place on a float32 flow: r = |v|,
    a = atan2(vy, vx), then v = (R cos A, R sin A) with R and A the filter's two user expressions of
@@ -367,6 +380,11 @@ int tf_hs_set_frame(tf_hs *hs, int slot, const uint8_t *grey, ptrdiff_t stride);
 int tf_hs_set_frame_bgr(tf_hs *hs, int slot, const uint8_t *bgr, int src_width, int src_height, ptrdiff_t stride);
 /* flow [H][W][2] float32 for the next call's `pair`, or NULL: the float64 chain.  Read by the next call only. */
 int tf_hs_set_initial_flow(tf_hs *hs, int pair, const float *flow);
+/* The same from a device address (NULL: the float64 chain), without a copy and without synchronising the host: the
+   pointer is BORROWED.  The next tf_hs_calc_slots reads it once, in its first kernel of the pair, on the calling
+   thread's stream; work queued on that stream after the call may write the buffer again (a chain buffer that
+   tf_flow_post_process_chain_dev fills after every call is the intended use). */
+int tf_hs_set_initial_flow_dev(tf_hs *hs, int pair, const void *flow_dev);
 int tf_hs_calc_slots(tf_hs *hs, const tf_hs_params *params, int n_pairs, const int *prev_slots, const int *next_slots);
 int tf_hs_waiting(tf_hs *hs, int *pairs_out /* [max_pairs] */, int *n_waiting);
 /* du = u - u_prev of a waiting pair: [H][W] float64 (*is_f64 = 1) or float32 */

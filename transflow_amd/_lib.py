@@ -144,6 +144,7 @@ PROTOTYPES = {
     "tf_hs_set_frame": (_I, [_P, _I, _P, C.c_ssize_t]),
     "tf_hs_set_frame_bgr": (_I, [_P, _I, _P, _I, _I, C.c_ssize_t]),
     "tf_hs_set_initial_flow": (_I, [_P, _I, _P]),
+    "tf_hs_set_initial_flow_dev": (_I, [_P, _I, _P]),
     "tf_hs_calc_slots": (_I, [_P, C.POINTER(TfHsParams), _I, _PI, _PI]),
     "tf_hs_waiting": (_I, [_P, _PI, _PI]),
     "tf_hs_delta_download": (_I, [_P, _I, _P, _PI]),
@@ -206,6 +207,7 @@ PROTOTYPES = {
     "tf_flow_convolve_dev": (_I, [_P, _P, _I, _I, _I, _P, _I, _I]),
     "tf_flow_post_process_dev": (_I, [_P, _I, _I, _I, _I, _P]),
     "tf_flow_post_process_ex_dev": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(TfFlowOp), _P, _P]),
+    "tf_flow_post_process_chain_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(TfFlowOp), _P, _P]),
     "tf_flow_polar_dev": (_I, [_P, C.c_size_t, _I, _P, _I, _P, _I, _I]),
     "tf_flow_render1d_dev": (_I, [_P, _P, C.c_size_t, C.c_float, C.POINTER(C.c_float), _I]),
     "tf_flow_render2d_dev": (_I, [_P, _P, C.c_size_t, C.c_float, C.POINTER(C.c_float)]),

@@ -9,6 +9,9 @@ backend unchanged.
   LiteFlowNetConfig <- the same, method "liteflownet" (no fields; opt-in: liteflownet=<weights path or dict>;
                        hip_lfn_precision chooses how its convolutions multiply)
 
+`hip_resident` (every method; for Farnebäck it matters with fb_flags & 4 only) keeps a method's flows, and the previous
+output a chaining call starts from, on the device; with it the other three methods take hip_device_flows and hip_batch.
+
 The four are MethodConfig subclasses; METHODS is the one table of the methods served and of what opts each in, which
 the flow_config_from_* readers (and through them HipFlowSource.from_args and the drop-in) ask.
 """
@@ -127,6 +130,12 @@ _HIP_KEYS = {
     # cores ("bf16": both operands rounded to bfloat16; "bf16x3": each split into a bfloat16 pair, three products) and
     # sum in float32; "f32" (the default) is float32 throughout.  Only the liteflownet method takes it.
     "hip_lfn_precision": _lfn_precision,
+    # "hip_resident": true -- Horn-Schunck, Lucas-Kanade and LiteFlowNet flows (and Farnebäck's when fb_flags has
+    # cv2.OPTFLOW_USE_INITIAL_FLOW) stay on the device from the kernel that makes them through the filters, the mask and
+    # the direction handling, and the previous output a call starts from is kept there too: one flow comes down per
+    # frame, or none with "hip_device_flows".  Off (the default) every source takes the route it took before the key
+    # existed.  Without it the three methods refuse "hip_device_flows" and "hip_batch": there is no resident flow.
+    "hip_resident": lambda v: bool(parse_bool_arg(v, False)),
 }
 
 
@@ -138,9 +147,12 @@ class MethodConfig:
     METHOD = None
     DEFAULTS: dict = {}
     HIP_KEYS: tuple = ()        # the keys of _HIP_KEYS the method accepts; another `hip_*` key is a ValueError
+    # ... and those of the resident route, "hip_resident" first: the others are accepted only where it is true
+    RESIDENT_KEYS: tuple = ("hip_resident", "hip_device_flows", "hip_batch")
     # the attributes of the keys a method does not accept: what they mean when they are not given
     hip_exact_sums, hip_prefetch, hip_device_flows, hip_batch = False, 0, False, 1
     hip_lfn_precision = "f32"
+    hip_resident = False
 
     def __init__(self, method: str, **kwargs):
         if method != self.METHOD:
@@ -148,18 +160,29 @@ class MethodConfig:
         self.method = method
         for k, v in self.DEFAULTS.items():
             setattr(self, k, kwargs.pop(k, v))
+        accepted = self._accepted_keys(kwargs)
         for k in kwargs:
-            if k.startswith("hip_") and k not in self.HIP_KEYS:
+            if k.startswith("hip_") and k not in accepted:
                 self._refuse_hip_key(k)
-        for k in self.HIP_KEYS:
+        for k in accepted:
             setattr(self, k, _HIP_KEYS[k](kwargs.pop(k, None)))
         self.extra = dict(kwargs)  # the other methods' fields, show_window ...: not used by this backend
 
     def _wrong_method(self, method) -> str:
         return f"{type(self).__name__} is the {self.METHOD!r} method, got {method!r}"
 
+    def _accepted_keys(self, given: dict) -> tuple:
+        """HIP_KEYS, and of RESIDENT_KEYS the switch alone unless it is given and true."""
+        switch = self.RESIDENT_KEYS[:1]
+        on = bool(switch) and _HIP_KEYS[switch[0]](given.get(switch[0]))
+        return self.HIP_KEYS + (self.RESIDENT_KEYS if on else switch)
+
     def _refuse_hip_key(self, key):
-        only = f" (only {', '.join(map(repr, self.HIP_KEYS))} is)" if self.HIP_KEYS else ""
+        if key in self.RESIDENT_KEYS:
+            raise ValueError(f"{key!r} is not available with the {self.METHOD} method without 'hip_resident': true "
+                             "(its flows come down raw and are post-processed from the host array)")
+        keys = self.HIP_KEYS + self.RESIDENT_KEYS
+        only = f" (only {', '.join(map(repr, keys))} {'are' if len(keys) > 1 else 'is'}, the last two with 'hip_resident')"
         raise ValueError(f"{key!r} is not available with the {self.METHOD} method{only}")
 
     def to_dict(self) -> dict:
@@ -167,7 +190,7 @@ class MethodConfig:
         d.update({k: getattr(self, k) for k in self.DEFAULTS})
         d.update(self.extra)
         for k in _HIP_KEYS:
-            if k in self.HIP_KEYS and getattr(self, k) != _HIP_KEYS[k](None):
+            if k in self.HIP_KEYS + self.RESIDENT_KEYS and getattr(self, k) != _HIP_KEYS[k](None):
                 d[k] = getattr(self, k)
         return d
 
@@ -196,6 +219,7 @@ class FlowConfig(MethodConfig):
     DEFAULTS = FB_DEFAULTS = dict(fb_pyr_scale=0.5, fb_levels=3, fb_winsize=15, fb_iterations=3, fb_poly_n=5,
                                   fb_poly_sigma=1.2, fb_flags=0)
     HIP_KEYS = ("hip_exact_sums", "hip_prefetch", "hip_device_flows", "hip_batch")
+    RESIDENT_KEYS = ("hip_resident",)       # matters with fb_flags & 4 only: without that flag Farnebäck is resident anyway
     from_file = classmethod(_from_file)
 
     def __init__(self, method: str = "farneback", **kwargs):

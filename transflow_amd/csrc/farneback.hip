@@ -599,6 +599,12 @@ static int fb_call_begin(tf_fb *fb, const ImagePlan &plan, hipStream_t *cs_out)
         fb->entry_pending[set] = true;
         if (fb->entry_pending[set ^ 1])
             TF_HIP(hipStreamWaitEvent(cs, fb->entry[set ^ 1], 0));
+        // ... except with OPTFLOW_USE_INITIAL_FLOW: the initial flows this call reads (fb_initial_flow) may have been
+        // written on the library stream after the previous call was issued -- through tf_fb_initial_flow_ptr, the
+        // previous output left there by tf_flow_post_process_chain_dev -- so the call waits for all of that stream's
+        // work up to here.  (tf_fb_set_initial_flow synchronises the host, which hid the need.)
+        if (fb->use_initial())
+            TF_HIP(hipStreamWaitEvent(cs, fb->entry[set], 0));
     }
     // Frames: tf_fb_set_frame returns with the frame in place; a caller writing frames on the device
     // orders that itself (tfhip.h).

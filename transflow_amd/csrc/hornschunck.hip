@@ -223,6 +223,7 @@ TF_API int tf_hs_create(tf_hs **out, int width, int height, int frame_slots, int
     TF_TRY(hs->norm.init(width, height));
     hs->host_blocks.resize((size_t)max_pairs * n_bound_blocks(width, height) * 4);
     hs->has_init.assign(max_pairs, 0);
+    hs->init_dev.assign(max_pairs, nullptr);
     hs->state.assign(max_pairs, tf_hs::DONE);
     hs->iter.assign(max_pairs, 0);
     hs->cur.assign(max_pairs, 0);
@@ -273,6 +274,7 @@ TF_API int tf_hs_set_initial_flow(tf_hs *hs, int pair, const float *flow)
 {
     TF_REQUIRE(hs, "tf_hs_set_initial_flow: null handle");
     TF_REQUIRE(pair >= 0 && pair < hs->max_pairs, "tf_hs_set_initial_flow: pair %d out of range", pair);
+    hs->init_dev[pair] = nullptr;
     if (!flow) {
         hs->has_init[pair] = 0;
         return TF_OK;
@@ -281,6 +283,16 @@ TF_API int tf_hs_set_initial_flow(tf_hs *hs, int pair, const float *flow)
     TF_HIP(hipMemcpyAsync((char *)hs->init_flow.p + (size_t)pair * bytes, flow, bytes, hipMemcpyHostToDevice, stream()));
     TF_HIP(hipStreamSynchronize(stream()));
     hs->has_init[pair] = 1;
+    return TF_OK;
+}
+
+TF_API int tf_hs_set_initial_flow_dev(tf_hs *hs, int pair, const void *flow_dev)
+{
+    TF_REQUIRE(hs, "tf_hs_set_initial_flow_dev: null handle");
+    TF_REQUIRE(pair >= 0 && pair < hs->max_pairs, "tf_hs_set_initial_flow_dev: pair %d out of range", pair);
+    TF_REQUIRE((uintptr_t)flow_dev % 8 == 0, "tf_hs_set_initial_flow_dev: the flow must be 8-byte aligned");
+    hs->init_dev[pair] = flow_dev; // borrowed: k_hs_init_f32 of the next call reads it, in stream order
+    hs->has_init[pair] = flow_dev != nullptr;
     return TF_OK;
 }
 
@@ -400,11 +412,12 @@ TF_API int tf_hs_calc_slots(tf_hs *hs, const tf_hs_params *params, int n_pairs, 
             TF_HIP(hipMemsetAsync(hs->plane(p, 0, 0), 0, hs->plane_bytes(), stream()));
             TF_HIP(hipMemsetAsync(hs->plane(p, 0, 1), 0, hs->plane_bytes(), stream()));
         } else {
-            TF_TRY(launch("hs_init", k_hs_init_f32, dim3(cdiv(n, 256)), dim3(256), 0,
-                          (const float2 *)hs->init_flow.p + (size_t)p * n, (float)params->decay, (float *)hs->plane(p, 0, 0),
+            const float2 *init = hs->init_dev[p] ? (const float2 *)hs->init_dev[p] : (const float2 *)hs->init_flow.p + (size_t)p * n;
+            TF_TRY(launch("hs_init", k_hs_init_f32, dim3(cdiv(n, 256)), dim3(256), 0, init, (float)params->decay, (float *)hs->plane(p, 0, 0),
                           (float *)hs->plane(p, 0, 1), n));
         }
         hs->has_init[p] = 0; // an initial flow serves one call
+        hs->init_dev[p] = nullptr;
     }
     TF_TRY(launch("hs_prepare", k_hs_prepare, dim3(cdiv(hs->W, PX), cdiv(hs->H, PY), n_pairs), dim3(256), 0,
                   hs->frames.as<const uint8_t>(), sp, hs->W, hs->H, (float)params->alpha_sq, hs->deriv.as<float4>()));

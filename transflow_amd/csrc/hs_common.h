@@ -119,6 +119,7 @@ struct tf_hs {
     tf::hs::NormScratch norm;
     std::vector<double> host_blocks;
     std::vector<int> has_init;               // per pair: an initial flow was set for the next call (float32 chain)
+    std::vector<const void *> init_dev;      // per pair: where that flow sits if not in init_flow (tf_hs_set_initial_flow_dev)
     // the call in progress
     tf_hs_params prm{};
     int n_pairs = 0, last_pairs = 0;

@@ -126,6 +126,189 @@ __global__ void k_pp_ops(float2 *__restrict__ flow, const float *__restrict__ ma
     flow[t] = f;
 }
 
+// ---- Out of place, and leaving the chain state (tf_flow_post_process_chain_dev): the same arithmetic as the kernels
+// above, on a flow that is read once from `src` (a method handle's own buffer, left as it is) and written to `dst`, and
+// -- where `chain` is given -- to the buffer the next call's initial flow is read from: the reference's prev_flow, which
+// sees the filters and, because the mask multiply makes a new array (source.py:342-343), not the mask.
+// A lane works on PX adjacent pixels: 2 (one 16-byte access per flow) where every buffer is 16-byte aligned (a pair of
+// a handle with an odd pixel count is not), else 1; a last lane of 2 that holds a single pixel takes it alone.
+
+// k_pp_ops's filters on one pixel
+__device__ __forceinline__ float2 ops_px(float2 f, const FlowOps &ops)
+{
+    for (int i = 0; i < ops.n; i++) {
+        const int kind = ops.op[i].kind, wide = ops.op[i].wide;
+        const double v = ops.op[i].value;
+        if (kind == TF_FLOW_SCALE) {
+            if (wide) {
+                f.x = (float)((double)f.x * v);
+                f.y = (float)((double)f.y * v);
+            } else {
+                f.x = f.x * (float)v;
+                f.y = f.y * (float)v;
+            }
+        } else {
+            const float norm = sqrtf(f.x * f.x + f.y * f.y);
+            if (kind == TF_FLOW_THRESHOLD) {
+                const bool hit = wide ? ((double)norm <= v) : (norm <= (float)v);
+                if (hit)
+                    f = make_float2(0.f, 0.f);
+            } else {
+                const bool hit = wide ? ((double)norm >= v) : (norm >= (float)v);
+                if (hit) {
+                    const double factor = wide ? v / (double)norm : (double)((float)v / norm);
+                    f.x = (float)((double)f.x * factor);
+                    f.y = (float)((double)f.y * factor);
+                }
+            }
+        }
+    }
+    return f;
+}
+
+template <int PX> struct PxLane {
+    unsigned t0; // the lane's first pixel
+    int n;       // how many it holds: PX, or 1 at an odd end
+    __device__ __forceinline__ PxLane(unsigned N) : t0((blockIdx.x * 256u + threadIdx.x) * PX), n(t0 >= N ? 0 : (N - t0 >= PX ? PX : 1)) {}
+    template <typename T> __device__ __forceinline__ void load(const T *__restrict__ p, T (&v)[PX]) const
+    {
+        if (PX == 2 && n == 2) {
+            struct alignas(2 * sizeof(T)) Two {
+                T a, b;
+            };
+            const Two two = *(const Two *)(p + t0);
+            v[0] = two.a, v[PX - 1] = two.b;
+        } else {
+            v[0] = v[PX - 1] = p[t0]; // (the second of an odd end: worked on, never stored)
+        }
+    }
+    template <typename T> __device__ __forceinline__ void store(T *__restrict__ p, const T (&v)[PX]) const
+    {
+        if (PX == 2 && n == 2) {
+            struct alignas(2 * sizeof(T)) Two {
+                T a, b;
+            };
+            *(Two *)(p + t0) = Two{v[0], v[PX - 1]};
+        } else {
+            p[t0] = v[0];
+        }
+    }
+};
+
+// the filters, the mask and the chain value of the lane's pixels: f comes back as what the direction handling reads
+template <int PX>
+__device__ __forceinline__ void chain_head(const PxLane<PX> &ln, float2 (&f)[PX], float2 *__restrict__ chain,
+                                           const float *__restrict__ mask, const FlowOps &ops)
+{
+#pragma unroll
+    for (int k = 0; k < PX; k++)
+        f[k] = ops_px(f[k], ops);
+    if (!mask)
+        return;
+    if (chain)
+        ln.store(chain, f);
+    float m[PX];
+    ln.load(mask, m);
+#pragma unroll
+    for (int k = 0; k < PX; k++) {
+        f[k].x = m[k] * f[k].x;
+        f[k].y = m[k] * f[k].y;
+    }
+}
+
+// BACKWARD (CLIP) and no direction handling: one pass
+template <int PX, bool CLIP>
+__global__ void __launch_bounds__(256)
+    k_pp_chain_line(const float2 *__restrict__ src, float2 *__restrict__ dst, float2 *__restrict__ chain,
+                    const float *__restrict__ mask, int W, int H, FastDiv dw, FlowOps ops)
+{
+    const PxLane<PX> ln((unsigned)(W * H));
+    if (ln.n == 0)
+        return;
+    float2 f[PX];
+    ln.load(src, f);
+    chain_head(ln, f, chain, mask, ops);
+    if (CLIP) {
+#pragma unroll
+        for (int k = 0; k < PX; k++) {
+            const int i = (int)fast_div(ln.t0 + k, dw);
+            f[k] = clip_to_frame(f[k], i, (int)(ln.t0 + k) - i * W, W, H);
+        }
+    }
+    ln.store(dst, f);
+    if (chain && !mask)
+        ln.store(chain, f);
+}
+
+// FORWARD, first pass: k_pp_fwd_scatter on the filtered and masked value, which stays in registers
+template <int PX>
+__global__ void __launch_bounds__(256)
+    k_pp_chain_scatter(const float2 *__restrict__ src, float2 *__restrict__ chain, const float *__restrict__ mask,
+                       int *__restrict__ winner, int W, int H, FastDiv dw, FlowOps ops)
+{
+    const int N = W * H;
+    const PxLane<PX> ln((unsigned)N);
+    if (ln.n == 0)
+        return;
+    float2 f[PX];
+    ln.load(src, f);
+    chain_head(ln, f, chain, mask, ops);
+#pragma unroll
+    for (int k = 0; k < PX; k++) {
+        if (k >= ln.n)
+            break;
+        const int t = (int)ln.t0 + k, i = (int)fast_div((uint32_t)t, dw);
+        const float2 c = clip_to_frame(f[k], i, t - i * W, W, H);
+        const int d = rint_i(c.y) * W + rint_i(c.x);
+        if (d != 0)
+            atomicMax(&winner[clampi(t + d, 0, N - 1)], t);
+    }
+}
+
+// FORWARD, second pass: k_pp_fwd_resolve into dst, and into the chain where no mask set it in the first pass
+template <int PX>
+__global__ void __launch_bounds__(256)
+    k_pp_chain_resolve(float2 *__restrict__ dst, float2 *__restrict__ chain, const int *__restrict__ winner, int W, int H,
+                       FastDiv dw)
+{
+    const PxLane<PX> ln((unsigned)(W * H));
+    if (ln.n == 0)
+        return;
+    int w[PX];
+    ln.load(winner, w);
+    float2 f[PX];
+#pragma unroll
+    for (int k = 0; k < PX; k++) {
+        const int t = (int)ln.t0 + k; // (past the end at an odd end: computed, never stored)
+        const int src = w[k] >= 0 ? w[k] : t;
+        const int i = (int)fast_div((uint32_t)t, dw), j = t - i * W;
+        const int si = (int)fast_div((uint32_t)src, dw);
+        f[k] = clip_to_frame(make_float2((float)(src - si * W - j), (float)(si - i)), i, j, W, H);
+    }
+    ln.store(dst, f);
+    if (chain)
+        ln.store(chain, f);
+}
+
+template <int PX>
+int chain_launch(const float2 *src, float2 *dst, float2 *chain, int W, int H, int direction, const FlowOps &fo,
+                 const float *mask, int *winner)
+{
+    const size_t N = (size_t)W * H;
+    const dim3 grid(cdiv(N, 256 * PX)), block(256);
+    const FastDiv dw = fast_div_setup((uint32_t)W);
+    if (direction == 0) {
+        TF_HIP(hipMemsetAsync(winner, 0xFF, N * 4, stream()));
+        TF_TRY(launch("flow_pp_chain_scatter", k_pp_chain_scatter<PX>, grid, block, 0, src, mask ? chain : nullptr, mask,
+                      winner, W, H, dw, fo));
+        return launch("flow_pp_chain_resolve", k_pp_chain_resolve<PX>, grid, block, 0, dst, mask ? nullptr : chain,
+                      (const int *)winner, W, H, dw);
+    }
+    if (direction == 1)
+        return launch("flow_pp_chain_line", k_pp_chain_line<PX, true>, grid, block, 0, src, dst, chain, mask, W, H, dw, fo);
+    return launch("flow_pp_chain_line", k_pp_chain_line<PX, false>, grid, block, 0, src, dst, chain, mask, W, H, dw, fo);
+}
+
 template <typename T2> int scatter(const T2 *flow, int W, int H, int *winner, const PpLabels &lb)
 {
     const size_t N = (size_t)W * H;
@@ -201,6 +384,41 @@ TF_API int tf_flow_post_process_ex_dev(void *flow_dev, int wide, int width, int 
     if (direction < 0)
         return TF_OK;
     return pp_direction(flow_dev, wide != 0, width, height, direction, (int *)winner_dev, PP_FLOW);
+}
+
+TF_API int tf_flow_post_process_chain_dev(const void *src_dev, void *dst_dev, void *chain_dev, int width, int height,
+                                          int direction, int n_ops, const tf_flow_op *ops, const void *mask_dev,
+                                          void *winner_dev)
+{
+    TF_REQUIRE(direction >= -1 && direction <= 1,
+               "tf_flow_post_process_chain: direction must be 0 (FORWARD), 1 (BACKWARD) or -1 (none)");
+    TF_REQUIRE(width >= 0 && height >= 0 && (long long)width * height < (1ll << 31), "tf_flow_post_process_chain: bad size");
+    TF_REQUIRE(n_ops >= 0 && n_ops <= TF_MAX_FLOW_OPS, "tf_flow_post_process_chain: at most %d flow filters, got %d",
+               TF_MAX_FLOW_OPS, n_ops);
+    TF_REQUIRE(n_ops == 0 || ops, "tf_flow_post_process_chain: null filter list");
+    if ((size_t)width * height == 0)
+        return TF_OK;
+    TF_REQUIRE(src_dev && dst_dev, "tf_flow_post_process_chain: null pointer");
+    TF_REQUIRE(src_dev != dst_dev && src_dev != chain_dev && dst_dev != chain_dev,
+               "tf_flow_post_process_chain: src, dst and chain must be three buffers");
+    TF_REQUIRE(direction != 0 || winner_dev, "tf_flow_post_process_chain: FORWARD needs a winner buffer of 4 bytes per pixel");
+    FlowOps fo;
+    memset(&fo, 0, sizeof(fo));
+    fo.n = n_ops;
+    for (int i = 0; i < n_ops; i++) {
+        TF_REQUIRE(ops[i].kind >= TF_FLOW_SCALE && ops[i].kind <= TF_FLOW_CLIP, "tf_flow_post_process_chain: unknown filter kind %d",
+                   ops[i].kind);
+        fo.op[i] = ops[i];
+    }
+    TF_TRY(ensure_init());
+    const uintptr_t flows = (uintptr_t)src_dev | (uintptr_t)dst_dev | (uintptr_t)chain_dev;
+    const uintptr_t words = (uintptr_t)mask_dev | (uintptr_t)winner_dev;
+    TF_REQUIRE(flows % 8 == 0 && words % 4 == 0, "tf_flow_post_process_chain: misaligned buffer");
+    if (flows % 16 == 0 && words % 8 == 0)
+        return chain_launch<2>((const float2 *)src_dev, (float2 *)dst_dev, (float2 *)chain_dev, width, height, direction, fo,
+                               (const float *)mask_dev, (int *)winner_dev);
+    return chain_launch<1>((const float2 *)src_dev, (float2 *)dst_dev, (float2 *)chain_dev, width, height, direction, fo,
+                           (const float *)mask_dev, (int *)winner_dev);
 }
 
 TF_API int tf_flow_post_process_dev(void *flow_dev, int wide, int width, int height, int direction, void *scratch_dev)

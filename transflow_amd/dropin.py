@@ -154,7 +154,10 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
     to the state dict, or a dict of arrays): flow sources of the "liteflownet" method are then this backend's
-    (transflow_amd/liteflownet.py); without them they stay the reference's.  motion_vectors: `use_mvs` requests (codec
+    (transflow_amd/liteflownet.py); without them they stay the reference's.  For these three methods the keys
+    "hip_resident" (flows and the previous output stay on the device through the post-process), "hip_device_flows" and
+    "hip_batch" travel in the cv_config JSON, as Farnebäck's keys do (transflow_amd/config.py): no argument here.
+    motion_vectors: `use_mvs` requests (codec
     motion vectors, transflow's -m) are this backend's too (transflow_amd/motionvectors.py; PyAV still decodes); by
     default they stay the reference's.  lazy_frames: the compositors built for the pipeline return
     DeviceFrames from render() (transflow_amd/deviceframe.py): the pipeline's `oq.put(frame)` (pipeline.py:518-522) then

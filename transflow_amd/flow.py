@@ -274,6 +274,7 @@ class FlowSource:
         # the resident tail (below): what read_next_flow handed out whose flow is still on the device, the mask on the
         # device, and where the yielded arrays / DeviceFlows (transflow_amd/deviceflow.py) live
         self._pending = self._mask_dev = self._flow_pool = self._flow_ring = None
+        self._scratch = {}       # device buffers of the out-of-place tail (_device_scratch)
         # the first pass starts where a checkpoint left off, later passes at start_frame (source.py:246-248)
         self.input_frame_index = 0
         self.start_frame, later_passes = ckpt_start_frame, start_frame
@@ -430,6 +431,44 @@ class FlowSource:
     def _download(self, handle, pair: int, out: np.ndarray) -> None:
         raise NotImplementedError()
 
+    def _chain_route(self):
+        """None: the handle post-processes its flow where it sits (post_process_ex).  Else (src, chain): the flow is
+        read from the device address `src`, which is left as it is, and post-processed into the output's own buffer
+        (tf_flow_post_process_chain_dev); `chain`, if not None, is where the next call's initial flow is left."""
+        return None
+
+    def _device_scratch(self, name: str, nbytes: int):
+        """A device buffer of the out-of-place tail ("winner": FORWARD's winner map; "staging": where a flow that goes
+        to a host array is post-processed before its one download), made on first use."""
+        if name not in self._scratch:
+            from .device import DevBuffer
+            self._scratch[name] = DevBuffer(max(1, nbytes))
+        return self._scratch[name]
+
+    def _post_process_chain(self, raw, src: int, chain, ops, mask_ptr):
+        import ctypes as C
+
+        from . import _lib
+        from .flowops import flow_ops_array
+        px = self.width * self.height
+        to_host = isinstance(raw, np.ndarray)
+        dst = self._device_scratch("staging", 8 * px).ptr if to_host else raw.dev_ptr
+        winner = self._device_scratch("winner", 4 * px).ptr if self.direction == FlowSource.Direction.FORWARD else None
+        arr, n = flow_ops_array(ops)
+        lib = _lib.load()
+        _lib.check(lib.tf_flow_post_process_chain_dev(
+            C.c_void_p(src), C.c_void_p(dst), C.c_void_p(chain) if chain else None, self.width, self.height,
+            self.direction.value, n, arr, C.c_void_p(mask_ptr) if mask_ptr else None,
+            C.c_void_p(winner) if winner else None))
+        if to_host:
+            # (with hip_prefetch this is the worker thread: the copy waits on that thread's stream, the consumer does not)
+            if raw.nbytes:
+                _lib.check(lib.tf_dev_download(C.c_void_p(raw.ctypes.data), C.c_void_p(dst), raw.nbytes))
+            return raw
+        raw._ready.record()
+        raw.in_frame = True          # both directions of post_process end with the clip (source.py:361-362)
+        return raw
+
     def _post_process_resident(self, raw):
         self._pending = None
         handle, pair = self._resident_flow()
@@ -438,7 +477,11 @@ class FlowSource:
             from .device import DevBuffer
             self._mask_dev = DevBuffer.from_array(
                 np.ascontiguousarray(self.mask, dtype=np.float32).reshape(self.height, self.width))
-        handle.post_process_ex(pair, self.direction.value, ops, None if self.mask is None else self._mask_dev.ptr)
+        mask_ptr = None if self.mask is None else self._mask_dev.ptr
+        route = self._chain_route()
+        if route is not None:
+            return self._post_process_chain(raw, route[0], route[1], ops, mask_ptr)
+        handle.post_process_ex(pair, self.direction.value, ops, mask_ptr)
         if isinstance(raw, np.ndarray):
             self._download(handle, pair, raw)
             return raw
@@ -466,6 +509,9 @@ class FlowSource:
             self._flow_ring.drain()
         self._flow_ring = None      # (buffers live as long as a DeviceFlow the caller still holds)
         self._flow_pool = None
+        for buf in self._scratch.values():
+            buf.close()
+        self._scratch = {}
         if self._pp is not None:
             self._pp.close()
             self._pp = None
@@ -626,24 +672,46 @@ def _open_farneback(source):
 
 def _open_horn_schunck(source):
     from .hornschunck import HornSchunck
-    return HornSchunck(source.width, source.height, device=source.device)
+    return HornSchunck(source.width, source.height, device=source.device)      # (every call chains: one pair)
 
 
 def _open_lucas_kanade(source):
     from .lucaskanade import LucasKanade
-    return LucasKanade(source.width, source.height, device=source.device)
+    batch = source._batch_size()      # 1 unless hip_resident
+    return LucasKanade(source.width, source.height, frame_slots=batch + 1, max_pairs=batch, device=source.device)
 
 
 def _open_liteflownet(source):
     from .liteflownet import LiteFlowNet
-    return LiteFlowNet(source.width, source.height, source.config.weights, device=source.device,
-                       precision=source.config.hip_lfn_precision)
+    batch = source._batch_size()
+    return LiteFlowNet(source.width, source.height, source.config.weights, frame_slots=batch + 1, max_pairs=batch,
+                       device=source.device, precision=source.config.hip_lfn_precision)
 
 
 def _previous_flow_or_zeros(source):
     if source.prev_flow is not None:
         return source.prev_flow
     return np.zeros((source.height, source.width, 2), np.float32)
+
+
+# The chain state on the device (hip_resident): what the reference keeps in `prev_flow` (source.py:314-321, 337-363; the
+# rule is DESIGN.md section 10's), written by tf_flow_post_process_chain_dev behind every call and read by the next.
+def _hs_chain_buffer(source, handle) -> int:
+    return source._device_scratch("chain", 8 * source.width * source.height).ptr      # the source's own, 8 B/px
+
+
+def _hs_chain_start(source, handle, valid: bool) -> None:
+    # borrowed by the handle until its next call has read it; no chain yet (the start, a rewind): the float64 chain
+    handle.set_initial_flow_dev(0, _hs_chain_buffer(source, handle) if valid else None)
+
+
+def _fb_chain_buffer(source, handle) -> int:
+    return handle.initial_flow_ptr(0)              # the handle reads its initial flow where the chain is written
+
+
+def _fb_chain_start(source, handle, valid: bool) -> None:
+    if not valid:
+        handle.set_initial_flow(0, _previous_flow_or_zeros(source))     # (prev_flow is None here: float32 zeros)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -662,14 +730,24 @@ class _Method:
     # raw and FlowSource.post_process works on the host array, through a flowops.PostProcess (a flow, a winner map and
     # the mask on the device; no second flow handle).
     resident: bool = False
+    # What the out-of-place resident tail (hip_resident; FlowSource._post_process_chain) needs of a handle that has no
+    # post_process_ex, or whose calls chain.  `flow_ptr`: (handle, pair) -> where the flow of a pair of the last call
+    # sits.  A method whose calls chain -- each starts from the previous output: `initial_flow` above, where its switch
+    # says so -- also says where that output is kept on the device, `chain_buffer`: (source, handle) -> address, and
+    # how a call is started from it, `chain_start`: (source, handle, valid); `valid` false: there is no previous output.
+    flow_ptr: object = lambda handle, pair: handle.flow_ptr(pair)
+    chain_buffer: object = None
+    chain_start: object = None
 
 
 _METHODS = {
     # cv.py:473-490; cv.py:478 with cv2.OPTFLOW_USE_INITIAL_FLOW: a copy of the previous flow, zeros before the first
     FlowConfig: _Method(_open_farneback, initial_flow=_previous_flow_or_zeros,
-                        initial_flow_switch=lambda config: bool(config.fb_flags & 4), resident=True),
+                        initial_flow_switch=lambda config: bool(config.fb_flags & 4), resident=True,
+                        chain_buffer=_fb_chain_buffer, chain_start=_fb_chain_start),
     # cv.py:491-500: the previous (post-processed) flow, or None (the float64 chain from zeros)
-    HornSchunckConfig: _Method(_open_horn_schunck, HornSchunckConfig.hs_kwargs, initial_flow=lambda source: source.prev_flow),
+    HornSchunckConfig: _Method(_open_horn_schunck, HornSchunckConfig.hs_kwargs, initial_flow=lambda source: source.prev_flow,
+                               chain_buffer=_hs_chain_buffer, chain_start=_hs_chain_start),
     # cv.py:501-508: no initial flow
     LucasKanadeConfig: _Method(_open_lucas_kanade, LucasKanadeConfig.lk_kwargs),
     # cv.py:464-465, 509-516: the two frames only, in colour
@@ -681,7 +759,9 @@ assert set(_METHODS) == set(CONFIG_CLASSES)
 class HipFlowSource(FlowSource):
     """CvFlowSource's flow methods on the GPU (cv.py:434-521).  The config says which: its class is the key of
     _METHODS above, where everything this source needs to know of a method is said.  Flows of a method without a
-    resident path always come down to the host, where the post-process runs."""
+    resident path come down to the host, where the post-process runs, unless the config says `hip_resident`: then
+    they go through the out-of-place tail (FlowSource._post_process_chain) and a chaining method's previous output
+    stays on the device too."""
 
     class Builder(FlowSource.Builder):
 
@@ -725,6 +805,7 @@ class HipFlowSource(FlowSource):
         self._pending_pair = 0   # the pair of the call behind the array read_next_flow handed out
         self._prefetch = None
         self._download_token = None
+        self.chain_valid = False  # hip_resident: the chain buffer holds the previous output (what prev_flow stands for)
         FlowSource.__init__(self, *args, **kwargs)
 
     def validate(self):
@@ -755,6 +836,7 @@ class HipFlowSource(FlowSource):
     def prev_gray(self, value):
         self._prev_frame = value
         self._prev_slot = None
+        self.chain_valid = False
         self._batch_left = self._batch_pos = 0     # flows of a hip_batch call made before the seek are not handed out after it
 
     def _ingest(self, slot: int, frame) -> None:
@@ -783,13 +865,15 @@ class HipFlowSource(FlowSource):
                 raise RuntimeError(f"An error occurred while reading frame at index {i}")
         self._prev_frame = frame
         self.prev_flow = None
+        self.chain_valid = False
         self._prev_slot = None
         self._batch_left = self._batch_pos = 0     # (an external rewind while a hip_batch call still had flows queued)
 
     def _batch_size(self) -> int:
-        return max(1, int(self.config.hip_batch)) if self._resident_ok() else 1
+        # a call that starts from the previous output computes one pair, whatever hip_batch says
+        return max(1, int(self.config.hip_batch)) if self._resident_ok() and not self._chains() else 1
 
-    def _advance(self, want: int = 1) -> int:
+    def _advance(self, want: int = 1, resident: bool = False) -> int:
         """cv.py:460-490 up to the call: read a frame, make it grey in a slot no pair still needs, order (prev, next) by
         direction, run the method's handle on the two slots.  The flow stays on the device.  `want` > 1 (FlowConfig.hip_batch): read
         up to that many frames and run their consecutive pairs in ONE call -- frame slots are a ring of hip_batch + 1, the
@@ -818,8 +902,11 @@ class HipFlowSource(FlowSource):
             newer.append(new_slot)
             slot = new_slot
         method = self._method
-        if method.initial_flow is not None and (method.initial_flow_switch is None or self._uses_initial_flow()):
-            fb.set_initial_flow(0, method.initial_flow(self))
+        if self._chains():
+            if resident:
+                method.chain_start(self, fb, self.chain_valid)
+            else:
+                fb.set_initial_flow(0, method.initial_flow(self))
         kw = method.calc_kwargs(self.config)
         if self.direction == FlowSource.Direction.FORWARD:      # cv.py:467-472
             fb.calc_slots(older, newer, **kw)
@@ -838,10 +925,32 @@ class HipFlowSource(FlowSource):
         switch = self._method.initial_flow_switch
         return switch is not None and switch(self.config)
 
+    def _chains(self) -> bool:
+        """Every call starts from the previous OUTPUT (cv.py:478, 495 pass prev_flow, which __next__ has post-processed
+        in place): Horn-Schunck always, Farnebäck where its switch is on."""
+        method = self._method
+        return method.initial_flow is not None and (method.initial_flow_switch is None or self._uses_initial_flow())
+
+    def _own_tail(self) -> bool:
+        """The handle post-processes its flows where they are, and no call reads a previous output: Farnebäck's own
+        resident path."""
+        return self._method.resident and not self._chains()
+
     def _resident_ok(self) -> bool:
-        # with the initial flow switched on every call starts from the previous OUTPUT (cv.py:478 passes a copy of
-        # prev_flow, which __next__ has post-processed in place): that array lives on the host
-        return self._method.resident and not self._uses_initial_flow() and FlowSource._resident_ok(self)
+        # a previous output lives on the host, and so does the raw flow of a method without a resident path, unless
+        # hip_resident keeps both on the device (the out-of-place tail and the chain buffer)
+        return (self._own_tail() or bool(self.config.hip_resident)) and FlowSource._resident_ok(self)
+
+    def _chain_route(self):
+        if self._own_tail():
+            return None
+        chain = self._method.chain_buffer(self, self._fb) if self._chains() else None
+        return self._method.flow_ptr(self._fb, self._pending_pair), chain
+
+    def _post_process_chain(self, raw, src, chain, ops, mask_ptr):
+        out = FlowSource._post_process_chain(self, raw, src, chain, ops, mask_ptr)
+        self.chain_valid = chain is not None
+        return out
 
     def read_next_flow(self):
         if not self._resident_ok():
@@ -852,7 +961,7 @@ class HipFlowSource(FlowSource):
         if self._batch_left == 0:
             # never across the wrap of the input (source.py:286-291: the frame after end_frame is start_frame's)
             until_wrap = self.end_frame - self.input_frame_index if self.end_frame > self.input_frame_index else self._batch_size()
-            self._batch_left = self._advance(min(self._batch_size(), max(1, until_wrap)))
+            self._batch_left = self._advance(min(self._batch_size(), max(1, until_wrap)), resident=True)
             self._batch_pos = 0
         self._pending_pair = self._batch_pos
         self._batch_pos += 1

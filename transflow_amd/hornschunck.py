@@ -78,6 +78,11 @@ class HornSchunck:
             raise ValueError(f"initial flow shape {f.shape} != {(self.height, self.width, 2)}")
         check(self._lib.tf_hs_set_initial_flow(self._h, int(pair), _ptr(f)))
 
+    def set_initial_flow_dev(self, pair: int, flow_dev: int | None) -> None:
+        """The same from a device address (float32 [H][W][2], 8-byte aligned; None: the float64 chain).  Borrowed, not
+        copied: the next calc_slots reads it once, in stream order, and nothing waits on the host."""
+        check(self._lib.tf_hs_set_initial_flow_dev(self._h, int(pair), C.c_void_p(flow_dev) if flow_dev else None))
+
     # -- calls ----------------------------------------------------------------------------
     @staticmethod
     def params(alpha=1, max_iters=3, decay=0, delta=1) -> TfHsParams:
