@@ -722,6 +722,18 @@ int tf_jpeg_copy_last(tf_jpeg *enc, uint8_t *out, size_t capacity, size_t *n_byt
 /* The interval restart_mcus = 0 stands for.  No GPU call: a process that only encodes on the host with the same
    settings (transflow_amd/output.py) asks here. */
 int tf_jpeg_default_restart_mcus(void);
+/* The same encoder with a choice of chroma layout.  `subsampling` is numbered as Pillow's: 0 = 4:4:4 (luma sampling
+   1x1: an MCU is 8 x 8 pixels, blocks Y Cb Cr, the chroma samples as converted), 1 = 4:2:2 (2x1: 16 x 8 pixels, blocks
+   Y0 Y1 Cb Cr, chroma by libjpeg's h2v1_downsample), 2 = 4:2:0 (2x2: tf_jpeg_create, which equals it) -- Pillow's
+   save(quality=q, subsampling=s, restart_marker_blocks=r), byte for byte; of the header only the luma sampling byte of
+   SOF0 differs (0x11, 0x21, 0x22).  `restart_mcus` counts MCUs of the layout's own size.  Every other call takes such
+   a handle as it takes tf_jpeg_create's, tf_jpeg_set_optimize included (its limit is then 3, 4 or 6 blocks * 64 per
+   MCU).  TF_ERR_UNSUPPORTED, with a message, for any other `subsampling`. */
+int tf_jpeg_create_sub(tf_jpeg **out, int height, int width, int quality, int restart_mcus, int subsampling);
+/* The interval restart_mcus = 0 stands for with that layout: 16, 12, 8 MCUs for 0, 1, 2 -- 48 blocks each.  The first two
+   are not tuned as the third is (profiles/jpeg_subsampling_bench.json has them beside half and twice as many).  No GPU
+   call.  TF_ERR_UNSUPPORTED for any other `subsampling`. */
+int tf_jpeg_default_restart_mcus_for(int subsampling);
 /* The Huffman tables of the files.  mode 0 (the default): the Annex K tables, the bytes the files always had.  mode 1:
    the frame's own tables, libjpeg's optimize_coding -- Pillow's save(..., optimize=True), byte for byte: the same pixels
    in a smaller file.  The symbols are counted in a pass of their own, the four tables are made on the device by

@@ -236,6 +236,8 @@ PROTOTYPES = {
     "tf_jpeg_encode": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_jpeg_copy_last": (_I, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_jpeg_default_restart_mcus": (_I, []),
+    "tf_jpeg_create_sub": (_I, [_PP, _I, _I, _I, _I, _I]),
+    "tf_jpeg_default_restart_mcus_for": (_I, [_I]),
     "tf_jpeg_set_optimize": (_I, [_P, _I]),
     "tf_jpeg_last_tables": (_I, [_P, _P, _P, _P]),
     "tf_jpeg_tables_from_counts": (_I, [_P, _P, _P, _P, C.POINTER(C.c_uint32)]),

@@ -311,7 +311,7 @@ class HipCompositor:
 
     def __init__(self, height: int, width: int, layers, background_color: str = "#ffffff", lazy_frames: bool = False,
                  jpeg_frames: int | None = None, png_frames: bool = False, png_code: str = "fixed",
-                 jpeg_optimize: bool = False):
+                 jpeg_optimize: bool = False, jpeg_subsampling=None):
         """lazy_frames: render() returns a DeviceFrame (transflow_amd/deviceframe.py) -- the uint8 (H, W, 3) array to
         everything numpy, its download started but not waited for, so that frame t comes down (pipeline.py:518,
         output/ffmpeg.py:32-54) beside frame t + 1's uploads and kernels (pipeline.py:565).  Default: a plain ndarray.
@@ -319,7 +319,9 @@ class HipCompositor:
         where it is, the deferred one-launch frame included, and only the file comes down (an output whose product is
         a compressed frame: output/mjpeg.py:58-60).  Not together with lazy_frames.  jpeg_optimize: the files carry the
         frame's own Huffman tables (JpegEncoder(optimize=True)): smaller files of the same pixels; False keeps writing
-        the bytes it wrote before.  Only with jpeg_frames.
+        the bytes it wrote before.  Only with jpeg_frames.  jpeg_subsampling: the files' chroma layout, 0 / "4:4:4",
+        1 / "4:2:2" or 2 / "4:2:0" (JpegEncoder(subsampling=...)); None keeps writing 4:2:0, the bytes it wrote before.
+        Only with jpeg_frames.
         png_frames: render() returns a PngFrame (transflow_amd/png.py): the same for the lossless frame-sequence output
         (output/frames.py).  Not together with lazy_frames or jpeg_frames.  png_frames="indexed": the files also carry
         the band index that lets transflow_amd/pngdec.py decode them on the device (PngEncoder(index=True)); True keeps
@@ -334,6 +336,11 @@ class HipCompositor:
             raise ValueError("png_frames excludes lazy_frames and jpeg_frames: a frame leaves in one form")
         if jpeg_optimize and jpeg_frames is None:
             raise ValueError("jpeg_optimize is for jpeg_frames: there is no JPEG to code")
+        if jpeg_subsampling is not None:
+            if jpeg_frames is None:
+                raise ValueError("jpeg_subsampling is for jpeg_frames: there is no JPEG to code")
+            from .jpeg import subsampling_value
+            jpeg_subsampling = subsampling_value(jpeg_subsampling)
         if jpeg_frames is not None:
             if lazy_frames:
                 raise ValueError("jpeg_frames and lazy_frames exclude each other: the encode is not overlapped")
@@ -350,6 +357,7 @@ class HipCompositor:
         self.png_index = isinstance(png_frames, str) and png_frames == "indexed"
         self.png_code = png_code
         self.jpeg_optimize = bool(jpeg_optimize)
+        self.jpeg_subsampling = 2 if jpeg_subsampling is None else jpeg_subsampling
         self._jpeg = None           # the encoder, made at the first render
         self._png = None
         self._comp = None
@@ -388,7 +396,8 @@ class HipCompositor:
         if self.jpeg_frames is not None:
             if self._jpeg is None:
                 from .jpeg import JpegEncoder
-                self._jpeg = JpegEncoder(self.height, self.width, self.jpeg_frames, optimize=self.jpeg_optimize)
+                self._jpeg = JpegEncoder(self.height, self.width, self.jpeg_frames, optimize=self.jpeg_optimize,
+                                         subsampling=self.jpeg_subsampling)
             return self._jpeg.frame(comp)
         if self.png_frames:
             if self._png is None:
@@ -408,7 +417,7 @@ class HipCompositor:
     @classmethod
     def from_args(cls, height: int, width: int, layer_configs, background_color: str = "#ffffff", rng: str = "numpy",
                   lazy_frames: bool = False, jpeg_frames: int | None = None, png_frames: bool = False,
-                  png_code: str = "fixed", jpeg_optimize: bool = False):
+                  png_code: str = "fixed", jpeg_optimize: bool = False, jpeg_subsampling=None):
         layers = []
         for config in layer_configs:
             classname = getattr(config, "classname", "moveref")
@@ -416,7 +425,8 @@ class HipCompositor:
                 raise ValueError(f"Unknown layer classname {classname}")                # layer.py:56
             layers.append(LAYER_CLASSES[classname](config, height, width, [], rng=rng))
         return cls(height, width, layers, background_color=background_color, lazy_frames=lazy_frames,
-                   jpeg_frames=jpeg_frames, png_frames=png_frames, png_code=png_code, jpeg_optimize=jpeg_optimize)
+                   jpeg_frames=jpeg_frames, png_frames=png_frames, png_code=png_code, jpeg_optimize=jpeg_optimize,
+                   jpeg_subsampling=jpeg_subsampling)
 
     def set_sources(self, pixmap_interfaces: dict):
         for i, layer in enumerate(self.layers):
@@ -433,6 +443,7 @@ class HipCompositor:
         self.png_index = bool(state.get("png_index", False))
         self.png_code = state.get("png_code", "fixed")
         self.jpeg_optimize = bool(state.get("jpeg_optimize", False))
+        self.jpeg_subsampling = int(state.get("jpeg_subsampling", 2))
         self._jpeg = None
         self._png = None
         self._comp = None

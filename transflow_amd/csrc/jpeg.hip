@@ -34,6 +34,13 @@
 // Chroma rows (jcprepct.c pre_process_data): the input is padded to an even row count only, and the DOWNSAMPLED plane
 // is then padded with its last row -- a chroma row below the image averages rows H - 2 and H - 1 of an image of even
 // height, not H - 1 twice.
+//
+// The other chroma layouts (tf_jpeg_create_sub; tests/jpeg_sub_ref.py, tests/golden/jpegsub_*.npz): k_jpeg_encode is a
+// template over the layout too.  4:4:4: an MCU is 8 x 8 pixels, blocks Y Cb Cr, the chroma samples as converted, no
+// dummy blocks.  4:2:2: 16 x 8 pixels, blocks Y0 Y1 Cb Cr, chroma by jcsample.c h2v1_downsample -- (a + b + bias) >> 1,
+// bias 0, 1, 0, 1 ... along the output row -- and Y1 a dummy in the last MCU column when ceil(W / 8) is odd.  Edges are
+// replicated samples, which is the clamp of the pixel's coordinates.  Only SOF0's luma sampling byte tells the files
+// apart: 0x11, 0x21, 0x22.
 #include "jpeg_common.h"
 #include "jpeg_huff.h"
 #include "stream_common.h"
@@ -138,12 +145,16 @@ template <int WORDS> __device__ __forceinline__ void place_bits(uint32_t *s_bits
 // tables made on the device (k_jpeg_tables), where a lane's symbols may take 75 bits.
 enum Pass { EMIT = 0, GATHER = 1, EMIT_WIDE = 2 };
 
-template <int PASS> __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const EncodeArgs a, const FastDiv div_mcus_x)
+// SUB is the chroma layout.  A trip of the MCU loop codes one 4:2:0 MCU, or two MCUs of 4:4:4 or 4:2:2 (the second may
+// lie at the start of the next MCU row; an interval of an odd count ends with a trip of one): block b of the trip is
+// block b % BPM of MCU b / BPM, the stages run once per trip, and the bits are flushed once per trip.
+template <int PASS, int SUB> __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const EncodeArgs a, const FastDiv div_mcus_x)
 {
-    constexpr int WORDS = PASS == EMIT_WIDE ? BIT_WORDS_WIDE : (PASS == GATHER ? 1 : BIT_WORDS);
+    constexpr int BPM = mcu_blocks(SUB), TRIP = trip_mcus(SUB), NB = trip_blocks(SUB);
+    constexpr int WORDS = PASS == EMIT_WIDE ? bit_words_wide(SUB) : (PASS == GATHER ? 1 : bit_words(SUB));
     constexpr int HIST = PASS == GATHER ? 4 * 256 : 1;
-    __shared__ int s_blk[6][64];          // samples - 128, then coefficients: Y00 Y01 Y10 Y11 Cb Cr
-    __shared__ uint32_t s_bits[WORDS];    // the MCU's bits, first bit of the stream in bit 31 of word 0
+    __shared__ int s_blk[NB][64];         // samples - 128, then coefficients: the trip's blocks in coding order
+    __shared__ uint32_t s_bits[WORDS];    // the trip's bits, first bit of the stream in bit 31 of word 0
     __shared__ uint32_t s_hist[HIST];     // GATHER: [DC luma, AC luma, DC chroma, AC chroma][symbol]
     const int lane = threadIdx.x;
     const Tables &t = *a.tables;
@@ -160,10 +171,36 @@ template <int PASS> __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const 
     uint32_t outpos = 0; // bytes in the slot
     const int cy = lane >> 3, cx = lane & 7;
     __syncthreads();
-    for (int m = first; m < last; m++) {
+    for (int m = first; m < last; m += TRIP) {
         const int my = (int)fast_div((uint32_t)m, div_mcus_x), mx = m - my * a.mcus_x;
+        const bool two = TRIP == 2 && m + 1 < last;                 // the trip has its second MCU (wave-uniform)
+        const int mx1 = mx + 1 < a.mcus_x ? mx + 1 : 0, my1 = mx + 1 < a.mcus_x ? my : my + 1; // where that one is
         // ---- colour, downsample
-        {
+        if constexpr (SUB == S444) { // lane l owns pixel l of each MCU; the edges are replicated samples
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                if (k == 1 && !two)
+                    break;
+                const int x = min((k ? mx1 : mx) * 8 + cx, a.W - 1), y = min((k ? my1 : my) * 8 + cy, a.H - 1);
+                const Px p = load_px(a.rgb, a.W, y, x);
+                s_blk[3 * k][lane] = ycc_y(p) - 128;
+                s_blk[3 * k + 1][lane] = ycc_cb(p) - 128;
+                s_blk[3 * k + 2][lane] = ycc_cr(p) - 128;
+            }
+        } else if constexpr (SUB == S422) { // lane l owns the 2 x 1 pixels under chroma sample l of each MCU
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                if (k == 1 && !two)
+                    break;
+                const int xb = (k ? mx1 : mx) * 16 + 2 * cx, y = min((k ? my1 : my) * 8 + cy, a.H - 1);
+                const Px p0 = load_px(a.rgb, a.W, y, min(xb, a.W - 1)), p1 = load_px(a.rgb, a.W, y, min(xb + 1, a.W - 1));
+                int *yb = &s_blk[4 * k + (cx >> 2)][cy * 8 + ((2 * cx) & 7)];
+                yb[0] = ycc_y(p0) - 128, yb[1] = ycc_y(p1) - 128;
+                const int bias = cx & 1; // 0, 1, 0, 1 ... along the output row (jcsample.c h2v1_downsample)
+                s_blk[4 * k + 2][lane] = ((ycc_cb(p0) + ycc_cb(p1) + bias) >> 1) - 128;
+                s_blk[4 * k + 3][lane] = ((ycc_cr(p0) + ycc_cr(p1) + bias) >> 1) - 128;
+            }
+        } else {
             const int x0 = min(mx * 16 + 2 * cx, a.W - 1), x1 = min(mx * 16 + 2 * cx + 1, a.W - 1);
             const int y0 = min(my * 16 + 2 * cy, a.H - 1), y1 = min(my * 16 + 2 * cy + 1, a.H - 1);
             Px p00 = load_px(a.rgb, a.W, y0, x0), p01 = load_px(a.rgb, a.W, y0, x1);
@@ -182,23 +219,32 @@ template <int PASS> __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const 
         }
         __syncthreads();
         // ---- DCT: rows, then columns
-        if (lane < 48)
+        const int dct_lanes = 8 * (TRIP == 1 || two ? NB : BPM);
+        if (lane < dct_lanes)
             fdct_pass<true>(&s_blk[lane >> 3][(lane & 7) * 8], 1);
         __syncthreads();
-        if (lane < 48)
+        if (lane < dct_lanes)
             fdct_pass<false>(&s_blk[lane >> 3][lane & 7], 8);
         __syncthreads();
         // ---- quantise and code, block by block
         int prev_dc = 0;
 #pragma unroll
-        for (int b = 0; b < 6; b++) {
-            const int comp = b < 4 ? 0 : b - 3, tb = b < 4 ? 0 : 1;
+        for (int b = 0; b < NB; b++) {
+            if (TRIP == 2 && b >= BPM && !two)
+                break;
+            const int bi = b % BPM, n_luma = BPM - 2; // the block within its MCU; the luma blocks come first
+            const int comp = bi < n_luma ? 0 : bi - n_luma + 1, tb = bi < n_luma ? 0 : 1;
             const int c = s_blk[b][zz];
             const uint32_t q8 = (uint32_t)(tb ? q_chroma : q_luma);
             const uint32_t mag = ((uint32_t)abs(c) + (q8 >> 1)) / q8;
             int v = c < 0 ? -(int)mag : (int)mag;
-            if (b > 0 && b < 4 && (2 * mx + (b & 1) >= a.lum_bx || 2 * my + (b >> 1) >= a.lum_by))
-                v = lane == 0 ? prev_dc : 0; // a dummy block
+            bool dummy = false; // (4:4:4 has none; 4:2:2 only the second luma block, in the last MCU column)
+            if (SUB == S420)
+                dummy = b > 0 && b < 4 && (2 * mx + (b & 1) >= a.lum_bx || 2 * my + (b >> 1) >= a.lum_by);
+            else if (SUB == S422)
+                dummy = bi == 1 && 2 * (b < BPM ? mx : mx1) + 1 >= a.lum_bx;
+            if (dummy)
+                v = lane == 0 ? prev_dc : 0;
             if (lane > 0)
                 v = max(-1023, min(1023, v)); // (never: an AC coefficient of 8-bit samples has 10 bits)
             const int dc = __builtin_amdgcn_readfirstlane(v);
@@ -271,8 +317,8 @@ template <int PASS> __global__ __launch_bounds__(WAVE) void k_jpeg_encode(const 
             __syncthreads(); // s_blk is the next MCU's
             continue;        // nothing to flush
         }
-        // ---- the MCU's whole bytes to the slot; the interval's last MCU pads with ones first (flush_bits)
-        if (m == last - 1 && (bitpos & 7)) {
+        // ---- the trip's whole bytes to the slot; the interval's last trip pads with ones first (flush_bits)
+        if (m + TRIP >= last && (bitpos & 7)) {
             const uint32_t pad = 8 - (bitpos & 7);
             if (lane == 0)
                 atomicOr(&s_bits[bitpos >> 5], ((1u << pad) - 1) << (32 - (bitpos & 31) - pad));
@@ -532,8 +578,9 @@ struct Dht {
 static const Dht ANNEX_K[4] = {{DC_LUMA_BITS, DC_LUMA_VALS}, {AC_LUMA_BITS, AC_LUMA_VALS}, {DC_CHROMA_BITS, DC_CHROMA_VALS},
                                {AC_CHROMA_BITS, AC_CHROMA_VALS}};
 
-static std::vector<uint8_t> make_header(int H, int W, const uint8_t q[2][64], int restart_mcus, const Dht *dht = ANNEX_K)
+static std::vector<uint8_t> make_header(int H, int W, const uint8_t q[2][64], int restart_mcus, int sub, const Dht *dht = ANNEX_K)
 {
+    const uint8_t luma_sampling = (uint8_t)((mcu_width(sub) / 8) << 4 | (mcu_height(sub) / 8)); // 0x11, 0x21, 0x22
     std::vector<uint8_t> out{0xFF, 0xD8};
     put_segment(out, 0xE0, {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
     for (int n = 0; n < 2; n++) {
@@ -542,7 +589,8 @@ static std::vector<uint8_t> make_header(int H, int W, const uint8_t q[2][64], in
             p.push_back(q[n][ZIGZAG[k]]);
         put_segment(out, 0xDB, p);
     }
-    put_segment(out, 0xC0, {8, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1});
+    put_segment(out, 0xC0, {8, (uint8_t)(H >> 8), (uint8_t)H, (uint8_t)(W >> 8), (uint8_t)W, 3, 1, luma_sampling, 0, 2, 0x11, 1, 3,
+                            0x11, 1});
     put_dht(out, 0x00, dht[0].bits, dht[0].vals);
     put_dht(out, 0x10, dht[1].bits, dht[1].vals);
     put_dht(out, 0x01, dht[2].bits, dht[2].vals);
@@ -562,9 +610,14 @@ using namespace tf::jpeg;
 // row, at 4K and at 1080p alike (tools/bench_jpeg.py, profiles/jpeg_bench.json; DESIGN.md section 15 has the table).
 // Shorter intervals pay in markers and restarted DC prediction, longer ones in waves that code more MCUs one by one.
 static constexpr int DEFAULT_RESTART_MCUS = 8;
+// The other layouts keep that interval's 48 blocks: 16 MCUs of three, 12 of four.  Not tuned: tools/bench_jpeg_subsampling.py
+// measures them beside half and twice as many.
+static constexpr int default_restart_mcus(int sub) { return DEFAULT_RESTART_MCUS * mcu_blocks(S420) / mcu_blocks(sub); }
+static_assert(default_restart_mcus(S444) == 16 && default_restart_mcus(S422) == 12 && default_restart_mcus(S420) == 8, "48 blocks");
 
 struct tf_jpeg {
     int H = 0, W = 0, quality = 0, restart_mcus = 0;
+    int sub = S420; // the chroma layout: a Sampling
     int mcus_x = 0, n_mcus = 0, n_intervals = 0;
     std::vector<uint8_t> header;
     DevBuf tables, upload;
@@ -625,7 +678,7 @@ TF_API int tf_jpeg_set_optimize(tf_jpeg *enc, int mode)
     TF_REQUIRE(enc, "tf_jpeg_set_optimize: null pointer");
     TF_REQUIRE(mode == 0 || mode == 1, "tf_jpeg_set_optimize: mode %d (0: the Annex K tables, 1: the frame's own)", mode);
     // a frequency stays at or below libjpeg's selection sentinel, and within uint32_t (jpeg_huff.h)
-    TF_REQUIRE(mode == 0 || (long long)6 * 64 * enc->n_mcus <= (long long)HUFF_SENTINEL,
+    TF_REQUIRE(mode == 0 || (long long)mcu_blocks(enc->sub) * 64 * enc->n_mcus <= (long long)HUFF_SENTINEL,
                "tf_jpeg_set_optimize: %dx%d has more than %u coefficients", enc->W, enc->H, HUFF_SENTINEL);
     if (mode != enc->optimize) {
         enc->optimize = mode;
@@ -637,7 +690,7 @@ TF_API int tf_jpeg_set_optimize(tf_jpeg *enc, int mode)
 
 TF_API void tf_jpeg_destroy(tf_jpeg *enc) { delete enc; }
 
-TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int restart_mcus)
+TF_API int tf_jpeg_create_sub(tf_jpeg **out, int height, int width, int quality, int restart_mcus, int subsampling)
 {
     TF_REQUIRE(out, "tf_jpeg_create: null pointer");
     *out = nullptr;
@@ -646,13 +699,15 @@ TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int
     TF_REQUIRE(quality >= 1 && quality <= 100, "tf_jpeg_create: quality %d (1 to 100)", quality);
     TF_REQUIRE(restart_mcus >= 0 && restart_mcus <= 65535, "tf_jpeg_create: restart interval %d (0 = default, 1 to 65535)",
                restart_mcus);
+    if (subsampling != S444 && subsampling != S422 && subsampling != S420)
+        return set_error(TF_ERR_UNSUPPORTED, "tf_jpeg_create_sub: subsampling %d (0: 4:4:4, 1: 4:2:2, 2: 4:2:0)", subsampling);
     TF_TRY(ensure_init());
     auto enc = make_handle<tf_jpeg>();
     TF_REQUIRE(enc, "tf_jpeg_create: out of memory");
-    enc->H = height, enc->W = width, enc->quality = quality;
-    enc->restart_mcus = restart_mcus ? restart_mcus : DEFAULT_RESTART_MCUS;
-    enc->mcus_x = (width + 15) / 16;
-    enc->n_mcus = enc->mcus_x * ((height + 15) / 16);
+    enc->H = height, enc->W = width, enc->quality = quality, enc->sub = subsampling;
+    enc->restart_mcus = restart_mcus ? restart_mcus : default_restart_mcus(subsampling);
+    enc->mcus_x = cdiv(width, mcu_width(subsampling));
+    enc->n_mcus = enc->mcus_x * cdiv(height, mcu_height(subsampling)); // (at most 8192 x 8192 = 2^26)
     enc->n_intervals = (enc->n_mcus + enc->restart_mcus - 1) / enc->restart_mcus;
 
     Tables t;
@@ -668,18 +723,23 @@ TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int
     huff_entries(DC_CHROMA_BITS, DC_CHROMA_VALS, t.dc[1], 16);
     huff_entries(AC_LUMA_BITS, AC_LUMA_VALS, t.ac[0], 256);
     huff_entries(AC_CHROMA_BITS, AC_CHROMA_VALS, t.ac[1], 256);
-    enc->header = make_header(height, width, q, enc->restart_mcus);
+    enc->header = make_header(height, width, q, enc->restart_mcus, enc->sub);
 
     for (int c = 0; c < 2; c++) // a lane's symbols: three ZRLs, a code, 10 value bits (11 with a DC code)
         if (3 * (t.ac[c][0xF0] >> 16) + 16 + 10 > (uint32_t)LANE_MAX_BITS)
             return set_error(TF_ERR_STATE, "tf_jpeg_create: a lane's symbols would not fit %d bits", LANE_MAX_BITS);
     TF_TRY(enc->tables.alloc(sizeof(Tables)));
     // (an interval longer than the image codes n_mcus MCUs: its slot need not be larger than that)
-    TF_TRY(enc->s.alloc(enc->n_intervals, (uint32_t)slot_bytes(enc->restart_mcus < enc->n_mcus ? enc->restart_mcus : enc->n_mcus), 2));
+    TF_TRY(enc->s.alloc(enc->n_intervals, (uint32_t)slot_bytes(enc->restart_mcus < enc->n_mcus ? enc->restart_mcus : enc->n_mcus, enc->sub), 2));
     TF_HIP(hipMemcpyAsync(enc->tables.p, &t, sizeof(Tables), hipMemcpyHostToDevice, stream()));
     TF_HIP(hipStreamSynchronize(stream())); // `t` is on this stack
     *out = enc.release();
     return TF_OK;
+}
+
+TF_API int tf_jpeg_create(tf_jpeg **out, int height, int width, int quality, int restart_mcus)
+{
+    return tf_jpeg_create_sub(out, height, width, quality, restart_mcus, S420);
 }
 
 TF_API int tf_jpeg_header(tf_jpeg *enc, const uint8_t **bytes, size_t *n)
@@ -691,6 +751,15 @@ TF_API int tf_jpeg_header(tf_jpeg *enc, const uint8_t **bytes, size_t *n)
     *bytes = enc->file_header().data();
     *n = enc->file_header().size();
     return TF_OK;
+}
+
+// one pass of the encode kernel, in the handle's layout
+template <int PASS> static int encode_pass(const char *label, const tf_jpeg *enc, const EncodeArgs &a, const FastDiv &div)
+{
+    const auto kernel = enc->sub == S444   ? k_jpeg_encode<PASS, S444>
+                        : enc->sub == S422 ? k_jpeg_encode<PASS, S422>
+                                           : k_jpeg_encode<PASS, S420>;
+    return launch(label, kernel, dim3(enc->n_intervals), dim3(WAVE), 0, a, div);
 }
 
 // the slots to their places in the packed stream, as far as `dev_capacity` reaches
@@ -724,12 +793,12 @@ TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, s
     if (enc->optimize) { // count, make the tables, code with them
         OwnTables *own = enc->own.as<OwnTables>();
         a.counts = &own->partial[0][0][0];
-        TF_TRY(launch("jpeg_gather", k_jpeg_encode<GATHER>, dim3(enc->n_intervals), dim3(WAVE), 0, a, div));
+        TF_TRY(encode_pass<GATHER>("jpeg_gather", enc, a, div));
         TF_TRY(make_tables(enc));
         a.tables = enc->own_tables.as<Tables>();
-        TF_TRY(launch("jpeg_emit", k_jpeg_encode<EMIT_WIDE>, dim3(enc->n_intervals), dim3(WAVE), 0, a, div));
+        TF_TRY(encode_pass<EMIT_WIDE>("jpeg_emit", enc, a, div));
     } else {
-        TF_TRY(launch("jpeg_encode", k_jpeg_encode<EMIT>, dim3(enc->n_intervals), dim3(WAVE), 0, a, div));
+        TF_TRY(encode_pass<EMIT>("jpeg_encode", enc, a, div));
     }
     TF_TRY(s.scan("jpeg_scan"));
     // (the frame's own header is not known before the kernels have run)
@@ -743,7 +812,7 @@ TF_API int tf_jpeg_encode_dev(tf_jpeg *enc, const void *rgb_dev, uint8_t *out, s
         const OwnResult &r = *enc->own_host.as<OwnResult>();
         TF_TRY(own_fault("tf_jpeg_encode_dev", r.fault));
         const Dht dht[4] = {{r.bits[0], r.vals[0]}, {r.bits[1], r.vals[1]}, {r.bits[2], r.vals[2]}, {r.bits[3], r.vals[3]}};
-        enc->own_header = make_header(enc->H, enc->W, enc->q, enc->restart_mcus, dht);
+        enc->own_header = make_header(enc->H, enc->W, enc->q, enc->restart_mcus, enc->sub, dht);
     }
     TF_TRY(s.finish("tf_jpeg_encode_dev", "an interval"));
     return s.copy_out("tf_jpeg_encode_dev", enc->file_header(), {}, out, capacity, n_bytes);
@@ -803,6 +872,14 @@ TF_API int tf_jpeg_tables_from_counts(tf_jpeg *enc, const uint32_t *counts, uint
 }
 
 TF_API int tf_jpeg_default_restart_mcus(void) { return DEFAULT_RESTART_MCUS; }
+
+TF_API int tf_jpeg_default_restart_mcus_for(int subsampling)
+{
+    if (subsampling != S444 && subsampling != S422 && subsampling != S420)
+        return set_error(TF_ERR_UNSUPPORTED, "tf_jpeg_default_restart_mcus_for: subsampling %d (0: 4:4:4, 1: 4:2:2, 2: 4:2:0)",
+                         subsampling);
+    return default_restart_mcus(subsampling);
+}
 
 TF_API int tf_jpeg_encode(tf_jpeg *enc, const uint8_t *rgb_host, uint8_t *out, size_t capacity, size_t *n_bytes)
 {

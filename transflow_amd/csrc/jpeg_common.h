@@ -93,23 +93,34 @@ struct Tables {
 // The interval is padded to a byte once, and every byte can be an 0xFF that takes an 0x00 after it.
 // The bound assumes a 16-bit code for every symbol, so it holds for the frame's own tables (mode 1) as it stands.
 constexpr int BLOCK_MAX_BITS = 16 + 11 + 63 * (16 + 10);
-constexpr int MCU_MAX_BITS = 6 * BLOCK_MAX_BITS;
-inline size_t slot_bytes(int restart_mcus)
+
+// ---- the chroma layouts, numbered as Pillow's `subsampling`.  An MCU is 8 x 8 pixels with blocks Y Cb Cr, 16 x 8 with
+// Y0 Y1 Cb Cr, or 16 x 16 with Y00 Y01 Y10 Y11 Cb Cr.  The kernel codes a "trip" at a time: one 4:2:0 MCU, or two MCUs of
+// the smaller layouts -- 6, 8 and 6 blocks, which keep the 48 or 64 lanes of the DCT passes busy.
+enum Sampling { S444 = 0, S422 = 1, S420 = 2 };
+constexpr int mcu_width(int sub) { return sub == S444 ? 8 : 16; }
+constexpr int mcu_height(int sub) { return sub == S420 ? 16 : 8; }
+constexpr int mcu_blocks(int sub) { return sub == S444 ? 3 : (sub == S422 ? 4 : 6); }
+constexpr int trip_mcus(int sub) { return sub == S420 ? 1 : 2; }
+constexpr int trip_blocks(int sub) { return mcu_blocks(sub) * trip_mcus(sub); }
+
+constexpr int mcu_max_bits(int sub) { return mcu_blocks(sub) * BLOCK_MAX_BITS; }
+inline size_t slot_bytes(int restart_mcus, int sub)
 {
-    const size_t bytes = ((size_t)restart_mcus * MCU_MAX_BITS + 7) / 8; // with the padding
-    return (2 * bytes + 3) & ~(size_t)3;                                // stuffed; slots stay dword-aligned
+    const size_t bytes = ((size_t)restart_mcus * mcu_max_bits(sub) + 7) / 8; // with the padding
+    return (2 * bytes + 3) & ~(size_t)3;                                     // stuffed; slots stay dword-aligned
 }
 
-// The LDS bit buffer of a wave holds one MCU and the 7 bits carried into it.  It is sized for what 64 lanes can
+// The LDS bit buffer of a wave holds one trip and the 7 bits carried into it.  It is sized for what 64 lanes can
 // physically OR into it per block -- a lane's symbols are at most 64 bits, checked on the host when the tables are made
 // -- not for the bound above: no data can make the kernel write outside it.
 constexpr int LANE_MAX_BITS = 64;
-constexpr int BIT_WORDS = (8 + 6 * 64 * LANE_MAX_BITS) / 32 + 3;
+constexpr int bit_words(int sub) { return (8 + trip_blocks(sub) * 64 * LANE_MAX_BITS) / 32 + 3; }
 // With the frame's own tables nothing is checked on the host: ZRL may have a 16-bit code like any other symbol, and a
 // lane's three ZRLs, its code and an 11-bit value come to 75 bits.  That kernel places a lane's bits as two pieces, the
 // ZRLs (at most 48 bits) and the code with its value (at most 27), and its buffer is sized for 75.
 constexpr int LANE_MAX_BITS_WIDE = 3 * 16 + 16 + 11;
-constexpr int BIT_WORDS_WIDE = (8 + 6 * 64 * LANE_MAX_BITS_WIDE) / 32 + 3;
+constexpr int bit_words_wide(int sub) { return (8 + trip_blocks(sub) * 64 * LANE_MAX_BITS_WIDE) / 32 + 3; }
 
 // ---- mode 1, the frame's own tables: what the gather pass counts and what k_jpeg_tables makes of it.  The four tables
 // are in the order of the file's DHT segments: DC luma, AC luma, DC chroma, AC chroma.

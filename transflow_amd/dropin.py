@@ -90,29 +90,38 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
 
 
 def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_frames=False, png_code="fixed",
-                          jpeg_optimize=False):
+                          jpeg_optimize=False, jpeg_subsampling=None):
     from .compositor import LAYER_CLASSES, HipCompositor
 
     def from_args(cls, height, width, layer_configs, background_color="#ffffff"):
         if all(getattr(c, "classname", None) in LAYER_CLASSES for c in layer_configs):
             return HipCompositor.from_args(height, width, layer_configs, background_color=background_color,
                                            lazy_frames=lazy_frames, jpeg_frames=jpeg_frames, png_frames=png_frames,
-                                           png_code=png_code, jpeg_optimize=jpeg_optimize)
+                                           png_code=png_code, jpeg_optimize=jpeg_optimize,
+                                           jpeg_subsampling=jpeg_subsampling)
         return original(height, width, layer_configs, background_color=background_color)
 
     return classmethod(from_args)
 
 
-def _output_from_args(original, quality, optimize=False):
-    from .output import HipMjpegOutput, RawFramesOnly, mjpeg_address
+def _output_from_args(original, quality, optimize=False, subsampling=2):
+    from .output import (HipFramesOutput, HipMjpegFileOutput, HipMjpegOutput, RawFramesOnly, jpeg_template, mjpeg_address,
+                         mjpeg_file_path)
 
     def from_args(cls, path, width, height, framerate=None, vcodec="h264", execute=False, replace=False, initial_counter=0):
         address = mjpeg_address(path)
-        if address is None:         # the reference's own output; it takes pixels, and says so if it is given a file
-            return RawFramesOnly(original(path, width, height, framerate=framerate, vcodec=vcodec, execute=execute,
-                                          replace=replace, initial_counter=initial_counter))
-        return HipMjpegOutput(address[0], address[1], width, height, 30 if framerate is None else framerate, quality,
-                              optimize=optimize)
+        if address is not None:
+            return HipMjpegOutput(address[0], address[1], width, height, 30 if framerate is None else framerate, quality,
+                                  optimize=optimize, subsampling=subsampling)
+        if jpeg_template(path):     # `out/%05d.jpg`: a file a frame
+            return HipFramesOutput(path, width, height, initial_counter, execute, quality=quality, subsampling=subsampling,
+                                   optimize=optimize)
+        if mjpeg_file_path(path):   # `out.mjpeg`: the files back to back, what the device decoder's inputs are read as
+            return HipMjpegFileOutput(path, width, height, 30 if framerate is None else framerate, quality,
+                                      subsampling=subsampling, optimize=optimize, execute=execute, replace=replace)
+        # the reference's own output; it takes pixels, and says so if it is given a file
+        return RawFramesOnly(original(path, width, height, framerate=framerate, vcodec=vcodec, execute=execute,
+                                      replace=replace, initial_counter=initial_counter))
 
     return classmethod(from_args)
 
@@ -149,7 +158,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
             device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed",
-            jpeg_optimize: bool = False) -> None:
+            jpeg_optimize: bool = False, jpeg_subsampling=None) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -168,11 +177,16 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     jpeg_frames: a JPEG quality -- the compositors built for the pipeline return JpegFrames from render()
     (transflow_amd/jpeg.py: encoded on the device, only the file comes down and crosses to the output process), and
     VideoOutput.from_args (pipeline.py's output process) builds a HipMjpegOutput (transflow_amd/output.py) for `mjpeg...`
-    paths; any other output is the reference's own and raises a TypeError that names this option when it is fed a
-    JpegFrame.  Not together with lazy_frames.  By default (None) nothing of this is touched.
+    paths, a HipFramesOutput for `%d` templates that end in .jpg / .jpeg (a file a frame) and a HipMjpegFileOutput for
+    paths with a .mjpeg / .mjpg extension (a raw MJPEG stream, the form `mjpeg_inputs` reads); any other output is the
+    reference's own and raises a TypeError that names this option when it is fed a JpegFrame.  Not together with lazy_frames.  By default (None) nothing of this is touched.
     jpeg_optimize: with jpeg_frames, the files carry the frame's own Huffman tables (JpegEncoder(optimize=True),
     DESIGN.md section 15; libjpeg's optimize_coding): smaller files of the same pixels, and a raw frame that reaches the
     MJPEG output is encoded on the host with the same setting; False (the default) keeps writing the bytes it wrote before.
+    jpeg_subsampling: with jpeg_frames, the files' chroma layout -- 0 / "4:4:4", 1 / "4:2:2" or 2 / "4:2:0"
+    (JpegEncoder(subsampling=...)): 4:4:4 keeps the one-pixel colour edges of a rendered frame that
+    4:2:0 averages; a raw frame that reaches one of the three JPEG outputs is encoded on the host with the same layout;
+    None (the default) keeps writing 4:2:0, the bytes it wrote before.
     png_frames: the compositors built for the pipeline return PngFrames from render() (transflow_amd/png.py: the
     lossless file, made on the device), and VideoOutput.from_args builds a HipFramesOutput (transflow_amd/output.py) for
     `%d` templates that end in `.png`; any other output is the reference's own and raises a TypeError that names this
@@ -212,6 +226,11 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         raise ValueError("png_code is for png_frames: without them no PNG is written")
     if jpeg_optimize and jpeg_frames is None:
         raise ValueError("jpeg_optimize is for jpeg_frames: without them no JPEG is written")
+    if jpeg_subsampling is not None:
+        if jpeg_frames is None:
+            raise ValueError("jpeg_subsampling is for jpeg_frames: without them no JPEG is written")
+        from .jpeg import subsampling_value
+        jpeg_subsampling = subsampling_value(jpeg_subsampling)
     if flow and "flow" not in _saved:
         from transflow.flow.sources.source import FlowSource as RefFlowSource
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
@@ -226,11 +245,12 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
         RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames,
                                                         "indexed" if png_frames == "indexed" else bool(png_frames), png_code,
-                                                        bool(jpeg_optimize))
+                                                        bool(jpeg_optimize), jpeg_subsampling)
     if jpeg_frames is not None and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
-        RefVideoOutput.from_args = _output_from_args(RefVideoOutput.from_args, int(jpeg_frames), bool(jpeg_optimize))
+        RefVideoOutput.from_args = _output_from_args(RefVideoOutput.from_args, int(jpeg_frames), bool(jpeg_optimize),
+                                                     2 if jpeg_subsampling is None else jpeg_subsampling)
     if png_frames and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])

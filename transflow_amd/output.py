@@ -8,7 +8,12 @@ opens the GPU.  The reference's server and handler are used unchanged and import
 else here works without aiohttp, netifaces or cv2.
 
 `HipFramesOutput` is the same for the frame-sequence output (transflow/output/frames.py, `-o out/%05d.png`): a `PngFrame`
-(transflow_amd/png.py) is written to its file as it is, a raw array is encoded by Pillow on the host.
+(transflow_amd/png.py) is written to its file as it is, a raw array is encoded by Pillow on the host.  A template that
+ends in `.jpg` / `.jpeg` takes `JpegFrame`s the same way.
+
+`HipMjpegFileOutput` appends the frames' JPEG files to one file, a raw MJPEG stream: the form the device decoder's
+inputs are read in (`MJPEG_EXTS`; transflow_amd/jpegdec.py MjpegFrameProvider, transflow_amd/pixmap.py), so a render
+recorded this way can be fed back as a flow or pixmap input without leaving the device path.
 """
 from __future__ import annotations
 
@@ -18,15 +23,25 @@ import re
 
 import numpy as np
 
-from .jpeg import JpegFrame, pillow_encode
+from .jpeg import JpegFrame, pillow_encode, subsampling_value
 from .png import PngFrame, pillow_encode_png
 
 
-def default_restart_mcus() -> int:
+def default_restart_mcus(subsampling=None) -> int:
     """What a raw frame is encoded with on the host: the device encoder's default interval, asked of the library (the
-    call loads it and touches no GPU)."""
+    call loads it and touches no GPU).  With a `subsampling`, that layout's default."""
     from . import _lib
-    return int(_lib.load().tf_jpeg_default_restart_mcus())
+    if subsampling is None:
+        return int(_lib.load().tf_jpeg_default_restart_mcus())
+    return int(_lib.load().tf_jpeg_default_restart_mcus_for(subsampling_value(subsampling)))
+
+
+def _host_jpeg(frame, quality: int, restart_mcus, optimize: bool, subsampling: int) -> bytes:
+    """A raw frame as the device encoder would have written it: Pillow with the same settings (restart_mcus None: the
+    library's default for the layout)."""
+    if restart_mcus is None:
+        restart_mcus = default_restart_mcus(subsampling)
+    return pillow_encode(np.asarray(frame), quality, restart_mcus, optimize, subsampling)
 
 
 class _Encoded:
@@ -47,8 +62,9 @@ class HipMjpegStream:
     `name`, `fps`, `set_frame`, `get_frame`, `get_frame_processed`, `get_bandwidth`."""
 
     def __init__(self, name: str, size, quality: int = 50, fps: float = 30, restart_mcus: int | None = None,
-                 optimize: bool = False):
+                 optimize: bool = False, subsampling=2):
         self.optimize = bool(optimize)                     # a raw frame is encoded with its own Huffman tables
+        self.subsampling = subsampling_value(subsampling)  # ... and with this chroma layout
         self.name = name.lower().casefold().replace(" ", "_")
         self.size = size                                   # (width, height)
         self.quality = max(1, min(int(quality), 100))
@@ -68,8 +84,8 @@ class HipMjpegStream:
             data = frame.tobytes()
         else:
             if self.restart_mcus is None:
-                self.restart_mcus = default_restart_mcus()
-            data = pillow_encode(np.asarray(frame), self.quality, self.restart_mcus, self.optimize)
+                self.restart_mcus = default_restart_mcus(self.subsampling)
+            data = _host_jpeg(frame, self.quality, self.restart_mcus, self.optimize, self.subsampling)
         self._sizes = (self._sizes + [len(data)])[-30:]
         return _Encoded(data)
 
@@ -87,12 +103,13 @@ class HipMjpegOutput:
     """Same constructor, context-manager protocol and `feed` as transflow's MjpegOutput."""
 
     def __init__(self, host: str, port: int, width: int, height: int, framerate: float, quality: int = 50,
-                 optimize: bool = False):
+                 optimize: bool = False, subsampling=2):
         self.width, self.height = int(width), int(height)
         self.host, self.port = host, port
         self.framerate = framerate
         self.quality = quality
-        self.stream = HipMjpegStream("transflow", (self.width, self.height), quality=quality, fps=framerate, optimize=optimize)
+        self.stream = HipMjpegStream("transflow", (self.width, self.height), quality=quality, fps=framerate, optimize=optimize,
+                                     subsampling=subsampling)
         self.server = None
 
     @property
@@ -141,17 +158,40 @@ def png_template(path) -> bool:
     return isinstance(path, str) and FRAMES_PATH.search(path) is not None and path.lower().endswith(".png")
 
 
+JPEG_FILE_EXTS = (".jpg", ".jpeg")
+
+
+def jpeg_template(path) -> bool:
+    """Whether an output path is a frame-sequence template whose files are JPEGs."""
+    return isinstance(path, str) and FRAMES_PATH.search(path) is not None and path.lower().endswith(JPEG_FILE_EXTS)
+
+
+def mjpeg_file_path(path) -> bool:
+    """Whether an output path names a raw MJPEG stream file: an extension the device decoder's inputs are found by."""
+    from .pixmap import MJPEG_EXTS
+    return isinstance(path, str) and FRAMES_PATH.search(path) is None and os.path.splitext(path)[1].lower() in MJPEG_EXTS
+
+
 class HipFramesOutput:
     """Same constructor, context-manager protocol and `feed` as transflow's FramesVideoOutput (frames.py:15-36): frame
     n goes to `template % (initial_counter + n)`.  A PngFrame's bytes are the file; a raw array (what the pipeline
-    feeds when the output is a flow rendering) is encoded by Pillow here.  Never opens the GPU."""
+    feeds when the output is a flow rendering) is encoded by Pillow here.  A template that ends in .jpg / .jpeg writes
+    JPEG files instead: a JpegFrame's bytes are the file, and a raw array is encoded by `pillow_encode` with this
+    output's `quality`, `subsampling`, `restart_mcus` (None: the library's default for the layout) and `optimize`.
+    Never opens the GPU."""
 
-    def __init__(self, template: str, width: int, height: int, initial_counter: int = 0, execute: bool = False):
+    def __init__(self, template: str, width: int, height: int, initial_counter: int = 0, execute: bool = False,
+                 quality: int = 50, subsampling=2, restart_mcus: int | None = None, optimize: bool = False):
         self.width, self.height = int(width), int(height)
         self.template = template
         self.directory = pathlib.Path(self.template).parent
         self.execute = execute
         self.counter = initial_counter
+        self.jpeg = template.lower().endswith(JPEG_FILE_EXTS)
+        self.quality = max(1, min(int(quality), 100))
+        self.subsampling = subsampling_value(subsampling)
+        self.restart_mcus = None if restart_mcus is None else int(restart_mcus)
+        self.optimize = bool(optimize)
 
     @property
     def output_path(self):
@@ -168,9 +208,17 @@ class HipFramesOutput:
             frame = frame[0]
         if tuple(frame.shape[:2]) != (self.height, self.width):
             raise ValueError(f"the output is {self.height} x {self.width}, the frame {tuple(frame.shape[:2])}")
-        if isinstance(frame, JpegFrame):
-            raise TypeError("HipFramesOutput writes PNG files, not JPEG files: install(jpeg_frames=...) serves the mjpeg output only")
-        data = frame.tobytes() if isinstance(frame, PngFrame) else pillow_encode_png(np.asarray(frame))
+        if self.jpeg:
+            if isinstance(frame, PngFrame):
+                raise TypeError(f"HipFramesOutput writes JPEG files to {self.template}, not PNG files: "
+                                "install(png_frames=True) serves %d ... .png frame templates")
+            data = frame.tobytes() if isinstance(frame, JpegFrame) else _host_jpeg(frame, self.quality, self.restart_mcus,
+                                                                                   self.optimize, self.subsampling)
+        else:
+            if isinstance(frame, JpegFrame):
+                raise TypeError("HipFramesOutput writes PNG files, not JPEG files: install(jpeg_frames=...) serves the mjpeg "
+                                "output, %d ... .jpg frame templates and .mjpeg files")
+            data = frame.tobytes() if isinstance(frame, PngFrame) else pillow_encode_png(np.asarray(frame))
         with open(self.template % self.counter, "wb") as f:
             f.write(data)
         self.counter += 1
@@ -181,10 +229,78 @@ class HipFramesOutput:
             startfile(self.directory.as_posix())
 
 
+def _unique_path(path: str) -> str:
+    """The reference's find_unique_path (utils.py:147-160), as FFmpegVideoOutput uses it (ffmpeg.py:21); where transflow
+    is not importable, this package's statement of the same naming (transflow_amd/archive.py)."""
+    try:
+        from transflow.utils import find_unique_path
+    except ImportError:
+        from .archive import unique_path as find_unique_path
+    return find_unique_path(path)
+
+
+class HipMjpegFileOutput:
+    """A raw MJPEG stream file: every frame's JPEG file appended to `path`, back to back -- what `ffmpeg -f mjpeg`
+    writes and what `MJPEG_EXTS` inputs are read as.  Same context-manager protocol and `feed` as the other outputs
+    (the constructor is FFmpegVideoOutput's, ffmpeg.py:17-25, with the JPEG settings in place of the codec).  A
+    JpegFrame's bytes are appended as they are; a raw array is encoded by `pillow_encode` with this output's `quality`,
+    `subsampling`, `restart_mcus` (None: the library's default for the layout) and `optimize`.  `path` is used as given
+    if `replace`, otherwise the first free name of the reference's rule.  The stream carries no frame rate: `framerate`
+    is kept for the reader to pass on.  Never opens the GPU."""
+
+    def __init__(self, path: str, width: int, height: int, framerate: float, quality: int = 50, subsampling=2,
+                 restart_mcus: int | None = None, optimize: bool = False, execute: bool = False, replace: bool = False):
+        self.width, self.height = int(width), int(height)
+        self.path = path if replace else _unique_path(path)
+        self.framerate = framerate
+        self.quality = max(1, min(int(quality), 100))
+        self.subsampling = subsampling_value(subsampling)
+        self.restart_mcus = None if restart_mcus is None else int(restart_mcus)
+        self.optimize = bool(optimize)
+        self.execute = execute
+        self.frames = 0
+        self._file = None
+
+    @property
+    def output_path(self):
+        """VideoOutput.output_path (ffmpeg.py:65-67): pipeline.py:481-483 writes the config beside it."""
+        return self.path
+
+    def __enter__(self):
+        dirname = os.path.dirname(self.path)                 # ffmpeg.py:28-30
+        if not os.path.isdir(dirname) and dirname != "":
+            os.makedirs(dirname)
+        self._file = open(self.path, "wb")
+        return self
+
+    def feed(self, frame):
+        if self._file is None:
+            raise ValueError("the output is not open")
+        if isinstance(frame, tuple):
+            frame = frame[0]
+        if isinstance(frame, PngFrame):
+            raise TypeError(f"HipMjpegFileOutput writes JPEG files to {self.path}, not PNG files: install(png_frames=True) "
+                            "serves %d ... .png frame templates")
+        if tuple(frame.shape[:2]) != (self.height, self.width):
+            raise ValueError(f"the output is {self.height} x {self.width}, the frame {tuple(frame.shape[:2])}")
+        data = frame.tobytes() if isinstance(frame, JpegFrame) else _host_jpeg(frame, self.quality, self.restart_mcus,
+                                                                               self.optimize, self.subsampling)
+        self._file.write(data)
+        self.frames += 1
+
+    def __exit__(self, exc_type, exc_value, exc_traceback):
+        if self._file is not None:
+            self._file.close()
+            self._file = None
+        if self.execute:                                     # ffmpeg.py:62-63
+            from transflow.utils import startfile
+            startfile(self.path)
+
+
 class RawFramesOnly:
     """Another output of the reference's, as it is, except that a JpegFrame or a PngFrame fed to it is refused by name:
-    those outputs take pixels (`install(jpeg_frames=...)` is for the MJPEG output, `install(png_frames=True)` for
-    `%d ... .png` templates)."""
+    those outputs take pixels (`install(jpeg_frames=...)` is for the MJPEG output, `%d ... .jpg` templates and .mjpeg
+    files, `install(png_frames=True)` for `%d ... .png` templates)."""
 
     def __init__(self, output):
         self._output = output
