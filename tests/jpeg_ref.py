@@ -1,21 +1,41 @@
-"""numpy restatement of libjpeg's baseline encoder as transflow_amd/csrc/jpeg.hip runs it: 8-bit YCbCr 4:2:0, one
-interleaved scan, the Annex K Huffman tables, jpeg_set_quality's tables, a restart interval counted in MCUs.
+"""numpy restatement of libjpeg's baseline encoder as transflow_amd/csrc/jpeg.hip runs it: 8-bit YCbCr at 4:4:4, 4:2:2 or
+4:2:0, one interleaved scan, jpeg_set_quality's tables, a restart interval counted in MCUs, and for Huffman tables either
+Annex K's or the frame's own (libjpeg's `optimize_coding`).
 
 Every rule is libjpeg's integer arithmetic, so `encode()` returns the very file Pillow writes for
-`save(quality=q, subsampling=2, restart_marker_blocks=r)` (tests/test_jpeg_ref.py holds it to that, byte for byte):
+`save(quality=q, subsampling=s, restart_marker_blocks=r, optimize=o)` (tests/test_jpeg_ref.py, test_jpeg_sub_ref.py and
+test_jpeg_optimize_ref.py hold it to that, byte for byte):
 
   jccolor.c   rgb_ycc_convert           16-bit fixed point
-  jcsample.c  h2v2_downsample           (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2 ... along the output row
-  jcprepct.c  pre_process_data          input rows replicated to an even count, the DOWNSAMPLED rows replicated below
+  jcsample.c  h2v2_downsample           4:2:0: (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2 ... along the output row
+  jcsample.c  h2v1_downsample           4:2:2: out[x] = (p[2x] + p[2x + 1] + (x & 1)) >> 1 -- the bias 0, 1, 0, 1 along the
+                                        output row; rows below the image repeat the last row
+  jcsample.c  fullsize_downsample       4:4:4: the converted samples, replicated right and down to whole blocks
+  jcprepct.c  pre_process_data          the converted plane replicated right to whole MCUs; at 4:2:0 the input rows
+                                        replicated to an even count, the DOWNSAMPLED rows replicated below
   jfdctint.c  jpeg_fdct_islow           CONST_BITS 13, PASS1_BITS 2, on samples - 128
   jcdctmgr.c  forward_DCT               divisor 8 Q[k], rounded half away from zero
-  jccoefct.c  compress_data             dummy luma blocks: AC zero, DC of the block before them in the MCU
+  jcmaster.c  per_scan_setup            the MCU: 8 x 8 pixels, blocks Y Cb Cr; 16 x 8, blocks Y0 Y1 Cb Cr; 16 x 16, Y00 Y01 Y10
+                                        Y11 Cb Cr.  The restart interval counts MCUs of the layout's own size
+  jccoefct.c  compress_data             the luma grid is ceil(W / 8) x ceil(H / 8), last column and row replicated; a luma
+                                        block of an MCU beyond it is a dummy (AC zero, DC of the block before it in the MCU):
+                                        none at 4:4:4, at 4:2:2 only the second block of the last MCU column when ceil(W / 8)
+                                        is odd
   jchuff.c    encode_one_block, emit_restart, flush_bits
-  jcmarker.c  the header
+  jchuff.c    encode_mcu_gather, htest_one_block   the symbols `encode_one_block` emits, counted; DC prediction restarts at
+                                        every interval, dummy blocks count like any other
+  jchuff.c    jpeg_gen_optimal_table    `gen_optimal_table`
+  jchuff.c    jpeg_make_c_derived_tbl   `huff_codes`
+  jcmarker.c  the header                write_frame_header: the luma sampling byte of SOF0 is 0x11, 0x21 or 0x22, chroma
+                                        stays 0x11; the four DHT segments carry the tables the scan is coded with
 
+Four tables are always in the order of the file's DHT segments: DC luma, AC luma, DC chroma, AC chroma.
 `trace()` is `encode()` with an account of what it coded: symbols, lane widths, MCU sizes, the bytes each MCU flushes.
+The images, the case tables and the fixtures' loader are tests/jpeg_cases.py's.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 
@@ -47,6 +67,27 @@ AC_CHROMA = ([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77], list(bytes.fro
     "a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")))
 
 
+ANNEX_K = (DC_LUMA, AC_LUMA, DC_CHROMA, AC_CHROMA)
+TABLE_NAMES = ("DC luma", "AC luma", "DC chroma", "AC chroma")
+
+
+class Layout(NamedTuple):
+    """A chroma layout: the luma sampling factors (chroma's are 1, 1) and the byte SOF0 states them in."""
+    name: str
+    h: int
+    v: int
+    sof0: int
+
+    @property
+    def mcu_size(self):
+        """(height, width) of an MCU in pixels."""
+        return 8 * self.v, 8 * self.h
+
+
+# Pillow's `subsampling` numbers
+LAYOUTS = {0: Layout("4:4:4", 1, 1, 0x11), 1: Layout("4:2:2", 2, 1, 0x21), 2: Layout("4:2:0", 2, 2, 0x22)}
+
+
 def quant_table(base: np.ndarray, quality: int) -> np.ndarray:
     """jpeg_set_quality(q, force_baseline=TRUE): jpeg_quality_scaling, then jpeg_add_quant_table's clamp to 1..255."""
     q = min(max(int(quality), 1), 100)
@@ -66,7 +107,7 @@ def huff_codes(bits, vals) -> dict:
     return table
 
 
-def header(height: int, width: int, quality: int, restart_mcus: int) -> bytes:
+def header(height: int, width: int, quality: int, restart_mcus: int, subsampling: int = 2, tables=ANNEX_K) -> bytes:
     """jcmarker.c write_file_header, write_frame_header, write_scan_header, in libjpeg's order."""
     def seg(marker, payload):
         return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + bytes(payload)
@@ -74,8 +115,8 @@ def header(height: int, width: int, quality: int, restart_mcus: int) -> bytes:
     for n, base in enumerate((QUANT_LUMA, QUANT_CHROMA)):
         out += seg(0xDB, bytes([n]) + bytes(int(v) for v in quant_table(base, quality)[ZIGZAG]))
     out += seg(0xC0, bytes([8]) + height.to_bytes(2, "big") + width.to_bytes(2, "big")
-               + bytes([3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1]))
-    for tc_th, (bits, vals) in ((0x00, DC_LUMA), (0x10, AC_LUMA), (0x01, DC_CHROMA), (0x11, AC_CHROMA)):
+               + bytes([3, 1, LAYOUTS[subsampling].sof0, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for tc_th, (bits, vals) in zip((0x00, 0x10, 0x01, 0x11), tables):
         out += seg(0xC4, bytes([tc_th]) + bytes(bits) + bytes(vals))
     out += seg(0xDD, restart_mcus.to_bytes(2, "big"))
     out += seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
@@ -102,6 +143,12 @@ def downsample(plane: np.ndarray) -> np.ndarray:
     """h2v2_downsample on a plane of even height and width."""
     bias = 1 + (np.arange(plane.shape[1] // 2) & 1)
     return (plane[0::2, 0::2] + plane[0::2, 1::2] + plane[1::2, 0::2] + plane[1::2, 1::2] + bias) >> 2
+
+
+def downsample_h2v1(plane: np.ndarray) -> np.ndarray:
+    """h2v1_downsample on a plane of even width."""
+    bias = np.arange(plane.shape[1] // 2) & 1
+    return (plane[:, 0::2] + plane[:, 1::2] + bias) >> 1
 
 
 def _descale(x, n):
@@ -239,262 +286,226 @@ def _encode_block(bits: _Bits, block, last_dc: int, dc_tbl, ac_tbl, trace=None, 
             trace.ac_symbols[table].add(0x00)
 
 
-def encode(rgb: np.ndarray, quality: int = 50, restart_mcus: int = 1, trace: Trace | None = None) -> bytes:
-    """The whole file for a uint8 (H, W, 3) RGB image.  A `trace` is filled with what was coded on the way."""
-    rgb = np.asarray(rgb)
-    assert rgb.dtype == np.uint8 and rgb.ndim == 3 and rgb.shape[2] == 3 and restart_mcus >= 1
+def _count_block(dc_hist, ac_hist, block, last_dc: int) -> None:
+    """htest_one_block."""
+    dc_hist[int(abs(int(block[0]) - last_dc)).bit_length()] += 1
+    prev = 0
+    for k in np.flatnonzero(block[1:]) + 1:
+        k = int(k)
+        run = k - prev - 1
+        ac_hist[0xF0] += run >> 4
+        ac_hist[((run & 15) << 4) | int(abs(int(block[k]))).bit_length()] += 1
+        prev = k
+    if prev != 63:
+        ac_hist[0x00] += 1
+
+
+class _Codes(dict):
+    """symbol -> (code, length).  The trace asks for ZRL's length in front of every coefficient, also where the frame has
+    no ZRL and so its own table no code for it: no bits then."""
+
+    def __missing__(self, symbol):
+        if symbol != 0xF0:
+            raise KeyError(symbol)
+        return (0, 0)
+
+
+def mcus(rgb: np.ndarray, quality: int, subsampling: int = 2):
+    """Per MCU in scan order: its (table, component, block) in coding order, blocks quantised and in zigzag order."""
+    layout = LAYOUTS[subsampling]
+    h, v, (mcu_h, mcu_w) = layout.h, layout.v, layout.mcu_size            # an MCU: h x v luma blocks, then Cb, then Cr
     H, W = rgb.shape[:2]
-    mcus_x, mcus_y = (W + 15) // 16, (H + 15) // 16
-    lum_bx, lum_by = (W + 7) // 8, (H + 7) // 8                        # the luma block grid; beyond it: dummy blocks
+    mcus_x, mcus_y = -(-W // mcu_w), -(-H // mcu_h)
+    lum_bx, lum_by = (W + 7) // 8, (H + 7) // 8                            # the luma block grid; beyond it: dummy blocks
     y, cb, cr = ycc(rgb)
     y = pad_bottom(pad_right(y, lum_bx * 8), lum_by * 8)
     chroma = []
     for plane in (cb, cr):
-        plane = pad_bottom(pad_right(plane, mcus_x * 16), H + (H & 1))    # rows only to an even count ...
-        chroma.append(pad_bottom(downsample(plane), mcus_y * 8))          # ... then the downsampled rows
+        plane = pad_right(plane, mcus_x * mcu_w)
+        if subsampling == 2:                                              # rows only to an even count, then the downsampled rows
+            plane = downsample(pad_bottom(plane, H + (H & 1)))
+        elif subsampling == 1:
+            plane = downsample_h2v1(plane)
+        chroma.append(pad_bottom(plane, mcus_y * 8))
     tl, tc = quant_table(QUANT_LUMA, quality), quant_table(QUANT_CHROMA, quality)
     cy, ccb, ccr = blocks_quantised(y, tl), blocks_quantised(chroma[0], tc), blocks_quantised(chroma[1], tc)
-    dc_l, ac_l, dc_c, ac_c = (huff_codes(*t) for t in (DC_LUMA, AC_LUMA, DC_CHROMA, AC_CHROMA))
-    zero = np.zeros(64, np.int64)
-    out = bytearray(header(H, W, quality, restart_mcus))
-    bits, last, n_mcu = _Bits(), [0, 0, 0], 0
     for my in range(mcus_y):
         for mx in range(mcus_x):
-            if n_mcu and n_mcu % restart_mcus == 0:                       # emit_restart (flush_bits ran behind the MCU)
-                out += bits.out + bytes([0xFF, 0xD0 + (n_mcu // restart_mcus - 1) % 8])
-                bits, last = _Bits(), [0, 0, 0]
-            n_mcu += 1
-            bits_before, raw_before = bits.total, len(bits.raw)
-            prev = None
-            for b in range(4):
-                by, bx = 2 * my + (b >> 1), 2 * mx + (b & 1)
+            out, prev = [], None
+            for b in range(h * v):
+                by, bx = v * my + b // h, h * mx + b % h
                 if by < lum_by and bx < lum_bx:
                     block = cy[by, bx]
                 else:                                                     # jccoefct.c: a dummy block
-                    block = zero.copy()
+                    block = np.zeros(64, np.int64)
                     block[0] = prev[0]
-                _encode_block(bits, block, last[0], dc_l, ac_l, trace, 0)
-                last[0] = int(block[0])
+                out.append((0, 0, block))
                 prev = block
-            for c, coef in ((1, ccb), (2, ccr)):
-                block = coef[my, mx]
-                _encode_block(bits, block, last[c], dc_c, ac_c, trace, 1)
-                last[c] = int(block[0])
-            mcu_bits = bits.total - bits_before
-            interval_end = n_mcu % restart_mcus == 0 or n_mcu == mcus_x * mcus_y
-            if interval_end:
-                bits.flush()
-            if trace is not None:
-                trace.mcu_bits.append(mcu_bits)
-                trace.flushed.append(bytes(bits.raw[raw_before:]))
-                trace.interval_end.append(interval_end)
+            out.append((1, 1, ccb[my, mx]))
+            out.append((1, 2, ccr[my, mx]))
+            yield out
+
+
+def _walk(rgb: np.ndarray, quality: int, restart_mcus: int, subsampling: int):
+    """The scan, as the coder and the gather pass both walk it.  Per MCU: (n of the RSTn in front of it or None, its
+    (table, block, the DC its own is predicted from), is it the last of its interval).  Prediction restarts at 0 behind
+    every marker."""
+    rgb = np.asarray(rgb)
+    assert rgb.dtype == np.uint8 and rgb.ndim == 3 and rgb.shape[2] == 3 and restart_mcus >= 1
+    every = list(mcus(rgb, quality, subsampling))
+    last = [0, 0, 0]
+    for n_mcu, mcu in enumerate(every):
+        rst = None
+        if n_mcu and n_mcu % restart_mcus == 0:
+            rst, last = (n_mcu // restart_mcus - 1) % 8, [0, 0, 0]
+        coded = []
+        for table, comp, block in mcu:
+            coded.append((table, block, last[comp]))
+            last[comp] = int(block[0])
+        yield rst, coded, (n_mcu + 1) % restart_mcus == 0 or n_mcu + 1 == len(every)
+
+
+def histograms(rgb: np.ndarray, quality: int = 50, restart_mcus: int = 1, subsampling: int = 2) -> np.ndarray:
+    """uint32 [4][257]: what the gather pass counts (entry 256, the reserved symbol, is 1)."""
+    hist = np.zeros((4, 257), np.int64)
+    hist[:, 256] = 1
+    for _, coded, _ in _walk(rgb, quality, restart_mcus, subsampling):
+        for table, block, last_dc in coded:
+            _count_block(hist[2 * table], hist[2 * table + 1], block, last_dc)
+    return hist.astype(np.uint32)
+
+
+MAX_CLEN = 32                                # jchuff.c: the longest code length the limiting step can repair
+SENTINEL = 1000000000                        # jchuff.c: a frequency above it is never selected
+
+
+class CodeLengthOverflow(ValueError):
+    """libjpeg's JERR_HUFF_CLEN_OVERFLOW: a code size above 32."""
+
+
+def gen_optimal_table(counts):
+    """jpeg_gen_optimal_table: 256 (or 257: the last is ignored) frequencies -> (bits[16], vals).  ValueError for a
+    histogram without a symbol (libjpeg would run off its array), CodeLengthOverflow for a code size above 32."""
+    freq = [int(v) for v in counts][:256]
+    assert len(freq) == 256 and min(freq) >= 0
+    if not any(freq):
+        raise ValueError("a histogram without a symbol")
+    freq.append(1)                                                        # the reserved symbol: no real code is all ones
+    codesize, others = [0] * 257, [-1] * 257
+
+    def pick(skip):
+        c, v = -1, SENTINEL
+        for i in range(257):                                              # upward with <=: among equals the largest index
+            if freq[i] and freq[i] <= v and i != skip:
+                c, v = i, freq[i]
+        return c
+
+    while True:
+        c1 = pick(-1)
+        c2 = pick(c1)
+        if c2 < 0:
+            break
+        freq[c1] += freq[c2]
+        freq[c2] = 0
+        codesize[c1] += 1
+        while others[c1] >= 0:
+            c1 = others[c1]
+            codesize[c1] += 1
+        others[c1] = c2
+        codesize[c2] += 1
+        while others[c2] >= 0:
+            c2 = others[c2]
+            codesize[c2] += 1
+    if max(codesize) > MAX_CLEN:
+        raise CodeLengthOverflow(f"a code size of {max(codesize)}, above {MAX_CLEN}")
+    bits = [0] * (MAX_CLEN + 1)
+    for size in codesize:
+        if size:
+            bits[size] += 1
+    for i in range(MAX_CLEN, 16, -1):
+        while bits[i] > 0:
+            j = i - 2
+            while bits[j] == 0:
+                j -= 1
+            bits[i] -= 2
+            bits[i - 1] += 1
+            bits[j + 1] += 2
+            bits[j] -= 1
+    i = 16
+    while bits[i] == 0:
+        i -= 1
+    bits[i] -= 1                                                          # the reserved symbol leaves
+    vals = [s for size in range(1, MAX_CLEN + 1) for s in range(256) if codesize[s] == size]
+    return bits[1:17], vals
+
+
+def code_sizes_before_limiting(counts) -> int:
+    """The longest code size `gen_optimal_table` sees before its limiting step (33 and more: it refuses)."""
+    freq = [int(v) for v in counts][:256] + [1]
+    depth = {i: 0 for i in range(257) if freq[i]}
+    groups = {i: [i] for i in depth}
+    live = {i: freq[i] for i in depth}
+    while len(live) > 1:
+        c1 = min(live, key=lambda i: (live[i], -i))
+        v1 = live.pop(c1)
+        c2 = min(live, key=lambda i: (live[i], -i))
+        v2 = live.pop(c2)
+        live[c1] = v1 + v2
+        groups[c1] += groups.pop(c2)
+        for s in groups[c1]:
+            depth[s] += 1
+    return max(depth.values())
+
+
+def tables(rgb: np.ndarray, quality: int = 50, restart_mcus: int = 1, subsampling: int = 2):
+    """The four (bits, vals) of the frame."""
+    return [gen_optimal_table(h) for h in histograms(rgb, quality, restart_mcus, subsampling)]
+
+
+def dht_tables(data: bytes):
+    """{tc_th: (bits, vals)} of a file's DHT segments."""
+    out, i = {}, 2
+    while data[i + 1] != 0xDA:
+        n = int.from_bytes(data[i + 2:i + 4], "big")
+        if data[i + 1] == 0xC4:
+            p = data[i + 4:i + 2 + n]
+            out[p[0]] = (list(p[1:17]), list(p[17:]))
+        i += 2 + n
+    return out
+
+
+def encode(rgb: np.ndarray, quality: int = 50, restart_mcus: int = 1, subsampling: int = 2, optimize: bool = False,
+           trace: Trace | None = None) -> bytes:
+    """The whole file for a uint8 (H, W, 3) RGB image, with Annex K's Huffman tables or (`optimize`) the frame's own.
+    A `trace` is filled with what was coded on the way."""
+    rgb = np.asarray(rgb)
+    four = tables(rgb, quality, restart_mcus, subsampling) if optimize else ANNEX_K
+    codes = [_Codes(huff_codes(*t)) for t in four]
+    out = bytearray(header(rgb.shape[0], rgb.shape[1], quality, restart_mcus, subsampling, four))
+    bits = _Bits()
+    for rst, coded, interval_end in _walk(rgb, quality, restart_mcus, subsampling):
+        if rst is not None:                                               # emit_restart (flush_bits ran behind the MCU)
+            out += bits.out + bytes([0xFF, 0xD0 + rst])
+            bits = _Bits()
+        bits_before, raw_before = bits.total, len(bits.raw)
+        for table, block, last_dc in coded:
+            _encode_block(bits, block, last_dc, codes[2 * table], codes[2 * table + 1], trace, table)
+        mcu_bits = bits.total - bits_before
+        if interval_end:
+            bits.flush()
+        if trace is not None:
+            trace.mcu_bits.append(mcu_bits)
+            trace.flushed.append(bytes(bits.raw[raw_before:]))
+            trace.interval_end.append(interval_end)
     out += bits.out + b"\xff\xd9"
     if trace is not None:
         trace.data = bytes(out)
     return bytes(out)
 
 
-def trace(rgb: np.ndarray, quality: int = 50, restart_mcus: int = 1) -> Trace:
+def trace(rgb: np.ndarray, quality: int = 50, restart_mcus: int = 1, subsampling: int = 2, optimize: bool = False) -> Trace:
     """`encode`, the same code, returning what it coded."""
     t = Trace()
-    encode(rgb, quality, restart_mcus, t)
+    encode(rgb, quality, restart_mcus, subsampling, optimize, trace=t)
     return t
 
-
-# ---- the fixtures' cases (tools/capture_golden_jpeg.py writes them, the tests read them) -----------------------------
-def formula_image(height: int, width: int) -> np.ndarray:
-    """The one image too large to store: arithmetic only, no generator.  Smooth ramps, a fine texture and hard edges."""
-    i, j = np.mgrid[0:height, 0:width].astype(np.int64)
-    r = (3 * j + i + ((i * j) >> 5)) & 255
-    g = (5 * i + (j >> 1) + 37 * ((i >> 3) & 1) * ((j >> 4) & 1)) & 255
-    b = ((i * i + 7 * j) >> 3) + 96 * (((i >> 2) + (j >> 2)) & 1) & 255
-    return np.stack([r, g, b], axis=-1).astype(np.uint8)
-
-
-def stored_image(height: int, width: int, seed: int) -> np.ndarray:
-    """What a fixture stores: ramps with noise on them, so that blocks have a few coefficients and some runs."""
-    rng = np.random.default_rng(seed)
-    i, j = np.mgrid[0:height, 0:width]
-    base = np.stack([4 * j + i, 255 - 3 * i - j, 2 * i + 2 * j + 40], axis=-1)
-    return np.clip(base + rng.integers(-40, 41, (height, width, 3)), 0, 255).astype(np.uint8)
-
-
-def noise_image(height: int, width: int, seed: int) -> np.ndarray:
-    return np.random.default_rng(seed).integers(0, 256, (height, width, 3), dtype=np.uint8)
-
-
-def checkerboard(height: int, width: int) -> np.ndarray:
-    """8 x 8 squares of black and white: every block flat, neighbouring DCs 2040 quantisation steps apart at quality 100."""
-    i, j = np.mgrid[0:height, 0:width]
-    return np.repeat(((((i >> 3) + (j >> 3)) & 1) * 255).astype(np.uint8)[..., None], 3, axis=-1)
-
-
-# ---- directed content: pure integer functions of (height, width, seed), so a fixture stores those, not pixels ---------
-def _hash(seed: int, stream: int, n: int) -> np.ndarray:
-    """n 64-bit values, splitmix64 of a counter: no generator whose stream a library might change."""
-    with np.errstate(over="ignore"):
-        z = (np.arange(1, n + 1, dtype=np.uint64) + np.uint64(seed) * np.uint64(0x632BE59BD9B4E019)
-             + np.uint64(stream) * np.uint64(0xD6E8FEB86659FD93)) * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-
-
-# 2^14 cos(k pi / 16), k = 0 .. 31, and the DCT's basis vectors in those units (u = 0: 1 / sqrt 2)
-_COS = np.array([16384, 16069, 15137, 13623, 11585, 9102, 6270, 3196, 0], np.int64)
-_COS = np.concatenate([_COS, -_COS[7::-1]])
-_COS = np.concatenate([_COS, _COS[15:0:-1]])
-_BASIS = np.array([[11585 if u == 0 else _COS[(2 * x + 1) * u % 32] for x in range(8)] for u in range(8)], np.int64)
-
-
-def _directed_blocks(by: int, bx: int, seed: int) -> np.ndarray:
-    """int64 [by, bx, 8, 8], each block within -128 .. 127: one or two DCT basis functions at zigzag positions drawn
-    from 1 .. 63, amplitudes (in units of the unquantised coefficient) from 1 .. 2047 with every size as likely as any
-    other, or the sign pattern of the function times 1 .. 127.  Past about 500 the cosine clips towards its sign pattern.
-    A block with two functions puts the run between them at the second's disposal: 0 .. 61."""
-    n = by * bx
-    h = [_hash(seed, stream, n).astype(np.int64) & 0x7FFFFFFF for stream in range(8)]
-    out = np.zeros((n, 8, 8), np.int64)
-    for b in range(n):
-        first = 1 + h[0][b] % 63
-        picks = [first]
-        if h[1][b] % 3:                                                   # two in three blocks: a second one behind it
-            gap = h[2][b] % 62
-            picks.append(1 + (first + gap) % 63)
-        for i, k in enumerate(picks):
-            v, u = divmod(int(ZIGZAG[k]), 8)
-            size = 1 + h[3 + i][b] % 11
-            amp = (1 << (size - 1)) + (h[3 + i][b] >> 8) % (1 << (size - 1))
-            sign = 1 - 2 * ((h[3 + i][b] >> 4) & 1)
-            basis = np.outer(_BASIS[v], _BASIS[u])                        # 2^28 cos cos
-            if (h[5 + i][b] & 3) == 0:
-                out[b] += sign * (1 + (h[5 + i][b] >> 2) % 127) * np.sign(basis) // len(picks)
-            else:
-                out[b] += (sign * amp * basis + (1 << 29)) >> 30         # amp cu cv cos cos / 4
-    return np.clip(out, -128, 127).reshape(by, bx, 8, 8)
-
-
-def _tile(blocks: np.ndarray, height: int, width: int, step: int) -> np.ndarray:
-    """[by, bx, 8, 8] -> a plane [height, width] with every value `step` pixels square."""
-    by, bx = blocks.shape[:2]
-    plane = blocks.transpose(0, 2, 1, 3).reshape(by * 8, bx * 8)
-    return np.repeat(np.repeat(plane, step, axis=0), step, axis=1)[:height, :width]
-
-
-def directed_luma(height: int, width: int, seed: int) -> np.ndarray:
-    """A grey image whose luma blocks are `_directed_blocks` on 128: one or two AC coefficients each, anywhere, any size."""
-    plane = 128 + _tile(_directed_blocks((height + 7) // 8, (width + 7) // 8, seed), height, width, 1)
-    return np.repeat(plane.astype(np.uint8)[..., None], 3, axis=-1)
-
-
-def directed_chroma(height: int, width: int, seed: int) -> np.ndarray:
-    """The same patterns at 2 x 2 pixels on Cb and Cr.  MCUs take turns: constant luma with Cb and Cr following the
-    pattern (the inverse of jccolor.c's matrix, clipped to the gamut), and the two saturated pairs blue / yellow
-    (Cb 255 / 0) and red / cyan (Cr 255 / 0) on the pattern's sign, which no constant luma reaches."""
-    my, mx = (height + 15) // 16, (width + 15) // 16
-    cb = _tile(_directed_blocks(my, mx, 2 * seed + 1000), height, width, 2)
-    cr = _tile(_directed_blocks(my, mx, 2 * seed + 1001), height, width, 2)
-    kind = _tile(np.broadcast_to((_hash(seed, 9, my * mx) % np.uint64(4)).astype(np.int64).reshape(my, mx, 1, 1),
-                                 (my, mx, 8, 8)), height, width, 2)
-    r = 128 + ((91881 * cr + 32768) >> 16)
-    g = 128 - ((22554 * cb + 46802 * cr + 32768) >> 16)
-    b = 128 + ((116130 * cb + 32768) >> 16)
-    smooth = np.clip(np.stack([r, g, b], axis=-1), 0, 255)
-    blue_yellow = np.where((cb >= 0)[..., None], (0, 0, 255), (255, 255, 0))
-    red_cyan = np.where((cr >= 0)[..., None], (255, 0, 0), (0, 255, 255))
-    kind = kind[..., None]
-    return np.where(kind < 2, smooth, np.where(kind == 2, blue_yellow, red_cyan)).astype(np.uint8)
-
-
-def binary_noise(height: int, width: int, seed: int) -> np.ndarray:
-    """Every channel of every pixel 0 or 255: the most bits an MCU gets from anything like a picture."""
-    return ((_hash(seed, 0, height * width * 3) >> np.uint64(40)) & np.uint64(1)).astype(np.uint8).reshape(height, width, 3) * 255
-
-
-def chroma_checker(height: int, width: int) -> np.ndarray:
-    """16 x 16 squares, blue and yellow in the left half, red and cyan in the right: every chroma block flat, the Cb
-    (left) and Cr (right) DCs of neighbouring MCUs 2040 quantisation steps apart at quality 100, as `checkerboard`'s luma."""
-    i, j = np.mgrid[0:height, 0:width]
-    odd = ((((i >> 4) + (j >> 4)) & 1) == 1)[..., None]
-    left = np.where(odd, (255, 255, 0), (0, 0, 255))
-    right = np.where(odd, (0, 255, 255), (255, 0, 0))
-    return np.where((j < width // 2)[..., None], left, right).astype(np.uint8)
-
-
-# name -> (height, width, content, quality, restart_mcus); content is a kind, or (kind, seed)
-CASES = {
-    "1x1": (1, 1, "stored", 50, 4),
-    "9x7": (9, 7, "stored", 50, 4),
-    "16x16": (16, 16, "stored", 50, 4),
-    "17x33": (17, 33, "stored", 50, 4),
-    "45x61": (45, 61, "stored", 50, 4),
-    "24x40": (24, 40, "stored", 50, 4),
-    "8x100": (8, 100, "stored", 50, 4),
-    "33x47_noise_q100": (33, 47, "noise", 100, 4),
-    "33x47_noise_q1": (33, 47, "noise", 1, 4),
-    "32x32_checker_q100": (32, 32, "checker", 100, 4),
-    "45x61_r1": (45, 61, "stored", 50, 1),
-    "45x61_r2": (45, 61, "stored", 50, 2),
-    "45x61_r3": (45, 61, "stored", 50, 3),
-    "45x61_r8": (45, 61, "stored", 50, 8),              # the library's default interval
-    "45x61_r100": (45, 61, "stored", 50, 100),          # more than the 12 MCUs: one interval, no marker
-    "270x480_q50": (270, 480, "formula", 50, 4),
-    "270x480_q95": (270, 480, "formula", 95, 4),
-    # directed content (kind, seed): the seeds and qualities are those at which tests/test_jpeg_ref.py's coverage holds
-    "luma_s10_q100": (96, 96, ("directed_luma", 10), 100, 3),
-    "luma_s57_q100": (96, 96, ("directed_luma", 57), 100, 5),
-    "luma_s19_q99": (96, 96, ("directed_luma", 19), 99, 1),
-    "luma_s22_q98": (96, 96, ("directed_luma", 22), 98, 8),
-    "luma_s24_q95": (96, 96, ("directed_luma", 24), 95, 2),
-    "luma_s0_q50": (96, 96, ("directed_luma", 0), 50, 4),
-    "chroma_s14_q100": (96, 96, ("directed_chroma", 14), 100, 3),
-    "chroma_s0_q100": (96, 96, ("directed_chroma", 0), 100, 5),
-    "chroma_s17_q100": (96, 96, ("directed_chroma", 17), 100, 6),
-    "chroma_s44_q99": (96, 96, ("directed_chroma", 44), 99, 1),
-    "chroma_s4_q98": (96, 96, ("directed_chroma", 4), 98, 8),
-    "chroma_s10_q98": (96, 96, ("directed_chroma", 10), 98, 7),
-    "chroma_s44_q65": (96, 96, ("directed_chroma", 44), 65, 2),
-    "chroma_s0_q50": (96, 96, ("directed_chroma", 0), 50, 4),
-    "32x48_binary_q100": (32, 48, ("binary_noise", 129), 100, 2),      # the fattest MCUs: 600 bytes, ten trips of the flush
-    "32x64_chroma_checker_q100": (32, 64, "chroma_checker", 100, 4),   # chroma DC categories 10 and 11
-    # interval counts around k_slot_scan's 1024 per trip
-    "512x512_r1": (512, 512, "formula", 50, 1),                         # 1024: one full trip
-    "16x16400_r1": (16, 16400, "formula", 50, 1),                       # 1025: one element in the second
-    "730x725_r1": (730, 725, "formula", 50, 1),                         # 46 x 46 = 2116: three trips, ragged edges
-    # the largest sizes libjpeg writes (JPEG_MAX_DIMENSION 65500; tf_jpeg_create admits the format's 65535, which
-    # tests/test_gpu_jpeg.py holds to `encode` itself), at the library's default interval
-    "1x65500": (1, 65500, "formula", 50, 8),                            # 4094 MCUs in a row, three of four luma blocks dummies
-    "65500x1": (65500, 1, "formula", 50, 8),                            # ... in a column
-    "40x4099": (40, 4099, "formula", 50, 8),                            # 257 MCUs a row: no power of two
-}
-
-
-def case_image(name: str) -> np.ndarray:
-    """The picture of a case: what tools/capture_golden_jpeg.py gives Pillow."""
-    h, w, content, _, _ = CASES[name]
-    kind, seed = content if isinstance(content, tuple) else (content, None)
-    if kind == "stored":
-        return stored_image(h, w, seed=h * 1000 + w)                     # the same picture for every case of a size
-    if kind == "noise":
-        return noise_image(h, w, seed=7)
-    return _made_image(kind, h, w, seed)
-
-
-def _made_image(kind: str, height: int, width: int, seed) -> np.ndarray:
-    """The content kinds that are pure functions of their parameters: a fixture stores those."""
-    if kind in ("directed_luma", "directed_chroma", "binary_noise"):
-        return {"directed_luma": directed_luma, "directed_chroma": directed_chroma,
-                "binary_noise": binary_noise}[kind](height, width, int(seed))
-    return {"checker": checkerboard, "chroma_checker": chroma_checker, "formula": formula_image}[kind](height, width)
-
-
-def load_case(path: str):
-    """(image, quality, restart_mcus, expected file bytes) of a tests/golden/jpeg_*.npz fixture."""
-    with np.load(path) as z:
-        quality, restart = int(z["quality"]), int(z["restart_mcus"])
-        if "image" in z.files:
-            image = z["image"]
-        else:                                                             # (the first such fixtures name no content)
-            kind = str(z["content"]) if "content" in z.files else "formula"
-            image = _made_image(kind, int(z["height"]), int(z["width"]), z["seed"] if "seed" in z.files else None)
-        return image, quality, restart, z["jpeg"].tobytes()

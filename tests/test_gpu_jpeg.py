@@ -7,36 +7,32 @@ import os
 import numpy as np
 import pytest
 
-from tests import jpeg_ref
+from tests import jpeg_cases, jpeg_ref
+from tests.jpeg_cases import GOLDEN, first_difference
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "jpeg_*.npz")))
 
 
 def _case(name):
-    return jpeg_ref.load_case(os.path.join(GOLDEN, f"jpeg_{name}.npz"))
-
-
-def _first_difference(got: bytes, want: bytes) -> str:
-    n = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
-    return f"{len(got)} bytes against {len(want)}, first difference at byte {n}: {got[n:n + 8].hex()} / {want[n:n + 8].hex()}"
+    case = jpeg_cases.load_case(jpeg_cases.fixture_path("jpeg", name))
+    return case.image, case.quality, case.restart_mcus, case.jpeg
 
 
 def test_every_case_is_here():
-    assert sorted(os.path.basename(p)[5:-4] for p in FIXTURES) == sorted(jpeg_ref.CASES)
+    assert sorted(os.path.basename(p)[5:-4] for p in FIXTURES) == sorted(jpeg_cases.BASELINE_CASES)
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[5:-4])
 def test_encoder_writes_libjpegs_file(path):
     from transflow_amd.jpeg import JpegEncoder
-    image, quality, restart, expected = jpeg_ref.load_case(path)
+    image, quality, restart, _, _, expected = jpeg_cases.load_case(path)
     enc = JpegEncoder(image.shape[0], image.shape[1], quality, restart)
     try:
         assert enc.header == expected[:len(enc.header)] == jpeg_ref.header(image.shape[0], image.shape[1], quality, restart)
         got = enc.encode(image)
-        assert got == expected, _first_difference(got, expected)
+        assert got == expected, first_difference(got, expected)
     finally:
         enc.close()
 
@@ -57,7 +53,7 @@ def test_default_interval_is_the_one_the_host_encodes_with():
 def test_one_encoder_keeps_no_state_between_images():
     from transflow_amd.jpeg import JpegEncoder
     a, quality, restart, want_a = _case("33x47_noise_q100")
-    b = jpeg_ref.stored_image(33, 47, seed=5)                              # far fewer bits: what a stale buffer would show in
+    b = jpeg_cases.stored_image(33, 47, seed=5)                            # far fewer bits: what a stale buffer would show in
     want_b = jpeg_ref.encode(b, quality, restart)
     enc = JpegEncoder(33, 47, quality, restart)
     try:
@@ -200,7 +196,7 @@ def test_an_encode_and_a_copy_last_launch_what_they_always_did(optimize, launche
     pack.  17 x 33 at the default restart length."""
     from transflow_amd import _lib
     from transflow_amd.jpeg import JpegEncoder
-    image = jpeg_ref.stored_image(17, 33, seed=3)
+    image = jpeg_cases.stored_image(17, 33, seed=3)
     enc = JpegEncoder(17, 33, optimize=optimize)
     try:
         out, again, n = np.zeros(1 << 16, np.uint8), np.zeros(1 << 16, np.uint8), C.c_size_t()
@@ -253,7 +249,7 @@ def test_every_interval_is_where_libjpeg_has_it_across_scan_chunks():
         assert len(got_iv) == len(want_iv) and not wrong, (
             f"{len(got_iv)} intervals against {len(want_iv)}; {len(wrong)} differ, the first is interval "
             f"{wrong[0] if wrong else None} (chunk {wrong[0] // 1024 if wrong else None}); "
-            + _first_difference(got, expected))
+            + first_difference(got, expected))
         assert got_rst == want_rst
         assert n.value == len(expected) and got == expected
         assert (out[n.value:] == 0x5A).all()
@@ -268,13 +264,13 @@ def test_the_largest_sizes_the_format_has(height, width):
     1x65500 and 65500x1 are its files.  Beyond it the restatement is the reference: 4096 MCUs in a row or a column,
     512 intervals, every luma block below or beside the first a dummy."""
     from transflow_amd.jpeg import JpegEncoder
-    image = jpeg_ref.formula_image(height, width)
+    image = jpeg_cases.formula_image(height, width)
     enc = JpegEncoder(height, width, 50)
     try:
         want = jpeg_ref.encode(image, 50, enc.restart_mcus)
         got = enc.encode(image)
         assert len(_intervals(want[len(enc.header):-2])[0]) == 512
-        assert got == want, _first_difference(got, want)
+        assert got == want, first_difference(got, want)
     finally:
         enc.close()
 
@@ -351,7 +347,7 @@ def test_compositor_returns_the_file_of_its_plain_render(layers, device_flows):
         for t, (frame, raw) in enumerate(zip(files, plain)):
             assert isinstance(frame, JpegFrame) and frame.shape == (H, W, 3) and frame.quality == 50
             want = enc.encode(np.array(raw))
-            assert frame.data == want, f"frame {t}: " + _first_difference(frame.data, want)
+            assert frame.data == want, f"frame {t}: " + first_difference(frame.data, want)
             assert want == jpeg_ref.encode(np.array(raw), 50, enc.restart_mcus)
     finally:
         enc.close()

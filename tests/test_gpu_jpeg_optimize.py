@@ -1,5 +1,5 @@
 """tf_jpeg in mode 1, the frame's own Huffman tables, on the GPU against libjpeg's optimize_coding
-(tests/golden/jpegopt_*.npz, written by tools/capture_golden_jpeg_optimize.py, and tests/jpeg_optimize_ref.py): the
+(tests/golden/jpegopt_*.npz, written by tools/capture_golden_jpeg.py, and tests/jpeg_ref.py with `optimize`): the
 whole file, byte for byte, the tables and the counts behind them."""
 import ctypes as C
 import functools
@@ -9,68 +9,63 @@ import os
 import numpy as np
 import pytest
 
-from tests import jpeg_optimize_ref as R
-from tests import jpeg_ref
+from tests import jpeg_cases, jpeg_ref
+from tests.jpeg_cases import GOLDEN, first_difference
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "jpegopt_*.npz")))
 
 
 def _case(name):
-    return R.load_case(os.path.join(GOLDEN, f"jpegopt_{name}.npz"))
+    case = jpeg_cases.load_case(jpeg_cases.fixture_path("jpegopt", name))
+    return case.image, case.quality, case.restart_mcus, case.jpeg
 
 
 @functools.lru_cache(maxsize=None)
 def _histograms(name):
     """The restatement's counts of a case: computed once, shared, never written."""
-    _, _, _, quality, restart = R.CASES[name]
-    hist = R.histograms(R.case_image(name), quality, restart)
+    _, _, _, quality, restart = jpeg_cases.OWN_TABLES_CASES[name]
+    hist = jpeg_ref.histograms(jpeg_cases.case_image("jpegopt", name), quality, restart)
     hist.setflags(write=False)
     return hist
 
 
-def _first_difference(got: bytes, want: bytes) -> str:
-    n = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
-    return f"{len(got)} bytes against {len(want)}, first difference at byte {n}: {got[n:n + 8].hex()} / {want[n:n + 8].hex()}"
-
-
 def test_every_case_is_here():
-    assert sorted(os.path.basename(p)[8:-4] for p in FIXTURES) == sorted(R.CASES)
+    assert sorted(os.path.basename(p)[8:-4] for p in FIXTURES) == sorted(jpeg_cases.OWN_TABLES_CASES)
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[8:-4])
 def test_encoder_writes_libjpegs_optimised_file(path):
     from transflow_amd.jpeg import JpegEncoder
-    image, quality, restart, expected = R.load_case(path)
+    image, quality, restart, _, _, expected = jpeg_cases.load_case(path)
     enc = JpegEncoder(image.shape[0], image.shape[1], quality, restart, optimize=True)
     try:
         with pytest.raises(RuntimeError):
             enc.header                                                     # the frame's: none before the first encode
         got = enc.encode(image)
-        assert got == expected, _first_difference(got, expected)
+        assert got == expected, first_difference(got, expected)
         assert enc.header == expected[:len(enc.header)] and expected[len(enc.header) - 14:len(enc.header) - 12] == b"\xff\xda"
     finally:
         enc.close()
 
 
-@pytest.mark.parametrize("name", sorted(R.CASES))
+@pytest.mark.parametrize("name", sorted(jpeg_cases.OWN_TABLES_CASES))
 def test_last_tables_are_the_restatements(name):
     from transflow_amd.jpeg import JpegEncoder
-    h, w, _, quality, restart = R.CASES[name]
+    h, w, _, quality, restart = jpeg_cases.OWN_TABLES_CASES[name]
     enc = JpegEncoder(h, w, quality, restart, optimize=True)
     try:
         with pytest.raises(RuntimeError):
             enc.last_tables()                                              # TF_ERR_STATE: nothing encoded
-        enc.encode(R.case_image(name))
+        enc.encode(jpeg_cases.case_image("jpegopt", name))
         tables, counts = enc.last_tables(counts=True)
         want = _histograms(name)
         wrong = np.argwhere(counts != want)
         assert not len(wrong), f"{len(wrong)} counters differ, the first [table, symbol] {wrong[0]}: " \
                                f"{counts[tuple(wrong[0])]} against {want[tuple(wrong[0])]}"
         for t in range(4):
-            assert tables[t] == R.gen_optimal_table(want[t]), R.TABLE_NAMES[t]
+            assert tables[t] == jpeg_ref.gen_optimal_table(want[t]), jpeg_ref.TABLE_NAMES[t]
     finally:
         enc.close()
 
@@ -83,10 +78,10 @@ def test_wide_lane_is_not_cut_at_64_bits():
     try:
         got = enc.encode(image)
         hdr = len(enc.header)
-        assert got[:hdr] == expected[:hdr], "the tables differ: " + _first_difference(got[:hdr], expected[:hdr])
+        assert got[:hdr] == expected[:hdr], "the tables differ: " + first_difference(got[:hdr], expected[:hdr])
         # block (0, 0) is the first of the scan: a cut lane shows within the first bytes behind the header
-        assert got[hdr:hdr + 16] == expected[hdr:hdr + 16], _first_difference(got, expected)
-        assert got == expected, _first_difference(got, expected)
+        assert got[hdr:hdr + 16] == expected[hdr:hdr + 16], first_difference(got, expected)
+        assert got == expected, first_difference(got, expected)
     finally:
         enc.close()
 
@@ -131,17 +126,17 @@ def test_tables_from_the_restatements_counts(stage, name):
     rc, fault, tables = stage.tables(_four(*counts))
     assert (rc, fault) == (stage._lib.TF_OK, 0)
     for t in range(4):
-        assert tables[t] == R.gen_optimal_table(counts[t]), R.TABLE_NAMES[t]
+        assert tables[t] == jpeg_ref.gen_optimal_table(counts[t]), jpeg_ref.TABLE_NAMES[t]
 
 
 def test_tables_of_hand_made_counts(stage):
     one = np.zeros(256, np.uint32)
     one[0x21] = 7
-    hists = [one, np.full(256, 3, np.uint32), R.limiting_counts(), R.fibonacci_counts(32)]
+    hists = [one, np.full(256, 3, np.uint32), jpeg_cases.limiting_counts(), jpeg_cases.fibonacci_counts(32)]
     rc, fault, tables = stage.tables(_four(*hists))
     assert (rc, fault) == (stage._lib.TF_OK, 0)
     for t in range(4):
-        assert tables[t] == R.gen_optimal_table(hists[t]), t
+        assert tables[t] == jpeg_ref.gen_optimal_table(hists[t]), t
     assert tables[1][1] == list(range(256)) and tables[1][0][8] == 1          # equal counts: symbol 255 shares the 9 bits
 
 
@@ -149,12 +144,12 @@ def test_fibonacci_counts_give_the_fault(stage):
     good = _histograms("45x61")
     for table in range(4):
         hists = [good[t] for t in range(4)]
-        hists[table] = R.fibonacci_counts(33)
+        hists[table] = jpeg_cases.fibonacci_counts(33)
         rc, fault, _ = stage.tables(_four(*hists))
         assert rc == stage._lib.TF_ERR_STATE and fault == 1 << table
         message = stage.lib.tf_last_error().decode()
-        assert R.TABLE_NAMES[table] in message and "32" in message, message
-    rc, fault, _ = stage.tables(_four(R.fibonacci_counts(40)))
+        assert jpeg_ref.TABLE_NAMES[table] in message and "32" in message, message
+    rc, fault, _ = stage.tables(_four(jpeg_cases.fibonacci_counts(40)))
     assert rc == stage._lib.TF_ERR_STATE and fault == 0xF
 
 
@@ -188,27 +183,27 @@ def test_bad_modes_are_refused(stage):
 @pytest.mark.parametrize("restart", [1, 3, 8, 100])
 def test_gather_pass_restarts_dc_prediction_like_the_emit_pass(restart):
     from transflow_amd.jpeg import JpegEncoder
-    image = jpeg_ref.stored_image(45, 61, seed=45061)
+    image = jpeg_cases.stored_image(45, 61, seed=45061)
     enc = JpegEncoder(45, 61, 50, restart, optimize=True)
     try:
-        want = R.encode(image, 50, restart)
+        want = jpeg_ref.encode(image, 50, restart, optimize=True)
         got = enc.encode(image)
         _, counts = enc.last_tables(counts=True)
-        want_counts = R.histograms(image, 50, restart)
+        want_counts = jpeg_ref.histograms(image, 50, restart)
         assert (counts[0] == want_counts[0]).all() and (counts[2] == want_counts[2]).all(), "the DC histograms differ"
         assert (counts == want_counts).all()
-        assert got == want, _first_difference(got, want)
+        assert got == want, first_difference(got, want)
     finally:
         enc.close()
     if restart in (1, 3):                                                  # (the intervals change the DC histograms at all)
-        assert (R.histograms(image, 50, restart)[0] != R.histograms(image, 50, 100)[0]).any()
+        assert (jpeg_ref.histograms(image, 50, restart)[0] != jpeg_ref.histograms(image, 50, 100)[0]).any()
 
 
 def test_modes_alternate_on_one_handle():
     from transflow_amd import _lib
     from transflow_amd.jpeg import JpegEncoder
     image, quality, restart, own = _case("45x61")
-    _, _, _, plain = jpeg_ref.load_case(os.path.join(GOLDEN, "jpeg_45x61.npz"))
+    plain = jpeg_cases.load_case(jpeg_cases.fixture_path("jpeg", "45x61")).jpeg
     enc = JpegEncoder(45, 61, quality, restart)
     try:
         assert enc.encode(image) == plain
@@ -216,7 +211,7 @@ def test_modes_alternate_on_one_handle():
             _lib.check(enc._lib.tf_jpeg_set_optimize(enc._h, mode))
             enc.optimize = bool(mode)
             got = enc.encode(image)
-            assert got == want, f"mode {mode}: " + _first_difference(got, want)
+            assert got == want, f"mode {mode}: " + first_difference(got, want)
             assert enc.header == want[:len(enc.header)]
             assert enc.frame(image).optimize == bool(mode)
         _lib.check(enc._lib.tf_jpeg_set_optimize(enc._h, 1))               # the mode changed: the last file is not this mode's
@@ -230,15 +225,15 @@ def test_modes_alternate_on_one_handle():
 def test_one_encoder_keeps_no_counts_between_images():
     from transflow_amd.jpeg import JpegEncoder
     a, quality, restart, want_a = _case("33x47_noise_q100")
-    b = jpeg_ref.stored_image(33, 47, seed=5)                              # far fewer symbols: stale counts would change its tables
-    want_b = R.encode(b, quality, restart)
-    assert R.tables(a, quality, restart) != R.tables(b, quality, restart)
+    b = jpeg_cases.stored_image(33, 47, seed=5)                            # far fewer symbols: stale counts would change its tables
+    want_b = jpeg_ref.encode(b, quality, restart, optimize=True)
+    assert jpeg_ref.tables(a, quality, restart) != jpeg_ref.tables(b, quality, restart)
     enc = JpegEncoder(33, 47, quality, restart, optimize=True)
     try:
         assert enc.encode(a) == want_a
         got = enc.encode(b)
-        assert got == want_b, _first_difference(got, want_b)
-        assert (enc.last_tables(counts=True)[1] == R.histograms(b, quality, restart)).all()
+        assert got == want_b, first_difference(got, want_b)
+        assert (enc.last_tables(counts=True)[1] == jpeg_ref.histograms(b, quality, restart)).all()
         assert enc.encode(a) == want_a
     finally:
         enc.close()
@@ -260,9 +255,9 @@ def test_grey_image_and_one_pixel_give_pillows_file():
     for image in (grey, np.array([[[200, 30, 90]]], np.uint8)):
         enc = JpegEncoder(image.shape[0], image.shape[1], 75, 4, optimize=True)
         try:
-            want = R.encode(image, 75, 4)
+            want = jpeg_ref.encode(image, 75, 4, optimize=True)
             got = enc.encode(image)
-            assert got == want, _first_difference(got, want)
+            assert got == want, first_difference(got, want)
             tables = enc.last_tables()
             if image.shape[0] > 1:
                 assert tables[3] == ([1] + [0] * 15, [0x00]) and tables[2] == ([1] + [0] * 15, [0])
@@ -325,7 +320,7 @@ def test_one_lane_tables_kernel_builds_the_same_tables(monkeypatch):
     enc = JpegEncoder(224, 224, quality, restart, optimize=True)
     try:
         got = enc.encode(image)
-        assert got == expected, _first_difference(got, expected)
+        assert got == expected, first_difference(got, expected)
     finally:
         enc.close()
 
@@ -334,7 +329,7 @@ def test_device_decoder_reads_the_optimised_file():
     from transflow_amd.jpeg import JpegEncoder
     from transflow_amd.jpegdec import JpegDecoder
     image, quality, restart, expected = _case("45x61")
-    _, _, _, plain = jpeg_ref.load_case(os.path.join(GOLDEN, "jpeg_45x61.npz"))
+    plain = jpeg_cases.load_case(jpeg_cases.fixture_path("jpeg", "45x61")).jpeg
     enc, dec = JpegEncoder(45, 61, quality, restart, optimize=True), JpegDecoder(61, 45)
     try:
         frame = enc.frame(image)
@@ -412,8 +407,8 @@ def test_compositor_returns_the_optimised_file_of_its_plain_render(layers, devic
     for t, (frame, raw) in enumerate(zip(files, plain)):
         assert isinstance(frame, JpegFrame) and frame.shape == (H, W, 3) and frame.quality == 50 and frame.optimize
         assert frame.restart_mcus == default_restart_mcus()
-        want = R.encode(raw, 50, frame.restart_mcus)
-        assert frame.data == want, f"frame {t}: " + _first_difference(frame.data, want)
+        want = jpeg_ref.encode(raw, 50, frame.restart_mcus, optimize=True)
+        assert frame.data == want, f"frame {t}: " + first_difference(frame.data, want)
         assert len(want) < len(jpeg_ref.encode(raw, 50, frame.restart_mcus))
 
 

@@ -1,5 +1,5 @@
 """tf_jpeg_create_sub on the GPU: 4:4:4 and 4:2:2 files against libjpeg's own (tests/golden/jpegsub_*.npz, written by
-tools/capture_golden_jpeg_sub.py), the whole file, byte for byte -- with the Annex K tables and with the frame's own --
+tools/capture_golden_jpeg.py), the whole file, byte for byte -- with the Annex K tables and with the frame's own --
 and the way such files go on: the device decoder, the compositor, the MJPEG file output."""
 import ctypes as C
 import glob
@@ -8,41 +8,37 @@ import os
 import numpy as np
 import pytest
 
-from tests import jpeg_sub_ref
+from tests import jpeg_cases, jpeg_ref
+from tests.jpeg_cases import GOLDEN, first_difference
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "jpegsub_*.npz")))
 SUBS = [0, 1]
 SUB_IDS = ["444", "422"]
 
 
 def _case(name, sub):
-    return jpeg_sub_ref.load_case(os.path.join(GOLDEN, jpeg_sub_ref.fixture_name(name, sub)))
-
-
-def _first_difference(got: bytes, want: bytes) -> str:
-    n = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
-    return f"{len(got)} bytes against {len(want)}, first difference at byte {n}: {got[n:n + 8].hex()} / {want[n:n + 8].hex()}"
+    return jpeg_cases.load_case(jpeg_cases.fixture_path("jpegsub", name, sub))
 
 
 def test_every_case_is_here():
-    names = sorted(jpeg_sub_ref.fixture_name(name, sub) for name in jpeg_sub_ref.CASES for sub in SUBS)
+    names = sorted(os.path.basename(jpeg_cases.fixture_path("jpegsub", name, sub))
+                   for name in jpeg_cases.LAYOUT_CASES for sub in SUBS)
     assert sorted(os.path.basename(p) for p in FIXTURES) == names
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[8:-4])
 def test_encoder_writes_libjpegs_file(path):
     from transflow_amd.jpeg import JpegEncoder
-    image, quality, restart, sub, optimize, expected = jpeg_sub_ref.load_case(path)
+    image, quality, restart, sub, optimize, expected = jpeg_cases.load_case(path)
     enc = JpegEncoder(image.shape[0], image.shape[1], quality, restart, optimize=optimize, subsampling=sub)
     try:
         assert enc.subsampling == sub and enc.restart_mcus == restart
         if not optimize:
-            assert enc.header == expected[:len(enc.header)] == jpeg_sub_ref.header(*image.shape[:2], quality, restart, sub)
+            assert enc.header == expected[:len(enc.header)] == jpeg_ref.header(*image.shape[:2], quality, restart, sub)
         got = enc.encode(image)
-        assert got == expected, _first_difference(got, expected)
+        assert got == expected, first_difference(got, expected)
         if optimize:
             assert enc.header == expected[:len(enc.header)]
         frame = enc.frame(image)
@@ -60,7 +56,7 @@ def test_one_encoder_keeps_no_state_between_images(sub, optimize):
     a, quality, restart, _, _, want_a = _case("33x47_noise_q100_opt" if optimize else "33x47_noise_q100", sub)
     b = np.empty((33, 47, 3), np.uint8)
     b[:] = (90, 160, 30)
-    want_b = jpeg_sub_ref.encode(b, quality, restart, sub, optimize)
+    want_b = jpeg_ref.encode(b, quality, restart, sub, optimize)
     enc = JpegEncoder(33, 47, quality, restart, optimize=optimize, subsampling=sub)
     try:
         assert enc.encode(a) == want_a
@@ -103,8 +99,8 @@ def test_gathered_histograms_are_the_restatements(sub, name):
     try:
         assert enc.encode(image) == expected
         tables, counts = enc.last_tables(counts=True)
-        np.testing.assert_array_equal(counts, jpeg_sub_ref.histograms(image, quality, restart, sub))
-        assert tables == [(list(b), list(v)) for b, v in jpeg_sub_ref.tables(image, quality, restart, sub)]
+        np.testing.assert_array_equal(counts, jpeg_ref.histograms(image, quality, restart, sub))
+        assert tables == [(list(b), list(v)) for b, v in jpeg_ref.tables(image, quality, restart, sub)]
     finally:
         enc.close()
 
@@ -128,12 +124,12 @@ def test_bad_subsampling_values_are_refused():
 
 def test_names_and_numbers_make_the_same_encoder():
     from transflow_amd.jpeg import JpegEncoder
-    image = jpeg_sub_ref.smooth_image(17, 33)
+    image = jpeg_cases.formula_image(17, 33)
     for name, value in (("4:4:4", 0), ("4:2:2", 1), ("4:2:0", 2)):
         enc = JpegEncoder(17, 33, 50, 4, subsampling=name)
         try:
             assert enc.subsampling == value
-            assert enc.encode(image) == jpeg_sub_ref.encode(image, 50, 4, value)
+            assert enc.encode(image) == jpeg_ref.encode(image, 50, 4, value)
         finally:
             enc.close()
 
@@ -146,12 +142,12 @@ def test_default_interval_is_the_one_the_host_encodes_with(sub, optimize):
     from transflow_amd.jpeg import JpegEncoder, pillow_encode
     default = int(_lib.load().tf_jpeg_default_restart_mcus_for(sub))
     assert default == (16, 12, 8)[sub]
-    image = jpeg_sub_ref.noise_image(45, 61, seed=9) // 2 + jpeg_sub_ref.smooth_image(45, 61) // 2
+    image = jpeg_cases.noise_image(45, 61, seed=9) // 2 + jpeg_cases.formula_image(45, 61) // 2
     enc = JpegEncoder(45, 61, 75, optimize=optimize, subsampling=sub)
     try:
         assert enc.restart_mcus == default
         got, want = enc.encode(image), pillow_encode(image, 75, default, optimize, sub)
-        assert got == want, _first_difference(got, want)
+        assert got == want, first_difference(got, want)
     finally:
         enc.close()
 
@@ -161,7 +157,7 @@ def test_device_decoder_returns_pillows_pixels_of_a_device_made_file(sub):
     from transflow_amd.framecodec import pillow_decode
     from transflow_amd.jpeg import JpegEncoder
     from transflow_amd.jpegdec import JpegDecoder, probe
-    image = jpeg_sub_ref.noise_image(23, 41, seed=2) // 2 + jpeg_sub_ref.smooth_image(23, 41) // 2
+    image = jpeg_cases.noise_image(23, 41, seed=2) // 2 + jpeg_cases.formula_image(23, 41) // 2
     enc = JpegEncoder(23, 41, 90, 3, subsampling=sub)
     dec = JpegDecoder(41, 23)
     try:
@@ -230,8 +226,8 @@ def test_compositor_returns_the_file_of_its_plain_render(plain_render, sub, opti
     for t, (frame, raw) in enumerate(zip(files, plain_render)):
         assert isinstance(frame, JpegFrame) and frame.shape == (H, W, 3)
         assert (frame.quality, frame.subsampling, frame.optimize, frame.restart_mcus) == (60, sub, optimize, default)
-        want = jpeg_sub_ref.encode(raw, 60, default, sub, optimize)
-        assert frame.data == want, f"frame {t}: " + _first_difference(frame.data, want)
+        want = jpeg_ref.encode(raw, 60, default, sub, optimize)
+        assert frame.data == want, f"frame {t}: " + first_difference(frame.data, want)
 
 
 # ---- recorded, and fed back ---------------------------------------------------------------------------------------------
@@ -241,7 +237,7 @@ def test_a_recorded_444_stream_is_read_back_on_the_device(tmp_path):
     from transflow_amd.jpeg import JpegEncoder
     from transflow_amd.jpegdec import MjpegFrameProvider
     from transflow_amd.output import HipMjpegFileOutput
-    images = [jpeg_sub_ref.noise_image(23, 41, seed=30 + i) // 2 + jpeg_sub_ref.smooth_image(23, 41) // 2 for i in range(3)]
+    images = [jpeg_cases.noise_image(23, 41, seed=30 + i) // 2 + jpeg_cases.formula_image(23, 41) // 2 for i in range(3)]
     enc = JpegEncoder(23, 41, 85, subsampling="4:4:4")
     try:
         frames = [enc.frame(image) for image in images]

@@ -10,7 +10,7 @@ import types
 import numpy as np
 import pytest
 
-from tests import jpeg_sub_ref
+from tests import jpeg_cases, jpeg_ref
 
 W, H = 41, 23
 
@@ -28,7 +28,7 @@ pytestmark = pytest.mark.skipif(not _pillow_with_restart(), reason="no Pillow wi
 
 def _frames(subsampling, n=3, quality=70, restart=5, optimize=False):
     from transflow_amd.jpeg import JpegFrame, pillow_encode
-    images = [jpeg_sub_ref.noise_image(H, W, seed=20 + i) // 2 + jpeg_sub_ref.smooth_image(H, W) // 2 for i in range(n)]
+    images = [jpeg_cases.noise_image(H, W, seed=20 + i) // 2 + jpeg_cases.formula_image(H, W) // 2 for i in range(n)]
     return images, [JpegFrame(pillow_encode(im, quality, restart, optimize, subsampling), im.shape, quality, restart, optimize,
                               subsampling) for im in images]
 
@@ -50,13 +50,13 @@ def test_jpeg_frame_carries_its_subsampling_and_older_states_are_420():
 
 def test_pillow_encode_takes_numbers_and_names():
     from transflow_amd.jpeg import pillow_encode, subsampling_value
-    image = jpeg_sub_ref.smooth_image(H, W)
+    image = jpeg_cases.formula_image(H, W)
     for value, name in ((0, "4:4:4"), (1, "4:2:2"), (2, "4:2:0")):
         assert subsampling_value(value) == subsampling_value(name) == value
         for optimize in (False, True):
             data = pillow_encode(image, 60, 3, optimize, subsampling=name)
             assert data == pillow_encode(image, 60, 3, optimize, subsampling=value)
-            assert data == jpeg_sub_ref.encode(image, 60, 3, value, optimize)
+            assert data == jpeg_ref.encode(image, 60, 3, value, optimize)
     assert pillow_encode(image, 60, 3) == pillow_encode(image, 60, 3, subsampling=2)
     with pytest.raises(ValueError):
         pillow_encode(image, 60, 3, subsampling=3)
@@ -66,7 +66,7 @@ def test_optimized_host_encode_of_a_long_thin_444_image_has_room():
     """8188 MCUs of 8 x 8 in a row, noise at quality 100: Pillow's buffer must hold the whole file at once (MAXBLOCK
     follows the MCU size)."""
     from transflow_amd.jpeg import pillow_encode
-    image = jpeg_sub_ref.noise_image(1, 65500, seed=4)
+    image = jpeg_cases.noise_image(1, 65500, seed=4)
     data = pillow_encode(image, 100, 16, optimize=True, subsampling=0)
     assert data[:2] == b"\xff\xd8" and data[-2:] == b"\xff\xd9" and len(data) > 65536
 

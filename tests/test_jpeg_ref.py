@@ -12,9 +12,8 @@ import types
 import numpy as np
 import pytest
 
-from tests import jpeg_ref
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+from tests import jpeg_cases, jpeg_ref
+from tests.jpeg_cases import GOLDEN
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "jpeg_*.npz")))
 
 
@@ -30,17 +29,17 @@ needs_pillow_restart = pytest.mark.skipif(not _pillow_with_restart(), reason="no
 
 
 def test_every_case_has_its_fixture():
-    assert sorted(os.path.basename(p)[5:-4] for p in FIXTURES) == sorted(jpeg_ref.CASES)
+    assert sorted(os.path.basename(p)[5:-4] for p in FIXTURES) == sorted(jpeg_cases.BASELINE_CASES)
     for path in FIXTURES:
-        image, quality, restart, expected = jpeg_ref.load_case(path)
-        h, w, _, q, r = jpeg_ref.CASES[os.path.basename(path)[5:-4]]
+        image, quality, restart, _, _, expected = jpeg_cases.load_case(path)
+        h, w, _, q, r = jpeg_cases.BASELINE_CASES[os.path.basename(path)[5:-4]]
         assert image.shape == (h, w, 3) and image.dtype == np.uint8 and (quality, restart) == (q, r)
         assert os.path.getsize(path) < (1 << 20)
 
 
 @pytest.mark.parametrize("path", FIXTURES, ids=lambda p: os.path.basename(p)[5:-4])
 def test_restatement_equals_libjpegs_file(path):
-    image, quality, restart, expected = jpeg_ref.load_case(path)
+    image, quality, restart, _, _, expected = jpeg_cases.load_case(path)
     got = jpeg_ref.encode(image, quality, restart)
     assert len(got) == len(expected)
     assert got == expected
@@ -49,7 +48,7 @@ def test_restatement_equals_libjpegs_file(path):
 def test_fixtures_exercise_what_they_are_for():
     """The failure modes the cases are chosen for do occur in their files."""
     def scan(name):
-        data = jpeg_ref.load_case(os.path.join(GOLDEN, f"jpeg_{name}.npz"))[3]
+        data = jpeg_cases.load_case(jpeg_cases.fixture_path("jpeg", name)).jpeg
         return data[data.index(b"\xff\xda") + 14:-2]
     noisy = scan("33x47_noise_q100")
     assert b"\xff\x00" in noisy                                            # byte stuffing
@@ -57,7 +56,7 @@ def test_fixtures_exercise_what_they_are_for():
     assert [wrapped.count(bytes([0xFF, 0xD0 + k])) for k in range(8)] == [2, 2, 2, 1, 1, 1, 1, 1]
     assert not any(bytes([0xFF, 0xD0 + k]) in scan("45x61_r100") for k in range(8))            # one interval: no marker
     # category 11: a DC step of 2040 between neighbouring blocks of the checkerboard
-    y = jpeg_ref.ycc(jpeg_ref.checkerboard(32, 32))[0]
+    y = jpeg_ref.ycc(jpeg_cases.checkerboard(32, 32))[0]
     dc = jpeg_ref.blocks_quantised(y, jpeg_ref.quant_table(jpeg_ref.QUANT_LUMA, 100))[..., 0]
     assert int(abs(dc[0, 1] - dc[0, 0])).bit_length() == 11
 
@@ -67,16 +66,16 @@ def test_fixtures_exercise_what_they_are_for():
                                                    ((49, 31), 100, 7), ((8, 8), 1, 3)])
 def test_restatement_equals_live_pillow(shape, quality, restart):
     from transflow_amd.jpeg import pillow_encode
-    for image in (jpeg_ref.stored_image(*shape, seed=quality), jpeg_ref.noise_image(*shape, seed=restart)):
+    for image in (jpeg_cases.stored_image(*shape, seed=quality), jpeg_cases.rng_noise_image(*shape, seed=restart)):
         assert jpeg_ref.encode(image, quality, restart) == pillow_encode(image, quality, restart)
 
 
 @needs_pillow_restart
 @pytest.mark.parametrize("image,quality,restart", [
-    (lambda: jpeg_ref.directed_luma(96, 96, 3), 100, 3), (lambda: jpeg_ref.directed_luma(40, 56, 4), 90, 2),
-    (lambda: jpeg_ref.directed_chroma(96, 96, 3), 100, 4), (lambda: jpeg_ref.directed_chroma(50, 70, 4), 75, 1),
-    (lambda: jpeg_ref.binary_noise(32, 48, 5), 100, 2), (lambda: jpeg_ref.chroma_checker(48, 80), 100, 3),
-    (lambda: jpeg_ref.formula_image(16, 16400), 50, 1)],                  # 1025 intervals
+    (lambda: jpeg_cases.directed_luma(96, 96, 3), 100, 3), (lambda: jpeg_cases.directed_luma(40, 56, 4), 90, 2),
+    (lambda: jpeg_cases.directed_chroma(96, 96, 3), 100, 4), (lambda: jpeg_cases.directed_chroma(50, 70, 4), 75, 1),
+    (lambda: jpeg_cases.binary_noise(32, 48, 5), 100, 2), (lambda: jpeg_cases.chroma_checker(48, 80), 100, 3),
+    (lambda: jpeg_cases.formula_image(16, 16400), 50, 1)],                # 1025 intervals
     ids=["directed_luma", "directed_luma_ragged", "directed_chroma", "directed_chroma_ragged", "binary_noise",
          "chroma_checker", "1025_intervals"])
 def test_restatement_equals_live_pillow_on_directed_content(image, quality, restart):
@@ -94,7 +93,7 @@ _traced = {}
 def _trace(name):
     """The trace of a fixture's image, whose file is the fixture's: made once."""
     if name not in _traced:
-        image, quality, restart, expected = jpeg_ref.load_case(os.path.join(GOLDEN, f"jpeg_{name}.npz"))
+        image, quality, restart, _, _, expected = jpeg_cases.load_case(jpeg_cases.fixture_path("jpeg", name))
         _traced[name] = jpeg_ref.trace(image, quality, restart)
         assert _traced[name].data == expected
     return _traced[name]
@@ -102,11 +101,11 @@ def _trace(name):
 
 def _small_cases():
     """Every case but the `formula` ones, which are there for their sizes and interval counts, not for their symbols."""
-    return [name for name, case in jpeg_ref.CASES.items() if case[2] != "formula"]
+    return [name for name, case in jpeg_cases.BASELINE_CASES.items() if case[2] != "formula"]
 
 
 def test_trace_is_encodes_own_account():
-    image, quality, restart, expected = jpeg_ref.load_case(os.path.join(GOLDEN, "jpeg_45x61_r3.npz"))
+    image, quality, restart, _, _, expected = jpeg_cases.load_case(jpeg_cases.fixture_path("jpeg", "45x61_r3"))
     t = _trace("45x61_r3")
     assert len(t.mcu_bits) == len(t.flushed) == len(t.interval_end) == 12
     assert t.interval_end == [False, False, True] * 4
@@ -153,7 +152,7 @@ def test_fattest_case_puts_ff_at_the_edges_of_the_flush_loop():
     assert any(byte == 0xFF and j % 64 == 0 and j >= 64 for chunk in t.flushed for j, byte in enumerate(chunk))
     ends = [chunk for chunk, end in zip(t.flushed, t.interval_end) if end]
     assert len(ends) == 3 and any(chunk[-1] == 0xFF for chunk in ends[:-1])
-    expected = jpeg_ref.load_case(os.path.join(GOLDEN, "jpeg_32x48_binary_q100.npz"))[3]
+    expected = jpeg_cases.load_case(jpeg_cases.fixture_path("jpeg", "32x48_binary_q100")).jpeg
     assert any(bytes([0xFF, 0x00, 0xFF, 0xD0 + k]) in expected for k in range(2))
 
 
@@ -161,7 +160,7 @@ def test_fattest_case_puts_ff_at_the_edges_of_the_flush_loop():
                                             ("1x65500", 512), ("65500x1", 512), ("40x4099", 97)])
 def test_interval_counts_are_the_ones_the_cases_are_for(name, intervals):
     """Counted from the file: RST markers plus one.  (An 0xFF of the entropy-coded data has an 0x00 behind it.)"""
-    data = jpeg_ref.load_case(os.path.join(GOLDEN, f"jpeg_{name}.npz"))[3]
+    data = jpeg_cases.load_case(jpeg_cases.fixture_path("jpeg", name)).jpeg
     scan = data[data.index(b"\xff\xda") + 14:-2]
     markers = [scan[i + 1] for i in range(len(scan) - 1) if scan[i] == 0xFF and 0xD0 <= scan[i + 1] <= 0xD7]
     assert len(markers) + 1 == intervals
@@ -171,7 +170,7 @@ def test_interval_counts_are_the_ones_the_cases_are_for(name, intervals):
 # ---- JpegFrame ---------------------------------------------------------------------------------------------------------
 def _frame(shape=(24, 40), quality=50, restart=4, seed=3):
     from transflow_amd.jpeg import JpegFrame
-    image = jpeg_ref.stored_image(*shape, seed=seed)
+    image = jpeg_cases.stored_image(*shape, seed=seed)
     return image, JpegFrame(jpeg_ref.encode(image, quality, restart), image.shape, quality, restart)
 
 

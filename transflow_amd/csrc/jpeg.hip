@@ -21,7 +21,7 @@
 //                  behind the last; no byte at or past `capacity` is written.
 //
 // Mode 1 (tf_jpeg_set_optimize), the frame's own Huffman tables -- libjpeg's optimize_coding, Pillow's optimize=True,
-// byte for byte (tests/jpeg_optimize_ref.py, tests/golden/jpegopt_*.npz).  k_jpeg_encode is a template over its pass:
+// byte for byte (tests/jpeg_ref.py, tests/golden/jpegopt_*.npz).  k_jpeg_encode is a template over its pass:
 //   k_jpeg_encode<GATHER>     the same front; in place of placing bits the lanes count their symbols (jchuff.c
 //                             encode_mcu_gather) into an LDS histogram of the wave, added to the frame's at the end.
 //   k_jpeg_tables             one work-group, a wave per table: jpeg_gen_optimal_table's rule (jpeg_huff.h) -> the DHT
@@ -35,7 +35,7 @@
 // is then padded with its last row -- a chroma row below the image averages rows H - 2 and H - 1 of an image of even
 // height, not H - 1 twice.
 //
-// The other chroma layouts (tf_jpeg_create_sub; tests/jpeg_sub_ref.py, tests/golden/jpegsub_*.npz): k_jpeg_encode is a
+// The other chroma layouts (tf_jpeg_create_sub; tests/jpeg_ref.py, tests/golden/jpegsub_*.npz): k_jpeg_encode is a
 // template over the layout too.  4:4:4: an MCU is 8 x 8 pixels, blocks Y Cb Cr, the chroma samples as converted, no
 // dummy blocks.  4:2:2: 16 x 8 pixels, blocks Y0 Y1 Cb Cr, chroma by jcsample.c h2v1_downsample -- (a + b + bias) >> 1,
 // bias 0, 1, 0, 1 ... along the output row -- and Y1 a dummy in the last MCU column when ceil(W / 8) is odd.  Edges are

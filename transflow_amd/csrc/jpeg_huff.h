@@ -1,6 +1,6 @@
 // The frame's own Huffman tables (jpeg.hip, mode 1): libjpeg's jpeg_gen_optimal_table (jchuff.c) as code that the host
 // and one thread of the device run alike, and jpeg_make_c_derived_tbl behind it.  tools/jpeg_huff_host_check.cpp runs
-// this file on the CPU; tests/jpeg_optimize_ref.py is the numpy statement of the same rule.
+// this file on the CPU; tests/jpeg_ref.py is the numpy statement of the same rule.
 //
 // The rule: 257 frequencies, the last a reserved symbol of frequency 1 so that no real code is all ones.  Until only
 // one is left, the two smallest non-zero frequencies are merged -- among equals the LARGEST index is taken, first c1,
