@@ -18,7 +18,8 @@ def image(height: int, width: int, seed: int, kind: str = "scene", grey: bool = 
         out = rng.integers(0, 256, shape, dtype=np.uint8)
         # one block of a one-level checkerboard: at quality 100 its only AC coefficient is the last, behind three ZRLs
         yy, xx = np.mgrid[0:8, 0:8]
-        out[8:16, 16:24] = (127 + ((yy + xx) & 1))[..., None] if out.ndim == 3 else 127 + ((yy + xx) & 1)
+        board = (127 + ((yy + xx) & 1))[:max(min(height, 16) - 8, 0), :max(min(width, 24) - 16, 0)]    # (what a small image has of it)
+        out[8:16, 16:24] = board[..., None] if out.ndim == 3 else board
         return out
     if kind == "flat":
         return np.full(shape, 128, np.uint8)
@@ -66,6 +67,38 @@ def valid_cases() -> list:
     out.append(("sym_flat", encode(image(32, 48, 0, "flat"), restart=1)))
     out.append(("sym_optimize", encode(image(31, 33, 42), restart=2, optimize=True)))
     out.append(("sym_handmade", _handmade("0" + "00", *HANDMADE_AC)))       # DC 0, EOB: tables of one and four codes
+    return out
+
+
+# ---- the pixel stages' geometry: IDCT to planes, upsampling, colour, the four-pixel store ------------------------------------
+GEOMETRY_LAYOUTS = {"grey": None, "444": 0, "422": 1, "420": 2}                    # Pillow's `subsampling`
+# widths 1..4: libjpeg replicates the chroma (downsampled_width <= 2); 5: the first fancy one; 7 / 8 / 9 and 16 / 17 / 33:
+# either side of the 8- and 16-pixel MCU edges.  Heights 1..3: one or two chroma rows, the context row the same row again.
+GEOMETRY_NODRI = ((1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 33), (1, 2, 3, 8, 9, 16, 17))     # (widths, heights): the parallel scan
+GEOMETRY_DRI1 = ((1, 2, 4, 5, 9, 17, 33), (1, 3, 9, 17))                            # restart interval 1: the serial path
+GEOMETRY_MORE = ((4, 4), (3, 5))                                                    # (width, height) without DRI, outside the grid
+
+
+def geometry_name(layout: str, width: int, height: int, dri: bool) -> str:
+    return f"px_{layout}_{width}x{height}" + ("_r1" if dri else "")
+
+
+def geometry_sizes(dri: bool) -> list:
+    """[(width, height)] of one layout's cases."""
+    widths, heights = GEOMETRY_DRI1 if dri else GEOMETRY_NODRI
+    return [(w, h) for w in widths for h in heights] + ([] if dri else list(GEOMETRY_MORE))
+
+
+def geometry_cases() -> list:
+    """[(name, file bytes)]: noise at quality 95, so that neighbouring chroma samples differ and a wrong upsampling rule,
+    context row or plane stride changes pixels."""
+    out = []
+    for dri in (False, True):
+        for n, layout in enumerate(GEOMETRY_LAYOUTS):
+            for w, h in geometry_sizes(dri):
+                pixels = image(h, w, 7000 + 1000 * n + 40 * h + w, "noise", grey=layout == "grey")
+                out.append((geometry_name(layout, w, h, dri),
+                            encode(pixels, quality=95, subsampling=GEOMETRY_LAYOUTS[layout], restart=int(dri))))
     return out
 
 

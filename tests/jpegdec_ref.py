@@ -1,6 +1,7 @@
 """The device JPEG decoder's rules, restated in numpy (transflow_amd/csrc/jpegdec_common.h, jpegdec.hip; DESIGN.md
 section 19): which files are taken, why the others are rejected, and libjpeg's arithmetic for the pixels -- jdhuff.c's
-decoding, jidctint.c's islow IDCT, jdsample.c's fancy upsampling with jdmainct.c's edge rows, jdcolor.c's tables.
+decoding, jidctint.c's islow IDCT, jdsample.c's upsampling (fancy, or replicating for a frame up to 4 pixels wide) with
+jdmainct.c's edge rows, jdcolor.c's tables.
 tests/test_jpegdec_ref.py holds it equal to Pillow; the GPU tests and tools/jpegdec_host_check.cpp are held equal to it.
 """
 from __future__ import annotations
@@ -353,6 +354,23 @@ def _h2v2(p: np.ndarray, dw: int, dh: int, width: int, height: int) -> np.ndarra
     return np.where(c == 0, first, np.where(c == dw - 1, last, mid))
 
 
+def _replicated(p: np.ndarray, vs: int, width: int, height: int) -> np.ndarray:
+    """h2v1_upsample / h2v2_upsample: every chroma sample is the pixel's own, no neighbour and no context row."""
+    return p[(np.arange(height) >> (vs - 1))[:, None], (np.arange(width) >> 1)[None, :]]
+
+
+def _upsampled(p: np.ndarray, hs: int, vs: int, width: int, height: int, narrow_rule: bool = True) -> np.ndarray:
+    """A chroma plane of whole MCUs at the picture's size, as jinit_upsampler chooses: the fancy filters only where the
+    component's downsampled_width = ceil(W / 2) is above 2, replication otherwise.  narrow_rule=False blends at every
+    width: not libjpeg's pixels for W <= 4, kept for the test that shows the corpus tells the two apart."""
+    dw, dh = (width + 1) // 2, (height + 1) // 2
+    if hs == 1:
+        return p[:height, :width]
+    if narrow_rule and dw <= 2:
+        return _replicated(p, vs, width, height)
+    return _h2v1(p[:height], dw, width) if vs == 1 else _h2v2(p, dw, dh, width, height)
+
+
 def _colour(y, cb, cr):
     """jdcolor.c ycc_rgb_convert with build_ycc_rgb_table's tables (SCALEBITS 16)."""
     cb, cr = cb - 128, cr - 128
@@ -391,6 +409,15 @@ def coefficients_crc(coefs: np.ndarray) -> int:
 
 def decode(data: bytes, order: str = "rgb", trace=None) -> np.ndarray:
     """uint8 (H, W, 3): the pixels of PIL.Image.open(...).convert("RGB"); Rejected for a file the device does not take."""
+    return _decode(data, order, trace)
+
+
+def _decode_blending_at_every_width(data: bytes) -> np.ndarray:
+    """decode() without jinit_upsampler's choice (see _upsampled): for tests/test_jpegdec_ref.py only."""
+    return _decode(data, "rgb", None, narrow_rule=False)
+
+
+def _decode(data: bytes, order: str, trace, narrow_rule: bool = True) -> np.ndarray:
     hd, coefs = decode_coefficients(data, trace)
     W, H, hs, vs = hd["width"], hd["height"], hd["h_samp"], hd["v_samp"]
     mx, my = hd["mcus_x"], hd["mcus_y"]
@@ -404,13 +431,7 @@ def decode(data: bytes, order: str = "rgb", trace=None) -> np.ndarray:
         out = np.stack([y, y, y], axis=-1).astype(np.uint8)
     else:
         planes = [samples[:, luma + i].reshape(my, mx, 8, 8).transpose(0, 2, 1, 3).reshape(my * 8, mx * 8) for i in range(2)]
-        dw, dh = (W + 1) // 2, (H + 1) // 2
-        if hs == 1:
-            cb, cr = (p[:H, :W] for p in planes)
-        elif vs == 1:
-            cb, cr = (_h2v1(p[:H], dw, W) for p in planes)
-        else:
-            cb, cr = (_h2v2(p, dw, dh, W, H) for p in planes)
+        cb, cr = (_upsampled(p, hs, vs, W, H, narrow_rule) for p in planes)
         out = _colour(y, cb, cr)
     return out[:, :, ::-1].copy() if order == "bgr" else out
 

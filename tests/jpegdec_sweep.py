@@ -129,15 +129,19 @@ def _seg(marker: int, payload, fill: int = 0) -> bytes:
 
 
 def build(blocks, size, colour: bool = False, dc=None, ac=None, quant=1, restart: int = 0, width=None, height=None,
-          merge_dht: bool = False, merge_dqt: bool = False, extra: bytes = b"", fill: int = 0) -> Built:
+          merge_dht: bool = False, merge_dqt: bool = False, extra: bytes = b"", fill: int = 0, sampling=(2, 2)) -> Built:
     """A baseline file.  size: (across, down) in MCUs -- 8 x 8 blocks of a grey file, 16 x 16 pixels of 6 blocks (4 luma,
     Cb, Cr) of a 4:2:0 one; width / height: the picture's, where it ends inside the last MCUs.  blocks: all of them in
-    scan order.  dc, ac: a (counts, vals) table, or one per component; quant: a number or 64 of them by zigzag position,
-    or one such per component.  Equal tables share an id.  restart: the interval in MCUs (0: no DRI).  merge_dht,
+    scan order.  sampling: a colour file's luma factors -- (2, 2), (2, 1) for 4:2:2 (16 x 8 pixels of 4 blocks: 2 luma,
+    Cb, Cr) or (1, 1) for 4:4:4 (8 x 8 pixels of 3 blocks).  dc, ac: a (counts, vals) table, or one per component; quant:
+    a number or 64 of them by zigzag position, or one such per component.  Equal tables share an id.  restart: the interval in MCUs (0: no DRI).  merge_dht,
     merge_dqt: one segment for all tables of the kind; extra: bytes put in front of SOS; fill: FF bytes in front of every
     marker of the header."""
     ncomp = 3 if colour else 1
-    per_mcu = 6 if colour else 1
+    assert sampling in ((1, 1), (2, 1), (2, 2)), sampling
+    hs, vs = sampling if colour else (1, 1)
+    luma = hs * vs
+    per_mcu = luma + 2 if colour else 1
     n_mcus = size[0] * size[1]
     assert len(blocks) == n_mcus * per_mcu, (len(blocks), n_mcus * per_mcu)
     each = lambda v, single: [v] * ncomp if single(v) else list(v)
@@ -156,13 +160,13 @@ def build(blocks, size, colour: bool = False, dc=None, ac=None, quant=1, restart
     q_tabs, q_ids = ids(quants)
     dc_tabs, dc_ids = ids(dcs)
     ac_tabs, ac_ids = ids(acs)
-    mw = 16 if colour else 8
-    w, h = width or size[0] * mw, height or size[1] * mw
-    assert -(-w // mw) == size[0] and -(-h // mw) == size[1]
+    mw, mh = 8 * hs, 8 * vs
+    w, h = width or size[0] * mw, height or size[1] * mh
+    assert -(-w // mw) == size[0] and -(-h // mh) == size[1]
     out = b"\xff\xd8"
     dqts = [[i] + q for i, q in enumerate(q_tabs)]
     out += _seg(0xDB, sum(dqts, []), fill) if merge_dqt else b"".join(_seg(0xDB, p, fill) for p in dqts)
-    comps = [[c + 1, (0x22 if colour and c == 0 else 0x11), q_ids[c]] for c in range(ncomp)]
+    comps = [[c + 1, ((hs << 4 | vs) if c == 0 else 0x11), q_ids[c]] for c in range(ncomp)]
     out += _seg(0xC0, [8, *h.to_bytes(2, "big"), *w.to_bytes(2, "big"), ncomp] + sum(comps, []), fill)
     dhts = [[i] + list(t[0]) + list(t[1]) for i, t in enumerate(dc_tabs)] + [[0x10 | i] + list(t[0]) + list(t[1]) for i, t in enumerate(ac_tabs)]
     out += _seg(0xC4, sum(dhts, []), fill) if merge_dht else b"".join(_seg(0xC4, p, fill) for p in dhts)
@@ -177,7 +181,7 @@ def build(blocks, size, colour: bool = False, dc=None, ac=None, quant=1, restart
         bits, iv_ops = [], []
         for m in range(first, min(first + per, n_mcus)):
             for blk in range(per_mcu):
-                c = 0 if not colour or blk < 4 else blk - 3
+                c = 0 if blk < luma else blk - luma + 1
                 b, o = _block_bits(blocks[m * per_mcu + blk], dc_codes[c], ac_codes[c])
                 bits.append(b)
                 iv_ops.append(o)
@@ -460,3 +464,113 @@ SUBS = (16, 64, 128)                    # the subsequence sizes whose entry rows
 
 def family_of(name: str) -> str:
     return name[0]
+
+
+# ---- the pixel stages: colour, MCU order, the IDCT's basis -------------------------------------------------------------------
+# Families G..I are not part of all_cases() / jpegdec_sweep.npz: tests/golden/jpegdec_geometry.npz keeps them with
+# Pillow's pixels (tools/capture_golden_jpegdec.py); tests/test_jpegdec_sweep_ref.py holds the restatement equal to Pillow on
+# each of them and tests/test_gpu_jpegdec_geometry.py the device to both.
+def flat_blocks(samples, components, restart_blocks: int = 0) -> list:
+    """DC-only blocks at quantiser 8, where a block's 64 samples are 128 + DC: the DC differences that give the blocks, in
+    scan order, the flat sample values `samples` (0..255).  components: each block's component; restart_blocks: the
+    predictions start over every so many blocks."""
+    out, pred = [], [0, 0, 0]
+    for i, (v, c) in enumerate(zip(samples, components)):
+        if restart_blocks and i % restart_blocks == 0:
+            pred = [0, 0, 0]
+        out.append((int(v) - 128 - pred[c], []))
+        pred[c] = int(v) - 128
+    return out
+
+
+LATTICE_Y = (0, 1, 16, 127, 128, 235, 254, 255)
+LATTICE_C = (0, 1, 16, 64, 127, 128, 129, 192, 240, 254, 255)
+LATTICE_SIZE = (44, 22)                 # 968 MCUs of 8 x 8: 352 x 176 pixels
+
+
+def lattice() -> list:
+    """[(Y, Cb, Cr)] of the colour lattice's MCUs, in scan order."""
+    return [(y, cb, cr) for y in LATTICE_Y for cb in LATTICE_C for cr in LATTICE_C]
+
+
+def _standard_colour() -> dict:
+    std = standard_tables()
+    return dict(colour=True, dc=[std["dc_luma"], std["dc_chroma"], std["dc_chroma"]], ac=[std["ac_luma"], std["ac_chroma"], std["ac_chroma"]],
+                quant=8)
+
+
+def family_g() -> list:
+    """The colour lattice: 4:4:4, one flat MCU per (Y, Cb, Cr), so every pixel of it is that triple through jdcolor.c's
+    tables -- each channel's clamp at 0 and at 255, and the rounding either side of Cb, Cr = 128."""
+    samples = [v for triple in lattice() for v in triple]
+    assert len(samples) == 3 * LATTICE_SIZE[0] * LATTICE_SIZE[1]
+    return [("g_lattice_444", build(flat_blocks(samples, [0, 1, 2] * (len(samples) // 3)), LATTICE_SIZE, sampling=(1, 1), **_standard_colour()))]
+
+
+H_SIZE = (6, 4)                         # MCUs: 24 of them
+
+
+def order_samples(sampling, size=H_SIZE) -> list:
+    """The flat sample values of family H's blocks in scan order: every luma block of an MCU another value (and another
+    from MCU to MCU), Cb 0 / 255 in a checkerboard of MCUs and Cr its opposite, so that a chroma block's neighbour is the
+    largest step away, across and down."""
+    luma = sampling[0] * sampling[1]
+    out = []
+    for my in range(size[1]):
+        for mx in range(size[0]):
+            m = my * size[0] + mx
+            out += [(29 * m + 67 * i + 11) % 256 for i in range(luma)]
+            out += [255 * ((mx + my) & 1), 255 * ((mx + my + 1) & 1)]
+    return out
+
+
+def family_h() -> list:
+    """MCU order of 4:2:2 and 4:2:0: flat blocks, see order_samples; the picture ends one pixel and fifteen pixels into
+    the last MCU across (and inside the last MCU down); without DRI, and at 16k + 1 with an interval of 5 MCUs (which
+    does not divide a row's 6)."""
+    out = []
+    for tag, sampling in (("422", (2, 1)), ("420", (2, 2))):
+        per_mcu = sampling[0] * sampling[1] + 2
+        comps = ([0] * (per_mcu - 2) + [1, 2]) * (H_SIZE[0] * H_SIZE[1])
+        samples = order_samples(sampling)
+        height = 8 * sampling[1] * (H_SIZE[1] - 1) + 3
+        for width in (16 * (H_SIZE[0] - 1) + 1, 16 * (H_SIZE[0] - 1) + 15):
+            kw = dict(sampling=sampling, width=width, height=height, **_standard_colour())
+            out.append((f"h_order_{tag}_{width}x{height}", build(flat_blocks(samples, comps), H_SIZE, **kw)))
+            if width % 16 == 1:
+                out.append((f"h_order_{tag}_{width}x{height}_dri5", build(flat_blocks(samples, comps, 5 * per_mcu), H_SIZE, restart=5, **kw)))
+    return out
+
+
+BASIS_SIZE = (16, 16)                   # 256 blocks: 128 x 128 pixels
+BASIS_QUANT = list(range(1, 65))        # by zigzag position
+
+
+def basis_blocks() -> list:
+    """[(zigzag position, coefficient as coded)] of family I's blocks in scan order: each position alone, at +-1 and at
+    +- the largest value whose dequantised amplitude (|DC| / 8, |AC| / 4 bound a sample's distance from 128) stays within
+    SAMPLE_BUDGET, and within category 10 (for DC too: from +1023 to -1023 is a difference of category 11, the last)."""
+    out = []
+    for k in range(64):
+        top = min(SAMPLE_BUDGET * (8 if k == 0 else 4) // BASIS_QUANT[k], 1023)
+        out += [(k, 1), (k, -1), (k, top), (k, -top)]
+    return out
+
+
+def family_i() -> list:
+    """The IDCT's basis: a grey file, one coefficient a block, the quantiser 1..64 by zigzag position."""
+    std = standard_tables()
+    blocks, pred = [], 0
+    for k, v in basis_blocks():
+        dc = v if k == 0 else 0
+        blocks.append((dc - pred, [] if k == 0 else at({k: v})))
+        pred = dc
+    return [("i_idct_basis", build(blocks, BASIS_SIZE, dc=std["dc_luma"], ac=std["ac_luma"], quant=BASIS_QUANT))]
+
+
+PIXEL_FAMILIES = {"g": family_g, "h": family_h, "i": family_i}
+
+
+def pixel_cases() -> list:
+    """[(name, Built)] of families G, H and I."""
+    return [case for key in PIXEL_FAMILIES for case in PIXEL_FAMILIES[key]()]

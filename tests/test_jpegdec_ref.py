@@ -72,6 +72,74 @@ def test_fixtures_are_what_the_generator_makes(generated):
     assert [str(n) for n in m["names"]] == [n for n, _ in malformed]
 
 
+# ---- the pixel stages' corpus (jpegdec_cases.geometry_cases, tests/golden/jpegdec_geometry.npz) -------------------------------
+def _geometry_fixture():
+    z = np.load(os.path.join(GOLDEN, "jpegdec_geometry.npz"))
+    return z, [str(n) for n in z["names"]]
+
+
+def test_the_geometry_corpus_is_the_sizes_it_is_for():
+    from tests import jpegdec_cases as JC
+    z, names = _geometry_fixture()
+    want = [JC.geometry_name(layout, w, h, dri) for dri in (False, True) for layout in JC.GEOMETRY_LAYOUTS for w, h in JC.geometry_sizes(dri)]
+    assert names == want and len(set(names)) == len(names) == 4 * (11 * 7 + 2 + 7 * 4)
+    sampling = {"grey": (1, 1, 1), "444": (3, 1, 1), "422": (3, 2, 1), "420": (3, 2, 2)}
+    for dri in (False, True):
+        for layout in JC.GEOMETRY_LAYOUTS:
+            for w, h in JC.geometry_sizes(dri):
+                info = JR.probe(z[JC.geometry_name(layout, w, h, dri) + ".file"].tobytes())
+                assert info["reject"] == "ok" and (info["width"], info["height"], info["restart_mcus"]) == (w, h, int(dri))
+                assert (info["components"], info["h_samp"], info["v_samp"]) == sampling[layout]
+    assert os.path.getsize(os.path.join(GOLDEN, "jpegdec_geometry.npz")) < os.path.getsize(os.path.join(GOLDEN, "jpegdec_par_valid.npz"))
+
+
+def test_restatement_equals_pillow_on_every_geometry_case():
+    """Live Pillow on freshly made files, and the fixture is those files with those pixels.  Before the restatement took
+    libjpeg's replicating upsampler for downsampled_width <= 2 this failed for 4:2:2 at W = 2, 3, 4 and for 4:2:0 at
+    W = 1, 2, 3, 4, and for nothing else."""
+    JC = _pillow_cases()
+    z, names = _geometry_fixture()
+    cases = JC.geometry_cases()
+    assert [name for name, _ in cases] == names
+    for name, data in cases:
+        want = JC.pillow_pixels(data)
+        np.testing.assert_array_equal(JR.decode(data), want, err_msg=name)
+        np.testing.assert_array_equal(JR.decode(data, "bgr"), want[:, :, ::-1], err_msg=name)
+        assert z[name + ".file"].tobytes() == data, name
+        np.testing.assert_array_equal(z[name + ".rgb"], want, err_msg=name)
+
+
+def test_restatement_equals_the_geometry_fixtures_pixels():
+    """The same against the Pillow decodes kept in tests/golden (whatever Pillow, if any, is installed here)."""
+    z, names = _geometry_fixture()
+    for name in names:
+        np.testing.assert_array_equal(JR.decode(z[name + ".file"].tobytes()), z[name + ".rgb"], err_msg=name)
+
+
+def test_the_geometry_corpus_tells_replication_from_blending():
+    """For every subsampled case up to 4 pixels wide, blending at every width (the rule the restatement and the kernel had)
+    gives other pixels than replication, so a decoder with either rule alone cannot pass: a smooth image would let both.
+    The exceptions are no choice at all: at W = 1 there is only column 0, where the h2v1 filter copies the sample (4:2:2
+    at W = 1), and the h2v2 filter gives (4 s + 8) >> 4 of s = 3 a + b, which is a where the context row b is the one
+    chroma row a again (4:2:0 at W = 1, H <= 2).  There, and from W = 5 on, the two are the same function."""
+    from tests import jpegdec_cases as JC
+    z, _ = _geometry_fixture()
+    told_apart = 0
+    for dri in (False, True):
+        for layout in ("422", "420"):
+            for w, h in JC.geometry_sizes(dri):
+                name = JC.geometry_name(layout, w, h, dri)
+                data = z[name + ".file"].tobytes()
+                same = np.array_equal(JR._decode_blending_at_every_width(data), JR.decode(data))
+                if w > 4 or (w == 1 and (layout == "422" or h <= 2)):
+                    assert same, name
+                else:
+                    assert not same, f"{name}: either upsampling rule gives these pixels"
+                    told_apart += 1
+    # W = 2, 3, 4 (2, 4 with DRI), 4 x 4 and 3 x 5 in both layouts; 4:2:0 at W = 1, H >= 3
+    assert told_apart == 2 * (3 * 7 + 2 + 2 * 4) + (5 + 3)
+
+
 def test_geometry_of_the_valid_cases(generated):
     _, valid, _, _ = generated
     info = {name: JR.probe(data) for name, data in valid}

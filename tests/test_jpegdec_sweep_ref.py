@@ -256,3 +256,120 @@ def test_a_block_of_raw_bits_is_the_block_it_spells():
     """The builder's other form of a block: DC category 2 (110 under the ladder) value +3, run 1 size 1 (10) value -1, EOB."""
     kw = dict(dc=SW.LADDER_DC, ac=SW.ladder_ac())
     assert SW.build(["110" "11" "10" "0" "0"], (1, 1), **kw).data == SW.build([(3, [(1, -1)])], (1, 1), **kw).data
+
+
+# ---- families G, H, I: the pixel stages ----------------------------------------------------------------------------------
+PIXEL_CASES = SW.pixel_cases()
+PIXEL_FILES = dict(PIXEL_CASES)
+
+
+def test_the_builder_writes_each_sampling():
+    """sampling (1, 1), (2, 1), (2, 2): 3, 4 or 6 blocks an MCU, 0x11, 0x21 or 0x22 in SOF, MCUs of 8 x 8, 16 x 8 or
+    16 x 16; and a call without it is the 4:2:0 file it always was."""
+    std = SW.standard_tables()
+    kw = dict(colour=True, dc=[std["dc_luma"], std["dc_chroma"], std["dc_chroma"]], ac=[std["ac_luma"], std["ac_chroma"], std["ac_chroma"]])
+    for sampling, per_mcu, byte in (((1, 1), 3, 0x11), ((2, 1), 4, 0x21), ((2, 2), 6, 0x22)):
+        built = SW.build([(1, [])] + [(0, [])] * (2 * 3 * per_mcu - 1), (2, 3), sampling=sampling, **kw)
+        hd = JR.parse_header(built.data)
+        sof, _ = JR.find_segment(built.data, 0xC0)
+        assert built.data[sof + 11] == byte and (hd["h_samp"], hd["v_samp"]) == sampling
+        assert (hd["blocks_per_mcu"], hd["width"], hd["height"]) == (per_mcu, 16 * sampling[0], 24 * sampling[1])
+        assert JR.verdict(built.data) == "ok"
+        with pytest.raises(AssertionError):
+            SW.build([(0, [])] * (2 * 3 * per_mcu - 1), (2, 3), sampling=sampling, **kw)
+    blocks = [(0, [])] * 6
+    assert SW.build(blocks, (1, 1), **kw).data == SW.build(blocks, (1, 1), sampling=(2, 2), **kw).data
+    assert SW.build([(0, [])], (1, 1), dc=std["dc_luma"], ac=std["ac_luma"], sampling=(2, 1)).data == SW.build([(0, [])], (1, 1), dc=std["dc_luma"], ac=std["ac_luma"]).data
+
+
+def test_pixel_families_have_their_files():
+    names = [name for name, _ in PIXEL_CASES]
+    assert [n[0] for n in names] == list("ghhhhhhi") and len(set(names)) == 8
+    assert not set(names) & set(FILES)                                      # jpegdec_sweep.npz keeps what it kept
+    for name, built in PIXEL_CASES:
+        assert JR.verdict(built.data) == "ok", name
+
+
+def test_pillow_equals_the_restatement_on_the_pixel_families():
+    pytest.importorskip("PIL")
+    from tests.jpegdec_cases import pillow_pixels
+    z = np.load(os.path.join(GOLDEN, "jpegdec_sweep_pixels.npz"))
+    assert [str(n) for n in z["names"]] == [name for name, _ in PIXEL_CASES]
+    for name, built in PIXEL_CASES:
+        want = pillow_pixels(built.data)
+        if name == "i_idct_basis":
+            _assert_basis(JR.decode(built.data), want)
+        np.testing.assert_array_equal(JR.decode(built.data), want, err_msg=name)
+        np.testing.assert_array_equal(JR.decode(built.data, "bgr"), want[:, :, ::-1], err_msg=name)
+        assert z[name + ".file"].tobytes() == built.data, name
+        np.testing.assert_array_equal(z[name + ".rgb"], want, err_msg=name)
+
+
+def test_the_restatement_equals_the_pixel_fixture():
+    """Pillow's pixels as kept in tests/golden, whatever Pillow is here."""
+    z = np.load(os.path.join(GOLDEN, "jpegdec_sweep_pixels.npz"))
+    for name, built in PIXEL_CASES:
+        assert z[name + ".file"].tobytes() == built.data, name
+        if name == "i_idct_basis":
+            _assert_basis(JR.decode(built.data), z[name + ".rgb"])
+        np.testing.assert_array_equal(JR.decode(built.data), z[name + ".rgb"], err_msg=name)
+
+
+def _assert_basis(got, want):
+    """The IDCT file block by block, so that a difference names the coefficient."""
+    for i, (k, v) in enumerate(SW.basis_blocks()):
+        by, bx = divmod(i, SW.BASIS_SIZE[0])
+        a, b = (p[8 * by:8 * by + 8, 8 * bx:8 * bx + 8, 0] for p in (got, want))
+        assert np.array_equal(a, b), f"zigzag position {k} (natural {int(JR.ZIGZAG[k])}), coefficient {v} x quantiser {SW.BASIS_QUANT[k]}:\n{a}\nnot\n{b}"
+
+
+def test_g_every_channel_clamps_both_ways_and_passes():
+    """The lattice's triples through jdcolor.c's arithmetic before the clamp: each of R, G, B falls below 0, rises above
+    255 and lies inside for some MCU; and the decoded file is, MCU for MCU, the triple's colour."""
+    triples = np.array(SW.lattice(), np.int64)
+    assert len(triples) == 968 == SW.LATTICE_SIZE[0] * SW.LATTICE_SIZE[1]
+    y, cb, cr = triples[:, 0], triples[:, 1] - 128, triples[:, 2] - 128
+    raw = {"r": y + ((91881 * cr + 32768) >> 16), "g": y + ((-22554 * cb + 32768 - 46802 * cr) >> 16), "b": y + ((116130 * cb + 32768) >> 16)}
+    for name, v in raw.items():
+        assert (v < 0).any() and (v > 255).any() and ((v > 0) & (v < 255)).any(), name
+        assert (v == 0).any() or (v == -1).any() or (v == 1).any(), name            # and next to a clamp's edge
+    data = PIXEL_FILES["g_lattice_444"].data
+    hd, coefs = JR.decode_coefficients(data)
+    assert (hd["h_samp"], hd["v_samp"], hd["blocks_per_mcu"], hd["mcus_x"], hd["mcus_y"]) == (1, 1, 3, 44, 22)
+    assert not coefs[:, :, 1:].any() and np.array_equal(coefs[:, :, 0] // 8 + 128, triples)
+    pixels = JR.decode(data)
+    assert pixels.shape == (176, 352, 3)
+    want = np.clip(np.stack([raw["r"], raw["g"], raw["b"]], -1), 0, 255).reshape(22, 44, 3)
+    np.testing.assert_array_equal(pixels, np.kron(want, np.ones((8, 8, 1), np.int64)))
+
+
+def test_h_the_blocks_of_an_mcu_differ_and_the_chroma_steps_are_the_largest():
+    for name in [n for n in PIXEL_FILES if n[0] == "h"]:
+        hd, coefs = JR.decode_coefficients(PIXEL_FILES[name].data)
+        luma = hd["h_samp"] * hd["v_samp"]
+        assert (hd["mcus_x"], hd["mcus_y"]) == SW.H_SIZE and luma == (2 if "_422_" in name else 4)
+        assert hd["width"] % 16 in (1, 15) and hd["height"] % (8 * hd["v_samp"]) == 3
+        assert hd["restart_mcus"] == (5 if name.endswith("dri5") else 0)
+        samples = coefs[:, :, 0] // 8 + 128
+        assert all(len(set(row[:luma])) == luma for row in samples.tolist())          # a swapped block order shows
+        cb = samples[:, luma].reshape(SW.H_SIZE[1], SW.H_SIZE[0])
+        assert set(cb.ravel().tolist()) == {0, 255} and (np.abs(np.diff(cb, axis=0)) == 255).all() and (np.abs(np.diff(cb, axis=1)) == 255).all()
+        np.testing.assert_array_equal(samples[:, luma + 1], 255 - samples[:, luma])
+    assert sum(n.endswith("dri5") for n in PIXEL_FILES) == 2
+
+
+def test_i_every_position_alone_at_both_ends():
+    blocks = SW.basis_blocks()
+    hd, coefs = JR.decode_coefficients(PIXEL_FILES["i_idct_basis"].data)
+    assert len(blocks) == 256 == hd["n_mcus"] and hd["components"] == 1
+    assert [int(q) for q in hd["tables"][0][2]] == list(range(1, 65))
+    for i, (k, v) in enumerate(blocks):
+        assert np.count_nonzero(coefs[i, 0]) == 1 and coefs[i, 0, JR.ZIGZAG[k]] == v * (k + 1), (i, k, v)
+    for k in range(64):
+        values = sorted(v for kk, v in blocks if kk == k)
+        top = values[-1]
+        assert values == [-top, -1, 1, top] and top >= 2
+        bound = top * (k + 1) / (8 if k == 0 else 4)
+        assert bound <= SW.SAMPLE_BUDGET and (top == 1023 or (top + 1) * (k + 1) / 4 > SW.SAMPLE_BUDGET), k
+    pixels = JR.decode(PIXEL_FILES["i_idct_basis"].data)
+    assert pixels.min() == 0 and pixels.max() == 255                                  # the large amplitudes reach both clamps

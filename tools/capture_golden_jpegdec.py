@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Writes tests/golden/jpegdec_valid.npz, jpegdec_malformed.npz and jpegdec_stream.npz from tests/jpegdec_cases.py
-(Pillow >= 10.2): every valid file with Pillow's pixels of it (`PIL.Image.open(...).convert("RGB")`: libjpeg's), every
-malformed file with the reject number the restatement (tests/jpegdec_ref.py) gives it, and the frames of the MJPEG
-stream of the integration tests.  The fixtures hold the pixels, so the Pillow of the machine that runs the GPU tests
+"""Writes tests/golden/jpegdec_valid.npz, jpegdec_malformed.npz, jpegdec_stream.npz and jpegdec_geometry.npz from
+tests/jpegdec_cases.py (Pillow >= 10.2): every valid file with Pillow's pixels of it (`PIL.Image.open(...).convert("RGB")`:
+libjpeg's), every malformed file with the reject number the restatement (tests/jpegdec_ref.py) gives it, the frames of the
+MJPEG stream of the integration tests, and the pixel stages' corpus -- the small frames of `geometry_cases` -- with
+Pillow's pixels (tests/test_gpu_jpegdec_geometry.py holds the device to them).  The fixtures hold the pixels, so the Pillow of the machine that runs the GPU tests
 does not matter.  tests/test_jpegdec_ref.py holds the restatement to these files; tests/test_gpu_jpegdec.py the device.
 
     python tools/capture_golden_jpegdec.py
@@ -49,6 +50,16 @@ def main() -> None:
     path = os.path.join(golden, "jpegdec_stream.npz")
     np.savez_compressed(path, **stream)
     print(f"stream: {len(frames)} frames, fixture {os.path.getsize(path)} bytes")
+    cases = JC.geometry_cases()
+    geometry = {"names": np.array([name for name, _ in cases])}
+    for name, data in cases:
+        pixels = JC.pillow_pixels(data)
+        assert np.array_equal(JR.decode(data), pixels), name
+        geometry[name + ".file"] = np.frombuffer(data, np.uint8)
+        geometry[name + ".rgb"] = pixels
+    path = os.path.join(golden, "jpegdec_geometry.npz")
+    np.savez_compressed(path, **geometry)
+    print(f"geometry: {len(cases)} files, fixture {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

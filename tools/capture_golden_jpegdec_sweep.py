@@ -4,7 +4,9 @@ the pixels tests/jpegdec_ref.py gives it and, for an accepted file without DRI, 
 subsequence boundary (tests/jpegdec_par_ref.py's entry_rows for subsequences of 16, 64 and 128 bytes).  Where Pillow is
 importable, asserts that its pixels are the restatement's on every family but the one pinned by the restatement alone.
 tests/test_jpegdec_sweep_ref.py holds the fixture to the builder and the restatement, and asserts what each family
-covers; tests/test_gpu_jpegdec_sweep.py holds the device to the fixture.
+covers; tests/test_gpu_jpegdec_sweep.py holds the device to the fixture.  With Pillow, also writes
+tests/golden/jpegdec_sweep_pixels.npz: the families of the pixel stages (colour lattice, MCU order, IDCT basis;
+`pixel_cases`) with Pillow's pixels, which tests/test_gpu_jpegdec_geometry.py holds the device to.
 
     python tools/capture_golden_jpegdec_sweep.py
 """
@@ -48,6 +50,20 @@ def main() -> None:
     path = os.path.join(ROOT, "tests", "golden", "jpegdec_sweep.npz")
     np.savez_compressed(path, **out)
     print(f"{len(cases)} files, fixture {os.path.getsize(path)} bytes")
+    if pillow_pixels is None:
+        print("no Pillow here: jpegdec_sweep_pixels.npz holds its pixels and is left as it is")
+        return
+    cases = SW.pixel_cases()
+    out = {"names": np.array([name for name, _ in cases])}
+    for name, built in cases:
+        pixels = pillow_pixels(built.data)
+        assert np.array_equal(JR.decode(built.data), pixels), name
+        out[name + ".file"] = np.frombuffer(built.data, np.uint8)
+        out[name + ".rgb"] = pixels
+        print(f"  {name}: {len(built.data)} bytes, {pixels.shape[1]} x {pixels.shape[0]}")
+    path = os.path.join(ROOT, "tests", "golden", "jpegdec_sweep_pixels.npz")
+    np.savez_compressed(path, **out)
+    print(f"{len(cases)} files of the pixel stages' families, fixture {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

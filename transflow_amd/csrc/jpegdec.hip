@@ -20,7 +20,7 @@
 //                  component's plane (padded to whole MCUs) as one 8-byte store.  A rejected interval leaves its
 //                  number and reason in the status word (the lowest interval wins) and stops.
 //   k_jd_colour    four adjacent pixels per lane: the chroma planes are upsampled (h2v2 / h2v1 fancy, with libjpeg's
-//                  edge rules), converted, and stored as three dwords.
+//                  edge rules; replicated, as libjpeg does, where ceil(W / 2) <= 2), converted, and stored as three dwords.
 //
 // A file is untrusted.  Nothing it holds steers an address: intervals are clamped to the scan, the window to the
 // interval, coefficient indices go through a table of 64 entries, and a plane store is placed by the MCU's number alone.
@@ -472,6 +472,9 @@ __global__ __launch_bounds__(COLOUR_BLOCK) void k_jd_colour(const Frame f, uint8
             int cb, cr;
             if (f.h_samp == 1) {
                 cb = f.planes[1][(size_t)y * f.c_stride + x], cr = f.planes[2][(size_t)y * f.c_stride + x];
+            } else if (dw <= 2) { // jinit_upsampler: h2v1_upsample / h2v2_upsample, the sample replicated, for W <= 4
+                const size_t at = (size_t)(y >> (f.v_samp - 1)) * f.c_stride + (x >> 1);
+                cb = f.planes[1][at], cr = f.planes[2][at];
             } else if (f.v_samp == 1) {
                 cb = up_h2v1(f.planes[1] + (size_t)y * f.c_stride, dw, x);
                 cr = up_h2v1(f.planes[2] + (size_t)y * f.c_stride, dw, x);
