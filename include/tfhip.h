@@ -803,6 +803,35 @@ int tf_png_last_bands(tf_png *enc, uint32_t *sizes, uint8_t *stored, size_t capa
 int tf_png_default_band_rows(int height, int width);
 int tf_png_code_lengths(uint8_t *out /* [286] */);
 
+/* ---- planar YUV of a frame in device memory (transflow/output/ffmpeg.py:32-54: the output that hands raw frames to an
+ * encoder) ---------------------------------------------------------------------------------------------------------------
+ * The frame in the layout a video encoder takes, made where the frame is: 1.5 to 3 bytes a pixel come down instead of
+ * the RGB frame's 3, and no host converts or subsamples.  One tightly packed buffer:
+ *   layout 0 yuv444p: Y W*H, U W*H, V W*H;  1 yuv422p: Y, U ceil(W/2)*H, V the same;
+ *   2 yuv420p: Y, U ceil(W/2)*ceil(H/2), V the same;  3 nv12: Y, then ceil(H/2) rows of ceil(W/2) pairs U V.
+ * matrix 0 bt601, 1 bt709; range 0 tv (Y 16-235, chroma 16-240), 1 pc (0-255).  Integer arithmetic with 16 fractional
+ * bits; a chroma sample is the exact mean of its block's unrounded values, rounded once, an odd edge's last column or
+ * row repeated (centre-sited: Y4M's C420jpeg).  DESIGN.md section 21 has the rule and the table of coefficients.
+ * No counterpart in the reference, whose ffmpeg child converts rgb24 with swscale; these are not swscale's pixels. */
+typedef struct tf_yuv tf_yuv;
+/* The bytes of a frame in that layout; 0 for a layout or a size that is none.  No GPU call. */
+size_t tf_yuv_frame_bytes(int width, int height, int layout);
+/* The coefficients as the library builds them: out = the Y, U and V rows, each over (R, G, B); *y_offset 16 or 0.  No
+   GPU call: a process that converts on the host with the same arithmetic (transflow_amd/yuv.py host_convert) asks here. */
+int tf_yuv_coefficients(int matrix, int range, int32_t out[9], int32_t *y_offset);
+/* width, height: 1 to 65535.  The handle owns a device buffer and a page-locked host buffer of one frame. */
+int tf_yuv_create(tf_yuv **out, int height, int width, int layout, int matrix, int range);
+void tf_yuv_destroy(tf_yuv *h);
+/* rgb_dev: uint8 [H][W][3] in device memory, at any address.  Queues the kernel on the calling thread's stream, copies
+   the planes to out_host -- directly if that is page-locked memory (tf_host_alloc), else by way of the handle's buffer --
+   and waits.  *n_bytes is tf_yuv_frame_bytes; more than `capacity` returns TF_ERR_ARG and nothing is written. */
+int tf_yuv_convert_dev(tf_yuv *h, const void *rgb_dev, uint8_t *out_host, size_t capacity, size_t *n_bytes);
+/* The same for an image in host memory: uploaded to a buffer of the handle first. */
+int tf_yuv_convert(tf_yuv *h, const uint8_t *rgb_host, uint8_t *out_host, size_t capacity, size_t *n_bytes);
+/* The planes into the caller's device memory (tf_yuv_frame_bytes bytes at any address, none written outside them):
+   queued, not waited for. */
+int tf_yuv_convert_to_dev(tf_yuv *h, const void *rgb_dev, void *out_dev);
+
 /* ---- flow archive members deflated on the device (transflow_amd/csrc/flowzip.hip) --------
  * The reference's flow export (transflow/pipeline.py:363-377, 505-506, output/numpy.py, output/zip.py) writes
  * numpy.save(flow) into a deflated zip member.  tf_flowzip makes that member's raw deflate stream -- no zlib header, no

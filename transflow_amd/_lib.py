@@ -253,6 +253,13 @@ PROTOTYPES = {
     "tf_png_last_bands": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_png_default_band_rows": (_I, [_I, _I]),
     "tf_png_code_lengths": (_I, [_P]),
+    "tf_yuv_frame_bytes": (C.c_size_t, [_I, _I, _I]),
+    "tf_yuv_coefficients": (_I, [_I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tf_yuv_create": (_I, [_PP, _I, _I, _I, _I, _I]),
+    "tf_yuv_destroy": (None, [_P]),
+    "tf_yuv_convert_dev": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_yuv_convert": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "tf_yuv_convert_to_dev": (_I, [_P, _P, _P]),
     "tf_flowzip_create": (_I, [_PP, C.c_size_t, _I]),
     "tf_flowzip_destroy": (None, [_P]),
     "tf_flowzip_band_bytes": (_I, [_P]),

@@ -311,7 +311,8 @@ class HipCompositor:
 
     def __init__(self, height: int, width: int, layers, background_color: str = "#ffffff", lazy_frames: bool = False,
                  jpeg_frames: int | None = None, png_frames: bool = False, png_code: str = "fixed",
-                 jpeg_optimize: bool = False, jpeg_subsampling=None):
+                 jpeg_optimize: bool = False, jpeg_subsampling=None, yuv_frames: str | None = None, yuv_matrix: str | None = None,
+                 yuv_range: str | None = None):
         """lazy_frames: render() returns a DeviceFrame (transflow_amd/deviceframe.py) -- the uint8 (H, W, 3) array to
         everything numpy, its download started but not waited for, so that frame t comes down (pipeline.py:518,
         output/ffmpeg.py:32-54) beside frame t + 1's uploads and kernels (pipeline.py:565).  Default: a plain ndarray.
@@ -327,7 +328,21 @@ class HipCompositor:
         the band index that lets transflow_amd/pngdec.py decode them on the device (PngEncoder(index=True)); True keeps
         writing the bytes it wrote before.  png_code="frame": the PNG files are coded with the frame's own literal/length
         code and a band that would not shrink is stored (PngEncoder(code="frame")): smaller files of the same pixels;
-        "fixed" keeps writing the bytes it wrote before.  Only with png_frames."""
+        "fixed" keeps writing the bytes it wrote before.  Only with png_frames.
+        yuv_frames: a layout, "yuv444p", "yuv422p", "yuv420p" or "nv12" -- render() returns a YuvFrame
+        (transflow_amd/yuv.py): the planes a video encoder takes, converted where the frame is, for the ffmpeg and Y4M
+        outputs (output/ffmpeg.py:32-54).  Not together with lazy_frames, jpeg_frames or png_frames.  yuv_matrix
+        ("bt601", the default, or "bt709") and yuv_range ("tv", the default, or "pc"): only with yuv_frames."""
+        if yuv_frames is None:
+            if yuv_matrix is not None or yuv_range is not None:
+                raise ValueError("yuv_matrix and yuv_range are for yuv_frames: there is no YUV frame to convert")
+        else:
+            if lazy_frames or jpeg_frames is not None or png_frames:
+                raise ValueError("yuv_frames excludes lazy_frames, jpeg_frames and png_frames: a frame leaves in one form")
+            from .yuv import check_options
+            yuv_matrix = "bt601" if yuv_matrix is None else yuv_matrix
+            yuv_range = "tv" if yuv_range is None else yuv_range
+            check_options(yuv_frames, yuv_matrix, yuv_range)
         if png_code not in ("fixed", "frame"):
             raise ValueError(f"png_code is \"fixed\" or \"frame\", not {png_code!r}")
         if png_code != "fixed" and not png_frames:
@@ -358,8 +373,10 @@ class HipCompositor:
         self.png_code = png_code
         self.jpeg_optimize = bool(jpeg_optimize)
         self.jpeg_subsampling = 2 if jpeg_subsampling is None else jpeg_subsampling
+        self.yuv_frames, self.yuv_matrix, self.yuv_range = yuv_frames, yuv_matrix, yuv_range
         self._jpeg = None           # the encoder, made at the first render
         self._png = None
+        self._yuv = None
         self._comp = None
         self._comp2 = None          # lazy frames: the second image (frame t downloads from one while t + 1 is rendered into the other)
         self._flip = False
@@ -404,6 +421,11 @@ class HipCompositor:
                 from .png import PngEncoder
                 self._png = PngEncoder(self.height, self.width, index=self.png_index, code=self.png_code)
             return self._png.frame(comp)
+        if self.yuv_frames is not None:
+            if self._yuv is None:
+                from .yuv import YuvEncoder
+                self._yuv = YuvEncoder(self.height, self.width, self.yuv_frames, self.yuv_matrix, self.yuv_range)
+            return self._yuv.frame(comp)
         if self._frame_pool is None:
             from .device import ArrayPool
             self._frame_pool = ArrayPool((self.height, self.width, 3), np.uint8, pinned=True)
@@ -417,7 +439,8 @@ class HipCompositor:
     @classmethod
     def from_args(cls, height: int, width: int, layer_configs, background_color: str = "#ffffff", rng: str = "numpy",
                   lazy_frames: bool = False, jpeg_frames: int | None = None, png_frames: bool = False,
-                  png_code: str = "fixed", jpeg_optimize: bool = False, jpeg_subsampling=None):
+                  png_code: str = "fixed", jpeg_optimize: bool = False, jpeg_subsampling=None, yuv_frames: str | None = None,
+                  yuv_matrix: str | None = None, yuv_range: str | None = None):
         layers = []
         for config in layer_configs:
             classname = getattr(config, "classname", "moveref")
@@ -426,14 +449,14 @@ class HipCompositor:
             layers.append(LAYER_CLASSES[classname](config, height, width, [], rng=rng))
         return cls(height, width, layers, background_color=background_color, lazy_frames=lazy_frames,
                    jpeg_frames=jpeg_frames, png_frames=png_frames, png_code=png_code, jpeg_optimize=jpeg_optimize,
-                   jpeg_subsampling=jpeg_subsampling)
+                   jpeg_subsampling=jpeg_subsampling, yuv_frames=yuv_frames, yuv_matrix=yuv_matrix, yuv_range=yuv_range)
 
     def set_sources(self, pixmap_interfaces: dict):
         for i, layer in enumerate(self.layers):
             layer.set_sources(pixmap_interfaces.get(i, []))
 
     def __getstate__(self):
-        return {k: v for k, v in self.__dict__.items() if k not in ("_comp", "_comp2", "_frame_pool", "_jpeg", "_png")}
+        return {k: v for k, v in self.__dict__.items() if k not in ("_comp", "_comp2", "_frame_pool", "_jpeg", "_png", "_yuv")}
 
     def __setstate__(self, state):
         self.__dict__.update(state)
@@ -444,8 +467,11 @@ class HipCompositor:
         self.png_code = state.get("png_code", "fixed")
         self.jpeg_optimize = bool(state.get("jpeg_optimize", False))
         self.jpeg_subsampling = int(state.get("jpeg_subsampling", 2))
+        self.yuv_frames = state.get("yuv_frames")
+        self.yuv_matrix, self.yuv_range = state.get("yuv_matrix"), state.get("yuv_range")
         self._jpeg = None
         self._png = None
+        self._yuv = None
         self._comp = None
         self._comp2 = None
         self._flip = False
@@ -465,3 +491,6 @@ class HipCompositor:
         if getattr(self, "_png", None) is not None:
             self._png.close()
             self._png = None
+        if getattr(self, "_yuv", None) is not None:
+            self._yuv.close()
+            self._yuv = None

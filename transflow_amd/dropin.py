@@ -90,7 +90,7 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
 
 
 def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_frames=False, png_code="fixed",
-                          jpeg_optimize=False, jpeg_subsampling=None):
+                          jpeg_optimize=False, jpeg_subsampling=None, yuv_frames=None, yuv_matrix=None, yuv_range=None):
     from .compositor import LAYER_CLASSES, HipCompositor
 
     def from_args(cls, height, width, layer_configs, background_color="#ffffff"):
@@ -98,7 +98,8 @@ def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_fra
             return HipCompositor.from_args(height, width, layer_configs, background_color=background_color,
                                            lazy_frames=lazy_frames, jpeg_frames=jpeg_frames, png_frames=png_frames,
                                            png_code=png_code, jpeg_optimize=jpeg_optimize,
-                                           jpeg_subsampling=jpeg_subsampling)
+                                           jpeg_subsampling=jpeg_subsampling, yuv_frames=yuv_frames, yuv_matrix=yuv_matrix,
+                                           yuv_range=yuv_range)
         return original(height, width, layer_configs, background_color=background_color)
 
     return classmethod(from_args)
@@ -138,6 +139,23 @@ def _png_output_from_args(original):
     return classmethod(from_args)
 
 
+def _yuv_output_from_args(original, layout, matrix, range):
+    from .output import HipFfmpegOutput, HipY4mOutput, RawFramesOnly, ffmpeg_path, y4m_path
+
+    def from_args(cls, path, width, height, framerate=None, vcodec="h264", execute=False, replace=False, initial_counter=0):
+        if y4m_path(path):          # `out.y4m`: the planes in the uncompressed container
+            return HipY4mOutput(path, width, height, 30 if framerate is None else framerate, layout, matrix, range,
+                                execute=execute, replace=replace)
+        if ffmpeg_path(path):       # what video_output.py:59-60 gives to FFmpegVideoOutput
+            return HipFfmpegOutput(path, width, height, 30 if framerate is None else framerate, vcodec, execute, replace,
+                                   layout=layout, matrix=matrix, range=range)
+        # the reference's own output; it takes pixels, and says so if it is given planes
+        return RawFramesOnly(original(path, width, height, framerate=framerate, vcodec=vcodec, execute=execute,
+                                      replace=replace, initial_counter=initial_counter))
+
+    return classmethod(from_args)
+
+
 def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=False, mjpeg_parallel=False):
     from .pixmap import HipPixmapSource
 
@@ -158,7 +176,8 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
             device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed",
-            jpeg_optimize: bool = False, jpeg_subsampling=None) -> None:
+            jpeg_optimize: bool = False, jpeg_subsampling=None, yuv_frames: str | None = None, yuv_matrix: str | None = None,
+            yuv_range: str | None = None) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -215,7 +234,24 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     png_inputs: a path with a `%...d` field that ends in .png and whose first frame (0 or 1) exists -- a PNG frame
     sequence -- is read by transflow_amd/pngdec.py, as a flow source's video (a PngSequenceFrameProvider under the
     HipFlowSource) and as a pixmap source (HipPngSequencePixmapSource): frames with a band index are decoded on the
-    device, the others by Pillow; by default such paths stay the reference's."""
+    device, the others by Pillow; by default such paths stay the reference's.
+    yuv_frames: a layout, "yuv444p", "yuv422p", "yuv420p" or "nv12" -- the compositors built for the pipeline return
+    YuvFrames from render() (transflow_amd/yuv.py: the planes a video encoder takes, converted on the device; half the
+    RGB frame's bytes come down at 4:2:0), and VideoOutput.from_args builds a HipFfmpegOutput (transflow_amd/output.py)
+    for every path the reference gives to FFmpegVideoOutput (video_output.py:59-60) and a HipY4mOutput for paths that end
+    in .y4m; any other output is the reference's own and raises a TypeError that names this option when it is fed a
+    YuvFrame.  yuv_matrix ("bt601", the default, or "bt709") and yuv_range ("tv", the default, or "pc") only with
+    yuv_frames.  Not together with jpeg_frames, png_frames or lazy_frames.  By default (None) nothing of this is touched."""
+    if yuv_frames is None:
+        if yuv_matrix is not None or yuv_range is not None:
+            raise ValueError("yuv_matrix and yuv_range are for yuv_frames: without them no YUV frame is made")
+    else:
+        if jpeg_frames is not None or png_frames or lazy_frames:
+            raise ValueError("yuv_frames excludes jpeg_frames, png_frames and lazy_frames")
+        from .yuv import check_options
+        yuv_matrix = "bt601" if yuv_matrix is None else yuv_matrix
+        yuv_range = "tv" if yuv_range is None else yuv_range
+        check_options(yuv_frames, yuv_matrix, yuv_range)
     if jpeg_frames is not None and lazy_frames:
         raise ValueError("jpeg_frames and lazy_frames exclude each other")
     if png_frames and (jpeg_frames is not None or lazy_frames):
@@ -245,7 +281,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
         RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames,
                                                         "indexed" if png_frames == "indexed" else bool(png_frames), png_code,
-                                                        bool(jpeg_optimize), jpeg_subsampling)
+                                                        bool(jpeg_optimize), jpeg_subsampling, yuv_frames, yuv_matrix, yuv_range)
     if jpeg_frames is not None and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
@@ -255,6 +291,10 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
         RefVideoOutput.from_args = _png_output_from_args(RefVideoOutput.from_args)
+    if yuv_frames is not None and "output" not in _saved:
+        from transflow.output.video_output import VideoOutput as RefVideoOutput
+        _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])
+        RefVideoOutput.from_args = _yuv_output_from_args(RefVideoOutput.from_args, yuv_frames, yuv_matrix, yuv_range)
     if device_flow_export and not _saved_export:
         import transflow.pipeline as ref_pipeline
 

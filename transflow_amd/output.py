@@ -14,6 +14,12 @@ ends in `.jpg` / `.jpeg` takes `JpegFrame`s the same way.
 `HipMjpegFileOutput` appends the frames' JPEG files to one file, a raw MJPEG stream: the form the device decoder's
 inputs are read in (`MJPEG_EXTS`; transflow_amd/jpegdec.py MjpegFrameProvider, transflow_amd/pixmap.py), so a render
 recorded this way can be fed back as a flow or pixmap input without leaving the device path.
+
+`HipFfmpegOutput` is the reference's default output (transflow/output/ffmpeg.py, every `-o out.mp4`) for frames that
+arrive as planes: a `YuvFrame` (transflow_amd/yuv.py: the compositor converted it on the device) is written to the ffmpeg
+child's pipe as it is, and the child is told the layout instead of `rgb24`, so its software scaler has nothing to do.
+`HipY4mOutput` writes the same frames to a `.y4m` file, the uncompressed container ffmpeg, mpv and the x264 / x265
+command lines read.  A raw array fed to either is converted by `host_convert`, the same arithmetic in numpy.
 """
 from __future__ import annotations
 
@@ -25,6 +31,7 @@ import numpy as np
 
 from .jpeg import JpegFrame, pillow_encode, subsampling_value
 from .png import PngFrame, pillow_encode_png
+from .yuv import YuvFrame, check_options, host_convert
 
 
 def default_restart_mcus(subsampling=None) -> int:
@@ -297,10 +304,183 @@ class HipMjpegFileOutput:
             startfile(self.path)
 
 
+def y4m_path(path) -> bool:
+    """Whether an output path names a Y4M file: no frame template, and the extension."""
+    return isinstance(path, str) and FRAMES_PATH.search(path) is None and path.lower().endswith(".y4m")
+
+
+def ffmpeg_path(path) -> bool:
+    """Whether video_output.py:55-60 sends an output path to FFmpegVideoOutput: a string that is neither an `mjpeg`
+    address nor a frame template."""
+    return isinstance(path, str) and MJPEG_PATH.match(path) is None and FRAMES_PATH.search(path) is None
+
+
+class _YuvOutput:
+    """What the two outputs of planes share: the settings, and the frame a `feed` ends with."""
+
+    def __init__(self, width: int, height: int, layout: str, matrix: str, range: str):
+        check_options(layout, matrix, range)
+        self.width, self.height = int(width), int(height)
+        self.layout, self.matrix, self.range = layout, matrix, range
+        self.frames = 0
+
+    def _planes(self, frame) -> YuvFrame:
+        """A YuvFrame of this output's settings as it is; a raw array by way of `host_convert`."""
+        if isinstance(frame, tuple):
+            frame = frame[0]
+        if isinstance(frame, (JpegFrame, PngFrame)):
+            kind = "JPEG" if isinstance(frame, JpegFrame) else "PNG"
+            raise TypeError(f"{type(self).__name__} writes {self.layout} planes, not {kind} files: install(yuv_frames=...) "
+                            "serves the ffmpeg and .y4m outputs")
+        if tuple(frame.shape[:2]) != (self.height, self.width):
+            raise ValueError(f"the output is {self.height} x {self.width}, the frame {tuple(frame.shape[:2])}")
+        if not isinstance(frame, YuvFrame):
+            return host_convert(np.asarray(frame).astype(np.uint8, copy=False), self.layout, self.matrix, self.range)
+        if (frame.layout, frame.matrix, frame.range) != (self.layout, self.matrix, self.range):
+            raise ValueError(f"the output takes {self.layout} / {self.matrix} / {self.range}, the frame is "
+                             f"{frame.layout} / {frame.matrix} / {frame.range}")
+        return frame
+
+
+class HipFfmpegOutput(_YuvOutput):
+    """Same constructor, context-manager protocol, `feed` and `output_path` as transflow's FFmpegVideoOutput
+    (ffmpeg.py:15-67), and `layout`, `matrix`, `range` and `ffmpeg_bin`.  The child's argv is the reference's
+    (ffmpeg.py:32-48) with the input `-pix_fmt` set to the layout; the output `-pix_fmt` stays yuv420p.  With bt601 and
+    tv nothing else is added and the file is tagged as the reference's is.
+    `feed` writes a YuvFrame's buffer to the pipe without a copy.  Never opens the GPU."""
+
+    def __init__(self, path: str, width: int, height: int, framerate: float, vcodec: str = "h264", execute: bool = False,
+                 replace: bool = False, layout: str = "yuv420p", matrix: str = "bt601", range: str = "tv",
+                 ffmpeg_bin: str = "ffmpeg"):
+        super().__init__(width, height, layout, matrix, range)
+        self.path = path if replace else _unique_path(path)
+        self.framerate = framerate
+        self.vcodec = vcodec
+        self.execute = execute
+        self.ffmpeg_bin = ffmpeg_bin
+        self.process = None
+
+    @property
+    def output_path(self):
+        return self.path
+
+    def colour_flags(self) -> list:
+        """What tells ffmpeg a matrix or a range other than the one it assumes; given once for the input, once for the
+        output.  NOT VERIFIED: the spelling of these flags (`-colorspace bt709`, `-color_range pc`) is taken from
+        ffmpeg's documentation and has not been run against an ffmpeg.  The default settings add none
+        of them."""
+        flags = []
+        if self.matrix != "bt601":
+            flags += ["-colorspace", self.matrix]
+        if self.range != "tv":
+            flags += ["-color_range", self.range]
+        return flags
+
+    def argv(self) -> list:
+        colour = self.colour_flags()
+        return [self.ffmpeg_bin,
+                "-hide_banner",
+                "-loglevel", "error",
+                "-f", "rawvideo",
+                "-vcodec", "rawvideo",
+                "-s", f"{self.width}x{self.height}",
+                "-pix_fmt", self.layout,
+                "-r", f"{self.framerate}",
+                *colour,
+                "-i", "-",
+                "-r", f"{self.framerate}",
+                "-pix_fmt", "yuv420p",
+                *colour,
+                "-an",
+                "-vcodec", self.vcodec,
+                self.path,
+                "-y"]
+
+    def __enter__(self):
+        import subprocess
+        dirname = os.path.dirname(self.path)                 # ffmpeg.py:28-30
+        if not os.path.isdir(dirname) and dirname != "":
+            os.makedirs(dirname)
+        self.process = subprocess.Popen(self.argv(), stdin=subprocess.PIPE)
+        return self
+
+    def feed(self, frame):
+        if self.process is None or self.process.stdin is None:
+            raise ValueError("Process not initialized")      # ffmpeg.py:52-53
+        self.process.stdin.write(self._planes(frame).memoryview())
+        self.frames += 1
+
+    def __exit__(self, exc_type, exc_value, exc_traceback):
+        if self.process is not None and self.process.stdin is not None:
+            self.process.stdin.close()
+        if self.process is not None:
+            self.process.wait()
+        if self.execute:                                     # ffmpeg.py:62-63
+            from transflow.utils import startfile
+            startfile(self.path)
+
+
+Y4M_CHROMA = {"yuv420p": "C420jpeg", "yuv422p": "C422", "yuv444p": "C444"}      # centre-sited samples
+Y4M_RANGE = {"tv": "LIMITED", "pc": "FULL"}
+
+
+class HipY4mOutput(_YuvOutput):
+    """A YUV4MPEG2 file: the header line, then `FRAME` and the planes for every frame.  The constructor is
+    FFmpegVideoOutput's (ffmpeg.py:17-25) with the layout, matrix and range in place of the codec; `path` is used as given
+    if `replace`, otherwise the first free name of the reference's rule.  The frame rate is written as a fraction of a
+    denominator up to 1001 (30000:1001 for 30000 / 1001, 2997:100 for 29.97).  Y4M has no tag for nv12 and none for the
+    matrix: the first is a ValueError here, the second is the reader's to know.  Never opens the GPU."""
+
+    def __init__(self, path: str, width: int, height: int, framerate: float, layout: str = "yuv420p", matrix: str = "bt601",
+                 range: str = "tv", execute: bool = False, replace: bool = False):
+        super().__init__(width, height, layout, matrix, range)
+        if layout not in Y4M_CHROMA:
+            raise ValueError(f"Y4M has no tag for {layout}: one of {sorted(Y4M_CHROMA)}")
+        self.path = path if replace else _unique_path(path)
+        self.framerate = framerate
+        self.execute = execute
+        self._file = None
+
+    @property
+    def output_path(self):
+        return self.path
+
+    def header(self) -> bytes:
+        import fractions
+        rate = fractions.Fraction(self.framerate).limit_denominator(1001)
+        return (f"YUV4MPEG2 W{self.width} H{self.height} F{rate.numerator}:{rate.denominator} Ip A1:1 "
+                f"{Y4M_CHROMA[self.layout]} XCOLORRANGE={Y4M_RANGE[self.range]}\n").encode("ascii")
+
+    def __enter__(self):
+        dirname = os.path.dirname(self.path)                 # ffmpeg.py:28-30
+        if not os.path.isdir(dirname) and dirname != "":
+            os.makedirs(dirname)
+        self._file = open(self.path, "wb")
+        self._file.write(self.header())
+        return self
+
+    def feed(self, frame):
+        if self._file is None:
+            raise ValueError("the output is not open")
+        planes = self._planes(frame)
+        self._file.write(b"FRAME\n")
+        self._file.write(planes.memoryview())
+        self.frames += 1
+
+    def __exit__(self, exc_type, exc_value, exc_traceback):
+        if self._file is not None:
+            self._file.close()
+            self._file = None
+        if self.execute:                                     # ffmpeg.py:62-63
+            from transflow.utils import startfile
+            startfile(self.path)
+
+
 class RawFramesOnly:
-    """Another output of the reference's, as it is, except that a JpegFrame or a PngFrame fed to it is refused by name:
-    those outputs take pixels (`install(jpeg_frames=...)` is for the MJPEG output, `%d ... .jpg` templates and .mjpeg
-    files, `install(png_frames=True)` for `%d ... .png` templates)."""
+    """Another output of the reference's, as it is, except that a JpegFrame, a PngFrame or a YuvFrame fed to it is refused
+    by name: those outputs take pixels (`install(jpeg_frames=...)` is for the MJPEG output, `%d ... .jpg` templates and
+    .mjpeg files, `install(png_frames=True)` for `%d ... .png` templates, `install(yuv_frames=...)` for the ffmpeg and
+    .y4m outputs)."""
 
     def __init__(self, output):
         self._output = output
@@ -320,6 +500,9 @@ class RawFramesOnly:
         if isinstance(first, PngFrame):
             raise TypeError(f"{type(self._output).__name__} takes raw frames, not PNG files: install(png_frames=True) "
                             "serves %d ... .png frame templates only")
+        if isinstance(first, YuvFrame):
+            raise TypeError(f"{type(self._output).__name__} takes raw frames, not YUV planes: install(yuv_frames=...) "
+                            "serves the ffmpeg and .y4m outputs only")
         return self._output.feed(frame)
 
     def __getattr__(self, name):
