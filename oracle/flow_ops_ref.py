@@ -18,20 +18,20 @@ MERGE_KINDS = ("first", "sum", "average", "difference", "product", "maskbin", "m
 def merge(kind: str, flows) -> np.ndarray:
     """Pipeline.FLOW_MERGING_FUNCTIONS, transflow/pipeline.py:149-158 (+ utils.py:359-381).
     All float32, operands combined strictly left to right (numpy.sum over the leading axis of a
-    stacked list adds the arrays one after the other)."""
+    stacked list adds the arrays one after the other).  Both sums start from +0.0 -- numpy.sum from
+    the identity of add, Python's sum() from its int 0 -- so operands that are all -0.0 sum to +0.0
+    (recorded from the reference: tests/golden/flow_ops_edges.npz, merge.sum.n1.c1026 and on)."""
     f = [np.asarray(a, np.float32) for a in flows]
     if kind == "first":                                             # :150
         return f[0]
     if kind in ("sum", "average"):                                  # :151-152
-        acc = f[0].copy()
-        for a in f[1:]:
+        acc = np.zeros_like(f[0])
+        for a in f:
             acc = acc + a
         return acc / np.float32(len(f)) if kind == "average" else acc
     if kind == "difference":                                        # :153  flows[0] - sum(flows[1:])
-        if len(f) == 1:
-            return f[0] - np.float32(0)
-        acc = f[1].copy()
-        for a in f[2:]:
+        acc = np.zeros_like(f[0])
+        for a in f[1:]:
             acc = acc + a
         return f[0] - acc
     if kind in ("product", "maskbin", "masklin"):                   # :154-156, utils.py:359-373

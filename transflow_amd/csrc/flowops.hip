@@ -22,7 +22,8 @@ struct MergeArgs {
     int n;
 };
 
-// Pipeline.FLOW_MERGING_FUNCTIONS: float32, operands combined left to right
+// Pipeline.FLOW_MERGING_FUNCTIONS: float32, operands combined left to right.  numpy.sum starts from the identity of
+// add and Python's sum() from 0, so both sums start from +0.0: operands that are all -0.0 sum to +0.0
 __global__ void k_flow_merge(MergeArgs a, float *__restrict__ out, size_t count, int kind)
 {
     size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -35,6 +36,7 @@ __global__ void k_flow_merge(MergeArgs a, float *__restrict__ out, size_t count,
         break;
     case TF_MERGE_SUM:
     case TF_MERGE_AVERAGE:
+        r = 0.f + f0;
         for (int i = 1; i < a.n; i++)
             r = r + a.in[i][t];
         if (kind == TF_MERGE_AVERAGE)
@@ -42,11 +44,8 @@ __global__ void k_flow_merge(MergeArgs a, float *__restrict__ out, size_t count,
         break;
     case TF_MERGE_DIFFERENCE: { // flows[0] - sum(flows[1:])
         float s = 0.f;
-        if (a.n > 1) {
-            s = a.in[1][t];
-            for (int i = 2; i < a.n; i++)
-                s = s + a.in[i][t];
-        }
+        for (int i = 1; i < a.n; i++)
+            s = s + a.in[i][t];
         r = f0 - s;
         break;
     }
