@@ -832,6 +832,31 @@ int tf_yuv_convert(tf_yuv *h, const uint8_t *rgb_host, uint8_t *out_host, size_t
    queued, not waited for. */
 int tf_yuv_convert_to_dev(tf_yuv *h, const void *rgb_dev, void *out_dev);
 
+/* ---- planar YUV frames back to pixels in device memory (transflow_amd/csrc/yuvdec.hip) -------------------------------------
+ * The way back: the planes of a Y4M or raw .yuv frame, in the layouts, matrices and ranges above, go up the link and
+ * become uint8 [H][W][3] pixels on the device.  With y = Y - 16 (tv) or Y (pc), u = U' - 128, v = V' - 128:
+ *   R = clamp((cy y + rv v + 32768) >> 16), G = clamp((cy y + gu u + gv v + 32768) >> 16), B = clamp((cy y + bu u + 32768) >> 16)
+ * chroma 0 replicate: U', V' are the sample of the pixel's block;  1 linear: the centre-sited triangle filter (libjpeg's
+ * fancy upsampling, neighbour indices clamped at every width).  order 0: R first, 1: B first.  DESIGN.md section 22 has
+ * the rule and the table of coefficients.  No counterpart in the reference; these are not swscale's pixels. */
+typedef struct tf_yuvdec tf_yuvdec;
+/* The coefficients as the library builds them: cy, rv, gu, gv, bu with 16 fractional bits.  No GPU call. */
+int tf_yuvdec_coefficients(int matrix, int range, int32_t out[5]);
+/* max_width, max_height: 1 to 65535.  The handle owns a page-locked staging buffer and a device buffer of
+   tf_yuv_frame_bytes(max_width, max_height, yuv444p) each. */
+int tf_yuvdec_create(tf_yuvdec **out, int max_width, int max_height);
+void tf_yuvdec_destroy(tf_yuvdec *h);
+/* planes_host: the tightly packed frame, nbytes == tf_yuv_frame_bytes(width, height, layout), in any host memory.  Copies it
+   to the staging buffer (once that buffer's previous upload has finished), uploads it with one copy on the calling
+   thread's stream and queues the kernel; does not wait for the pixels.  out_dev: 3*width*height bytes at any address;
+   nothing is written outside them.  TF_ERR_ARG for a bad layout, matrix, range, chroma or order, a size beyond the
+   handle, or another nbytes. */
+int tf_yuvdec_convert(tf_yuvdec *h, const uint8_t *planes_host, size_t nbytes, int width, int height, int layout, int matrix,
+                      int range, int chroma, void *out_dev, int order);
+/* The same for planes already in device memory, at any address (a tf_yuv_convert_to_dev result): no copy. */
+int tf_yuvdec_convert_dev(tf_yuvdec *h, const void *planes_dev, size_t nbytes, int width, int height, int layout, int matrix,
+                          int range, int chroma, void *out_dev, int order);
+
 /* ---- flow archive members deflated on the device (transflow_amd/csrc/flowzip.hip) --------
  * The reference's flow export (transflow/pipeline.py:363-377, 505-506, output/numpy.py, output/zip.py) writes
  * numpy.save(flow) into a deflated zip member.  tf_flowzip makes that member's raw deflate stream -- no zlib header, no

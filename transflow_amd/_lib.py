@@ -260,6 +260,11 @@ PROTOTYPES = {
     "tf_yuv_convert_dev": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_yuv_convert": (_I, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "tf_yuv_convert_to_dev": (_I, [_P, _P, _P]),
+    "tf_yuvdec_coefficients": (_I, [_I, _I, C.POINTER(C.c_int32)]),
+    "tf_yuvdec_create": (_I, [_PP, _I, _I]),
+    "tf_yuvdec_destroy": (None, [_P]),
+    "tf_yuvdec_convert": (_I, [_P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _P, _I]),
+    "tf_yuvdec_convert_dev": (_I, [_P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _P, _I]),
     "tf_flowzip_create": (_I, [_PP, C.c_size_t, _I]),
     "tf_flowzip_destroy": (None, [_P]),
     "tf_flowzip_band_bytes": (_I, [_P]),

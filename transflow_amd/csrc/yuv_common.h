@@ -74,5 +74,34 @@ inline bool make_coef(int matrix, int range, Coef *c)
     return true;
 }
 
+// ---- the way back (yuvdec.hip) ----
+
+enum Chroma { REPLICATE = 0, LINEAR = 1, N_CHROMAS = 2 };
+
+// What the inverse kernel is launched with: R = cy y + rv v, G = cy y + gu u + gv v, B = cy y + bu u, with 16
+// fractional bits; y_off: 16 (tv) or 0 (pc).
+struct InvCoef {
+    int32_t cy, rv, gu, gv, bu;
+    int32_t y_off;
+};
+
+// The rule of DESIGN.md section 22 in exact integer arithmetic: Kr, Kb in 1/10000; s_y = 255/219, s_c = 255/224 for tv.
+// Each entry is the real value times 65536, rounded half to even.
+inline bool make_inv_coef(int matrix, int range, InvCoef *c)
+{
+    if (matrix < 0 || matrix >= N_MATRICES || range < 0 || range >= N_RANGES)
+        return false;
+    const int64_t one = 10000, kr = matrix == BT601 ? 2990 : 2126, kb = matrix == BT601 ? 1140 : 722, kg = one - kr - kb;
+    const int64_t s_n = range == TV ? 255 : 1, sy_d = range == TV ? 219 : 1, sc_d = range == TV ? 224 : 1;
+    const int64_t unit = (int64_t)1 << FRAC_BITS;
+    c->cy = (int32_t)rint_ratio(s_n * unit, sy_d);
+    c->rv = (int32_t)rint_ratio(2 * (one - kr) * s_n * unit, one * sc_d);
+    c->gu = (int32_t)rint_ratio(-2 * (one - kb) * kb * s_n * unit, one * kg * sc_d);
+    c->gv = (int32_t)rint_ratio(-2 * (one - kr) * kr * s_n * unit, one * kg * sc_d);
+    c->bu = (int32_t)rint_ratio(2 * (one - kb) * s_n * unit, one * sc_d);
+    c->y_off = range == TV ? 16 : 0;
+    return true;
+}
+
 } // namespace yuv
 } // namespace tf

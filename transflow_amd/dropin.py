@@ -27,7 +27,7 @@ import os
 import re
 
 _saved = {}
-_pixmap_options = {"stills": False, "mjpeg": False, "png": False, "mjpeg_parallel": False}   # what the installed pixmap factory serves
+_pixmap_options = {"stills": False, "mjpeg": False, "png": False, "mjpeg_parallel": False, "yuv": False, "yuv_matrix": "bt601"}   # what the installed pixmap factory serves
 _saved_export = []      # (the reference's pipeline module, its NumpyOutput, deviceflow.DEVICE_ROUND) while device_flow_export is on
 
 
@@ -52,8 +52,14 @@ def _is_png_sequence(path) -> bool:
     return is_png_sequence(path)
 
 
+def _is_y4m(path) -> bool:
+    from .yuvdec import is_y4m
+    return is_y4m(path)
+
+
 def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None, motion_vectors=False,
-                    device_flow_replay=False, mjpeg_inputs=False, png_inputs=False, mjpeg_parallel=False):
+                    device_flow_replay=False, mjpeg_inputs=False, png_inputs=False, mjpeg_parallel=False, yuv_inputs=False,
+                    yuv_input_matrix="bt601"):
     from .flow import HipFlowSource
 
     def from_args(cls, flow_path, use_mvs=False, mask_path=None, kernel_path=None, cv_config=None,
@@ -81,6 +87,10 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
         elif png_inputs and not use_mvs and _is_png_sequence(flow_path):   # a PNG frame sequence: likewise
             from .pngdec import PngSequenceFrameProvider
             flow_path = PngSequenceFrameProvider(flow_path, size=size)
+        elif yuv_inputs and not use_mvs and _is_y4m(flow_path):   # a Y4M file: its planes go up, the device converts them
+            from .yuvdec import Y4mFrameProvider
+            flow_path = Y4mFrameProvider(flow_path, size=size, matrix=yuv_input_matrix,
+                                         chroma="linear" if yuv_inputs == "linear" else "replicate")
         return HipFlowSource.from_args(flow_path, use_mvs, mask_path, kernel_path, cv_config, flow_filters, size,
                                        direction, seek_ckpt, seek_time, duration_time, repeat, lock_expr, lock_mode,
                                        lucas_kanade=lucas_kanade, liteflownet=liteflownet,
@@ -156,18 +166,19 @@ def _yuv_output_from_args(original, layout, matrix, range):
     return classmethod(from_args)
 
 
-def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=False, mjpeg_parallel=False):
+def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=False, mjpeg_parallel=False, yuv_inputs=False,
+                      yuv_input_matrix="bt601"):
     from .pixmap import HipPixmapSource
 
     def from_args(cls, path, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat=1, flow_path=None):
         still = stills and re.match(HipPixmapSource.STILL_RE, path.lower().strip()) is not None
         image = stills and os.path.isfile(path) and os.path.splitext(path)[1].lower() in HipPixmapSource.IMAGE_EXTS
-        video = (mjpeg_inputs and _is_mjpeg(path)) or (png_inputs and _is_png_sequence(path))
+        video = (mjpeg_inputs and _is_mjpeg(path)) or (png_inputs and _is_png_sequence(path)) or (yuv_inputs and _is_y4m(path))
         if not (still or image or video):                                  # a video: the reference's CvPixmapSource
             return original(path, size, seek=seek, seed=seed, seek_time=seek_time, alteration_path=alteration_path,
                             repeat=repeat, flow_path=flow_path)
         return HipPixmapSource.from_args(path, size, seek, seed, seek_time, alteration_path, repeat, flow_path,
-                                         mjpeg_parallel_scan=mjpeg_parallel)
+                                         mjpeg_parallel_scan=mjpeg_parallel, y4m_inputs=yuv_inputs, y4m_matrix=yuv_input_matrix)
 
     return classmethod(from_args)
 
@@ -177,7 +188,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
             device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed",
             jpeg_optimize: bool = False, jpeg_subsampling=None, yuv_frames: str | None = None, yuv_matrix: str | None = None,
-            yuv_range: str | None = None) -> None:
+            yuv_range: str | None = None, yuv_inputs=False, yuv_input_matrix: str = "bt601") -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -241,7 +252,18 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     for every path the reference gives to FFmpegVideoOutput (video_output.py:59-60) and a HipY4mOutput for paths that end
     in .y4m; any other output is the reference's own and raises a TypeError that names this option when it is fed a
     YuvFrame.  yuv_matrix ("bt601", the default, or "bt709") and yuv_range ("tv", the default, or "pc") only with
-    yuv_frames.  Not together with jpeg_frames, png_frames or lazy_frames.  By default (None) nothing of this is touched."""
+    yuv_frames.  Not together with jpeg_frames, png_frames or lazy_frames.  By default (None) nothing of this is touched.
+    yuv_inputs: an existing file whose name ends in .y4m (YUV4MPEG2: what `ffmpeg -i any.mp4 out.y4m` and HipY4mOutput
+    write) is read by transflow_amd/yuvdec.py, as a flow source's video (a Y4mFrameProvider under the HipFlowSource; not
+    with use_mvs) and as a pixmap source (HipY4mPixmapSource): the planes go up the link as they are and the device
+    converts them to pixels (these are not swscale's pixels).  True expands the chroma by
+    replication, "linear" by the centre-sited triangle filter; any other value is a ValueError.  yuv_input_matrix
+    ("bt601", the default, or "bt709") is the matrix the file was made with: Y4M has no tag for it.  By default such
+    paths stay the reference's, like every other video."""
+    if not isinstance(yuv_inputs, bool) and not (isinstance(yuv_inputs, str) and yuv_inputs == "linear"):
+        raise ValueError(f"yuv_inputs is True or \"linear\", not {yuv_inputs!r}")
+    if yuv_input_matrix not in ("bt601", "bt709"):
+        raise ValueError(f"yuv_input_matrix is \"bt601\" or \"bt709\", not {yuv_input_matrix!r}")
     if yuv_frames is None:
         if yuv_matrix is not None or yuv_range is not None:
             raise ValueError("yuv_matrix and yuv_range are for yuv_frames: without them no YUV frame is made")
@@ -272,7 +294,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
         RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet,
                                                      motion_vectors, bool(device_flow_replay), bool(mjpeg_inputs),
-                                                     bool(png_inputs), mjpeg_inputs == "parallel")
+                                                     bool(png_inputs), mjpeg_inputs == "parallel", yuv_inputs, yuv_input_matrix)
     if compositor and "compositor" not in _saved:
         from transflow.compositor.compositor import Compositor as RefCompositor
 
@@ -307,27 +329,30 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         else:
             ref_pipeline.NumpyOutput = DeviceFlowArchiveWriter
         deviceflow.DEVICE_ROUND = True
-    if pixmaps or mjpeg_inputs or png_inputs:
+    if pixmaps or mjpeg_inputs or png_inputs or yuv_inputs:
         # one factory serves both options: a later call that asks for the other one adds it to what is installed
         from transflow.pixmap.source import PixmapSource as RefPixmapSource
         if "pixmaps" not in _saved:
             _saved["pixmaps"] = (RefPixmapSource, RefPixmapSource.__dict__["from_args"])
-            _pixmap_options.update(stills=False, mjpeg=False, png=False, mjpeg_parallel=False)
+            _pixmap_options.update(stills=False, mjpeg=False, png=False, mjpeg_parallel=False, yuv=False, yuv_matrix="bt601")
         wanted = dict(stills=_pixmap_options["stills"] or bool(pixmaps), mjpeg=_pixmap_options["mjpeg"] or bool(mjpeg_inputs),
                       png=_pixmap_options["png"] or bool(png_inputs),
-                      mjpeg_parallel=_pixmap_options["mjpeg_parallel"] or mjpeg_inputs == "parallel")
+                      mjpeg_parallel=_pixmap_options["mjpeg_parallel"] or mjpeg_inputs == "parallel",
+                      yuv=yuv_inputs or _pixmap_options["yuv"],
+                      yuv_matrix=yuv_input_matrix if yuv_inputs else _pixmap_options["yuv_matrix"])
         if wanted != _pixmap_options:
             _pixmap_options.update(wanted)
             RefPixmapSource.from_args = _saved["pixmaps"][1]              # the reference's own, to be wrapped once
             RefPixmapSource.from_args = _pixmap_from_args(RefPixmapSource.from_args, wanted["stills"], wanted["mjpeg"],
-                                                          wanted["png"], wanted["mjpeg_parallel"])
+                                                          wanted["png"], wanted["mjpeg_parallel"], wanted["yuv"],
+                                                          wanted["yuv_matrix"])
 
 
 def uninstall() -> None:
     for key in list(_saved):
         cls, original = _saved.pop(key)
         cls.from_args = original
-    _pixmap_options.update(stills=False, mjpeg=False, png=False, mjpeg_parallel=False)
+    _pixmap_options.update(stills=False, mjpeg=False, png=False, mjpeg_parallel=False, yuv=False, yuv_matrix="bt601")
     while _saved_export:
         from . import deviceflow
         module, original, switch = _saved_export.pop()

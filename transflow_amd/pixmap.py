@@ -289,9 +289,10 @@ class HipPixmapSource:
 
     @classmethod
     def from_args(cls, path: str, size, seek=None, seed=None, seek_time=None, alteration_path=None, repeat: int = 1,
-                  flow_path=None, mjpeg_parallel_scan: bool = False):
+                  flow_path=None, mjpeg_parallel_scan: bool = False, y4m_inputs=False, y4m_matrix: str = "bt601"):
         """source.py:71-120; of the video paths (CvPixmapSource there) a raw MJPEG stream file and a `%0Nd.png` frame
-        sequence are served.  mjpeg_parallel_scan: HipMjpegPixmapSource's `parallel_scan`."""
+        sequence are served, and with `y4m_inputs` (True, or "linear" for that chroma filter) a .y4m file, read with
+        `y4m_matrix`.  mjpeg_parallel_scan: HipMjpegPixmapSource's `parallel_scan`."""
         ext = os.path.splitext(path)[1]
         still_match = re.match(cls.STILL_RE, path.lower().strip())
         if still_match is not None:
@@ -323,6 +324,9 @@ class HipPixmapSource:
         from .pngdec import is_png_sequence
         if is_png_sequence(path):
             return HipPngSequencePixmapSource(path, seek, seek_time, alteration_path, repeat)
+        if y4m_inputs and os.path.isfile(path) and ext.lower() == ".y4m":
+            return HipY4mPixmapSource(path, seek, seek_time, alteration_path, repeat, matrix=y4m_matrix,
+                                      chroma="linear" if y4m_inputs == "linear" else "replicate")
         raise NotImplementedError(f"video pixmap source '{path}': not served by this backend (CvPixmapSource)")
 
 
@@ -547,6 +551,22 @@ class HipPngSequencePixmapSource(HipMjpegPixmapSource):
     def _open(self):
         from .pngdec import PngSequenceFrameProvider
         return PngSequenceFrameProvider(self.path, framerate=self._framerate)
+
+
+class HipY4mPixmapSource(HipMjpegPixmapSource):
+    """CvPixmapSource (pixmap/cv.py:11-66) over a YUV4MPEG2 file: the same rewind, seek, `repeat`, `length` and alteration
+    as `HipMjpegPixmapSource`; the planes go up as they are and every frame is converted on the device
+    (transflow_amd/yuvdec.py) and handed out as an RGB `DevicePixmap`.  The frame rate is the header's; `matrix`, `range`
+    (None: the header's) and `chroma` are Y4mFrameProvider's."""
+
+    def __init__(self, path, seek: int | None = None, seek_time: float | None = None, alteration_path: str | None = None,
+                 repeat: int = 1, matrix: str = "bt601", range: str | None = None, chroma: str = "replicate"):
+        HipMjpegPixmapSource.__init__(self, path, seek, seek_time, alteration_path, repeat)
+        self.matrix, self.range, self.chroma = matrix, range, chroma
+
+    def _open(self):
+        from .yuvdec import Y4mFrameProvider
+        return Y4mFrameProvider(self.path, matrix=self.matrix, range=self.range, chroma=self.chroma)
 
 
 class EndOfPixmap(StopIteration):
