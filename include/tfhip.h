@@ -307,6 +307,18 @@ int tf_flow_post_process_ex_dev(void *flow_dev, int wide, int width, int height,
 int tf_flow_post_process_chain_dev(const void *src_dev, void *dst_dev, void *chain_dev, int width, int height,
                                    int direction, int n_ops, const tf_flow_op *ops, const void *mask_dev,
                                    void *winner_dev);
+/* The convolution tail, source.py:344-362, out of place and without the intermediate array: src_dev (float32
+   [H][W][2]) is left as it is, dst_dev (T [H][W][2]; T float64 with wide = 1, else float32, as is the kernel) receives
+   exactly the bits tf_flow_convolve_dev followed by tf_flow_post_process_dev(wide, direction) would leave.  direction
+   1 (BACKWARD) and -1 (the convolution alone) are one launch; 0 (FORWARD) is two: the convolution launch claims the
+   targets in winner_dev (4 bytes per pixel, the caller's) and never stores the convolved flow, a resolve launch writes
+   dst_dev.  Refused: null or aliased buffers, FORWARD without winner_dev, an empty kernel. */
+int tf_flow_convolve_post_process_dev(const void *src_dev, const void *kernel_dev, int kh, int kw, int wide, void *dst_dev,
+                                      int width, int height, int direction, void *winner_dev);
+/* float32(rint(x)) (mode 0) or float32(floor(x)) (mode 1) of n_values float64 values, computed in double: what the
+   compositor's layers make of a float64 flow (numpy.round, movement.py:21; numpy.floor, sum.py:10).  Ties go to even,
+   -0.5 gives -0.0, NaN stays NaN.  src 8-byte and dst 4-byte aligned; both 16-byte aligned: two pixels a lane. */
+int tf_flow_narrow_dev(const void *src_f64_dev, void *dst_f32_dev, size_t n_values, int mode);
 
 /* The `polar` flow filter, transflow/flow/filters.py:75-87, in place on a float32 flow: r = |v|,
    a = atan2(vy, vx), then v = (R cos A, R sin A) with R and A the filter's two user expressions of

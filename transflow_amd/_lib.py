@@ -208,6 +208,8 @@ PROTOTYPES = {
     "tf_flow_post_process_dev": (_I, [_P, _I, _I, _I, _I, _P]),
     "tf_flow_post_process_ex_dev": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(TfFlowOp), _P, _P]),
     "tf_flow_post_process_chain_dev": (_I, [_P, _P, _P, _I, _I, _I, _I, C.POINTER(TfFlowOp), _P, _P]),
+    "tf_flow_convolve_post_process_dev": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _P]),
+    "tf_flow_narrow_dev": (_I, [_P, _P, C.c_size_t, _I]),
     "tf_flow_polar_dev": (_I, [_P, C.c_size_t, _I, _P, _I, _P, _I, _I]),
     "tf_flow_render1d_dev": (_I, [_P, _P, C.c_size_t, C.c_float, C.POINTER(C.c_float), _I]),
     "tf_flow_render2d_dev": (_I, [_P, _P, C.c_size_t, C.c_float, C.POINTER(C.c_float)]),

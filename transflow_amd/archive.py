@@ -248,8 +248,8 @@ class DeviceFlowArchiveWriter:
         from .flowzip import DISTANCES, DeviceInt64Flow, npy_prefix, round_i64_dev
         member = frame_member(self.index)
         if rounded:
-            if isinstance(array, DeviceFlow) and not array.on_host:
-                array = round_i64_dev(array)
+            if isinstance(array, DeviceFlow) and not array.on_host and array.dtype == np.float32:
+                array = round_i64_dev(array)      # (a float64 flow comes down: numpy's own round, as DEVICE_ROUND does)
             else:
                 array = np.round(array).astype(int)
         if isinstance(array, (DeviceFlow, DeviceInt64Flow)) and not array.on_host:

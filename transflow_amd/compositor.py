@@ -146,10 +146,11 @@ class _HipLayer:
         self._deferred = None
         layer = self._dev
         flow.wait_on_stream()
+        flow_ptr = layer.device_flow_ptr(flow)      # (a float64 flow: rounded in double into the layer's float32 scratch)
         if comp is not None:
-            layer.step_dev(comp, flow.dev_ptr, ptr, channels, clip_flow=False, seed=seed)
+            layer.step_dev(comp, flow_ptr, ptr, channels, clip_flow=False, seed=seed)
         else:
-            layer.update_dev(flow.dev_ptr, None, seed)
+            layer.update_dev(flow_ptr, None, seed)
             layer.gather_dev(0, ptr, channels)
         flow.mark_used()
         layer.staged_used()

@@ -1,7 +1,9 @@
 // B1: FlowSource.post_process (source.py:337-363) on a device flow -- the clip, the FORWARD scatter (last write wins)
 // and its resolve, in float32 or (after a float64 convolution kernel, :344-348) float64 -- and the flow filters / mask
 // multiply that precede it (filters.py:36-72).  One implementation for every caller: the tf_fb_post_process* entry
-// points (farneback.hip) and the handle-free tf_flow_post_process*_dev bring their own winner buffer.
+// points (farneback.hip) and the handle-free tf_flow_post_process*_dev bring their own winner buffer.  Also the
+// convolution kernel fused with what follows it (tf_flow_convolve_post_process_dev) and the rounding of a float64 flow
+// for the compositor's layers (tf_flow_narrow_dev).
 #include <cstring>
 
 #include "common.h"
@@ -309,6 +311,194 @@ int chain_launch(const float2 *src, float2 *dst, float2 *chain, int W, int H, in
     return launch("flow_pp_chain_line", k_pp_chain_line<PX, false>, grid, block, 0, src, dst, chain, mask, W, H, dw, fo);
 }
 
+// ---- The convolution tail (tf_flow_convolve_post_process_dev): source.py:344-362 out of place and in one pass over
+// the flow.  The sums are k_flow_convolve's / k_flow_convolve_tiled's (flowops.hip), statement for statement -- kernel
+// rows j, then columns k, every product and sum rounded in T, the fill value taking part -- so the convolved vector is
+// theirs to the bit; what follows it in T happens in registers.  END says what: the plain store (no direction), the
+// clip and the store (BACKWARD: k_pp_clip's statement), or the clip, the round and the claim in the winner map (FORWARD:
+// k_pp_fwd_scatter's statements; the convolved flow is never stored, k_pp_tail_resolve writes the output).
+template <typename T> struct Vec2;
+template <> struct Vec2<float> {
+    typedef float2 type;
+};
+template <> struct Vec2<double> {
+    typedef double2 type;
+};
+
+enum TailEnd { TAIL_STORE, TAIL_CLIP, TAIL_SCATTER };
+
+constexpr int CT_TW = 64, CT_TH = 16; // k_flow_convolve_tiled's tile: 64 x 16 outputs per block of 256
+
+template <typename T, int END>
+__device__ __forceinline__ void tail_end(T sx, T sy, int i, int j, int W, int H, typename Vec2<T>::type *__restrict__ out,
+                                         int *__restrict__ winner)
+{
+    typename Vec2<T>::type r;
+    r.x = sx;
+    r.y = sy;
+    const int t = i * W + j;
+    if (END != TAIL_STORE)
+        r = clip_to_frame(r, i, j, W, H);
+    if (END != TAIL_SCATTER) {
+        out[t] = r;
+        return;
+    }
+    const int d = rint_i(r.y) * W + rint_i(r.x);
+    if (d != 0)
+        atomicMax(&winner[clampi(t + d, 0, W * H - 1)], t); // mode="clip"; the largest source wins
+}
+
+template <typename T, int END>
+__global__ void __launch_bounds__(256)
+    k_conv_tail(const float2 *__restrict__ flow, const T *__restrict__ kern, int kh, int kw,
+                typename Vec2<T>::type *__restrict__ out, int *__restrict__ winner, int W, int H)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)W * H)
+        return;
+    const int n = (int)(t % W), m = (int)(t / W);
+    const int oy = (kh - 1) >> 1, ox = (kw - 1) >> 1;
+    T sx = 0, sy = 0;
+    for (int j = 0; j < kh; j++) {
+        const int y = m + oy - j;
+        const bool row_in = y >= 0 && y < H;
+        for (int k = 0; k < kw; k++) {
+            const int x = n + ox - k;
+            const T hv = kern[j * kw + k];
+            T vx = 0, vy = 0;
+            if (row_in && x >= 0 && x < W) {
+                const float2 f = flow[(size_t)y * W + x];
+                vx = (T)f.x;
+                vy = (T)f.y;
+            }
+            sx = sx + hv * vx; // the fill value takes part: 0 * h
+            sy = sy + hv * vy;
+        }
+    }
+    tail_end<T, END>(sx, sy, m, n, W, H, out, winner);
+}
+
+template <typename T, int END>
+__global__ void __launch_bounds__(256)
+    k_conv_tail_tiled(const float2 *__restrict__ flow, const T *__restrict__ kern, int kh, int kw,
+                      typename Vec2<T>::type *__restrict__ out, int *__restrict__ winner, int W, int H)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_ct[];
+    const int LW = CT_TW + kw - 1, LH = CT_TH + kh - 1;
+    float2 *tile = reinterpret_cast<float2 *>(s_ct);
+    T *sk = reinterpret_cast<T *>(s_ct + (((size_t)LW * LH * sizeof(float2) + 15) & ~(size_t)15));
+    const int x0 = blockIdx.x * CT_TW, y0 = blockIdx.y * CT_TH;
+    const int oy = (kh - 1) >> 1, ox = (kw - 1) >> 1;
+    // tile (ry, rx) <-> image (y0 + oy - (kh-1) + ry, x0 + ox - (kw-1) + rx)
+    const int ty0 = y0 + oy - (kh - 1), tx0 = x0 + ox - (kw - 1);
+    for (int idx = threadIdx.x; idx < LW * LH; idx += 256) {
+        const int ry = idx / LW, rx = idx - ry * LW;
+        const int y = ty0 + ry, x = tx0 + rx;
+        tile[idx] = (y >= 0 && y < H && x >= 0 && x < W) ? flow[(size_t)y * W + x] : make_float2(0.f, 0.f);
+    }
+    for (int idx = threadIdx.x; idx < kh * kw; idx += 256)
+        sk[idx] = kern[idx];
+    __syncthreads();
+    const int tx = threadIdx.x & 63, tq = threadIdx.x >> 6;
+    T sx[4] = {0, 0, 0, 0}, sy[4] = {0, 0, 0, 0};
+    for (int j = 0; j < kh; j++) {
+        for (int k = 0; k < kw; k++) {
+            const T hv = sk[j * kw + k];
+            const float2 *p = tile + (tq + (kh - 1) - j) * LW + tx + (kw - 1) - k;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const float2 f = p[4 * q * LW];
+                sx[q] = sx[q] + hv * (T)f.x;
+                sy[q] = sy[q] + hv * (T)f.y;
+            }
+        }
+    }
+    const int x = x0 + tx;
+    if (x >= W)
+        return;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int y = y0 + tq + 4 * q;
+        if (y < H)
+            tail_end<T, END>(sx[q], sy[q], y, x, W, H, out, winner);
+    }
+}
+
+// FORWARD's second launch: k_pp_fwd_resolve's statements, written to the output instead of over the flow
+template <typename T2>
+__global__ void __launch_bounds__(256) k_pp_tail_resolve(T2 *__restrict__ dst, const int *__restrict__ winner, int W, int H, FastDiv dw)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= W * H)
+        return;
+    typedef decltype(dst[0].x) T;
+    const int w = winner[t];
+    const int src = w >= 0 ? w : t;
+    const int i = (int)fast_div((uint32_t)t, dw), j = t - i * W;
+    const int si = (int)fast_div((uint32_t)src, dw);
+    T2 f;
+    f.x = (T)(src - si * W - j); // source.py:359-360
+    f.y = (T)(si - i);
+    dst[t] = clip_to_frame(f, i, j, W, H); // :361-362
+}
+
+template <typename T, int END>
+int conv_tail_launch(const float2 *src, const T *kern, int kh, int kw, typename Vec2<T>::type *dst, int *winner, int W, int H)
+{
+    const size_t N = (size_t)W * H;
+    // tf_flow_convolve_dev's rule: the tiled form where the float2 tile (padded to 16 bytes) and the kernel fit 64 KB
+    const size_t tile_bytes = (((size_t)(CT_TW + kw - 1) * (CT_TH + kh - 1) * sizeof(float2) + 15) & ~(size_t)15) +
+                              (size_t)kh * kw * sizeof(T);
+    const char *name = sizeof(T) == 8 ? "flow_conv_tail_f64" : "flow_conv_tail_f32";
+    static const bool no_tiles = tune("TF_CONV_NO_TILES", 0) != 0;
+    if (tile_bytes <= 64 * 1024 && !no_tiles)
+        return launch(name, k_conv_tail_tiled<T, END>, dim3(cdiv(W, CT_TW), cdiv(H, CT_TH)), dim3(256), tile_bytes, src, kern,
+                      kh, kw, dst, winner, W, H);
+    return launch(name, k_conv_tail<T, END>, dim3(cdiv(N, 256)), dim3(256), 0, src, kern, kh, kw, dst, winner, W, H);
+}
+
+template <typename T>
+int conv_tail(const float2 *src, const T *kern, int kh, int kw, typename Vec2<T>::type *dst, int W, int H, int direction,
+              int *winner)
+{
+    if (direction < 0)
+        return conv_tail_launch<T, TAIL_STORE>(src, kern, kh, kw, dst, nullptr, W, H);
+    if (direction == 1)
+        return conv_tail_launch<T, TAIL_CLIP>(src, kern, kh, kw, dst, nullptr, W, H);
+    const size_t N = (size_t)W * H;
+    TF_HIP(hipMemsetAsync(winner, 0xFF, N * 4, stream()));
+    TF_TRY((conv_tail_launch<T, TAIL_SCATTER>(src, kern, kh, kw, dst, winner, W, H)));
+    return launch("flow_conv_tail_resolve", k_pp_tail_resolve<typename Vec2<T>::type>, dim3(cdiv(N, 256)), dim3(256), 0, dst,
+                  (const int *)winner, W, H, fast_div_setup((uint32_t)W));
+}
+
+// float32(rint(x)) or float32(floor(x)) of a float64 flow, in double (numpy.round / numpy.floor of the float64 array, then
+// the cast: movement.py:21, sum.py:10): ties to even, -0.5 -> -0.0, NaN stays NaN.  VEC: a lane takes two pixels -- four
+// values, 32 bytes in and 16 out -- where both buffers are 16-byte aligned; what is left of the end goes value by value.
+template <int FLOOR> __device__ __forceinline__ float narrow1(double v) { return (float)(FLOOR ? floor(v) : rint(v)); }
+
+template <int FLOOR, bool VEC>
+__global__ void __launch_bounds__(256) k_flow_narrow(const double *__restrict__ src, float *__restrict__ dst, size_t n)
+{
+    const size_t lane = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (!VEC) {
+        if (lane < n)
+            dst[lane] = narrow1<FLOOR>(src[lane]);
+        return;
+    }
+    const size_t v0 = lane * 4;
+    if (v0 >= n)
+        return;
+    if (v0 + 4 <= n) {
+        const double2 a = *reinterpret_cast<const double2 *>(src + v0), b = *reinterpret_cast<const double2 *>(src + v0 + 2);
+        *reinterpret_cast<float4 *>(dst + v0) =
+            make_float4(narrow1<FLOOR>(a.x), narrow1<FLOOR>(a.y), narrow1<FLOOR>(b.x), narrow1<FLOOR>(b.y));
+        return;
+    }
+    for (size_t v = v0; v < n; v++)
+        dst[v] = narrow1<FLOOR>(src[v]);
+}
+
 template <typename T2> int scatter(const T2 *flow, int W, int H, int *winner, const PpLabels &lb)
 {
     const size_t N = (size_t)W * H;
@@ -425,4 +615,48 @@ TF_API int tf_flow_post_process_dev(void *flow_dev, int wide, int width, int hei
 {
     TF_REQUIRE(direction == 0 || direction == 1, "tf_flow_post_process: direction must be 0 (FORWARD) or 1 (BACKWARD)");
     return tf_flow_post_process_ex_dev(flow_dev, wide, width, height, direction, 0, nullptr, nullptr, scratch_dev);
+}
+
+TF_API int tf_flow_convolve_post_process_dev(const void *src_dev, const void *kernel_dev, int kh, int kw, int wide,
+                                             void *dst_dev, int width, int height, int direction, void *winner_dev)
+{
+    TF_REQUIRE(direction >= -1 && direction <= 1,
+               "tf_flow_convolve_post_process: direction must be 0 (FORWARD), 1 (BACKWARD) or -1 (none)");
+    TF_REQUIRE(width >= 0 && height >= 0 && (long long)width * height < (1ll << 31), "tf_flow_convolve_post_process: bad size");
+    TF_REQUIRE(kh >= 1 && kw >= 1, "tf_flow_convolve_post_process: an empty convolution kernel (%d x %d)", kh, kw);
+    if ((size_t)width * height == 0)
+        return TF_OK;
+    TF_REQUIRE(src_dev && dst_dev && kernel_dev, "tf_flow_convolve_post_process: null pointer");
+    TF_REQUIRE(src_dev != dst_dev && kernel_dev != dst_dev && winner_dev != dst_dev && winner_dev != src_dev,
+               "tf_flow_convolve_post_process: src, the kernel, dst and the winner map must be separate buffers");
+    TF_REQUIRE(direction != 0 || winner_dev, "tf_flow_convolve_post_process: FORWARD needs a winner buffer of 4 bytes per pixel");
+    TF_REQUIRE((uintptr_t)src_dev % 8 == 0 && (uintptr_t)dst_dev % (wide ? 16 : 8) == 0 &&
+                   (uintptr_t)kernel_dev % (wide ? 8 : 4) == 0 && (uintptr_t)winner_dev % 4 == 0,
+               "tf_flow_convolve_post_process: misaligned buffer");
+    TF_TRY(ensure_init());
+    if (wide)
+        return conv_tail<double>((const float2 *)src_dev, (const double *)kernel_dev, kh, kw, (double2 *)dst_dev, width, height,
+                                 direction, (int *)winner_dev);
+    return conv_tail<float>((const float2 *)src_dev, (const float *)kernel_dev, kh, kw, (float2 *)dst_dev, width, height,
+                            direction, (int *)winner_dev);
+}
+
+TF_API int tf_flow_narrow_dev(const void *src_f64_dev, void *dst_f32_dev, size_t n_values, int mode)
+{
+    TF_REQUIRE(mode == 0 || mode == 1, "tf_flow_narrow: mode must be 0 (rint) or 1 (floor), got %d", mode);
+    if (n_values == 0)
+        return TF_OK;
+    TF_REQUIRE(src_f64_dev && dst_f32_dev && src_f64_dev != dst_f32_dev, "tf_flow_narrow: null or aliased pointer");
+    TF_REQUIRE((uintptr_t)src_f64_dev % 8 == 0 && (uintptr_t)dst_f32_dev % 4 == 0, "tf_flow_narrow: misaligned buffer");
+    TF_TRY(ensure_init());
+    const double *src = (const double *)src_f64_dev;
+    float *dst = (float *)dst_f32_dev;
+    if (((uintptr_t)src_f64_dev | (uintptr_t)dst_f32_dev) % 16 == 0) {
+        const dim3 grid(cdiv((n_values + 3) / 4, 256));
+        return mode ? launch("flow_narrow", k_flow_narrow<1, true>, grid, dim3(256), 0, src, dst, n_values)
+                    : launch("flow_narrow", k_flow_narrow<0, true>, grid, dim3(256), 0, src, dst, n_values);
+    }
+    const dim3 grid(cdiv(n_values, 256));
+    return mode ? launch("flow_narrow", k_flow_narrow<1, false>, grid, dim3(256), 0, src, dst, n_values)
+                : launch("flow_narrow", k_flow_narrow<0, false>, grid, dim3(256), 0, src, dst, n_values);
 }

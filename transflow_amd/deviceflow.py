@@ -5,7 +5,7 @@ multiprocessing queue when the source runs in its child process (transflow/pipel
 (pipeline.py:562-567).  With a GPU on both sides of that seam the array is 66 MB per 4K frame down the link and up again.
 `DeviceFlow` is what `HipFlowSource` yields instead when its configuration says `hip_device_flows`:
 
-* it looks like the float32 (H, W, 2) array it stands for -- `shape`, `dtype`, indexing, arithmetic, `numpy.asarray(flow)`,
+* it looks like the (H, W, 2) array it stands for (float32; float64 behind a float64 convolution kernel, see the class) -- `shape`, `dtype`, indexing, arithmetic, `numpy.asarray(flow)`,
   anything numpy does with an object that has `__array__` -- and comes down (once, into a page-locked array) only when
   something actually reads it on the host; readers get read-only views, writing goes through the flow itself
   (`flow[...] = v`, `flow *= 2`) and marks the device copy stale;
@@ -177,9 +177,10 @@ class FlowRing:
     DRAIN_TIMEOUT = 10.0     # seconds drain() waits for tokens on their way and for their acknowledgements
     TRANSIT_TIMEOUT = 1.0    # ... of which for flows that were handed out but never became a token (nothing else pending)
 
-    def __init__(self, shape, slots: int = 4, wait_for_acks: bool = True):
+    def __init__(self, shape, slots: int = 4, wait_for_acks: bool = True, dtype=np.float32):
         self.shape = tuple(int(v) for v in shape)
-        self.nbytes = int(np.prod(self.shape)) * 4
+        self.dtype = np.dtype(dtype)         # of the flows its buffers hold: the slots are sized by it
+        self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         self.slots = max(2, int(slots))
         self.wait_for_acks = bool(wait_for_acks)
         self._all: list[_Slot] = []
@@ -274,7 +275,12 @@ DEVICE_ROUND = False
 
 
 class DeviceFlow(NDArrayOperatorsMixin):
-    """float32 (H, W, 2) flow in HBM; see the module text."""
+    """(H, W, 2) flow in HBM; see the module text.  `dtype` is float32, or float64 for the flow a source with a float64
+    (or integer) convolution kernel yields (source.py:344-348: post_process carries on in the convolution's type).  A
+    float64 flow is everything a float32 one is -- the compositor's layers read it where it is, rounding it in double
+    on the device (tf_flow_narrow_dev) -- with two exceptions: it crosses a process boundary as the host array, even
+    where "ipc" was asked for, and the DEVICE_ROUND export path does not take it: numpy.round of it gives what numpy
+    gives, and the flow comes down."""
 
     dtype = np.dtype(np.float32)
     ndim = 3
@@ -282,8 +288,11 @@ class DeviceFlow(NDArrayOperatorsMixin):
     _HANDLED = (np.ndarray, np.generic, int, float, complex, bool, list, tuple)
 
     def __init__(self, shape, dev_ptr: int, ready: _Event | None, *, ring: FlowRing | None = None, slot=None, owner=None,
-                 cross_process: str | None = None):
+                 cross_process: str | None = None, dtype=np.float32):
         self.shape = tuple(int(v) for v in shape)
+        self.dtype = np.dtype(dtype)
+        if self.dtype != np.float32:
+            cross_process = None           # IPC tokens carry float32 flows only: a float64 flow crosses as the host array
         self._ptr = int(dev_ptr)
         self._ready = ready
         self._ring, self._slot, self._owner = ring, slot, owner
@@ -321,7 +330,7 @@ class DeviceFlow(NDArrayOperatorsMixin):
 
     @property
     def nbytes(self) -> int:
-        return self.size * 4
+        return self.size * self.dtype.itemsize
 
     def __len__(self) -> int:
         return self.shape[0]
@@ -330,7 +339,7 @@ class DeviceFlow(NDArrayOperatorsMixin):
         """The flow's values on the host: downloaded on first use (page-locked memory), the same array afterwards."""
         if self._host is None:
             from .device import pinned_empty
-            out = pinned_empty(self.shape, np.float32)
+            out = pinned_empty(self.shape, self.dtype)
             self.wait_on_stream()
             check(_lib.load().tf_dev_download(C.c_void_p(out.ctypes.data), C.c_void_p(self._ptr), out.nbytes))
             self._host = out
@@ -373,7 +382,8 @@ class DeviceFlow(NDArrayOperatorsMixin):
         return out[0] if isinstance(out[0], DeviceFlow) else res
 
     def __array_function__(self, func, types, args, kwargs):
-        if DEVICE_ROUND and func in (np.round, np.around) and not self._dirty and args and args[0] is self:
+        if (DEVICE_ROUND and func in (np.round, np.around) and not self._dirty and args and args[0] is self
+                and self.dtype == np.float32):         # (a float64 flow: numpy's own round, on the host values)
             decimals = args[1] if len(args) > 1 else kwargs.get("decimals", 0)
             if len(args) <= 2 and decimals == 0 and kwargs.get("out") is None and set(kwargs) <= {"decimals", "out"}:
                 from .flowzip import RoundedFlow
@@ -404,7 +414,7 @@ class DeviceFlow(NDArrayOperatorsMixin):
 
     def __repr__(self):
         where = "modified on the host" if self._dirty else ("read on the host" if self._host is not None else "on the device")
-        return f"DeviceFlow(shape={self.shape}, float32, {where})"
+        return f"DeviceFlow(shape={self.shape}, {self.dtype.name}, {where})"
 
     # ---- pickling -----------------------------------------------------------------------------------------------
     def __reduce__(self):
@@ -433,7 +443,7 @@ _OPENED: dict = {}      # (producer pid, slot index, handle bytes) -> mapped dev
 
 def _reduce_for_queue(flow: DeviceFlow):
     """ForkingPickler's reducer (multiprocessing queues and pipes only).  Runs in the queue's feeder thread."""
-    if flow._cross == "ipc" and flow._slot is not None and flow._host is None:
+    if flow._cross == "ipc" and flow._slot is not None and flow._host is None and flow.dtype == np.float32:
         try:
             slot = flow._slot
             if slot.ipc_handle is None:

@@ -59,7 +59,7 @@ def _is_y4m(path) -> bool:
 
 def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflownet=None, motion_vectors=False,
                     device_flow_replay=False, mjpeg_inputs=False, png_inputs=False, mjpeg_parallel=False, yuv_inputs=False,
-                    yuv_input_matrix="bt601"):
+                    yuv_input_matrix="bt601", resident_steps=False):
     from .flow import HipFlowSource
 
     def from_args(cls, flow_path, use_mvs=False, mask_path=None, kernel_path=None, cv_config=None,
@@ -94,7 +94,7 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
         return HipFlowSource.from_args(flow_path, use_mvs, mask_path, kernel_path, cv_config, flow_filters, size,
                                        direction, seek_ckpt, seek_time, duration_time, repeat, lock_expr, lock_mode,
                                        lucas_kanade=lucas_kanade, liteflownet=liteflownet,
-                                       archive_device_inflate=device_flow_replay)
+                                       archive_device_inflate=device_flow_replay, resident_steps=resident_steps)
 
     return classmethod(from_args)
 
@@ -188,7 +188,8 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
             device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed",
             jpeg_optimize: bool = False, jpeg_subsampling=None, yuv_frames: str | None = None, yuv_matrix: str | None = None,
-            yuv_range: str | None = None, yuv_inputs=False, yuv_input_matrix: str = "bt601") -> None:
+            yuv_range: str | None = None, yuv_inputs=False, yuv_input_matrix: str = "bt601",
+            resident_steps: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -235,7 +236,8 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     device_flow_replay: the archive source FlowSource.from_args builds for a `.flow.zip` path is
     archive.ArchiveFlowSource(device_inflate=True): members with a band index are inflated on the device
     (transflow_amd/flowunzip.py) straight into the flow that is post-processed there; members without one, and every
-    member while a lock expression or a polar filter needs the raw flow on the host, are read as before.
+    member while a lock expression or (without resident_steps) a polar filter or a kernel needs the raw flow on the
+    host, are read as before.
     mjpeg_inputs: an existing file with extension .mjpeg / .mjpg (a raw MJPEG stream) is decoded on the device
     (transflow_amd/jpegdec.py), as a flow source's video (a MjpegFrameProvider under the HipFlowSource) and as a pixmap
     source (HipMjpegPixmapSource); by default such paths stay the reference's, like every other video.
@@ -259,7 +261,12 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     converts them to pixels (these are not swscale's pixels).  True expands the chroma by
     replication, "linear" by the centre-sited triangle filter; any other value is a ValueError.  yuv_input_matrix
     ("bt601", the default, or "bt709") is the matrix the file was made with: Y4M has no tag for it.  By default such
-    paths stay the reference's, like every other video."""
+    paths stay the reference's, like every other video.
+    resident_steps: the flow sources built for the pipeline are made with `resident_steps=True` (FlowSource.__init__,
+    DESIGN.md section 10): a convolution kernel (`--kernel`) and `polar` flow filters then stay on the device wherever the
+    source has a resident tail -- Farnebäck, a method with "hip_resident", motion vectors, device_flow_replay -- and a
+    source with a float64 kernel and "hip_device_flows" yields float64 DeviceFlows.  By default such sources take the host
+    route, as before."""
     if not isinstance(yuv_inputs, bool) and not (isinstance(yuv_inputs, str) and yuv_inputs == "linear"):
         raise ValueError(f"yuv_inputs is True or \"linear\", not {yuv_inputs!r}")
     if yuv_input_matrix not in ("bt601", "bt709"):
@@ -294,7 +301,8 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         _saved["flow"] = (RefFlowSource, RefFlowSource.__dict__["from_args"])
         RefFlowSource.from_args = _flow_from_args(RefFlowSource.from_args, horn_schunck, lucas_kanade, liteflownet,
                                                      motion_vectors, bool(device_flow_replay), bool(mjpeg_inputs),
-                                                     bool(png_inputs), mjpeg_inputs == "parallel", yuv_inputs, yuv_input_matrix)
+                                                     bool(png_inputs), mjpeg_inputs == "parallel", yuv_inputs, yuv_input_matrix,
+                                                     bool(resident_steps))
     if compositor and "compositor" not in _saved:
         from transflow.compositor.compositor import Compositor as RefCompositor
 

@@ -184,8 +184,9 @@ class FlowSource:
 
         def __init__(self, direction="backward", mask_path=None, kernel_path=None, flow_filters=None,
                      seek_ckpt=None, seek_time=None, duration_time=None, repeat: int = 1, lock_expr=None,
-                     lock_mode="stay"):
+                     lock_mode="stay", resident_steps: bool = False):
             self.direction = FlowSource.Direction.from_arg(direction)
+            self.resident_steps = bool(resident_steps)     # (FlowSource.__init__ says what it asks for)
             self.lock_mode = FlowSource.LockMode.from_arg(lock_mode)
             self.mask_path, self.kernel_path = mask_path, kernel_path
             self.flow_filters_string, self.lock_expr_string = flow_filters, lock_expr
@@ -211,7 +212,7 @@ class FlowSource:
 
         def kwargs(self) -> dict:
             return {name: getattr(self, name) for name in ("mask", "kernel", "flow_filters", "lock_mode",
-                                                           "lock_expr_stay", "lock_expr_skip")}
+                                                           "lock_expr_stay", "lock_expr_skip", "resident_steps")}
 
         def _load_inputs(self):
             if self.mask_path is not None:                       # a float mask, one trailing axis (source.py:127-129)
@@ -253,7 +254,11 @@ class FlowSource:
 
     def __init__(self, direction, width: int, height: int, framerate: float, length, start_frame: int,
                  ckpt_start_frame: int, end_frame: int, mask=None, kernel=None, flow_filters=(),
-                 lock_mode=None, lock_expr_stay=None, lock_expr_skip=None):
+                 lock_mode=None, lock_expr_stay=None, lock_expr_skip=None, resident_steps: bool = False):
+        """resident_steps (opt-in): a convolution kernel and polar filters ride the resident tail of a source that has
+        one (_post_process_steps) instead of sending it down the host route; off, such a source takes the route it
+        took before the argument existed."""
+        self.resident_steps = bool(resident_steps)
         self.direction = FlowSource.Direction.from_arg(direction)
         self.width, self.height, self.framerate = width, height, framerate
         self.length, self.end_frame = length, end_frame
@@ -274,6 +279,7 @@ class FlowSource:
         # the resident tail (below): what read_next_flow handed out whose flow is still on the device, the mask on the
         # device, and where the yielded arrays / DeviceFlows (transflow_amd/deviceflow.py) live
         self._pending = self._mask_dev = self._flow_pool = self._flow_ring = None
+        self._kernel_dev = None  # (the convolution kernel on the device, its shape): _kernel_on_device
         self._scratch = {}       # device buffers of the out-of-place tail (_device_scratch)
         # the first pass starts where a checkpoint left off, later passes at start_frame (source.py:246-248)
         self.input_frame_index = 0
@@ -388,7 +394,8 @@ class FlowSource:
     # ---- the resident tail ---------------------------------------------------------------------
     # __next__ (source.py:293-321) calls read_next_flow() and hands its result straight to post_process().  When
     # nothing can look at the raw flow in between (_resident_ok) a source that makes its flows on the device keeps
-    # them there through the filters, the mask and the direction handling, and only the final flow comes down, or
+    # them there through the filters (polar ones too), the mask, the convolution kernel and the direction handling
+    # (_post_process_steps where a polar filter or a kernel is set, with resident_steps), and only the final flow comes down, or
     # none (a DeviceFlow).  Such a source's read_next_flow leaves the raw flow in a post-processing handle and
     # returns _take_output(); post_process, given that very object back, fills it.  It says where the flow sits
     # (_resident_flow) and how a host array is filled from there (_download).
@@ -402,25 +409,43 @@ class FlowSource:
 
     def _resident_ok(self) -> bool:
         """Nothing reads a raw flow or prev_flow on the host (the lock expressions do), and every step of
-        post_process has a device form."""
-        return (self.lock_expr_stay is None and self.lock_expr_skip is None and self.kernel is None
-                and not any(f.name == "polar" for f in self.flow_filters))
+        post_process has a device form (a convolution kernel of a type the device does not convolve in has none: the
+        host route raises for it, as before)."""
+        if self.lock_expr_stay is not None or self.lock_expr_skip is not None:
+            return False
+        steps = self.kernel is not None or any(f.name == "polar" for f in self.flow_filters)
+        if steps and not self.resident_steps:
+            return False         # (the device form of these two is asked for: resident_steps)
+        try:
+            self._output_dtype()
+        except NotImplementedError:
+            return False
+        return True
+
+    def _output_dtype(self) -> np.dtype:
+        """The type post_process returns: float32, or the convolution's (source.py:344-348), float64 unless the kernel
+        is float32."""
+        if self.kernel is None:
+            return np.dtype(np.float32)
+        from .flowops import kernel_result_type
+        return np.dtype(kernel_result_type(self.kernel))
 
     def _take_output(self, device_flows, depth: int):
         """What the resident post_process fills: a DeviceFlow over a buffer of the source's ring (device_flows: True
-        or "ipc"), else a pinned host array of its pool; `depth` of them can be out at a time."""
-        shape = (self.height, self.width, 2)
+        or "ipc"), else a pinned host array of its pool; `depth` of them can be out at a time.  Both are of the type
+        post_process returns (_output_dtype): float64 behind a float64 convolution kernel."""
+        shape, dtype = (self.height, self.width, 2), self._output_dtype()
         if device_flows:
             from .deviceflow import DeviceFlow, FlowRing
             if self._flow_ring is None:
-                self._flow_ring = FlowRing(shape, slots=depth)
+                self._flow_ring = FlowRing(shape, slots=depth, dtype=dtype)
             slot = self._flow_ring.take()
             self._pending = DeviceFlow(shape, slot.flow_ptr, slot.ready, ring=self._flow_ring, slot=slot,
-                                       cross_process="ipc" if device_flows == "ipc" else None)
+                                       cross_process="ipc" if device_flows == "ipc" else None, dtype=dtype)
         else:
             if self._flow_pool is None:
                 from .device import ArrayPool
-                self._flow_pool = ArrayPool(shape, np.float32, limit=depth, pinned=True)
+                self._flow_pool = ArrayPool(shape, dtype, limit=depth, pinned=True)
             self._pending = self._flow_pool.take()
         return self._pending
 
@@ -445,43 +470,140 @@ class FlowSource:
             self._scratch[name] = DevBuffer(max(1, nbytes))
         return self._scratch[name]
 
-    def _post_process_chain(self, raw, src: int, chain, ops, mask_ptr):
-        import ctypes as C
+    def _output_buffer(self, raw) -> int:
+        """Where the last launch of the out-of-place tail writes: the DeviceFlow's own buffer, or the staging buffer a
+        host array's one download starts from."""
+        if not isinstance(raw, np.ndarray):
+            return raw.dev_ptr
+        return self._device_scratch(f"staging {raw.dtype.name}", raw.dtype.itemsize * 2 * self.width * self.height).ptr
 
-        from . import _lib
-        from .flowops import flow_ops_array
-        px = self.width * self.height
-        to_host = isinstance(raw, np.ndarray)
-        dst = self._device_scratch("staging", 8 * px).ptr if to_host else raw.dev_ptr
-        winner = self._device_scratch("winner", 4 * px).ptr if self.direction == FlowSource.Direction.FORWARD else None
-        arr, n = flow_ops_array(ops)
-        lib = _lib.load()
-        _lib.check(lib.tf_flow_post_process_chain_dev(
-            C.c_void_p(src), C.c_void_p(dst), C.c_void_p(chain) if chain else None, self.width, self.height,
-            self.direction.value, n, arr, C.c_void_p(mask_ptr) if mask_ptr else None,
-            C.c_void_p(winner) if winner else None))
-        if to_host:
+    def _winner_buffer(self):
+        if self.direction != FlowSource.Direction.FORWARD:
+            return None
+        return self._device_scratch("winner", 4 * self.width * self.height).ptr
+
+    def _hand_out(self, raw, dst: int):
+        """The flow at `dst` (_output_buffer) is complete on this thread's stream: down into the host array, or marked."""
+        if isinstance(raw, np.ndarray):
             # (with hip_prefetch this is the worker thread: the copy waits on that thread's stream, the consumer does not)
             if raw.nbytes:
-                _lib.check(lib.tf_dev_download(C.c_void_p(raw.ctypes.data), C.c_void_p(dst), raw.nbytes))
+                import ctypes as C
+
+                from . import _lib
+                _lib.check(_lib.load().tf_dev_download(C.c_void_p(raw.ctypes.data), C.c_void_p(dst), raw.nbytes))
             return raw
         raw._ready.record()
         raw.in_frame = True          # both directions of post_process end with the clip (source.py:361-362)
         return raw
 
+    def _chain_launch(self, src: int, dst: int, chain, direction: int, ops, mask_ptr) -> None:
+        import ctypes as C
+
+        from . import _lib
+        from .flowops import flow_ops_array
+        arr, n = flow_ops_array(ops)
+        winner = self._winner_buffer() if direction == 0 else None
+        _lib.check(_lib.load().tf_flow_post_process_chain_dev(
+            C.c_void_p(src), C.c_void_p(dst), C.c_void_p(chain) if chain else None, self.width, self.height,
+            direction, n, arr, C.c_void_p(mask_ptr) if mask_ptr else None, C.c_void_p(winner) if winner else None))
+
+    def _chain_written(self, chain) -> None:
+        """The out-of-place tail has run; `chain`, if not None, now holds the next call's initial flow."""
+
+    def _post_process_chain(self, raw, src: int, chain, ops, mask_ptr):
+        dst = self._output_buffer(raw)
+        self._chain_launch(src, dst, chain, self.direction.value, ops, mask_ptr)
+        self._chain_written(chain)
+        return self._hand_out(raw, dst)
+
+    def _kernel_on_device(self):
+        """The convolution kernel in the convolution's type, converted once and kept for the life of the source."""
+        if self._kernel_dev is None:
+            from .device import DevBuffer
+            k = np.ascontiguousarray(self.kernel, dtype=self._output_dtype())
+            if k.ndim != 2 or k.size == 0:
+                raise ValueError("the convolution kernel must be a non-empty 2-D array")
+            self._kernel_dev = (DevBuffer.from_array(k), k.shape)
+        return self._kernel_dev
+
+    def _post_process_steps(self, raw, handle, pair: int, route, mask_ptr):
+        """The resident tail with a polar filter or a convolution kernel, in the reference's order (source.py:337-363):
+        runs of scale / threshold / clip as one launch each, every polar filter in place where it falls, then the mask,
+        then the kernel (tf_flow_convolve_post_process_dev: the direction handling and the clip in the convolution's
+        type, straight into the output).  A flow that sits in a method handle's buffer (`route`, _chain_route) is left
+        as it is: the first launch that has to write moves it into a scratch of the source's.  With a kernel the chain
+        state -- the reference's prev_flow -- is the float32 flow after the filters and before the mask and the kernel;
+        without one it is what tf_flow_post_process_chain_dev leaves, as ever."""
+        import ctypes as C
+
+        from . import _lib
+        from .flowops import flow_ops_array, polar_filter_dev
+        lib, P = _lib.load(), C.c_void_p
+        w, h, px, direction = self.width, self.height, self.width * self.height, self.direction.value
+        if route is None:
+            cur, writable, chain = handle.flow_ptr(pair), True, None
+        else:
+            (cur, chain), writable = route, False
+
+        def in_place(ops, mask):
+            if ops or mask:
+                arr, n = flow_ops_array(ops)
+                _lib.check(lib.tf_flow_post_process_ex_dev(P(cur), 0, w, h, -1, n, arr, P(mask) if mask else None, None))
+
+        run = []
+        for f in self.flow_filters:
+            if f.name != "polar":
+                run.append((f.name, f.expr(self.t)))
+                continue
+            if not writable:
+                work = self._device_scratch("filtered", 8 * px).ptr
+                self._chain_launch(cur, work, None, -1, run, None)
+                cur, writable = work, True
+            else:
+                in_place(run, None)
+            run = []
+            polar_filter_dev(cur, px, f.polar, self.t)
+        if self.kernel is None:
+            if route is None:
+                handle.post_process_ex(pair, direction, run, mask_ptr)
+                return None               # (the handle's own way out: _post_process_resident)
+            return self._post_process_chain(raw, cur, chain, run, mask_ptr)
+        if writable and not chain:
+            in_place(run, mask_ptr)
+        elif chain and not run and not mask_ptr:
+            # the chain state is the flow as it is: its one copy, and the convolution reads the flow where it sits
+            _lib.check(lib.tf_dev_copy(P(chain), P(cur), 8 * px))
+        elif run or mask_ptr or chain:
+            masked = self._device_scratch("masked", 8 * px).ptr
+            self._chain_launch(cur, masked, chain, -1, run, mask_ptr)
+            cur = masked
+        kernel, (kh, kw) = self._kernel_on_device()
+        dst, winner = self._output_buffer(raw), self._winner_buffer()
+        _lib.check(lib.tf_flow_convolve_post_process_dev(
+            P(cur), P(kernel.ptr), kh, kw, int(self._output_dtype() == np.float64), P(dst), w, h, direction,
+            P(winner) if winner else None))
+        if route is not None:
+            self._chain_written(chain)
+        return self._hand_out(raw, dst)
+
     def _post_process_resident(self, raw):
         self._pending = None
         handle, pair = self._resident_flow()
-        ops = [(f.name, f.expr(self.t)) for f in self.flow_filters]
         if self.mask is not None and self._mask_dev is None:
             from .device import DevBuffer
             self._mask_dev = DevBuffer.from_array(
                 np.ascontiguousarray(self.mask, dtype=np.float32).reshape(self.height, self.width))
         mask_ptr = None if self.mask is None else self._mask_dev.ptr
         route = self._chain_route()
-        if route is not None:
-            return self._post_process_chain(raw, route[0], route[1], ops, mask_ptr)
-        handle.post_process_ex(pair, self.direction.value, ops, mask_ptr)
+        if self.kernel is not None or any(f.name == "polar" for f in self.flow_filters):
+            out = self._post_process_steps(raw, handle, pair, route, mask_ptr)
+            if out is not None:
+                return out
+        else:
+            ops = [(f.name, f.expr(self.t)) for f in self.flow_filters]
+            if route is not None:
+                return self._post_process_chain(raw, route[0], route[1], ops, mask_ptr)
+            handle.post_process_ex(pair, self.direction.value, ops, mask_ptr)
         if isinstance(raw, np.ndarray):
             self._download(handle, pair, raw)
             return raw
@@ -499,6 +621,9 @@ class FlowSource:
         if self._mask_dev is not None:
             self._mask_dev.close()
             self._mask_dev = None
+        if self._kernel_dev is not None:
+            self._kernel_dev[0].close()
+            self._kernel_dev = None
         self._pending = None
         if self._flow_ring is not None:
             # flows that left this process as IPC tokens: multiprocessing's Queue.get() frees the queue's slot before it
@@ -947,10 +1072,8 @@ class HipFlowSource(FlowSource):
         chain = self._method.chain_buffer(self, self._fb) if self._chains() else None
         return self._method.flow_ptr(self._fb, self._pending_pair), chain
 
-    def _post_process_chain(self, raw, src, chain, ops, mask_ptr):
-        out = FlowSource._post_process_chain(self, raw, src, chain, ops, mask_ptr)
+    def _chain_written(self, chain):
         self.chain_valid = chain is not None
-        return out
 
     def read_next_flow(self):
         if not self._resident_ok():
@@ -1017,16 +1140,18 @@ class HipFlowSource(FlowSource):
     def from_args(cls, flow_path, use_mvs: bool = False, mask_path=None, kernel_path=None, cv_config=None,
                   flow_filters=None, size=None, direction=None, seek_ckpt=None, seek_time=None,
                   duration_time=None, repeat: int = 1, lock_expr=None, lock_mode="stay", lucas_kanade: bool = False,
-                  liteflownet=None, archive_device_inflate: bool = False):
+                  liteflownet=None, archive_device_inflate: bool = False, resident_steps: bool = False):
         """Same signature as FlowSource.from_args (source.py:365-411); `flow_path` may also be
         a frame provider object.  lucas_kanade: a config naming "lukas-kanade" is served (else it raises ValueError);
         liteflownet: the network's weights (a path or a dict of arrays), with which a config naming "liteflownet" is.  `.flow.zip` archives go to ArchiveFlowSource (source.py:397-399), with archive_device_inflate to its
         device_inflate form (indexed members are inflated on the device, DESIGN.md section 18);
+        resident_steps: a convolution kernel and polar filters stay on the device where the source has a resident tail
+        (FlowSource.__init__; DESIGN.md section 10);
         use_mvs: codec motion vectors (source.py:400-402) go to MotionVectorFlowSource (transflow_amd/motionvectors.py),
         `flow_path` being a video path for PyAV (`avformat::path` as the reference splits it) or a vector provider."""
         common = dict(direction=direction, mask_path=mask_path, kernel_path=kernel_path, flow_filters=flow_filters,
                       seek_ckpt=seek_ckpt, seek_time=seek_time, duration_time=duration_time, repeat=repeat,
-                      lock_expr=lock_expr, lock_mode=lock_mode)
+                      lock_expr=lock_expr, lock_mode=lock_mode, resident_steps=resident_steps)
         if isinstance(flow_path, str) and flow_path.split("::")[-1].endswith(".flow.zip"):
             from .archive import ArchiveFlowSource
             return ArchiveFlowSource.Builder(flow_path.split("::")[-1], device_inflate=archive_device_inflate, **common)

@@ -182,20 +182,25 @@ class PostProcess:
 def polar_filter(flow, polar, t: float) -> np.ndarray:
     """PolarFlowFilter.apply (filters.py:81-88), in place on a C-contiguous float32 flow; `polar` is a
     transflow_amd.exprs.PolarFilter."""
-    from ._lib import TfPolarStep
     if not (isinstance(flow, np.ndarray) and flow.dtype == np.float32 and flow.flags.c_contiguous
             and flow.ndim == 3 and flow.shape[2] == 2):
         raise ValueError("the polar filter works in place on a C-contiguous float32 (H, W, 2) array")
-    sr, st, wide_trig, wide_product = polar.programs(t)
-    ar = (TfPolarStep * len(sr))(*[TfPolarStep(o, w, v) for o, w, v in sr])
-    at = (TfPolarStep * len(st))(*[TfPolarStep(o, w, v) for o, w, v in st])
-    lib = _lib.load()
     buf = DevBuffer.from_array(flow)
-    check(lib.tf_flow_polar_dev(C.c_void_p(buf.ptr), flow.shape[0] * flow.shape[1], len(sr), ar, len(st), at,
-                                int(wide_trig), int(wide_product)))
+    polar_filter_dev(buf.ptr, flow.shape[0] * flow.shape[1], polar, t)
     flow[...] = buf.download(flow.shape, np.float32)
     buf.close()
     return flow
+
+
+def polar_filter_dev(flow_dev: int, n_pixels: int, polar, t: float) -> None:
+    """The same in place on a float32 flow in device memory (tf_flow_polar_dev); the parts of the two expressions that
+    are not arrays are evaluated here, with this `t`."""
+    from ._lib import TfPolarStep
+    sr, st, wide_trig, wide_product = polar.programs(t)
+    ar = (TfPolarStep * len(sr))(*[TfPolarStep(o, w, v) for o, w, v in sr])
+    at = (TfPolarStep * len(st))(*[TfPolarStep(o, w, v) for o, w, v in st])
+    check(_lib.load().tf_flow_polar_dev(C.c_void_p(flow_dev), int(n_pixels), len(sr), ar, len(st), at, int(wide_trig),
+                                        int(wide_product)))
 
 
 def _colors(colors, n):

@@ -195,6 +195,8 @@ def round_i64_dev(flow) -> DeviceInt64Flow:
     from . import _lib
     from .device import DevBuffer
     from .deviceflow import _Event
+    if np.dtype(flow.dtype) != np.float32:
+        raise TypeError(f"the device rounds float32 flows for export, not {np.dtype(flow.dtype).name} ones")
     nbytes = flow.size * 8
     spare = _spare.get(nbytes)
     buf = spare.pop() if spare else DevBuffer(nbytes)

@@ -89,6 +89,7 @@ class RemapLayer:
                  mask_src=None, mask_dst=None, mask_alpha=None, reset_mask=None):
         self._lib = _lib.load()
         self._h = C.c_void_p()
+        self._u_dev = self._narrow_dev = None    # device scratch made on first use: an uploaded reset field, a narrowed float64 flow
         self.height, self.width = int(height), int(width)
         if reset_mode not in RESET_MODES:
             raise ValueError(f"Unknown reset mode {reset_mode}")  # reference.py:35
@@ -140,12 +141,12 @@ class RemapLayer:
                 u = np.ascontiguousarray(uniform, dtype=np.float64)
                 if u.shape != (self.height, self.width):
                     raise ValueError("uniform field has the wrong shape")
-                if getattr(self, "_u_dev", None) is None:
+                if self._u_dev is None:
                     self._u_dev = DevBuffer(u.nbytes)
                 self._u_dev.upload(u)
                 u_dev = self._u_dev.ptr
             flow.wait_on_stream()
-            self.update_dev(flow.dev_ptr, u_dev, seed)
+            self.update_dev(self.device_flow_ptr(flow), u_dev, seed)
             flow.mark_used()
             self.flow_was_on_device = True
             if not getattr(flow, "in_frame", False) and self.out_of_frame():
@@ -168,6 +169,23 @@ class RemapLayer:
             if u.shape != (self.height, self.width):
                 raise ValueError("uniform field has the wrong shape")
         check(self._lib.tf_remap_update(self._h, _ptr(flow), _ptr(u), C.c_uint64(seed & (2**64 - 1))))
+
+    def device_flow_ptr(self, flow) -> int:
+        """Where the kernels read a DeviceFlow whose stream wait has been queued: its own address, or -- a float64 flow
+        (behind a float64 convolution kernel, source.py:344-348) -- a float32 scratch of this layer's (8 B/px, made on
+        first use) that tf_flow_narrow_dev fills with the flow rounded in double: numpy.floor for `sum` (sum.py:10),
+        numpy.round for the moving layers (movement.py:21), as the host branch of update() does.  The integers that come
+        out are exact in float32, and the kernels' own rint / floor keep them."""
+        if np.dtype(flow.dtype) == np.float32:
+            return flow.dev_ptr
+        if np.dtype(flow.dtype) != np.float64:
+            raise ValueError(f"a device flow of type {flow.dtype}")
+        if self._narrow_dev is None:
+            from .device import DevBuffer
+            self._narrow_dev = DevBuffer(max(1, 8 * self.height * self.width))
+        check(self._lib.tf_flow_narrow_dev(C.c_void_p(flow.dev_ptr), C.c_void_p(self._narrow_dev.ptr),
+                                           2 * self.height * self.width, int(self.layer_class == "sum")))
+        return self._narrow_dev.ptr
 
     def update_dev(self, flow_dev: int, uniform_dev: int | None = None, seed: int = 0) -> None:
         check(self._lib.tf_remap_update_dev(self._h, C.c_void_p(flow_dev),
@@ -291,6 +309,11 @@ class RemapLayer:
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.tf_remap_destroy(self._h)
             self._h = C.c_void_p()
+        for name in ("_u_dev", "_narrow_dev"):
+            buf = getattr(self, name, None)
+            if buf is not None:
+                buf.close()
+                setattr(self, name, None)
 
     def __del__(self):
         try:
