@@ -281,6 +281,14 @@ int tf_flow_merge_dev(int kind, int n, const void *const *flows_dev, void *out_d
 /* utils.upscale_array (utils.py:417-418): out [H*hf][W*wf][2] = (x*wf, y*hf) of the nearest source pixel. */
 int tf_flow_upscale_dev(const void *in_dev, void *out_dev, int width, int height, int wf, int hf);
 
+/* The two steps above in one pass, for flows that stay on the device (pipeline.py:502-504): n flows [height][width][2]
+   merged by `kind`, then upscaled by the integer factors wf, hf >= 1 into out [height*hf][width*wf][2] -- bit for bit
+   tf_flow_merge_dev followed by tf_flow_upscale_dev.  wf = hf = 1 is the merge alone, n = 1 with TF_MERGE_FIRST the
+   upscale alone.  Pointers are 8-byte aligned; the output is stored 16 bytes a lane wherever its address allows.
+   TF_ERR_ARG before any launch: a kind out of range, n outside 1..TF_MAX_MERGE, TF_MERGE_ABSMAX with n != 2, a factor
+   below 1, a null pointer with a non-empty size, height*hf or width*wf beyond int.  An empty flow is a success. */
+int tf_flow_seam_dev(int kind, int n, const void *const *flows_dev, int width, int height, int wf, int hf, void *out_dev);
+
 /* The convolution-kernel pre-step of post_process (source.py:344-348):
    scipy.signal.convolve2d(channel, kernel, mode="same", boundary="fill", fillvalue=0) on both
    channels.  wide = 1: kernel float64 [kh][kw], out float64 [H][W][2] (numpy.result_type of a float32
@@ -340,6 +348,13 @@ int tf_flow_polar_dev(void *flow_dev, size_t n_pixels, int n_radius, const tf_po
    [n][2] -> rgb uint8 [n][3].  colors_rgb: 2 (render1d) or 4 (render2d) colours as float triples. */
 int tf_flow_render1d_dev(const void *arr_dev, void *rgb_dev, size_t n, float scale, const float colors_rgb[6], int binary);
 int tf_flow_render2d_dev(const void *flow_dev, void *rgb_dev, size_t n, float scale, const float colors_rgb[12]);
+
+/* The flow-magnitude view (pipeline.py:515-516): sqrt(x*x + y*y) of every vector of flow float32 [n_pixels][2], in
+   float32 as numpy.sqrt(numpy.sum(numpy.power(flow, 2), axis=2)) computes it, straight into render1d's pixel rule:
+   rgb uint8 [n_pixels][3] equals tf_flow_render1d_dev of that magnitude, which is never stored.  flow_dev is 8-byte,
+   rgb_dev 4-byte aligned. */
+int tf_flow_view_magnitude_dev(const void *flow_dev, void *rgb_dev, size_t n_pixels, float scale,
+                               const float colors_rgb[6], int binary);
 
 /* Frame ingest, transflow/flow/sources/cv.py:461-466: cv2.resize(INTER_NEAREST) to (width, height)
    then cv2.cvtColor(COLOR_BGR2GRAY), fused: bgr uint8 [src_height][src_width][3] -> grey uint8

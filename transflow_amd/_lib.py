@@ -204,6 +204,7 @@ PROTOTYPES = {
     "tf_remap_staged_used": (_I, [_P]),
     "tf_flow_merge_dev": (_I, [_I, _I, _PP, _P, C.c_size_t]),
     "tf_flow_upscale_dev": (_I, [_P, _P, _I, _I, _I, _I]),
+    "tf_flow_seam_dev": (_I, [_I, _I, _PP, _I, _I, _I, _I, _P]),
     "tf_flow_convolve_dev": (_I, [_P, _P, _I, _I, _I, _P, _I, _I]),
     "tf_flow_post_process_dev": (_I, [_P, _I, _I, _I, _I, _P]),
     "tf_flow_post_process_ex_dev": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(TfFlowOp), _P, _P]),
@@ -213,6 +214,7 @@ PROTOTYPES = {
     "tf_flow_polar_dev": (_I, [_P, C.c_size_t, _I, _P, _I, _P, _I, _I]),
     "tf_flow_render1d_dev": (_I, [_P, _P, C.c_size_t, C.c_float, C.POINTER(C.c_float), _I]),
     "tf_flow_render2d_dev": (_I, [_P, _P, C.c_size_t, C.c_float, C.POINTER(C.c_float)]),
+    "tf_flow_view_magnitude_dev": (_I, [_P, _P, C.c_size_t, C.c_float, C.POINTER(C.c_float), _I]),
     "tf_frame_grey_dev": (_I, [_P, _I, _I, _P, _I, _I]),
     "tf_remap_introduce": (_I, [_P, _I, _P, _I, _I]),
     "tf_remap_introduce_dev": (_I, [_P, _I, _P, _I, _I]),

@@ -411,6 +411,12 @@ class HipCompositor:
             comp.begin()
             for layer in self.layers:
                 layer.render_into(comp)
+        return self._frame_of(comp)
+
+    def _frame_of(self, comp):
+        """The painted image in the form this compositor's frames leave in: a JpegFrame, PngFrame or YuvFrame made on the
+        device, a DeviceFrame whose download has begun, or the downloaded array.  (seam.FlowView hands the flow views
+        out through it too, from a compositor without layers.)"""
         if self.jpeg_frames is not None:
             if self._jpeg is None:
                 from .jpeg import JpegEncoder

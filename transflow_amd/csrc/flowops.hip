@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "flow_rules.h"
 
 using namespace tf;
 
@@ -22,54 +23,13 @@ struct MergeArgs {
     int n;
 };
 
-// Pipeline.FLOW_MERGING_FUNCTIONS: float32, operands combined left to right.  numpy.sum starts from the identity of
-// add and Python's sum() from 0, so both sums start from +0.0: operands that are all -0.0 sum to +0.0
+// Pipeline.FLOW_MERGING_FUNCTIONS, one value per thread (the rule: flow_rules.h)
 __global__ void k_flow_merge(MergeArgs a, float *__restrict__ out, size_t count, int kind)
 {
     size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (t >= count)
         return;
-    const float f0 = a.in[0][t];
-    float r = f0;
-    switch (kind) {
-    case TF_MERGE_FIRST:
-        break;
-    case TF_MERGE_SUM:
-    case TF_MERGE_AVERAGE:
-        r = 0.f + f0;
-        for (int i = 1; i < a.n; i++)
-            r = r + a.in[i][t];
-        if (kind == TF_MERGE_AVERAGE)
-            r = r / (float)a.n;
-        break;
-    case TF_MERGE_DIFFERENCE: { // flows[0] - sum(flows[1:])
-        float s = 0.f;
-        for (int i = 1; i < a.n; i++)
-            s = s + a.in[i][t];
-        r = f0 - s;
-        break;
-    }
-    case TF_MERGE_PRODUCT:
-        for (int i = 1; i < a.n; i++)
-            r = r * a.in[i][t];
-        break;
-    case TF_MERGE_MASKBIN: // utils.py:367-373: |x| > 0.2 (float32) -> 1, else 0
-        for (int i = 1; i < a.n; i++)
-            r = r * (fabsf(a.in[i][t]) > 0.2f ? 1.f : 0.f);
-        break;
-    case TF_MERGE_MASKLIN:
-        for (int i = 1; i < a.n; i++)
-            r = r * fabsf(a.in[i][t]);
-        break;
-    case TF_MERGE_ABSMAX: { // utils.py:376-381: numpy.argmax keeps the first maximum; a NaN is a maximum
-        const float f1 = a.in[1][t];
-        const float a0 = fabsf(f0), a1 = fabsf(f1);
-        if (a1 > a0 || (a1 != a1 && a0 == a0))
-            r = f1;
-        break;
-    }
-    }
-    out[t] = r;
+    out[t] = merge_rule<1>(kind, a.n, [&](int i) { return Vals<1>{{a.in[i][t]}}; }).v[0];
 }
 
 // utils.upscale_array: (x * wf, y * hf) repeated hf x wf times
@@ -182,13 +142,6 @@ k_flow_convolve_tiled(const float2 *__restrict__ flow, const T *__restrict__ ker
     }
 }
 
-struct Colors {
-    float c[4][3];
-};
-
-__device__ __forceinline__ float clip01(float v) { return clip_nan(v, 0.f, 1.f); }
-__device__ __forceinline__ uint8_t to_u8(float v) { return (uint8_t)(int)clip_nan(v, 0.f, 255.f); }
-
 // Four pixels per thread: their 12 output bytes leave as three dwords.
 __device__ __forceinline__ void store_rgb4(uint8_t *__restrict__ rgb, size_t t4, size_t N, const uint8_t (&px)[12])
 {
@@ -221,20 +174,8 @@ __global__ void k_render1d(const float *__restrict__ arr, uint8_t *__restrict__ 
             a4[i] = arr[min(t4 + i, N - 1)];
     }
 #pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const float sa = scale * a4[i];
-        float ka, kb;
-        if (binary) {
-            kb = clip01(rintf(sa));
-            ka = 1.f - kb;
-        } else {
-            ka = clip01(1.f - sa);
-            kb = clip01(sa);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-            px[3 * i + c] = to_u8(ka * col.c[0][c] + kb * col.c[1][c]);
-    }
+    for (int i = 0; i < 4; i++)
+        render1d_rule(a4[i], scale, col, binary, px + 3 * i);
     store_rgb4(rgb, t4, N, px);
 }
 
@@ -531,16 +472,6 @@ TF_API int tf_flow_convolve_dev(const void *flow_dev, const void *kernel_dev, in
                       (const float2 *)flow_dev, (const double *)kernel_dev, kh, kw, (double2 *)out_dev, width, height);
     return launch("flow_convolve_f32", k_flow_convolve<float>, dim3(cdiv(n, BLOCK)), dim3(BLOCK), 0,
                   (const float2 *)flow_dev, (const float *)kernel_dev, kh, kw, (float2 *)out_dev, width, height);
-}
-
-static Colors make_colors(const float *rgb, int n)
-{
-    Colors c;
-    memset(&c, 0, sizeof(c));
-    for (int i = 0; i < n; i++)
-        for (int k = 0; k < 3; k++)
-            c.c[i][k] = rgb[i * 3 + k];
-    return c;
 }
 
 TF_API int tf_flow_render1d_dev(const void *arr_dev, void *rgb_dev, size_t n, float scale, const float colors_rgb[6],

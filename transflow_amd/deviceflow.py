@@ -273,6 +273,12 @@ class FlowRing:
 # dropin.install(device_flow_export=True) turns it on.
 DEVICE_ROUND = False
 
+# While this is on, numpy.power(flow, 2) of a float32 DeviceFlow whose device copy is current (the exponent a scalar equal
+# to 2, no `out`, no other keyword) is a lazy seam.FlowSquares: numpy.sum of it over axis 2 and numpy.sqrt of that end in
+# a seam.FlowMagnitude, which the magnitude view renders from the flow where it is (transflow/pipeline.py:515-516); any
+# other use of any of them gives what numpy gives.  Off by default: dropin.install(device_seam=True) turns it on.
+DEVICE_VIEW = False
+
 
 class DeviceFlow(NDArrayOperatorsMixin):
     """(H, W, 2) flow in HBM; see the module text.  `dtype` is float32, or float64 for the flow a source with a float64
@@ -372,6 +378,11 @@ class DeviceFlow(NDArrayOperatorsMixin):
         return a.copy() if copy else a
 
     def __array_ufunc__(self, ufunc, method, *inputs, out=None, **kwargs):
+        if DEVICE_VIEW and ufunc is np.power and method == "__call__" and out is None:
+            from .seam import lazy_squares
+            squares = lazy_squares(self, inputs, kwargs)
+            if squares is not None:
+                return squares
         args = [x._read() if isinstance(x, DeviceFlow) else x for x in inputs]
         if out is None:
             return getattr(ufunc, method)(*args, **kwargs)

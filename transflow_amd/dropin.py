@@ -29,6 +29,8 @@ import re
 _saved = {}
 _pixmap_options = {"stills": False, "mjpeg": False, "png": False, "mjpeg_parallel": False, "yuv": False, "yuv_matrix": "bt601"}   # what the installed pixmap factory serves
 _saved_export = []      # (the reference's pipeline module, its NumpyOutput, deviceflow.DEVICE_ROUND) while device_flow_export is on
+_saved_seam = []        # (the pipeline module, its upscale_array, render1d, render2d, the merging dict's entries,
+                        # deviceflow.DEVICE_VIEW, the FlowView) while device_seam is on
 
 
 def _served_config(cv_config, horn_schunck: bool, lucas_kanade: bool = False, liteflownet=None) -> bool:
@@ -183,13 +185,38 @@ def _pixmap_from_args(original, stills=True, mjpeg_inputs=False, png_inputs=Fals
     return classmethod(from_args)
 
 
+def _seam_wrappers(originals, view):
+    """The four names device_seam replaces: each takes the device route for float32 DeviceFlows whose device copy is
+    current (transflow_amd/seam.py) and calls the original otherwise."""
+    from . import seam
+    upscale_original, render1d_original, render2d_original, merging = originals
+
+    def upscale_array(arr, wf, hf):
+        return seam.upscale(arr, wf, hf, fallback=upscale_original)
+
+    def render1d(arr, scale=1, colors=None, binary=False):
+        if isinstance(arr, seam.FlowMagnitude) and arr.resident:
+            return view.view_magnitude(arr, scale, colors, binary)
+        return render1d_original(arr, scale, colors, binary)
+
+    def render2d(arr, scale=1, colors=None):
+        if seam.is_resident(arr):
+            return view.view2d(arr, scale, colors)
+        return render2d_original(arr, scale, colors)
+
+    def merger(kind, original):
+        return lambda flows: seam.merge(kind, flows, fallback=original)
+
+    return upscale_array, render1d, render2d, {k: merger(k, f) for k, f in merging.items() if k in seam.MERGE_KINDS}
+
+
 def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = False, horn_schunck: bool = False,
             lucas_kanade: bool = False, liteflownet=None, motion_vectors: bool = False, pixmaps: bool = False,
             jpeg_frames: int | None = None, png_frames: bool = False, device_flow_export=False,
             device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed",
             jpeg_optimize: bool = False, jpeg_subsampling=None, yuv_frames: str | None = None, yuv_matrix: str | None = None,
             yuv_range: str | None = None, yuv_inputs=False, yuv_input_matrix: str = "bt601",
-            resident_steps: bool = False) -> None:
+            resident_steps: bool = False, device_seam: bool = False) -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -266,7 +293,14 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     DESIGN.md section 10): a convolution kernel (`--kernel`) and `polar` flow filters then stay on the device wherever the
     source has a resident tail -- Farnebäck, a method with "hip_resident", motion vectors, device_flow_replay -- and a
     source with a float64 kernel and "hip_device_flows" yields float64 DeviceFlows.  By default such sources take the host
-    route, as before."""
+    route, as before.
+    device_seam: the steps of the main loop between the flow sources and the compositor keep a DeviceFlow on the device
+    (transflow_amd/seam.py): the pipeline module's `upscale_array`, `render1d` and `render2d` and the
+    entries of `Pipeline.FLOW_MERGING_FUNCTIONS` are replaced by wrappers that serve float32 DeviceFlows whose device copy
+    is current -- merged and upscaled flows are DeviceFlows again, `--view-flow` and `--view-flow-magnitude` frames are
+    rendered from the flow where it is (deviceflow.DEVICE_VIEW) and leave in the form this call's frame options
+    (lazy_frames, jpeg_frames, png_frames, yuv_frames and theirs) give the compositor's frames -- and call the
+    reference's function for everything else.  By default nothing of this is touched."""
     if not isinstance(yuv_inputs, bool) and not (isinstance(yuv_inputs, str) and yuv_inputs == "linear"):
         raise ValueError(f"yuv_inputs is True or \"linear\", not {yuv_inputs!r}")
     if yuv_input_matrix not in ("bt601", "bt709"):
@@ -337,6 +371,21 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         else:
             ref_pipeline.NumpyOutput = DeviceFlowArchiveWriter
         deviceflow.DEVICE_ROUND = True
+    if device_seam and not _saved_seam:
+        import transflow.pipeline as ref_pipeline
+
+        from . import deviceflow
+        from .seam import FlowView
+        merging = ref_pipeline.Pipeline.FLOW_MERGING_FUNCTIONS
+        view = FlowView(lazy_frames=lazy_frames, jpeg_frames=jpeg_frames,
+                        png_frames="indexed" if png_frames == "indexed" else bool(png_frames), png_code=png_code,
+                        jpeg_optimize=bool(jpeg_optimize), jpeg_subsampling=jpeg_subsampling, yuv_frames=yuv_frames,
+                        yuv_matrix=yuv_matrix, yuv_range=yuv_range)     # (its images are made at the first view)
+        originals = (ref_pipeline.upscale_array, ref_pipeline.render1d, ref_pipeline.render2d, dict(merging))
+        _saved_seam.append((ref_pipeline, *originals, deviceflow.DEVICE_VIEW, view))
+        ref_pipeline.upscale_array, ref_pipeline.render1d, ref_pipeline.render2d, mergers = _seam_wrappers(originals, view)
+        merging.update(mergers)         # in place: Pipeline.__init__ reads this dict
+        deviceflow.DEVICE_VIEW = True
     if pixmaps or mjpeg_inputs or png_inputs or yuv_inputs:
         # one factory serves both options: a later call that asks for the other one adds it to what is installed
         from transflow.pixmap.source import PixmapSource as RefPixmapSource
@@ -366,3 +415,10 @@ def uninstall() -> None:
         module, original, switch = _saved_export.pop()
         module.NumpyOutput = original
         deviceflow.DEVICE_ROUND = switch
+    while _saved_seam:
+        from . import deviceflow
+        module, upscale_array, render1d, render2d, merging, switch, view = _saved_seam.pop()
+        module.upscale_array, module.render1d, module.render2d = upscale_array, render1d, render2d
+        module.Pipeline.FLOW_MERGING_FUNCTIONS.update(merging)
+        deviceflow.DEVICE_VIEW = switch
+        view.close()
