@@ -81,6 +81,10 @@ int tf_device_count(int *count);
                           path's synchronisation, 64, 128 or 256 (0: the measured best, 64; read per decode).
                           "jd_par_staged" 0: 1 = the synchronisation reads a work-group's share of the scan from LDS
                           where the subsequence is a power of two and the share fits 48 KB.  Test knobs
+     "mt_segments"    0   > 0: the segments tf_mt_random_sample_dev cuts a field into, one wave each, up to 4096 (a
+                          segment is never shorter than 256 words); 1 = one wave walks the field and no state ever
+                          jumps; 0 = the measured default: one segment below 2^16 words, about 2^15 words a segment
+                          above (read per draw: a change re-derives the segments' states).  Same doubles either way
    Unknown names and out-of-range values return TF_ERR_ARG.  The environment is never read. */
 int tf_set_option(const char *name, long value);
 int tf_get_option(const char *name, long *value);
@@ -1043,6 +1047,38 @@ int tf_pngdec_decode(tf_pngdec *dec, const uint8_t *file_host, size_t n, uint8_t
 /* The name of a reject word's reason ("ok" for 0, "unknown" for a number that is none).  No counterpart in the
    reference, whose capture.read() says only success or not (transflow/pixmap/cv.py:54-55). */
 const char *tf_pngdec_reject_name(uint32_t reject);
+
+/* ---- numpy's legacy random stream on the device (MT19937; numpy.random.random, reference.py:59) --------------------
+ * A handle draws the stream RandomState draws, bit for bit, into device memory: fields of n doubles, each double from two
+ * consecutive tempered 32-bit words a, b as ((a >> 5) * 2^26 + (b >> 6)) / 2^53.  It works on word positions: the raw
+ * words obey x[k + 624] = x[k + 397] ^ twist(x[k], x[k + 1]) at every k, so any 624 consecutive raw words are a state.
+ * A field's 2 n words are cut into segments, one wave each; every segment's start state for the next field is t^(2 n)
+ * mod the characteristic polynomial applied to its start state for this one.  A new state or another n costs a one-time
+ * bootstrap (one wave walks the field's span) and, with more than one segment, that polynomial (host, milliseconds). */
+typedef struct tf_mt tf_mt;
+int tf_mt_create(tf_mt **out);      /* the state of seed 5489 until tf_mt_set_state */
+void tf_mt_destroy(tf_mt *mt);
+/* numpy's state tuple: key[624] and pos, 0..624 (odd ones included; the first words come from the current block). */
+int tf_mt_set_state(tf_mt *mt, const uint32_t *key /*[624]*/, int pos);
+/* An equivalent state of the stream's position: the next 624 raw words and *pos = 0.  Waits for the draws queued. */
+int tf_mt_get_state(tf_mt *mt, uint32_t *key /*[624]*/, int *pos);
+/* The next n doubles of the stream (1 <= n <= 2^30) into out_dev (8-byte aligned), queued on the caller's stream. */
+int tf_mt_random_sample_dev(tf_mt *mt, void *out_dev, size_t n);
+/* The plan of the last draw: segments, words of a segment, milliseconds of the last bootstrap's walk (any may be NULL). */
+int tf_mt_info(tf_mt *mt, int *segments, int *segment_words, float *bootstrap_ms);
+/* Host-only entry points, callable without a GPU.  Polynomials over GF(2): TF_MT_POLY_WORDS 64-bit words, bit i of word
+   i / 64 the coefficient of t^i.
+   _charpoly: the characteristic polynomial phi by Berlekamp-Massey over the generator's own output (its degree, 19937,
+   in *degree; the coefficients below t^19937 in coeff_words -- the leading one is implied).
+   _jump_poly: t^J mod phi.  _apply: out[j] = XOR over poly's set coefficients i of x[i + j], j < 624, x the raw stream
+   whose first 624 words are key (word 0 taken as the recurrence would have produced it: only its top bit is state):
+   with poly = t^J mod phi, J >= 1, that is x[J .. J + 623].  _random_sample: RandomState.random_sample(n) from numpy's
+   (key, pos), in numpy's own block-by-block form. */
+#define TF_MT_POLY_WORDS 312
+int tf_mt_stage_charpoly(int *degree, uint64_t *coeff_words /*[TF_MT_POLY_WORDS]*/);
+int tf_mt_stage_jump_poly(uint64_t J, uint64_t *out /*[TF_MT_POLY_WORDS]*/);
+int tf_mt_stage_apply(const uint64_t *poly, const uint32_t *key, uint32_t *out /*[624]*/);
+int tf_mt_stage_random_sample(const uint32_t *key, int pos, size_t n, double *out);
 
 /* ---- batch-of-frames mode over the GPUs of one node ----------------------
  * With flags == 0 every Farnebäck pair is independent (transflow/flow/sources/cv.py:478-490: the

@@ -303,6 +303,16 @@ PROTOTYPES = {
     "tf_pngdec_decode_dev": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
     "tf_pngdec_decode": (_I, [_P, _P, C.c_size_t, _P, _I, C.POINTER(C.c_uint32)]),
     "tf_pngdec_reject_name": (C.c_char_p, [C.c_uint32]),
+    "tf_mt_create": (_I, [_PP]),
+    "tf_mt_destroy": (None, [_P]),
+    "tf_mt_set_state": (_I, [_P, _P, _I]),
+    "tf_mt_get_state": (_I, [_P, _P, _PI]),
+    "tf_mt_random_sample_dev": (_I, [_P, _P, C.c_size_t]),
+    "tf_mt_info": (_I, [_P, _PI, _PI, C.POINTER(C.c_float)]),
+    "tf_mt_stage_charpoly": (_I, [_PI, _P]),
+    "tf_mt_stage_jump_poly": (_I, [C.c_uint64, _P]),
+    "tf_mt_stage_apply": (_I, [_P, _P, _P]),
+    "tf_mt_stage_random_sample": (_I, [_P, _I, C.c_size_t, _P]),
     "tf_batch_unique_id": (_I, [_P]),
     "tf_batch_init": (_I, [_PP, _I, _I, _P]),
     "tf_batch_destroy": (None, [_P]),

@@ -23,6 +23,9 @@ from .config import LayerConfig
 from .masks import load_bool_mask, load_float_mask, parse_color
 
 
+RNGS = ("numpy", "device", "mt19937")   # where a random reset's field is drawn (_HipLayer.__init__)
+
+
 class _HipLayer:
     """What every layer class shares (layer.py:11-34): config, size, sources, mask_alpha, lazy device
     state, host-only pickling.  Subclasses set LAYER_CLASS / DEPTH / INDEX_* and write `update`."""
@@ -47,7 +50,11 @@ class _HipLayer:
                 raise ValueError(f"Unknown reset mode {self.config.reset_mode}")       # reference.py:35
         # "numpy": draw the reset field with numpy.random.random on the host, exactly like
         # reference.py:59 (same global stream => same frames for the same numpy seed);
-        # "device": counter-based generator on the GPU (no 8 B/px upload)
+        # "device": counter-based generator on the GPU (no 8 B/px upload);
+        # "mt19937": numpy's own global stream drawn on the GPU (transflow_amd/mtstream.py): the frames of "numpy",
+        # no draw on the host and no upload
+        if rng not in RNGS:
+            raise ValueError(f"rng is one of {', '.join(RNGS)}, not {rng!r}")
         self.rng = rng
         self.seed = 0
         self._dev = None
@@ -96,10 +103,27 @@ class _HipLayer:
         self.sources = list(sources)
         self._sources_dirty = True
 
+    def _draws(self, rng: str) -> bool:
+        return self.HAS_RESET and self.config.reset_mode == "random" and self.rng == rng
+
     def _reset_field(self):
-        if self.HAS_RESET and self.config.reset_mode == "random" and self.rng == "numpy":
+        if self._draws("numpy"):
+            from .mtstream import Mt19937Stream
+            Mt19937Stream.sync_active()     # a "mt19937" layer of this process has drawn ahead of numpy's state
             return np.random.random(size=(self.height, self.width))                    # reference.py:59
         return None
+
+    def _reset_field_dev(self):
+        """The same field drawn on the device from numpy's stream (rng "mt19937"): its address, else None."""
+        if self._draws("mt19937"):
+            from .mtstream import Mt19937Stream
+            return Mt19937Stream.instance().field(self.height * self.width)
+        return None
+
+    def _sync_stream(self):
+        if self._draws("mt19937"):
+            from .mtstream import Mt19937Stream
+            Mt19937Stream.sync_active()
 
     def update(self, flow):
         raise NotImplementedError()                                                    # layer.py:29-30
@@ -124,17 +148,18 @@ class _HipLayer:
                 and getattr(flow, "in_frame", False)     # (an unclipped flow is checked at update time: RemapLayer.update)
                 and tuple(flow.shape) == (self.height, self.width, 2)):
             return False
-        if self.HAS_RESET and self.config.reset_mode == "random" and self.rng == "numpy":
+        if self._draws("numpy"):
             return False                    # the reset field is drawn on the host: it has to go up, the ordinary way
+        u_dev = self._reset_field_dev()     # drawn now, where the reference draws it (reference.py:59 runs in update)
         try:
             pixmap = self.sources[0].next()
         except BaseException:
             # the reference has moved the layer by the time a source runs dry (movement.py:20-60 come before
             # reference.py:99): so has this one when the exception reaches the pipeline (pipeline.py:580-586)
-            layer.update(flow, None, self.seed)
+            layer.update(flow, None, self.seed, uniform_dev=u_dev)
             raise
         ptr, channels = layer.stage_pixmap(pixmap, beside=self.height * self.width >= (1 << 22))
-        self._deferred = (flow, ptr, channels, self.seed)
+        self._deferred = (flow, ptr, channels, self.seed, u_dev)
         return True
 
     def _run_deferred(self, comp=None) -> None:
@@ -142,15 +167,15 @@ class _HipLayer:
         layer first -- move + reset and gather as two launches, render() will paint as usual."""
         if self._deferred is None:
             return
-        flow, ptr, channels, seed = self._deferred
+        flow, ptr, channels, seed, u_dev = self._deferred
         self._deferred = None
         layer = self._dev
         flow.wait_on_stream()
         flow_ptr = layer.device_flow_ptr(flow)      # (a float64 flow: rounded in double into the layer's float32 scratch)
         if comp is not None:
-            layer.step_dev(comp, flow_ptr, ptr, channels, clip_flow=False, seed=seed)
+            layer.step_dev(comp, flow_ptr, ptr, channels, clip_flow=False, uniform_dev=u_dev, seed=seed)
         else:
-            layer.update_dev(flow_ptr, None, seed)
+            layer.update_dev(flow_ptr, u_dev, seed)
             layer.gather_dev(0, ptr, channels)
         flow.mark_used()
         layer.staged_used()
@@ -174,6 +199,7 @@ class _HipLayer:
     # ---- pickling (checkpoints, pipeline.py:225-242) --------------------------------------
     def __getstate__(self):
         self._run_deferred()
+        self._sync_stream()     # a checkpoint's process draws from numpy's state: it is the stream's position now
         state = {k: v for k, v in self.__dict__.items() if k not in ("_dev", "_pending_state", "sources", "_deferred")}
         state["sources"] = []   # the pipeline strips sources before pickling (pipeline.py:236-238)
         if self._dev is not None:
@@ -192,6 +218,7 @@ class _HipLayer:
 
     def close(self):
         self._deferred = None
+        self._sync_stream()
         if self._dev is not None:
             self._dev.close()
             self._dev = None
@@ -235,7 +262,7 @@ class HipMoveReferenceLayer(_HipDataLayer):
         self._run_deferred()
         if self._defer_step(layer, flow):
             return
-        layer.update(flow, self._reset_field(), self.seed)
+        layer.update(flow, self._reset_field(), self.seed, uniform_dev=self._reset_field_dev())
         beside = self._pixmap_beside(layer)
         for i, source in enumerate(self.sources):                                      # reference.py:94-105
             layer.gather(i, source.next(), beside=beside)
@@ -249,7 +276,7 @@ class HipSumLayer(_HipDataLayer):
 
     def update(self, flow):
         layer = self._layer()
-        layer.update(flow, self._reset_field(), self.seed)                             # sum.py:10 + reference.py:108
+        layer.update(flow, self._reset_field(), self.seed, uniform_dev=self._reset_field_dev())   # sum.py:10 + reference.py:108
         beside = self._pixmap_beside(layer)
         for i, source in enumerate(self.sources):                                      # reference.py:109
             layer.gather(i, source.next(), beside=beside)

@@ -49,6 +49,7 @@ static OptDef g_opts[OPT_COUNT] = {
     {"jd_par_group_subs", 0, 0, 256},          // > 0: subsequences per work-group of that path's synchronisation, 64, 128 or 256 (0: the measured best; read per decode)
     {"jd_par_staged", 0, 0, 1},                // 1: that synchronisation reads a work-group's share of the scan from LDS where it fits (0: through the cache, the measured best; read per decode)
     {"remap_lean", 1, 0, 1},                   // 1: a one-source moveref layer with no masks but the reset mask, no reset_source and no supplied uniform field takes the remap step's lean kernel (that configuration at compile time, 32-bit indices); 0: the general kernels
+    {"mt_segments", 0, 0, 4096},               // > 0: segments a tf_mt field is cut into, one wave each (0: the measured default; 1 never jumps; read per draw)
 };
 long option(Opt which) { return g_opts[which].value; }
 

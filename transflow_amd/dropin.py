@@ -102,12 +102,13 @@ def _flow_from_args(original, horn_schunck=False, lucas_kanade=False, liteflowne
 
 
 def _compositor_from_args(original, lazy_frames=False, jpeg_frames=None, png_frames=False, png_code="fixed",
-                          jpeg_optimize=False, jpeg_subsampling=None, yuv_frames=None, yuv_matrix=None, yuv_range=None):
+                          jpeg_optimize=False, jpeg_subsampling=None, yuv_frames=None, yuv_matrix=None, yuv_range=None,
+                          reset_rng="numpy"):
     from .compositor import LAYER_CLASSES, HipCompositor
 
     def from_args(cls, height, width, layer_configs, background_color="#ffffff"):
         if all(getattr(c, "classname", None) in LAYER_CLASSES for c in layer_configs):
-            return HipCompositor.from_args(height, width, layer_configs, background_color=background_color,
+            return HipCompositor.from_args(height, width, layer_configs, background_color=background_color, rng=reset_rng,
                                            lazy_frames=lazy_frames, jpeg_frames=jpeg_frames, png_frames=png_frames,
                                            png_code=png_code, jpeg_optimize=jpeg_optimize,
                                            jpeg_subsampling=jpeg_subsampling, yuv_frames=yuv_frames, yuv_matrix=yuv_matrix,
@@ -216,7 +217,7 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
             device_flow_replay: bool = False, mjpeg_inputs=False, png_inputs: bool = False, png_code: str = "fixed",
             jpeg_optimize: bool = False, jpeg_subsampling=None, yuv_frames: str | None = None, yuv_matrix: str | None = None,
             yuv_range: str | None = None, yuv_inputs=False, yuv_input_matrix: str = "bt601",
-            resident_steps: bool = False, device_seam: bool = False) -> None:
+            resident_steps: bool = False, device_seam: bool = False, reset_rng: str = "numpy") -> None:
     """Needs `transflow` importable.  Idempotent.  horn_schunck: flow sources of the Horn-Schunck method are this
     backend's too (transflow_amd/hornschunck.py; by default they stay the reference's).  lucas_kanade: likewise for
     the Lucas-Kanade method ("lukas-kanade", transflow_amd/lucaskanade.py).  liteflownet: the network's weights (a path
@@ -300,7 +301,15 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
     is current -- merged and upscaled flows are DeviceFlows again, `--view-flow` and `--view-flow-magnitude` frames are
     rendered from the flow where it is (deviceflow.DEVICE_VIEW) and leave in the form this call's frame options
     (lazy_frames, jpeg_frames, png_frames, yuv_frames and theirs) give the compositor's frames -- and call the
-    reference's function for everything else.  By default nothing of this is touched."""
+    reference's function for everything else.  By default nothing of this is touched.
+    reset_rng: where the compositors built for the pipeline draw a random reset's field (`reset_mode: "random"`,
+    reference.py:59) -- HipCompositor.from_args' `rng`.  "numpy" (the default): numpy.random.random on the host, as
+    before.  "mt19937": numpy's own global stream drawn on the device (transflow_amd/mtstream.py):
+    the same frames for the same numpy seed, no draw on the host, no upload, and a lone moveref layer fed DeviceFlows
+    takes the one-launch step.  "device": the library's counter-based generator -- other frames."""
+    from .compositor import RNGS
+    if reset_rng not in RNGS:
+        raise ValueError(f"reset_rng is one of {', '.join(RNGS)}, not {reset_rng!r}")
     if not isinstance(yuv_inputs, bool) and not (isinstance(yuv_inputs, str) and yuv_inputs == "linear"):
         raise ValueError(f"yuv_inputs is True or \"linear\", not {yuv_inputs!r}")
     if yuv_input_matrix not in ("bt601", "bt709"):
@@ -345,7 +354,8 @@ def install(flow: bool = True, compositor: bool = True, lazy_frames: bool = Fals
         _saved["compositor"] = (RefCompositor, RefCompositor.__dict__["from_args"])
         RefCompositor.from_args = _compositor_from_args(RefCompositor.from_args, lazy_frames, jpeg_frames,
                                                         "indexed" if png_frames == "indexed" else bool(png_frames), png_code,
-                                                        bool(jpeg_optimize), jpeg_subsampling, yuv_frames, yuv_matrix, yuv_range)
+                                                        bool(jpeg_optimize), jpeg_subsampling, yuv_frames, yuv_matrix, yuv_range,
+                                                        reset_rng)
     if jpeg_frames is not None and "output" not in _saved:
         from transflow.output.video_output import VideoOutput as RefVideoOutput
         _saved["output"] = (RefVideoOutput, RefVideoOutput.__dict__["from_args"])

@@ -89,7 +89,7 @@ class RemapLayer:
                  mask_src=None, mask_dst=None, mask_alpha=None, reset_mask=None):
         self._lib = _lib.load()
         self._h = C.c_void_p()
-        self._u_dev = self._narrow_dev = None    # device scratch made on first use: an uploaded reset field, a narrowed float64 flow
+        self._u_dev = self._narrow_dev = self._flow_dev = None  # device scratch made on first use: an uploaded reset field, a narrowed float64 flow, a host flow beside a device reset field
         self.height, self.width = int(height), int(width)
         if reset_mode not in RESET_MODES:
             raise ValueError(f"Unknown reset mode {reset_mode}")  # reference.py:35
@@ -127,7 +127,12 @@ class RemapLayer:
         arr = (C.c_void_p * max(1, len(masks)))(*[m.ctypes.data for m in masks])
         check(self._lib.tf_remap_set_sources(self._h, len(masks), arr))
 
-    def update(self, flow: np.ndarray, uniform: np.ndarray | None = None, seed: int = 0) -> None:
+    def update(self, flow: np.ndarray, uniform: np.ndarray | None = None, seed: int = 0, uniform_dev: int | None = None) -> None:
+        """uniform_dev: the reset field where it already is on the device (float64 (H, W), written on this thread's
+        stream: transflow_amd/mtstream.py) instead of `uniform`; a host flow then goes up into a scratch of this layer's
+        and the update runs as for a device flow."""
+        if uniform_dev is not None and uniform is not None:
+            raise ValueError("the reset field is given on the host or on the device, not both")
         if getattr(flow, "dev_ptr", None) is not None and not flow.on_host:
             # a DeviceFlow nobody brought down (transflow_amd/deviceflow.py): the kernels read it where it is.  A flow a
             # source's post_process clipped (`in_frame`) cannot leave the frame and is only queued; any other is checked
@@ -135,7 +140,7 @@ class RemapLayer:
             # out of update() as it does for a host array (round 6; before, it came at the next render()).
             if tuple(flow.shape) != (self.height, self.width, 2):
                 raise ValueError(f"flow shape {tuple(flow.shape)} != {(self.height, self.width, 2)}")
-            u_dev = None
+            u_dev = uniform_dev
             if uniform is not None:
                 from .device import DevBuffer
                 u = np.ascontiguousarray(uniform, dtype=np.float64)
@@ -163,6 +168,15 @@ class RemapLayer:
         flow = np.ascontiguousarray(flow, dtype=np.float32)
         if flow.shape != (self.height, self.width, 2):
             raise ValueError(f"flow shape {flow.shape} != {(self.height, self.width, 2)}")
+        if uniform_dev is not None:
+            from .device import DevBuffer
+            if self._flow_dev is None:
+                self._flow_dev = DevBuffer(max(1, flow.nbytes))
+            self._flow_dev.upload(flow)
+            self.update_dev(self._flow_dev.ptr, uniform_dev, seed)
+            if self.out_of_frame():
+                raise IndexError("a rounded flow vector leaves the frame (run post_process first)")
+            return
         u = None
         if uniform is not None:
             u = np.ascontiguousarray(uniform, dtype=np.float64)
@@ -309,7 +323,7 @@ class RemapLayer:
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.tf_remap_destroy(self._h)
             self._h = C.c_void_p()
-        for name in ("_u_dev", "_narrow_dev"):
+        for name in ("_u_dev", "_narrow_dev", "_flow_dev"):
             buf = getattr(self, name, None)
             if buf is not None:
                 buf.close()
